@@ -8,11 +8,16 @@ e2e_ctc_loss_fwd_bwd, raw logits in, per-utterance losses and d loss/d logits ou
 batch-mean reduction; with N>1 ranks each GPU gets its own 256 utterances (weak scaling, no
 data-path collective) and the scalar loss is all-reduced over RCCL.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no RANK in the environment) it launches the N ranks itself,
 as children, before anything touches a GPU, and relays rank 0's line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --dump-outputs DIR then
+writes what rank 0's last timed step returned (losses.npy, grads.npy, mean_loss.npy, float32; the
+inputs are seeded, so two builds compare output for output).  Everything below value / ms_per_step
+is measured only with --full.
 
 Rank 0 prints ONE JSON line:
   value / ms_per_step       the C-ABI step above (the drop-in boundary), whole job
@@ -41,15 +46,29 @@ WORKLOAD = dict(name="ctc_fwd_bwd_B256_T1000_V29_S200_f32", B=256, T=1000, V=29,
 WIDE = dict(name="ctc_fwd_bwd_B512_T256_V8000_S64_f32", B=512, T=256, V=8000, S=64)
 
 
-def parse_args():
+def _count(minimum):
+    def parse(s):
+        v = int(s)
+        if v < minimum:
+            raise argparse.ArgumentTypeError("must be >= %d" % minimum)
+        return v
+    return parse
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true", help="skip the secondary decode-throughput numbers")
-    ap.add_argument("--no-wide", action="store_true", help="skip the V=8000 share")
-    return ap.parse_args()
+    ap.add_argument("--gpus", type=_count(1), default=1)
+    ap.add_argument("--steps", type=_count(1), default=50)
+    ap.add_argument("--warmup", type=_count(0), default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write rank 0's outputs of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (module surface, roofline, ragged lengths, f32 "
+                         "chains, wide alphabet, CPU baselines, decode, regimes, shape cliffs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-decode", action="store_true", help="with --full: skip the secondary decode-throughput numbers")
+    ap.add_argument("--no-wide", action="store_true", help="with --full: skip the V=8000 share")
+    return ap.parse_args(argv)
 
 
 def launch_ranks(args):
@@ -122,6 +141,15 @@ class HotPath:
         self.call(m)
         self.k += 1
         return m
+
+
+def dump_outputs(path, hp, mean):
+    """What one step hands its caller: per-utterance losses, d mean-loss / d logits and the batch-mean loss (under the
+    launcher: summed over ranks, as the step's bucketed all-reduce leaves it).  30 MB of float32 at the headline shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("losses", hp.losses), ("grads", hp.grads), ("mean_loss", mean)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def time_events(torch, fn, reps):
@@ -583,141 +611,139 @@ def main():
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(args.steps):
-        step()
+        last = step()
     drain()
     ev1.record()
     fence()
     wall = max_over_ranks(time.perf_counter() - t0)
+    event_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hp, last)
 
-    # dominant kernels' duration: HIP events on the launch stream around each of K launches (second pass,
-    # kernels only, so that the mean/all-reduce tail is not attributed to them)
-    kernel_ms = time_events(torch, lambda: hp.call(hp.means[0, :1]), args.steps)
+    # everything below the headline: --full only
+    if args.full:
+        sharded_wall = None
+        wide = wide_bf16 = None
+        # dominant kernels' duration: HIP events on the launch stream around each of K launches (second pass,
+        # kernels only, so that the mean/all-reduce tail is not attributed to them)
+        kernel_ms = time_events(torch, lambda: hp.call(hp.means[0, :1]), args.steps)
 
-    # ---- SURVEY.md 8(d)'s ragged-length variant of the same shape: x_len = randint(T//2, T+1) ------------------------------
-    gr = torch.Generator().manual_seed(2000 + rank)
-    xl_r = torch.randint(w["T"] // 2, w["T"] + 1, (w["B"],), generator=gr)
-    hpr = HotPath((dev_batch[0], dev_batch[1], xl_r.to(dev), dev_batch[3]))
-    for _ in range(max(2, args.warmup)):
-        hpr.call(hpr.means[0, :1])
-    ragged_ms = time_events(torch, lambda: hpr.call(hpr.means[0, :1]), args.steps)
-    ragged_frames = int(xl_r.sum().item())
-    del hpr
+        # ---- SURVEY.md 8(d)'s ragged-length variant of the same shape: x_len = randint(T//2, T+1) ------------------------------
+        gr = torch.Generator().manual_seed(2000 + rank)
+        xl_r = torch.randint(w["T"] // 2, w["T"] + 1, (w["B"],), generator=gr)
+        hpr = HotPath((dev_batch[0], dev_batch[1], xl_r.to(dev), dev_batch[3]))
+        for _ in range(max(2, args.warmup)):
+            hpr.call(hpr.means[0, :1])
+        ragged_ms = time_events(torch, lambda: hpr.call(hpr.means[0, :1]), args.steps)
+        ragged_frames = int(xl_r.sum().item())
+        del hpr
 
-    # ---- the caller's option e2e_ctc_loss_opts.chains = E2E_CHAINS_F32 (not the headline: looser gradient tolerance) ---
-    from end2end_amd import _lib as _lib_mod
-    hp32 = HotPath(dev_batch, chains=_lib_mod.CHAINS_F32)
-    for _ in range(max(2, args.warmup)):
-        hp32.call(hp32.means[0, :1])
-    f32_ms = time_events(torch, lambda: hp32.call(hp32.means[0, :1]), args.steps)
-    hp.call()
-    hp32.call()                       # (unscaled gradients for the comparison)
-    f32_grad_dev = float((hp32.grads - hp.grads).abs().max().item())
-    f32_loss_dev = float(((hp32.losses - hp.losses).abs() / hp.losses.abs().clamp_min(1.0)).max().item())
-    del hp32
+        # ---- the caller's option e2e_ctc_loss_opts.chains = E2E_CHAINS_F32 (not the headline: looser gradient tolerance) ---
+        from end2end_amd import _lib as _lib_mod
+        hp32 = HotPath(dev_batch, chains=_lib_mod.CHAINS_F32)
+        for _ in range(max(2, args.warmup)):
+            hp32.call(hp32.means[0, :1])
+        f32_ms = time_events(torch, lambda: hp32.call(hp32.means[0, :1]), args.steps)
+        hp.call()
+        hp32.call()                       # (unscaled gradients for the comparison)
+        f32_grad_dev = float((hp32.grads - hp.grads).abs().max().item())
+        f32_loss_dev = float(((hp32.losses - hp.losses).abs() / hp.losses.abs().clamp_min(1.0)).max().item())
+        del hp32
 
-    # ---- leg 2: the metric through the Python surface (module_ms_per_step) ------------------------------------------
-    from end2end_amd import CTCLoss
-    crit = CTCLoss(reduce=True, size_average=True, blank_idx=0)
-    xm = dev_batch[0].clone().requires_grad_()
-    tg, xl, tl = dev_batch[1], dev_batch[2], dev_batch[3]
+        # ---- leg 2: the metric through the Python surface (module_ms_per_step) ------------------------------------------
+        from end2end_amd import CTCLoss
+        crit = CTCLoss(reduce=True, size_average=True, blank_idx=0)
+        xm = dev_batch[0].clone().requires_grad_()
+        tg, xl, tl = dev_batch[1], dev_batch[2], dev_batch[3]
 
-    def module_step():
-        xm.grad = None
-        loss = crit(xm, tg, xl, tl)
-        loss.backward()
-        return loss
-
-    for _ in range(args.warmup):
-        module_step()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        lm_ = module_step()
-    fence()
-    module_wall = max_over_ranks(time.perf_counter() - t0)
-    module_loss = float(lm_.item())
-    c_abi_loss = float(hp.means[0, 0].item())
-
-    # ---- leg 2b (under the launcher): what the package ships for a batch spread over ranks -- end2end_amd.parallel.ShardedCTCLoss
-    #      (per-utterance losses, ONE synchronous 16-byte all-reduce of [sum, count] per call, gradient of the GLOBAL mean) +
-    #      backward().  The C-ABI leg above reduces its scalar losses in buckets of 8 steps, asynchronously; this is the module. ----
-    sharded_wall = None
-    if distributed:
-        from end2end_amd.parallel import ShardedCTCLoss
-        scrit = ShardedCTCLoss(size_average=True, blank_idx=0)
-        xs = dev_batch[0].clone().requires_grad_()
-
-        def sharded_step():
-            xs.grad = None
-            loss = scrit(xs, tg, xl, tl)
+        def module_step():
+            xm.grad = None
+            loss = crit(xm, tg, xl, tl)
             loss.backward()
             return loss
 
         for _ in range(args.warmup):
-            sharded_step()
+            module_step()
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            ls_ = sharded_step()
+            lm_ = module_step()
         fence()
-        sharded_wall = max_over_ranks(time.perf_counter() - t0)
-        sharded_loss = float(ls_.item())
+        module_wall = max_over_ranks(time.perf_counter() - t0)
+        module_loss = float(lm_.item())
+        c_abi_loss = float(hp.means[0, 0].item())
 
-    # ---- leg 3: one GPU's share of configs[4] (V=8000), the HBM-bound shape, at every N ------------------------------
-    wide = wide_bf16 = None
-    if not args.no_wide:
-        ww = WIDE
-        _, wb = make_batch(5000 + rank, ww["B"], ww["T"], ww["V"], ww["S"], dev)
-        wp = HotPath(wb)
-        for _ in range(2):
-            wp.call()
-        fence()
-        reps = 5
-        t0 = time.perf_counter()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            wp.call()
-        e1.record()
-        fence()
-        wwall = max_over_ranks(time.perf_counter() - t0)
-        wms = max_over_ranks(e0.elapsed_time(e1) / reps)
-        walgo = 2.0 * ww["V"] * 4 * ww["B"] * ww["T"]
-        wide = {"workload": "B=512 per GPU, T=256 V=8000 S<=64 f32 (BASELINE configs[4] sharded by utterance)",
-                "n_gpus": n_gpus, "ms": wms, "frames_per_s": n_gpus * ww["B"] * ww["T"] * reps / wwall,
-                "algorithmic_bytes_per_gpu": walgo,
-                "roofline": {"bound": "hbm", "achieved": walgo / (wms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": walgo / (wms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                "note": "same C-ABI call as the headline; ms = device time per call (max over ranks), frames_per_s = "
-                        "whole job over the wall clock of %d back-to-back calls" % reps}
-        # the same share with bf16 logits, read and written natively: 2 * V * 2 algorithmic bytes per frame
-        wb16 = (wb[0].to(torch.bfloat16),) + tuple(wb[1:])
-        del wp
-        wp = HotPath(wb16)
-        for _ in range(2):
-            wp.call()
-        fence()
-        wms16 = max_over_ranks(time_events(torch, wp.call, reps))
-        walgo16 = 2.0 * ww["V"] * 2 * ww["B"] * ww["T"]
-        wide_bf16 = {"workload": "B=512 per GPU, T=256 V=8000 S<=64 bf16 logits in, bf16 gradient out (f32 lattice on the compact columns)",
-                     "n_gpus": n_gpus, "ms": wms16, "frames_per_s": n_gpus * ww["B"] * ww["T"] / (wms16 * 1e-3),
-                     "algorithmic_bytes_per_gpu": walgo16,
-                     "roofline": {"bound": "hbm", "achieved": walgo16 / (wms16 * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": walgo16 / (wms16 * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                     "note": "HIP events around each call (mean of %d); no f32 copy of the logits or of the gradient exists" % reps}
-        del wp, wb, wb16
-        torch.cuda.empty_cache()
+        # ---- leg 2b (under the launcher): what the package ships for a batch spread over ranks -- end2end_amd.parallel.ShardedCTCLoss
+        #      (per-utterance losses, ONE synchronous 16-byte all-reduce of [sum, count] per call, gradient of the GLOBAL mean) +
+        #      backward().  The C-ABI leg above reduces its scalar losses in buckets of 8 steps, asynchronously; this is the module. ----
+        if distributed:
+            from end2end_amd.parallel import ShardedCTCLoss
+            scrit = ShardedCTCLoss(size_average=True, blank_idx=0)
+            xs = dev_batch[0].clone().requires_grad_()
+
+            def sharded_step():
+                xs.grad = None
+                loss = scrit(xs, tg, xl, tl)
+                loss.backward()
+                return loss
+
+            for _ in range(args.warmup):
+                sharded_step()
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                ls_ = sharded_step()
+            fence()
+            sharded_wall = max_over_ranks(time.perf_counter() - t0)
+            sharded_loss = float(ls_.item())
+
+        # ---- leg 3: one GPU's share of configs[4] (V=8000), the HBM-bound shape, at every N ------------------------------
+        if not args.no_wide:
+            ww = WIDE
+            _, wb = make_batch(5000 + rank, ww["B"], ww["T"], ww["V"], ww["S"], dev)
+            wp = HotPath(wb)
+            for _ in range(2):
+                wp.call()
+            fence()
+            reps = 5
+            t0 = time.perf_counter()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                wp.call()
+            e1.record()
+            fence()
+            wwall = max_over_ranks(time.perf_counter() - t0)
+            wms = max_over_ranks(e0.elapsed_time(e1) / reps)
+            walgo = 2.0 * ww["V"] * 4 * ww["B"] * ww["T"]
+            wide = {"workload": "B=512 per GPU, T=256 V=8000 S<=64 f32 (BASELINE configs[4] sharded by utterance)",
+                    "n_gpus": n_gpus, "ms": wms, "frames_per_s": n_gpus * ww["B"] * ww["T"] * reps / wwall,
+                    "algorithmic_bytes_per_gpu": walgo,
+                    "roofline": {"bound": "hbm", "achieved": walgo / (wms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": walgo / (wms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                    "note": "same C-ABI call as the headline; ms = device time per call (max over ranks), frames_per_s = "
+                            "whole job over the wall clock of %d back-to-back calls" % reps}
+            # the same share with bf16 logits, read and written natively: 2 * V * 2 algorithmic bytes per frame
+            wb16 = (wb[0].to(torch.bfloat16),) + tuple(wb[1:])
+            del wp
+            wp = HotPath(wb16)
+            for _ in range(2):
+                wp.call()
+            fence()
+            wms16 = max_over_ranks(time_events(torch, wp.call, reps))
+            walgo16 = 2.0 * ww["V"] * 2 * ww["B"] * ww["T"]
+            wide_bf16 = {"workload": "B=512 per GPU, T=256 V=8000 S<=64 bf16 logits in, bf16 gradient out (f32 lattice on the compact columns)",
+                         "n_gpus": n_gpus, "ms": wms16, "frames_per_s": n_gpus * ww["B"] * ww["T"] / (wms16 * 1e-3),
+                         "algorithmic_bytes_per_gpu": walgo16,
+                         "roofline": {"bound": "hbm", "achieved": walgo16 / (wms16 * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": walgo16 / (wms16 * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                         "note": "HIP events around each call (mean of %d); no f32 copy of the logits or of the gradient exists" % reps}
+            del wp, wb, wb16
+            torch.cuda.empty_cache()
 
     if rank == 0:
         total_frames = frames * n_gpus
         ms_per_step = wall * 1e3 / args.steps
-        algo_bytes = 2.0 * w["V"] * 4 * frames          # per launch (one GPU's batch)
-        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-        copy_gbs = measured_copy_gbs(torch, dev)
-        # the VALU bound of the recurrence (DESIGN.md 4.1c): every lattice cell costs >= 4 lane-operations per direction in
-        # the chains and the same again in the segment kernel's recompute
-        cells = float((host_batch[2].double() * (2.0 * host_batch[3].double() + 1.0)).sum().item())
-        lane_ops = cells * 2 * 4 * 2
         out = {
             "metric": "ctc_fwd_bwd_frames_per_sec", "value": total_frames * args.steps / wall, "unit": "frames/s",
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -727,21 +753,29 @@ def main():
                        "api": "C ABI e2e_ctc_loss_fwd_bwd_opt (losses, d mean-loss / d logits, mean loss: one call)"
                        + (" + RCCL all_reduce of the per-step losses, bucketed by 8 steps" if distributed else ""),
                        "sharding": "utterances, %d per GPU" % w["B"]},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": recorded_traffic(w["name"]),
-                         "peak_measured": copy_gbs, "frac_of_measured": achieved / copy_gbs,
-                         "kernel": "e2e_ctc_loss_fwd_bwd: every kernel of the call counted",
-                         "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": algo_bytes,
-                         "valu_frac": lane_ops / (kernel_ms * 1e-3) / VALU_PEAK_LANE_OPS,
-                         "valu_note": "minimal lane-operations (lattice cells x 2 directions x 4 x 2 for the recompute = %.3g) "
-                                      "/ kernel time / %.3g lane-ops/s (256 CU x 4 SIMD x 32 lanes x 2.4 GHz, the f32 "
-                                      "vector peak of MI355X_MICROARCH.md; f64 runs at half of it)" % (lane_ops, VALU_PEAK_LANE_OPS)},
-            "event_ms_per_step": ev0.elapsed_time(ev1) / args.steps,
-            "module_ms_per_step": module_wall * 1e3 / args.steps,
-            "module_frames_per_s": total_frames * args.steps / module_wall,
-            "module_api": "loss = end2end_amd.CTCLoss(reduce=True, size_average=True)(logits, targets, lengths...); "
-                          "loss.backward()  (same batch; loss %.6f vs C-ABI %.6f)" % (module_loss, c_abi_loss),
+            "event_ms_per_step": event_ms,
         }
+    if rank == 0 and args.full:
+        algo_bytes = 2.0 * w["V"] * 4 * frames          # per launch (one GPU's batch)
+        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+        copy_gbs = measured_copy_gbs(torch, dev)
+        # the VALU bound of the recurrence (DESIGN.md 4.1c): every lattice cell costs >= 4 lane-operations per direction in
+        # the chains and the same again in the segment kernel's recompute
+        cells = float((host_batch[2].double() * (2.0 * host_batch[3].double() + 1.0)).sum().item())
+        lane_ops = cells * 2 * 4 * 2
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": recorded_traffic(w["name"]),
+                           "peak_measured": copy_gbs, "frac_of_measured": achieved / copy_gbs,
+                           "kernel": "e2e_ctc_loss_fwd_bwd: every kernel of the call counted",
+                           "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": algo_bytes,
+                           "valu_frac": lane_ops / (kernel_ms * 1e-3) / VALU_PEAK_LANE_OPS,
+                           "valu_note": "minimal lane-operations (lattice cells x 2 directions x 4 x 2 for the recompute = %.3g) "
+                                        "/ kernel time / %.3g lane-ops/s (256 CU x 4 SIMD x 32 lanes x 2.4 GHz, the f32 "
+                                        "vector peak of MI355X_MICROARCH.md; f64 runs at half of it)" % (lane_ops, VALU_PEAK_LANE_OPS)}
+        out["module_ms_per_step"] = module_wall * 1e3 / args.steps
+        out["module_frames_per_s"] = total_frames * args.steps / module_wall
+        out["module_api"] = ("loss = end2end_amd.CTCLoss(reduce=True, size_average=True)(logits, targets, lengths...); "
+                             "loss.backward()  (same batch; loss %.6f vs C-ABI %.6f)" % (module_loss, c_abi_loss))
         if sharded_wall is not None:
             out["sharded_module_ms_per_step"] = sharded_wall * 1e3 / args.steps
             out["sharded_module_frames_per_s"] = total_frames * args.steps / sharded_wall
@@ -766,6 +800,7 @@ def main():
             out["fallback_regime"] = fallback_regime_numbers(dev)
             out["shape_cliffs"] = shape_cliff_numbers(dev)
             out["emission_regimes"] = emission_regime_numbers(dev)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if distributed:
         dist.barrier()

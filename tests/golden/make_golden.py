@@ -9,7 +9,7 @@ What is executed here is the REFERENCE itself:
     because it eagerly imports the decoder extension, which cannot be built
     here -- KenLM headers are absent and no stand-ins are written).
 The outputs (inputs + expected outputs, data only) are committed as
-loss_engine.npz / loss_module.npz / encoder.json.
+loss_engine.npz / loss_module.npz / live_engine.npz / encoder.json.
 
 known_answers.json holds the known-answer vectors the reference's own tests
 carry (tests/test_ctc.py:69-165, tests/test_ctc_decoder.py:44-59,86-166):
@@ -116,6 +116,19 @@ def gen_engine():
     return meta
 
 
+def gen_live_engine_case():
+    """test_oracle_loss.py::test_oracle_vs_live_reference_engine's input and the engine's answer, for checkouts where
+    oracle/_ref cannot be built."""
+    g = torch.Generator().manual_seed(11)
+    lp = torch.log_softmax(torch.randn(5, 37, 11, generator=g, dtype=torch.float64), -1)
+    tg = torch.randint(1, 11, (5, 9), generator=g)
+    xl = torch.tensor([37, 30, 25, 37, 19])
+    tl = torch.tensor([9, 4, 0, 7, 9])
+    losses, grads = cpp_ctc_loss.CTCLossEngine(0).compute(lp, tg, xl, tl)
+    np.savez_compressed(os.path.join(HERE, "live_engine.npz"), lp=lp.numpy(), targets=tg.numpy(), x_len=xl.numpy(),
+                        t_len=tl.numpy(), losses=losses.numpy(), grads=grads.numpy())
+
+
 def gen_module(CTCLoss):
     """Module-level loss and logits.grad (pytorch_end2end/modules/ctc_loss.py:25-57)."""
     out = {}
@@ -177,6 +190,7 @@ def gen_encoder(CTCEncoder):
 def main():
     CTCLoss, CTCEncoder = import_reference_loss_module()
     meta = {"engine": gen_engine(), "module": gen_module(CTCLoss)}
+    gen_live_engine_case()
     gen_encoder(CTCEncoder)
     with open(os.path.join(HERE, "meta.json"), "w") as f:
         json.dump(meta, f, indent=1)

@@ -32,7 +32,7 @@ def _ranks():
 
 def test_bench_runs_under_the_launcher_and_reduces_over_rccl():
     n = _ranks()
-    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--no-decode",
+    r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--full", "--no-decode",
                  "--no-wide", "--no-cpu-baseline"], n)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

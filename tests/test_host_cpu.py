@@ -182,8 +182,16 @@ def test_kenlm_binary_models_are_refused_with_a_clear_message(tmp_path):
 
 def test_bench_helpers(tmp_path, monkeypatch):
     """bench.py's host-side pieces: the recorded PMC traffic is found for the headline workload, the synthetic ARPA is
-    deterministic, and `--gpus N` without a launcher starts N ranks through torch.distributed.run on 127.0.0.1."""
+    deterministic, the options parse (a plain run is lean, a step count must be positive), and `--gpus N` without a
+    launcher starts N ranks through torch.distributed.run on 127.0.0.1."""
     import bench
+    a = bench.parse_args([])
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "3", "--warmup", "0", "--full", "--dump-outputs", "d"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 0, True, "d")
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
     t = bench.recorded_traffic(bench.WORKLOAD["name"])
     assert t is not None and 1.5e8 < t < 3.5e8
     labels = ["_"] + [chr(97 + i) for i in range(26)] + [" ", "'"]

@@ -58,19 +58,19 @@ def test_padded_rows_are_softmax_and_infeasible_is_nan():
 
 
 def test_oracle_vs_live_reference_engine():
-    ref = O.load_reference_engine()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+    """The engine's answer comes from oracle/_ref when that was built, else from live_engine.npz (make_golden.py: the same
+    engine on the same input); where both exist they must agree bit for bit."""
     import torch
-    g = torch.Generator().manual_seed(11)
-    lp = torch.log_softmax(torch.randn(5, 37, 11, generator=g, dtype=torch.float64), -1)
-    tg = torch.randint(1, 11, (5, 9), generator=g)
-    xl = torch.tensor([37, 30, 25, 37, 19])
-    tl = torch.tensor([9, 4, 0, 7, 9])
-    l_ref, g_ref = ref.CTCLossEngine(0).compute(lp, tg, xl, tl)
+    c = G.npz("live_engine.npz")
+    lp, tg, xl, tl = (torch.from_numpy(c[k]) for k in ("lp", "targets", "x_len", "t_len"))
+    l_ref, g_ref = c["losses"], c["grads"]
+    ref = O.load_reference_engine()
+    if ref is not None:
+        l_live, g_live = ref.CTCLossEngine(0).compute(lp, tg, xl, tl)
+        assert np.array_equal(l_live.numpy(), l_ref) and np.array_equal(g_live.numpy(), g_ref)
     l_o, g_o = O.ctc_loss(lp.numpy(), tg.numpy(), xl.numpy(), tl.numpy(), 0)
-    same(l_o, l_ref.numpy(), 1e-14, 0)
-    same(g_o, g_ref.numpy(), 1e-12, 1e-15)
+    same(l_o, l_ref, 1e-14, 0)
+    same(g_o, g_ref, 1e-12, 1e-15)
 
 
 def test_thread_per_utterance_equals_pool():
