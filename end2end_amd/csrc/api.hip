@@ -124,11 +124,9 @@ __global__ __launch_bounds__(256) void stream_copy_kernel(copy_f4* __restrict__ 
     const copy_f4* s = src + pc * kCopyPiece; copy_f4* d = dst + pc * kCopyPiece;
     for (int i = lane; i < kCopyPiece; i += 8 * 64) {
       copy_f4 v[8];
+      // (non-temporal loads: 5.80 TB/s, plain ones 5.51 -- tools/diag/ab_copy.py)
 #pragma unroll
-#ifndef E2E_COPY_NT_LOADS
-#define E2E_COPY_NT_LOADS 1
-#endif
-      for (int u = 0; u < 8; u++) v[u] = E2E_COPY_NT_LOADS ? __builtin_nontemporal_load(&s[i + 64 * u]) : s[i + 64 * u];
+      for (int u = 0; u < 8; u++) v[u] = __builtin_nontemporal_load(&s[i + 64 * u]);
 #pragma unroll
       for (int u = 0; u < 8; u++) __builtin_nontemporal_store(v[u], &d[i + 64 * u]);
     }
@@ -251,9 +249,8 @@ int e2e_ctc_loss_fwd_bwd_opt(const void* x, int dtype, int input_is_logprobs,
              B, T, V, Smax, blank, losses, grads, workspace, workspace_bytes, (hipStream_t)stream};
   if (opts) { a.grad_scale = opts->grad_scale; a.reduced = opts->reduced; a.reduction = opts->reduction; a.chains = opts->chains; }
   // AUTO with f32 I/O: wherever the exact kernel stands in for (or finishes) an f32 path it may use its scaled f64 form;
-  // E2E_ALGO_EXACT and f64 always run the reference's log-domain arithmetic.  (E2E_EXACT_LOGDOMAIN=1: everywhere.)
-  static const bool logdomain_only = [] { const char* e = getenv("E2E_EXACT_LOGDOMAIN"); return e && e[0] == '1'; }();
-  a.scaled_exact = (algo == E2E_ALGO_AUTO && (dtype == E2E_F32 || dtype_is_16bit(dtype)) && !logdomain_only) ? 1 : 0;
+  // E2E_ALGO_EXACT and f64 always run the reference's log-domain arithmetic.
+  a.scaled_exact = (algo == E2E_ALGO_AUTO && (dtype == E2E_F32 || dtype_is_16bit(dtype))) ? 1 : 0;
   const int r = resolve_algo(algo, dtype, T, V, Smax);
   if (dtype_is_16bit(dtype) && r == E2E_ALGO_EXACT) {
     set_error("16-bit logits are taken by the fast and wide paths only (algo AUTO / FAST, shapes they support): up-cast to f32");

@@ -26,9 +26,6 @@
 #pragma once
 #include <type_traits>
 
-#ifndef E2E_EXT_ABL                 // tools/diag: timing builds with parts of the chain waves' work switched off (results meaningless)
-#define E2E_EXT_ABL 0               //  1: probabilities loaded once, 2: no lattice arithmetic, 4: no halo exchange, 8: no checkpoint stores
-#endif
 constexpr int kXZero = -(1 << 30);            // exponent of a zero cell (below anything a row of 2^22 frames can reach)
 constexpr int kXHalo = 8, kXOwnLanes = 64 - kXHalo;
 constexpr int kExtDone = 2048;                // flag bit: the extended-range chains of the utterance are done (checkpoints, Z, loss)
@@ -206,39 +203,37 @@ __device__ __forceinline__ void ext_chain_wave(const ExactParams& p, unsigned ch
     const int m = DIR == 0 ? q : M - q;
     if (q > 0) {
       // ---- the boundary: edge lanes out, barrier, halo in ----
-      if (!(E2E_EXT_ABL & 4)) {
-        if (active && edge) {
+      if (active && edge) {
 #pragma unroll
-          for (int r = 0; r < NP; r++) {
-            unsigned char* a = rec_mine + (size_t)(((q & 1) * kXHalo + (lane & (kXHalo - 1))) * 2 + r) * ExtLds::kRec;
-            *reinterpret_cast<double2*>(a) = double2{Bm[r], Lm[r]};
-            *reinterpret_cast<int2*>(a + 16) = int2{Be[r], Le[r]};
-          }
+        for (int r = 0; r < NP; r++) {
+          unsigned char* a = rec_mine + (size_t)(((q & 1) * kXHalo + (lane & (kXHalo - 1))) * 2 + r) * ExtLds::kRec;
+          *reinterpret_cast<double2*>(a) = double2{Bm[r], Lm[r]};
+          *reinterpret_cast<int2*>(a + 16) = int2{Be[r], Le[r]};
         }
-        // (a barrier that waits for LDS only: __syncthreads() would also drain the tile loads and the checkpoint stores)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (has_up && halo) {
+      }
+      // (a barrier that waits for LDS only: __syncthreads() would also drain the tile loads and the checkpoint stores)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (has_up && halo) {
 #pragma unroll
-          for (int r = 0; r < NP; r++) {
-            const unsigned char* a = rec_up + (size_t)(((q & 1) * kXHalo + (lane & (kXHalo - 1))) * 2 + r) * ExtLds::kRec;
-            const double2 v = *reinterpret_cast<const double2*>(a);
-            const int2 e = *reinterpret_cast<const int2*>(a + 16);
-            Bm[r] = v.x; Lm[r] = v.y; Be[r] = e.x; Le[r] = e.y;
-          }
+        for (int r = 0; r < NP; r++) {
+          const unsigned char* a = rec_up + (size_t)(((q & 1) * kXHalo + (lane & (kXHalo - 1))) * 2 + r) * ExtLds::kRec;
+          const double2 v = *reinterpret_cast<const double2*>(a);
+          const int2 e = *reinterpret_cast<const int2*>(a + 16);
+          Bm[r] = v.x; Lm[r] = v.y; Be[r] = e.x; Le[r] = e.y;
         }
       }
     }
     // ---- the tile after this one is asked for now and staged at this tile's end (into the other buffer: its readers left it
     //      before the barrier above): one tile -- 8 steps, ~2 us -- hides the round trip, and no loaded register lives across
     //      the loop's back edge (where the compiler waits for everything outstanding) ----
-    if (!(E2E_EXT_ABL & 1) && stager) fetch.load(rt, b, tile_of(q + 1), Tmax, V, d_tid);
-    if (!active) { if (!(E2E_EXT_ABL & 1) && stager) fetch.store(rt, tiles + ((q + 1) & 1) * tile_b, V, d_tid); return; }
+    if (stager) fetch.load(rt, b, tile_of(q + 1), Tmax, V, d_tid);
+    if (!active) { if (stager) fetch.store(rt, tiles + ((q + 1) & 1) * tile_b, V, d_tid); return; }
     // ---- checkpoints: alpha row t = 16 k - 1 -> slot k, beta-with-emission row t = 16 k -> slot k (0 < 16 k < T), cells in lattice
     //      order (blank g = cell 2 g, label g = cell 2 g + 1), the mantissa as f32.  The row is the one the tile before ended
     //      with (freshly normalised; the halo refill above does not touch the lanes that store).  Stored HERE, behind the
     //      request for the next tile: vmcnt counts in order, and a store issued in front of that request would have to
     //      land before the tile can be staged (measured: 30 us per 1000 frames) ----
-    if (!(E2E_EXT_ABL & 8) && q > 0) {
+    if (q > 0) {
       const int tb_ = DIR == 0 ? 8 * m : 8 * m + 8;                   // alpha: the row 8 m - 1 -> slot m / 2; beta: the row 8 (m + 1)
       if ((tb_ & 15) == 0 && tb_ > 0 && tb_ < T) {
         const int slot = tb_ >> 4;
@@ -259,7 +254,7 @@ __device__ __forceinline__ void ext_chain_wave(const ExactParams& p, unsigned ch
     // ---- this tile's probabilities of the lane's columns ----
     float yb[kXTile], yl[NP][kXTile];
     {
-      const unsigned char* tb = tiles + ((E2E_EXT_ABL & 1) ? 0 : (q & 1) * tile_b);
+      const unsigned char* tb = tiles + (q & 1) * tile_b;
       const x_f4 u0 = *(const lds_f32x4*)(tb + blank * 32), u1 = *(const lds_f32x4*)(tb + blank * 32 + 16);
       yb[0] = u0.x; yb[1] = u0.y; yb[2] = u0.z; yb[3] = u0.w; yb[4] = u1.x; yb[5] = u1.y; yb[6] = u1.z; yb[7] = u1.w;
 #pragma unroll
@@ -283,9 +278,6 @@ __device__ __forceinline__ void ext_chain_wave(const ExactParams& p, unsigned ch
           const double vb = (isB && cond) ? ybt : 0.0, vl = isL ? (double)yl[r][tt] : 0.0;
           Bm[r] = vb; Be[r] = x_fix(vb, 0); Lm[r] = vl; Le[r] = x_fix(vl, 0);
         }
-      } else if (E2E_EXT_ABL & 2) {
-#pragma unroll
-        for (int r = 0; r < NP; r++) { Bm[r] += ybt; Lm[r] += (double)yl[r][tt]; }
       } else if (DIR == 0) {
         double Pm = lane_shift_up(Lm[NP - 1]); int Pe = x_shift_up_e(Le[NP - 1]);
 #pragma unroll
@@ -308,7 +300,7 @@ __device__ __forceinline__ void ext_chain_wave(const ExactParams& p, unsigned ch
         for (int r = 0; r < NP; r++) { x_norm(Bm[r], Be[r]); x_norm(Lm[r], Le[r]); }
       }
     }
-    if (!(E2E_EXT_ABL & 1)) fetch.store(rt, tiles + ((q + 1) & 1) * tile_b, V, d_tid);
+    fetch.store(rt, tiles + ((q + 1) & 1) * tile_b, V, d_tid);
   };
   do_tile(0, std::false_type{});
   for (int q = 1; q < M; q++) do_tile(q, std::true_type{});
@@ -355,10 +347,7 @@ __device__ __forceinline__ void ext_chains(const ExactParams& p, int b, int half
     z[tid] = (tid & 1) ? (double)kXZero : 0.0;
   }
   __syncthreads();
-#ifndef E2E_EXT_FORCE_NP2          // (tools/diag A/B: two pairs per lane whatever the width)
-#define E2E_EXT_FORCE_NP2 0
-#endif
-  if (!E2E_EXT_FORCE_NP2 && S + 1 <= 4 * kXOwnLanes) {
+  if (S + 1 <= 4 * kXOwnLanes) {
     if (dir == 0) ext_chain_wave<0, 1, LT>(p, smem, b, T, S, w, lane); else ext_chain_wave<1, 1, LT>(p, smem, b, T, S, w, lane);
   } else {
     if (dir == 0) ext_chain_wave<0, 2, LT>(p, smem, b, T, S, w, lane); else ext_chain_wave<1, 2, LT>(p, smem, b, T, S, w, lane);
@@ -408,7 +397,7 @@ __device__ __forceinline__ void ext_chains(const ExactParams& p, int b, int half
 // pairs 32 c - 16 .. 32 c + 47: what the 16 steps can reach from either side), c = wid, wid + 8, ...
 //
 // Round 6.  What an item cost was not its lattice -- with the chunk loop compiled out the call took as long as with only its LDS
-// atomics removed (sharp_unrelated: 1 325 against 1 504 us; tools/diag: -DE2E_EXT_ABL=128 / 64) -- but the dependent round trips to
+// atomics removed (sharp_unrelated: 1 325 against 1 504 us; ablation builds, E2E_EXT_ABL in 904eb5c) -- but the dependent round trips to
 // memory around it, on a CU that holds nothing else to run meanwhile: the wait for the utterance's flag and the acquire fence
 // behind it, Z, the targets, the probability rows behind the targets, the checkpoints, the probabilities again for the gradient
 // rows; ~15 us of a 17 us item.  So a workgroup now takes a CONTIGUOUS run of the list's items -- mostly segments of ONE utterance
@@ -470,7 +459,7 @@ __device__ __forceinline__ void ext_segment(const ExactParams& p, const XSegUtt&
 #pragma unroll
   for (int k = 0; k < 2; k++) {
     const int c = wid + 8 * k;
-    if (c >= ((E2E_EXT_ABL & 128) ? 0 : nchunk)) continue;
+    if (c >= nchunk) continue;
     const XSegChunk& q = u.ch[k];
     const int g = q.g, lab = q.lab;
     const bool own = q.own, lvalid = q.lvalid;
@@ -534,11 +523,9 @@ __device__ __forceinline__ void ext_segment(const ExactParams& p, const XSegUtt&
       const double pB = ldexp(aBm[tt] * bBm * Zinv, aBe[tt] + bBe - Ze);
       const double pL = ldexp(aLm[tt] * bLm * Zinv, aLe[tt] + bLe - Ze);
       double pb = own ? pB : 0.0;
-      if (!(E2E_EXT_ABL & 32)) pb = wave_sum_lane63(pb);
-      if (!(E2E_EXT_ABL & 64)) {
-        if (lane == 63 && pb != 0.0) atomicAdd(&post[tt * (V + 1) + blank], pb);
-        if (own && lvalid && pL != 0.0) atomicAdd(&post[tt * (V + 1) + lab], pL);
-      }
+      pb = wave_sum_lane63(pb);
+      if (lane == 63 && pb != 0.0) atomicAdd(&post[tt * (V + 1) + blank], pb);
+      if (own && lvalid && pL != 0.0) atomicAdd(&post[tt * (V + 1) + lab], pL);
       // q of row t
       const double ybt = (double)yb[tt], ylt = lvalid ? (double)yl[tt] : 0.0;
       qBm = bBm * ybt; qBe = ybt != 0.0 ? bBe : kXZero;

@@ -128,15 +128,9 @@ __global__ __launch_bounds__(kThreads) void ctc_greedy_kernel(GreedyParams p) {
 // symbols of a super-tile and its compacted output live in LDS as bytes (V <= 64); the output is written coalesced.
 // LDS per workgroup stays below 40 KB so that four workgroups share a CU: B = 1024 utterances then run in one round.
 constexpr int kChunk = 64;           // frames per wave and chunk
-#ifndef E2E_GREEDY_SUPER
-#define E2E_GREEDY_SUPER 2048
-#endif
-#ifndef E2E_GREEDY_DEPTH
-#define E2E_GREEDY_DEPTH 1
-#endif
-constexpr int kSuper = E2E_GREEDY_SUPER;   // frames per super-tile (round 6: 2048 -- BASELINE configs[2]'s 1500 frames are ONE super-tile, so a
+constexpr int kSuper = 2048;         // frames per super-tile (round 6: 2048 -- BASELINE configs[2]'s 1500 frames are ONE super-tile, so a
                                      // wave's stream of chunk loads is not cut in the middle by a collapse phase and a fresh round trip)
-constexpr int kDepth = E2E_GREEDY_DEPTH;   // chunks a wave has asked for beyond the one it works on.  (Round 6, one process, B=1024, T=1500, V=29: one
+constexpr int kDepth = 1;            // chunks a wave has asked for beyond the one it works on.  (Round 6, one process, B=1024, T=1500, V=29: one
                                      // chunk ahead 34.6 us, two 35.2, three 39.8; with the old super-tile of 1024 frames 35.6 -- the kernel moves its
                                      // 190 MB at 5.4-5.5 TB/s, the box's streaming rate, and a deeper pipeline has nothing to hide.)
 constexpr int kStreamWaves = 4;
@@ -174,12 +168,9 @@ __global__ __launch_bounds__(64 * kStreamWaves) void ctc_greedy_stream_kernel(Gr
     const i4* const xp = reinterpret_cast<const i4*>(x);
     auto request = [&](int c, i4 (&dst)[NPF]) {
       const int p0 = (s0 + c * kChunk) * V / EPV;                 // (64 * V is a multiple of EPV)
+      // (plain loads: round 6, one process, configs[2]: 32.5 us, non-temporal ones 33.2)
 #pragma unroll
-#ifndef E2E_GREEDY_NT_LOADS         // (round 6, one process, configs[2]: plain loads 32.5 us, non-temporal ones 33.2)
-#define E2E_GREEDY_NT_LOADS 0
-#endif
-      for (int u = 0; u < NPF; u++) dst[u] = E2E_GREEDY_NT_LOADS ? __builtin_nontemporal_load(&xp[min(p0 + lane + 64 * u, slab_pieces - 1)])
-                                                                 : xp[min(p0 + lane + 64 * u, slab_pieces - 1)];
+      for (int u = 0; u < NPF; u++) dst[u] = xp[min(p0 + lane + 64 * u, slab_pieces - 1)];
     };
 #pragma unroll
     for (int d = 0; d < kDepth; d++) if (wid + d * kStreamWaves < nchunks) request(wid + d * kStreamWaves, pf[d]);

@@ -331,9 +331,6 @@ __device__ __forceinline__ bool retry_segment_f64(const ExactParams& p, unsigned
   return !__any(bad);
 }
 
-#ifndef E2E_EXT_ON                   // (tools/diag: 0 compiles the extended-range redo out of the flagged kernel)
-#define E2E_EXT_ON 1
-#endif
 #include "ctc_ext.h"
 
 // One utterance b, with the alpha slab `slot` of the workspace.
@@ -822,9 +819,6 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
 
 constexpr int kFlagCache = 2048;    // utterances whose flag words and segment counts a workgroup keeps in LDS
 constexpr int kRedoFailed = 512;    // flag bit set by the segment redo
-#ifndef E2E_EXT_NOSPLIT             // (tools/diag A/B: 1 = both directions of a flagged utterance always on one workgroup)
-#define E2E_EXT_NOSPLIT 0
-#endif
 
 __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
@@ -912,7 +906,7 @@ __global__ __launch_bounds__(kThreads) void ctc_exact_kernel(ExactParams p_in) {
   // flagged for its numbers, not for its inputs (1: lengths, 2: blank inside the targets, 128: protocol, 256: probabilities the f32
   // table cannot hold; 64 alone -- probabilities below 2^-100 but still normal f32 numbers -- is a matter of range)
   auto ext_candidate = [&](int f) -> bool {
-    return E2E_EXT_ON && p.mode == 1 && p.has_ext && ((f & (4 | 32 | 64)) != 0 || (!p.has_retry && (f & (8 | 16)) != 0)) && (f & (1 | 2 | 128 | 256)) == 0;
+    return p.mode == 1 && p.has_ext && ((f & (4 | 32 | 64)) != 0 || (!p.has_retry && (f & (8 | 16)) != 0)) && (f & (1 | 2 | 128 | 256)) == 0;
   };
 
   bool last_by_arrival = false;       // (set where step 1's bounded wait already told which workgroup is the last: see step 3)
@@ -1007,7 +1001,7 @@ __global__ __launch_bounds__(kThreads) void ctc_exact_kernel(ExactParams p_in) {
       }
       __syncthreads();
     };
-    if (E2E_EXT_ON && p.has_ext) {
+    if (p.has_ext) {
       bool mine = false;
       for (int b = tid; b < p.B; b += kThreads) mine |= ext_candidate(flag_of(b));
       any_ext0 = __syncthreads_or(mine ? 1 : 0) != 0;
@@ -1070,9 +1064,9 @@ __global__ __launch_bounds__(kThreads) void ctc_exact_kernel(ExactParams p_in) {
     // Rows of a successful redo have no reader inside the launch -- unless ANOTHER segment of the same utterance failed and nothing
     // but step 3 is left to settle it (no extended-range redo in this launch, or its wait ran out: below): then the last workgroup
     // rewrites those rows from its own XCD, and the first writer's dirty lines must have left this one's L2 by then.
-    if (wrote_here && !(E2E_EXT_ON && p.has_ext)) owes_release = true;
+    if (wrote_here && !p.has_ext) owes_release = true;
     stamp(1);
-    if (E2E_EXT_ON && p.has_ext) {
+    if (p.has_ext) {
       // Which round?  0 (known from the start): some utterance needs the chains -- alpha / beta log Z mismatch, a partition sum out
       // of range, probabilities below 2^-100 -- and everything flagged for its numbers goes with it.  1: step 1 ran, and some redo
       // could not settle its utterance.  To learn that, every workgroup has to have finished step 1: a bounded wait (a grid
@@ -1131,7 +1125,7 @@ __global__ __launch_bounds__(kThreads) void ctc_exact_kernel(ExactParams p_in) {
         build_list(round);
         const int nx = s_next;
         // (few utterances: alpha and beta of an utterance on two workgroups, item 2 i + side)
-        const bool split = 2 * nx <= (int)gridDim.x && !E2E_EXT_NOSPLIT;
+        const bool split = 2 * nx <= (int)gridDim.x;
         for (int i2 = blockIdx.x; i2 < (split ? 2 * nx : nx); i2 += gridDim.x) {
           const int i = split ? i2 >> 1 : i2;
           if (round == 1) {
@@ -1258,7 +1252,7 @@ int launch_exact_flagged(const LossArgs& a, int* flags, int mode, const FastRetr
   if (mode == 1 && retry && retry_lds_bytes(a.V, retry->PPL) > lds) lds = retry_lds_bytes(a.V, retry->PPL);
   // the extended-range redo stands in where the scaled form may (f32 lattice behind an AUTO call); its LDS must fit beside the rest
   const bool ext_ok = mode == 1 && retry && a.scaled_exact && (a.dtype == E2E_F32 || dtype_is_16bit(a.dtype)) &&
-                      retry->PPL >= 1 && 2 * a.Smax + 2 <= retry->CELLS && ExtLds::bytes(a.V) <= 120 * 1024 && getenv("E2E_NO_EXT") == nullptr;
+                      retry->PPL >= 1 && 2 * a.Smax + 2 <= retry->CELLS && ExtLds::bytes(a.V) <= 120 * 1024;
   if (ext_ok && ExtLds::bytes(a.V) > lds) lds = ExtLds::bytes(a.V);
   // (the flagged launch keeps 12.5 KB of static LDS -- flag cache, extended-range lists -- beside the dynamic part; the
   //  all-utterances kernel of mode 0 has none and may take the whole 160 KiB)

@@ -357,10 +357,10 @@ struct ChainF64 {
   typedef double T; typedef h_d2 V2; typedef double R;
   static constexpr bool kF32 = false, kBigV = false;
   static constexpr int kRing = kRingBlks, kRingElem = 8;
-#ifndef E2E_F64_PRODUCERS             // Two producers per direction: 12 waves, i.e. three per SIMD and 168 registers for the chain
-#define E2E_F64_PRODUCERS 2           // waves' paired interior loop (with three producers -- 14 waves, 128 registers -- that loop
-#endif                                // spills in the beta wave: 155 against 131 us per step at the headline shape)
-  static constexpr int kMaxW = 2, kProducers = E2E_F64_PRODUCERS, kRowElems = kRow, kElem = 8;      // (three waves per direction: 174
+  // Two producers per direction: 12 waves, i.e. three per SIMD and 168 registers for the chain waves' paired interior loop
+  // (with three producers -- 14 waves, 128 registers -- that loop spills in the beta wave: 155 against 131 us per step at the
+  // headline shape)
+  static constexpr int kMaxW = 2, kProducers = 2, kRowElems = kRow, kElem = 8;                      // (three waves per direction: 174
                                                                                        //  against 167 us at S in [200, 255] -- six chain waves on four SIMDs)
   static constexpr int kWaves = 2 * kMaxW + 2 + 2 * kProducers + 2;
   static constexpr bool kPairedLoop = true;
@@ -384,21 +384,17 @@ struct ChainF64L : ChainF64 {
 //             all): the probability ring is f32 -- what the producers compute anyway -- and four blocks deep, 87 KB at 224
 //             columns (f64 and eight deep: 290 KB); a chain wave converts what it reads (four conversions per step) and forms
 //             the tilted blank probability itself.  Same cells, same recurrence, same results as ChainF64.
-#ifndef E2E_W_PRODUCERS
-#define E2E_W_PRODUCERS 4
-#endif
-#ifndef E2E_W_RING                 // (tools/diag; round 5, whole call at B=256 T=1000 V=128 S<=100: 4 blocks 247 us, 6: 244, 8: 240 -- and
-#define E2E_W_RING 4               //  beyond ~150 columns more than four do not fit the LDS: not worth an instance of its own)
-#endif
 struct ChainF64W : ChainF64 {
   typedef float R;
   static constexpr bool kBigV = true;
-  static constexpr int kRing = E2E_W_RING, kRingElem = 4, kRowElems = kRow32;
+  // (ring depth, round 5, whole call at B=256 T=1000 V=128 S<=100: 4 blocks 247 us, 6: 244, 8: 240 -- and beyond ~150 columns
+  //  more than four do not fit the LDS: not worth an instance of its own)
+  static constexpr int kRing = 4, kRingElem = 4, kRowElems = kRow32;
   // the producers are what bounds these chains (28 columns per lane and block: ~700 instructions): four per direction, 16 waves,
   // 128 registers -- the plain block loop, as ChainF64L
-  static constexpr int kProducers = E2E_W_PRODUCERS;
+  static constexpr int kProducers = 4;
   static constexpr int kWaves = 2 * kMaxW + 2 + 2 * kProducers + 2;
-  static constexpr bool kPairedLoop = E2E_W_PRODUCERS <= 2;
+  static constexpr bool kPairedLoop = false;
 };
 
 //   ChainF64LW: ChainF64L over the f32 ring -- alphabets of up to 448 columns with targets of up to 447 labels (word-piece
@@ -660,15 +656,11 @@ __device__ __forceinline__ void hf_chain_wave(const FastParams& p, int b, int T,
     const int steady_end = DIR == 0 ? T / kBlk : nblk;         // blocks [1, steady_end) are steady
     run_block(0, std::false_type{}, Any{}, Any{});
     int n = 1;
-#ifndef E2E_F1_FAST_DIRS             // bit 0: alpha, bit 1: beta (tools/diag A/B)
-#define E2E_F1_FAST_DIRS 3
-#endif
-#ifndef E2E_F1_PLAIN_LOOP
     // Interior blocks in pairs (even block, odd block) with everything that depends on the block's parity resolved at
     // compile time.  alpha: blocks 1 .. (T-1)/8 - 1, a checkpoint row (t = 16k-1) ends every odd block; beta: blocks
     // 1 .. M-1, M = (T-1)/8, a checkpoint row (t = 16k) ends the blocks of M's parity.
     const int fast_end = (T - 1) >> 3;
-    if (X::kPairedLoop && fast_end - n >= 3 && ((E2E_F1_FAST_DIRS >> DIR) & 1)) {
+    if (X::kPairedLoop && fast_end - n >= 3) {
       run_block(n, std::true_type{}, Any{}, Any{}); n++;      // (n = 2 now)
       if (DIR == 0 || (((T - 1) >> 3) & 1)) {
         for (; n + 1 < fast_end; n += 2) { run_block(n, std::true_type{}, I0{}, I0{}); run_block(n + 1, std::true_type{}, I1{}, I1{}); }
@@ -676,7 +668,6 @@ __device__ __forceinline__ void hf_chain_wave(const FastParams& p, int b, int T,
         for (; n + 1 < fast_end; n += 2) { run_block(n, std::true_type{}, I0{}, I1{}); run_block(n + 1, std::true_type{}, I1{}, I0{}); }
       }
     }
-#endif
     for (; n < steady_end; n++) run_block(n, std::true_type{}, Any{}, Any{});
     for (; n < nblk; n++) run_block(n, std::false_type{}, Any{}, Any{});
   }
@@ -845,10 +836,7 @@ __global__ E2E_KERNEL_ALIGN __launch_bounds__(X::kWaves * 64) void ctc_fast_chai
 // The probabilities of every live frame for ChainF64W (see prep_wave_big): a wave takes kProbRows consecutive frames at once
 // (their loads are all in flight together: one frame per wave left the kernel latency-bound at 3.3 TB/s), up to four columns per
 // lane; fused log-softmax for raw logits (ctc_loss.cpp reads log-probabilities: CTCLoss applies log_softmax first).
-#ifndef E2E_PROB_ROWS              // (tools/diag; round 5, whole call at V = 200 / 448: 4 rows 313 / 959 us, 8 rows 328 / 980, 16 rows 401 / 1 053)
-#define E2E_PROB_ROWS 4
-#endif
-constexpr int kProbRows = E2E_PROB_ROWS;
+constexpr int kProbRows = 4;       // (round 5, whole call at V = 200 / 448: 4 rows 313 / 959 us, 8 rows 328 / 980, 16 rows 401 / 1 053)
 template <int NK>                  // columns per lane: 4 (<= kMaxBigV) or 7 (<= kMaxHugeV)
 __global__ __launch_bounds__(256) void ctc_fast_prob_kernel(FastParams p) {
   const int lane = threadIdx.x & 63, V = p.V;
@@ -906,9 +894,6 @@ __global__ __launch_bounds__(256) void ctc_fast_prob_kernel(FastParams p) {
 // ============================================================================================
 // F2: one wave per (utterance, 16-step segment)
 // ============================================================================================
-#ifndef E2E_F2_ABL                  // tools/diag: timing builds with parts of the segment kernel switched off (results meaningless)
-#define E2E_F2_ABL 0
-#endif
 // the segment kernel's parameters with the gradient's element width as a compile-time fact (an instance per width: three
 // copies of the gradient passes behind a run-time test cost the f32 kernel 80 bytes of scratch and 5 us)
 // (BIG: alphabets of 97..224 columns -- the probability tile is staged in two rounds, a gradient lane takes up to four labels)
@@ -916,33 +901,14 @@ template <bool O16, bool BIG = false> struct SegParams : FastParams { static con
 constexpr int kHalf = 8;           // rows of alpha*beta buffered in LDS before they are summed and written out
 // Between the segment wave's LDS phases (scatter -> scan -> per-label reads -> next half's scatter).  The LDS executes one
 // wave's operations in order, so a read issued after a write of the same wave sees it without a wait; only the compiler has
-// to keep the order.  (E2E_F2_DRAIN: the full drain this used to be, for A/B.)
-#if defined(E2E_F2_DRAIN)
-#define F2_LDS_ORDER asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#elif defined(E2E_F2_NOFENCE)
-#define F2_LDS_ORDER
-#else
+// to keep the order.  (It used to be a full drain, s_waitcnt lgkmcnt(0); 904eb5c still has that and no fence at all as
+// build switches.)
 #define F2_LDS_ORDER asm volatile("" ::: "memory");
-#endif
-#ifndef E2E_F2_HALF                 // four pairs per lane: keep eight of the segment's alpha rows and compute the other eight twice
-#define E2E_F2_HALF 0              // (three waves per SIMD, 92 bytes of scratch, 8 more alpha steps: the kernel takes 61.8 - 63.0 us
-#endif                             //  against 61.3 with all sixteen rows kept: not on)
-#ifndef E2E_SMIN                    // (both overridable for tools/diag experiments)
-#define E2E_SMIN 0x1p-120f         // smallest row sum sum_j alpha*beta the gradient rows are trusted with
-#endif
-#ifndef E2E_ZTOL
-#define E2E_ZTOL 4e-6f
-#endif
-constexpr float kZTol = E2E_ZTOL;   // |log2| tolerance of the rows' self-check (2.8e-6 relative; rounding alone stays below 1e-6)
-#ifndef E2E_ZTOL_F32
-#define E2E_ZTOL_F32 1e-5f
-#endif
-constexpr float kZTolF32 = E2E_ZTOL_F32;   // the same with f32 chains (ctc_fast_chain_hf_kernel), whose own rounding reaches 3e-6
-#ifndef E2E_KYS
-#define E2E_KYS (kSeg + 4)
-#endif
-constexpr int kYs = E2E_KYS;      // row stride (floats) of the transposed probability tile: 80 B spreads the
-                                   // 16-byte gathers of different labels over the LDS bank row
+constexpr float kSMin = 0x1p-120f;  // smallest row sum sum_j alpha*beta the gradient rows are trusted with
+constexpr float kZTol = 4e-6f;      // |log2| tolerance of the rows' self-check (2.8e-6 relative; rounding alone stays below 1e-6)
+constexpr float kZTolF32 = 1e-5f;   // the same with f32 chains (ctc_fast_chain_hf_kernel), whose own rounding reaches 3e-6
+constexpr int kYs = kSeg + 4;       // row stride (floats) of the transposed probability tile: 80 B spreads the
+                                    // 16-byte gathers of different labels over the LDS bank row
 
 template <int PPL>
 struct F2Lds {
@@ -1003,16 +969,13 @@ __device__ __forceinline__ void finish_rows(const P& p, int b, int t0, int n, in
   float btot8[kHalf];                     // blank cells: the lanes' partial sums never went through the LDS
   wave_sum8(pb, btot8, lane);
   float st8[kHalf];                       // (wave-uniform)
-  if (E2E_F2_ABL & 1) {
-#pragma unroll
-    for (int k = 0; k < kHalf; k++) st8[k] = btot8[k] + 1.f;
-  } else {
+  {                                       // (a scope of its own: without it the segment kernels grow by ~1000 instructions)
     float c[kHalf][PPL], inc[kHalf];
 #pragma unroll
     for (int k = 0; k < kHalf; k++) {
 #pragma unroll
       for (int r = 0; r < PPL; r++) c[k][r] = lds.Ps[k * PROW + PPL * lane + r];
-    }
+  }
 #pragma unroll
     for (int r = 1; r < PPL; r++) {
 #pragma unroll
@@ -1046,25 +1009,23 @@ __device__ __forceinline__ void finish_rows(const P& p, int b, int t0, int n, in
   // part): log2(st) + u must equal zt2's fraction.  Cells that mattered but were flushed -- too few bits in the f32
   // checkpoints, a recomputed row sinking below the lane's unit -- only ever LOWER the sum, so the deviation bounds
   // the posterior mass the row lost.  (Rounding alone: < 1e-6, measured over the fuzz sweeps.)  Lane k checks row k.
-  if (!(E2E_F2_ABL & 4)) {
-    float my_st = 1.f;
+  float my_st = 1.f;
 #pragma unroll
-    for (int k = 0; k < kHalf; k++) my_st = lane == k ? st8[k] : my_st;
-    const int u = lane == kHalf - 1 ? u_hi : u_lo;
-    const float dev = __builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(my_st)) - zfrac + (float)(__builtin_amdgcn_frexp_expf(my_st) + u);
-    const bool live = lane < rows;
+  for (int k = 0; k < kHalf; k++) my_st = lane == k ? st8[k] : my_st;
+  const int u = lane == kHalf - 1 ? u_hi : u_lo;
+  const float dev = __builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(my_st)) - zfrac + (float)(__builtin_amdgcn_frexp_expf(my_st) + u);
+  const bool live = lane < rows;
 #ifdef E2E_FAST_PROFILE
-    { const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
-      if (wg < 16384 && live) atomicMax(reinterpret_cast<int*>(&g_zdev[wg]), __float_as_int(fminf(fabsf(dev), 1e30f))); }
+  { const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
+    if (wg < 16384 && live) atomicMax(reinterpret_cast<int*>(&g_zdev[wg]), __float_as_int(fminf(fabsf(dev), 1e30f))); }
 #endif
-    // (smin / smax: see the range check at the end of the kernel)
-    const bool bad = live && !(fabsf(dev) <= p.ztol && my_st >= E2E_SMIN);
-    if (__any(bad)) smin = 0.f;
-    // borderline: within the tolerance, but beyond what rounding alone leaves (< 1e-6).  Not a reason to flag the utterance;
-    // if OTHER rows flag it for range, the f64 redo takes this segment along (smin == 1 marks it: see the kernel's end)
-    else if (__any(live && !(fabsf(dev) <= 0.25f * p.ztol))) smin = fminf(smin, 1.f);
-    if (__any(live && !(my_st < __builtin_huge_valf()))) smax = __builtin_huge_valf();
-  }
+  // (smin / smax: see the range check at the end of the kernel)
+  const bool bad = live && !(fabsf(dev) <= p.ztol && my_st >= kSMin);
+  if (__any(bad)) smin = 0.f;
+  // borderline: within the tolerance, but beyond what rounding alone leaves (< 1e-6).  Not a reason to flag the utterance;
+  // if OTHER rows flag it for range, the f64 redo takes this segment along (smin == 1 marks it: see the kernel's end)
+  else if (__any(live && !(fabsf(dev) <= 0.25f * p.ztol))) smin = fminf(smin, 1.f);
+  if (__any(live && !(my_st < __builtin_huge_valf()))) smax = __builtin_huge_valf();
   F2_LDS_ORDER
   F2_STAMP(5)
   // gradient rows: y - posterior (d loss/d logits in fused mode; exp(lp) - posterior otherwise).  Lane v writes column
@@ -1080,43 +1041,41 @@ __device__ __forceinline__ void finish_rows(const P& p, int b, int t0, int n, in
       reinterpret_cast<unsigned short*>(p.grads)[g0 + idx] = out_bf16 ? hb : hh;
     }
   };
-  if (!(E2E_F2_ABL & 2)) {
-    // RPP rows per pass: the lane's row is k + rsel; the rows' normalisers and blank sums are wave-uniform, the lane picks its row's
-    auto pass = [&](auto rpp_tag) {
-      constexpr int RPP = decltype(rpp_tag)::value;
-      const float* pre_hi = lds.Ps + gl.hi[0];
-      const float* pre_lo = lds.Ps + gl.lo[0];
-      const float* yrow = lds.ys + gl.y[0] + h * kHalf;
+  // RPP rows per pass: the lane's row is k + rsel; the rows' normalisers and blank sums are wave-uniform, the lane picks its row's
+  auto pass = [&](auto rpp_tag) {
+    constexpr int RPP = decltype(rpp_tag)::value;
+    const float* pre_hi = lds.Ps + gl.hi[0];
+    const float* pre_lo = lds.Ps + gl.lo[0];
+    const float* yrow = lds.ys + gl.y[0] + h * kHalf;
 #pragma unroll
-      for (int k = 0; k < kHalf; k += RPP) {
-        if (FULL || k < rows) {
-          float st = st8[k], bt = btot8[k];
+    for (int k = 0; k < kHalf; k += RPP) {
+      if (FULL || k < rows) {
+        float st = st8[k], bt = btot8[k];
 #pragma unroll
-          for (int j = 1; j < RPP; j++) { st = gl.rsel == j ? st8[k + j] : st; bt = gl.rsel == j ? btot8[k + j] : bt; }
-          const float pv = (pre_hi[k * PROW] - pre_lo[k * PROW]) + gl.isblank[0] * bt;
-          const float g = (yrow[k] - pv * __builtin_amdgcn_rcpf(st)) * p.gscale;
-          if (gl.goff >= 0 && (FULL || k + gl.rsel < rows)) put((size_t)k * V + gl.goff, g);
-        }
+        for (int j = 1; j < RPP; j++) { st = gl.rsel == j ? st8[k + j] : st; bt = gl.rsel == j ? btot8[k + j] : bt; }
+        const float pv = (pre_hi[k * PROW] - pre_lo[k * PROW]) + gl.isblank[0] * bt;
+        const float g = (yrow[k] - pv * __builtin_amdgcn_rcpf(st)) * p.gscale;
+        if (gl.goff >= 0 && (FULL || k + gl.rsel < rows)) put((size_t)k * V + gl.goff, g);
       }
-    };
-    if (gl.rpp == 2) pass(std::integral_constant<int, 2>{});
-    else if (gl.rpp == 4) pass(std::integral_constant<int, 4>{});
-    else {
-      const int nsets = (V + 63) >> 6;
+    }
+  };
+  if (gl.rpp == 2) pass(std::integral_constant<int, 2>{});
+  else if (gl.rpp == 4) pass(std::integral_constant<int, 4>{});
+  else {
+    const int nsets = (V + 63) >> 6;
 #pragma unroll
-      for (int s = 0; s < GL::kSets; s++) {
-        if (s < nsets) {
-          const int v = lane + 64 * s;
-          const float* pre_hi = lds.Ps + gl.hi[s];
-          const float* pre_lo = lds.Ps + gl.lo[s];
-          const float* yrow = lds.ys + gl.y[s] + h * kHalf;
+    for (int s = 0; s < GL::kSets; s++) {
+      if (s < nsets) {
+        const int v = lane + 64 * s;
+        const float* pre_hi = lds.Ps + gl.hi[s];
+        const float* pre_lo = lds.Ps + gl.lo[s];
+        const float* yrow = lds.ys + gl.y[s] + h * kHalf;
 #pragma unroll
-          for (int k = 0; k < kHalf; k++) {
-            if (FULL || k < rows) {
-              const float pv = (pre_hi[k * PROW] - pre_lo[k * PROW]) + gl.isblank[s] * btot8[k];
-              const float g = (yrow[k] - pv * __builtin_amdgcn_rcpf(st8[k])) * p.gscale;
-              if (v < V && (!(E2E_F2_ABL & 64) || g == 1234.5f)) put((size_t)k * V + v, g);
-            }
+        for (int k = 0; k < kHalf; k++) {
+          if (FULL || k < rows) {
+            const float pv = (pre_hi[k * PROW] - pre_lo[k * PROW]) + gl.isblank[s] * btot8[k];
+            const float g = (yrow[k] - pv * __builtin_amdgcn_rcpf(st8[k])) * p.gscale;
+            if (v < V) put((size_t)k * V + v, g);
           }
         }
       }
@@ -1428,10 +1387,10 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
   };
 
   // ---- alpha rows of the segment, kept in registers ----
-  // E2E_F2_HALF: only the eight rows of the half that beta is walking are kept -- the sweep below keeps rows 8..15, and rows
-  // 0..7 are computed a second time before beta reaches them: 64 registers less (three waves per SIMD) for 8 more alpha steps
-  constexpr int kKeep = E2E_F2_HALF ? kHalf : kSeg;
-  h_f2 ABA[kKeep], ALA[kKeep], ABB[kKeep], ALB[kKeep];
+  // (Keeping only the eight rows of the half that beta is walking, and computing rows 0..7 a second time before beta reaches
+  // them, was built (904eb5c): 64 registers less, three waves per SIMD, 92 bytes of scratch, 8 more alpha steps -- the kernel
+  // takes 61.8 - 63.0 us against 61.3 with all sixteen rows kept.)
+  h_f2 ABA[kSeg], ALA[kSeg], ABB[kSeg], ALB[kSeg];
   h_f2 BA = {0.f, 0.f}, LA = {0.f, 0.f}, BB = {0.f, 0.f}, LB = {0.f, 0.f};
   int eA = 0, shA = 0;
   if (seg != 0) {
@@ -1442,6 +1401,7 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
     eA = mstar >= 0 ? pmax - kSlope * mstar : own;
     shA = max(own - eA, -200);
   }
+  // (alpha_start and alpha_rows run once each but stay lambdas: written inline, they change the kernel's register allocation)
   auto alpha_start = [&]() {
     if (seg != 0) {
       BA.x = ldexpf(in.a[0], shA); LA.x = ldexpf(in.a[1], shA); BB.x = ldexpf(in.a[2], shA); LB.x = ldexpf(in.a[3], shA);
@@ -1463,16 +1423,15 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
   const f4* yblank = reinterpret_cast<const f4*>(ys + blank * kYs);
   f4 e4[PPL], b4;
 
-  auto alpha_rows = [&](auto first_tag, auto last_tag, auto keep_tag) {
-    constexpr int T0 = decltype(first_tag)::value, T1 = decltype(last_tag)::value, KEEP0 = decltype(keep_tag)::value;
+  auto alpha_rows = [&]() {
 #pragma unroll
-    for (int tt = T0; tt < T1; tt++) {
+    for (int tt = 0; tt < kSeg; tt++) {
       if ((tt & 3) == 0) {
         b4 = yblank[tt >> 2];
 #pragma unroll
         for (int r = 0; r < PPL; r++) e4[r] = ylab[r][tt >> 2];
       }
-      if ((FULL || tt < n) && !(E2E_F2_ABL & 16)) {
+      if (FULL || tt < n) {
         const float yb = b4[tt & 3];
         if (!FULL && t0 + tt == 0) {
           BA = h_f2{0.f, 0.f}; LA = BA; BB = BA; LB = BA;
@@ -1491,11 +1450,10 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
         }
         if ((tt & 7) == 7) rescale(BA, LA, BB, LB, tt == 7 ? eA7 : eA15);
       }
-      if (tt >= KEEP0) { ABA[tt - KEEP0] = BA; ALA[tt - KEEP0] = LA; ABB[tt - KEEP0] = BB; ALB[tt - KEEP0] = LB; }
+      ABA[tt] = BA; ALA[tt] = LA; ABB[tt] = BB; ALB[tt] = LB;
     }
   };
-  typedef std::integral_constant<int, 0> I0_; typedef std::integral_constant<int, kHalf> I8_; typedef std::integral_constant<int, kSeg> I16_;
-  if (E2E_F2_HALF) alpha_rows(I0_{}, I16_{}, I8_{}); else alpha_rows(I0_{}, I16_{}, I0_{});
+  alpha_rows();
 
   F2_STAMP(2)
   // ---- beta backwards through the segment, posteriors, per-label accumulation (see segment_body) ----
@@ -1505,8 +1463,8 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
   int unit_exp = 0;
   if (FULL || !last_seg) {
     const int ownB = in.ownB;
-    float a_end = fmaxf(fmaxf(fmaxf(ABA[kKeep - 1].x, ABA[kKeep - 1].y), fmaxf(ALA[kKeep - 1].x, ALA[kKeep - 1].y)),
-                        fmaxf(fmaxf(ABB[kKeep - 1].x, ABB[kKeep - 1].y), fmaxf(ALB[kKeep - 1].x, ALB[kKeep - 1].y)));
+    float a_end = fmaxf(fmaxf(fmaxf(ABA[kSeg - 1].x, ABA[kSeg - 1].y), fmaxf(ALA[kSeg - 1].x, ALA[kSeg - 1].y)),
+                        fmaxf(fmaxf(ABB[kSeg - 1].x, ABB[kSeg - 1].y), fmaxf(ALB[kSeg - 1].x, ALB[kSeg - 1].y)));
     const int e_end = a_end >= 0x1p-120f ? (int)((__float_as_uint(a_end) >> 23) & 0xffu) - 127 : -200;
     const int emax = wave_max(eA + ownB + e_end);
     unit_exp = emax;
@@ -1527,7 +1485,6 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
 #pragma unroll
   for (int h = kSeg / kHalf - 1; h >= 0; h--) {
     if (!FULL && h * kHalf >= n) continue;
-    if (E2E_F2_HALF && h == 0) { alpha_start(); alpha_rows(I0_{}, I8_{}, I0_{}); }      // rows 0..7 again, kept this time
     float pb[kHalf];
 #pragma unroll
     for (int k = 0; k < kHalf; k++) pb[k] = 0.f;
@@ -1543,8 +1500,7 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
         const int t = t0 + tt;
         const float yb = b4[tt & 3];
         h_f2 bsBA, bsLA, bsBB, bsLB;                     // beta_t[j] (no emission at t)
-        if (E2E_F2_ABL & 8) { bsBA = qBA; bsLA = qLA; bsBB = qBB; bsLB = qLB; }
-        else if (!FULL && t == T - 1) {
+        if (!FULL && t == T - 1) {
           const int i0 = PPL * lane;
           bsBA.x = (2 * i0 == L - 1 && cond) ? end_unit : 0.f;           bsLA.x = (2 * i0 + 1 == L - 2) ? rr * end_unit : 0.f;
           bsBB.x = (2 * (i0 + 1) == L - 1 && cond) ? end_unit : 0.f;     bsLB.x = (2 * (i0 + 1) + 1 == L - 2) ? rr * end_unit : 0.f;
@@ -1560,10 +1516,9 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
           bsBB = qBB + RR * qLB;
         }
         // alpha*beta of this lane's cells: label cells go to their label-sorted slot, blank cells are pre-summed
-        constexpr int kA = E2E_F2_HALF ? kHalf - 1 : kSeg - 1;       // (index mask of the kept rows)
-        const h_f2 pbl = ABA[tt & kA] * bsBA + ABB[tt & kA] * bsBB;
+        const h_f2 pbl = ABA[tt] * bsBA + ABB[tt] * bsBB;
         pb[k] = pbl.x + pbl.y;
-        const h_f2 PA = ALA[tt & kA] * bsLA, PB = ALB[tt & kA] * bsLB;
+        const h_f2 PA = ALA[tt] * bsLA, PB = ALB[tt] * bsLB;
         ps_put(rank[0], k * PROW, PA.x); ps_put(rank[1], k * PROW, PB.x);
         ps_put(rank[2], k * PROW, PA.y); ps_put(rank[3], k * PROW, PB.y);
         // q_t = beta_t * y_t
@@ -1582,18 +1537,10 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
   }
 }
 
-#ifndef E2E_F2_LDSPAD
-#define E2E_F2_LDSPAD 0
-#endif
-#ifndef E2E_F2_WPB                  // independent segment waves per workgroup (tools/diag)
-#define E2E_F2_WPB 1
-#endif
 template <int PPL, typename P>
 __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
-  const int b = blockIdx.y, seg = blockIdx.x * E2E_F2_WPB + (E2E_F2_WPB > 1 ? (int)(threadIdx.x >> 6) : 0), lane = threadIdx.x & 63;
-  if (E2E_F2_WPB > 1 && seg >= p.NS) return;
+  const int b = blockIdx.y, seg = blockIdx.x, lane = threadIdx.x & 63;
   const int V = p.V, Tmax = p.T, t0 = seg * kSeg;
-  if (E2E_F2_WPB > 1) smem += (threadIdx.x >> 6) * ((F2Lds<PPL>::bytes(V) + E2E_F2_LDSPAD + 15) & ~(size_t)15);
   const F2Lds<PPL> lds(smem, V);
   typedef float f4 __attribute__((ext_vector_type(4)));
   F2_STAMP(-1)
@@ -1686,7 +1633,7 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
         if (64 * j + lane < 4 * V) *reinterpret_cast<f4*>(dst + 16 * j * kYs) = v;
       }
     }
-  } else if (!(E2E_F2_ABL & 32)) {
+  } else {
     // the lane's columns into the transposed tile: four 16-byte writes per column
     auto put_cols = [&](int c0) {
 #pragma unroll
@@ -1712,13 +1659,10 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
   F2_STAMP(0)
   float smin = __builtin_huge_valf(), smax = 0.f;
   const bool full = __builtin_amdgcn_readfirstlane((seg > 0 && n == kSeg && t0 + n < T) ? 1 : 0) != 0;
-#ifndef E2E_F2_SCALAR                // (the scalar body for every width: tools/diag A/B)
   if constexpr (PPL == 4) {
     if (full) segment_body_pk<true>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax);
     else segment_body_pk<false>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax);
-  } else
-#endif
-  if (full) segment_body<PPL, true>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax);
+  } else if (full) segment_body<PPL, true>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax);
   else segment_body<PPL, false>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax);
 #ifdef E2E_FAST_PROFILE
   if (lane == 0) s_prof_acc[7] = ((unsigned long long)__float_as_uint(smin) << 32) | __float_as_uint(smax);
@@ -1739,9 +1683,6 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
   } else if (smin < __builtin_huge_valf()) {
     if (lane == 0) atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31));
   }
-#ifdef E2E_F2_MASK_ALL              // (tools/diag: every segment of a range-flagged utterance is redone)
-  if (lane == 0) atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31));
-#endif
   if (seg == 0 && lane == 0) {
     const double za = p.logz[2 * b], zb = p.logz[2 * b + 1];
     if (!(fabs(za - zb) <= 1e-6 * fabs(za) + 1e-4)) atomicOr(&p.flags[b], 32);
@@ -1753,16 +1694,14 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
 // the wave has to wait for its outstanding gradient stores instead of retiring under them, 65 -> 97 us for the kernel;
 // with a release fence at agent scope, which is an L2 write-back on this multi-XCD part, 411 us.  An empty launch costs
 // ~4.5 us here whatever it does, so the scan stays in the fallback launch, which also writes the optional reduction.)
-#ifndef E2E_F2_MINW                 // (both overridable for tools/diag occupancy experiments)
-#define E2E_F2_MINW 2
-#endif
-#define E2E_F2_MINW4 (E2E_F2_HALF ? 3 : E2E_F2_MINW)     // four pairs per lane: three waves per SIMD with half the alpha rows kept
-#ifndef E2E_F2_MINW2                // two pairs per lane: 134 registers by themselves = three waves per SIMD; held to 128 (five spilled, 24 bytes
-#define E2E_F2_MINW2 4              // of scratch) four fit -- round 6: B=256, T=1000, S<=100 111.3 -> 102.8 us per call, the compact lattice of
-#endif                              // configs[4] (B=512, T=256, 65 columns) 78.5 -> 75.6
+
+constexpr int kSegMinWaves = 2;     // waves per SIMD the segment kernel is held to
+constexpr int kSegMinWaves2 = 4;    // two pairs per lane: 134 registers by themselves = three waves per SIMD; held to 128 (five
+                                    // spilled, 24 bytes of scratch) four fit -- round 6: B=256, T=1000, S<=100 111.3 -> 102.8 us
+                                    // per call, the compact lattice of configs[4] (B=512, T=256, 65 columns) 78.5 -> 75.6
 // (eight pairs per lane: 16 alpha rows of 16 cells are 256 registers by themselves -- one wave per SIMD, no spills)
 template <int PPL, bool O16, bool BIG = false>
-__global__ E2E_KERNEL_ALIGN __launch_bounds__(64 * E2E_F2_WPB, PPL == 8 ? 1 : PPL == 4 ? E2E_F2_MINW4 : PPL == 2 ? E2E_F2_MINW2 : E2E_F2_MINW) void ctc_fast_segment_kernel(FastParams p) {
+__global__ E2E_KERNEL_ALIGN __launch_bounds__(64, PPL == 8 ? 1 : PPL == 2 ? kSegMinWaves2 : kSegMinWaves) void ctc_fast_segment_kernel(FastParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   SegParams<O16, BIG> q;
   static_cast<FastParams&>(q) = p;
@@ -1772,8 +1711,7 @@ __global__ E2E_KERNEL_ALIGN __launch_bounds__(64 * E2E_F2_WPB, PPL == 8 ? 1 : PP
 // the segment kernel behind a chain kernel: the instance of the gradient's element width
 template <int PPL, bool BIG = false>
 int launch_segments(const FastParams& p, size_t lds, hipStream_t stream) {
-  const dim3 grid((p.NS + E2E_F2_WPB - 1) / E2E_F2_WPB, p.B), block(64 * E2E_F2_WPB);
-  if (E2E_F2_WPB > 1) lds = ((lds + 15) & ~(size_t)15) * E2E_F2_WPB;
+  const dim3 grid(p.NS, p.B), block(64);
   if constexpr (BIG) {
     if (dtype_is_16bit(p.xdt)) hipLaunchKernelGGL((ctc_fast_segment_kernel<PPL, true, true>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((ctc_fast_segment_kernel<PPL, false, true>), grid, block, lds, stream, p);
@@ -1794,93 +1732,83 @@ int launch_segments(const FastParams& p, size_t lds, hipStream_t stream) {
 // requested one segment ahead by LDS-DMA (global_load_lds, no destination registers) and a counted vmcnt wait that lets the
 // gradient stores drain under the next segment -- were built, parity-green, and measured: 137 against 131 us per step.  The
 // one-segment waves already overlap each other's load latency and store tails; a register prefetch spills (tried twice).)
-// targets of 256..447 labels: the halo chains on four waves per direction, the segment kernel with eight pairs per lane
-// ... over the f32 ring and the probability table of the wide-row form (ChainF64LW) where the alphabet asks for it -- or where the
-// f64 ring of ChainF64L on its sixteen waves does not fit the LDS (73..96 columns: 170..192 KB; until round 5 such a call failed
-// with "hipFuncSetAttribute: invalid argument")
-bool long_wide_rows(int V) { return V > kMaxSmallV || HfLds::of<ChainF64L>(V).total > 160 * 1024; }
-int launch_fast_long(const FastParams& p, hipStream_t stream) {
-  if (long_wide_rows(p.V)) {       // the wide-row form (see ChainF64LW)
-    hipLaunchKernelGGL(ctc_fast_prob_kernel<(kMaxHugeV + 63) / 64>, dim3((unsigned)(((int64_t)p.B * p.T + 4 * kProbRows - 1) / (4 * kProbRows))), dim3(256), 0, stream, p);
-    E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_prob_kernel launch");
-    const HfLds hl = HfLds::of<ChainF64LW>(p.V);
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_hf_kernel<8, ChainF64LW>), hl.total), "hipFuncSetAttribute");
-    hipLaunchKernelGGL((ctc_fast_chain_hf_kernel<8, ChainF64LW>), dim3(p.B), dim3(ChainF64LW::kWaves * 64), hl.total, stream, p);
-    E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_chain_hf_kernel launch");
-    return launch_segments<8, true>(p, F2Lds<8>::bytes(p.V), stream);
-  }
-  const HfLds hl = HfLds::of<ChainF64L>(p.V);
-  E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_hf_kernel<8, ChainF64L>), hl.total), "hipFuncSetAttribute");
-  hipLaunchKernelGGL((ctc_fast_chain_hf_kernel<8, ChainF64L>), dim3(p.B), dim3(ChainF64L::kWaves * 64), hl.total, stream, p);
-  E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_chain_hf_kernel launch");
-  return launch_segments<8>(p, F2Lds<8>::bytes(p.V), stream);
+
+// one workgroup per utterance, its dynamic LDS allowed first
+int launch_chains(const Chains& c, const FastParams& p, hipStream_t stream) {
+  E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(c.kernel), (int)c.lds), "hipFuncSetAttribute");
+  hipLaunchKernelGGL(c.kernel, dim3(p.B), dim3(c.threads), c.lds, stream, p);
+  E2E_HIP_CHECK(hipGetLastError(), "chain kernel launch");
+  return E2E_OK;
+}
+template <int PPL, typename X>
+Chains hf_chains(int V) { return Chains{&ctc_fast_chain_hf_kernel<PPL, X>, X::kWaves * 64, (size_t)HfLds::of<X>(V).total}; }
+
+// the probability table of the wide-row forms, NK columns per lane
+template <int NK>
+int launch_probs(const FastParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(ctc_fast_prob_kernel<NK>, dim3((unsigned)(((int64_t)p.B * p.T + 4 * kProbRows - 1) / (4 * kProbRows))), dim3(256), 0, stream, p);
+  E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_prob_kernel launch");
+  return E2E_OK;
 }
 
-constexpr bool kLeanDefault = true;    // (targets of 128..223 labels: 132.4 against 134.2 us per call at the headline shape)
+// eight pairs per lane (targets of 256..447 labels) over the f32 ring and the probability table of the wide-row form
+// (ChainF64LW) where the alphabet asks for it -- or where the f64 ring of ChainF64L on its sixteen waves does not fit the LDS
+// (73..96 columns: 170..192 KB; until round 5 such a call failed with "hipFuncSetAttribute: invalid argument")
+bool long_wide_rows(int V) { return V > kMaxSmallV || HfLds::of<ChainF64L>(V).total > 160 * 1024; }
 
+// A call's chain kernel, then the segment kernel behind it (of the gradient's element width; PPL = ppl_of(V, Smax)).  The
+// first rule that applies picks the chains:
+//   1. wide rows (more than 96 columns; PPL 8: long_wide_rows): the probability table, then ChainF64W (PPL 4) or ChainF64LW
+//      (PPL 8), and the segment kernel's wide-row form;
+//   2. PPL 8: ChainF64L;
+//   3. E2E_F1_F32 set, or f32 chains allowed (e2e_ctc_loss_opts.chains) and PPL 4: ChainF32, rows checked against kZTolF32.
+//      (Only at the widest rows by default: 145 against 165 us per step at S <= 200, but 115 / 93 against 120 / 94 us at
+//      S <= 127 / 63 with looser gradients);
+//   4. E2E_F1_SINGLE unset, PPL 4 or PPL 2 with B <= 256, and h1_supported: the lean halo chains (ctc_loss_fast_h1.hip).
+//      (PPL 4: 132.4 against 134.2 us per call at the headline shape.  PPL 2, round 6: they win while every utterance has a
+//      CU to itself -- B=256, T=1000, S<=100: 108.3 against 116.9 us per call, S<=127: 115.4 against 117.6 -- and lose
+//      beyond, where two workgroups of the single-wave kernel share a CU and one of the lean kernel fills it: B=512, T=256,
+//      S<=64 73.8 against 59.3 us);
+//   5. E2E_F1_SINGLE unset, PPL 4 or E2E_F1_HALO set, and S <= 223: the f64 halo chains, ChainF64.  (158 against 166 us per
+//      step at S <= 200; at S <= 127 the single wave carries two pairs per lane itself and wins, 120 against 131 us);
+//   6. the single-wave chains, whose frame the segment kernel takes from cumA / cumB; their ring is four blocks deep instead
+//      of eight where B > 256 and eight blocks need more than 80 KB of LDS and four do not (eight would keep a second
+//      workgroup off a CU that the batch has work for).
+// E2E_F1_F32 / _SINGLE / _HALO are for the tests: they force kernels onto shapes that the rule gives to others.
 template <int PPL>
 int launch_fast_ppl(const FastParams& p, hipStream_t stream) {
-  if (p.V > kMaxSmallV) {
-    // 97..224 columns: the halo chains over the f32 ring, the segment kernel's wide-row form (fast_supported: PPL == 4 here)
-    if constexpr (PPL == 4) {
-      hipLaunchKernelGGL(ctc_fast_prob_kernel<(kMaxBigV + 63) / 64>, dim3((unsigned)(((int64_t)p.B * p.T + 4 * kProbRows - 1) / (4 * kProbRows))), dim3(256), 0, stream, p);
-      E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_prob_kernel launch");
-      const HfLds hl = HfLds::of<ChainF64W>(p.V);
-      E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_hf_kernel<4, ChainF64W>), hl.total), "hipFuncSetAttribute");
-      hipLaunchKernelGGL((ctc_fast_chain_hf_kernel<4, ChainF64W>), dim3(p.B), dim3(ChainF64W::kWaves * 64), hl.total, stream, p);
-      E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_chain_hf_kernel launch");
-      return launch_segments<4, true>(p, F2Lds<4>::bytes(p.V) + E2E_F2_LDSPAD, stream);
-    } else { set_error("fast CTC path: %d columns need four pairs per lane", p.V); return E2E_ERR_UNSUPPORTED; }
-  }
-  const size_t lds1 = F1Lds::bytes(p.V);
-  E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_kernel<PPL>), (int)lds1), "hipFuncSetAttribute");
-  const size_t lds2 = F2Lds<PPL>::bytes(p.V) + E2E_F2_LDSPAD;
-  // f32 chains: where the caller allows them (e2e_ctc_loss_opts.chains) and they are faster, i.e. at the widest rows
-  // (145 against 165 us per step at S <= 200, but 115 / 93 against 120 / 94 us at S <= 127 / 63, with looser gradients: not
-  // worth it there); E2E_F1_F32=1 forces them everywhere (tests)
-  static const bool force_f32_chains = getenv("E2E_F1_F32") != nullptr;
-  if (force_f32_chains || (p.chains == E2E_CHAINS_F32 && PPL == 4)) {
-    const HfLds hl = HfLds::of<ChainF32>(p.V);
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_hf_kernel<PPL, ChainF32>), hl.total), "hipFuncSetAttribute");
-    hipLaunchKernelGGL((ctc_fast_chain_hf_kernel<PPL, ChainF32>), dim3(p.B), dim3(ChainF32::kWaves * 64), hl.total, stream, p);
-    E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_chain_hf_kernel launch");
-    FastParams q = p; q.ztol = kZTolF32;                          // (trkA / trkB: written by the frame waves)
-    return launch_segments<PPL>(q, lds2, stream);
-  }
-  static const bool force_single = getenv("E2E_F1_SINGLE") != nullptr, force_halo = getenv("E2E_F1_HALO") != nullptr;
-  // the lean halo chains of ctc_loss_fast_h1.hip.  E2E_F1_LEAN=0 / 1: never / wherever they fit (A/B, tests)
-  static const char* lean_env = getenv("E2E_F1_LEAN");
-  const bool no_h1 = lean_env && lean_env[0] == '0', force_h1 = lean_env && lean_env[0] == '1';
-  // (targets of 64..127 labels, round 6: the lean chains win while every utterance has a CU to itself -- B=256, T=1000, S<=100: 108.3
-  //  against 116.9 us per call, S<=127: 115.4 against 117.6 -- and lose beyond, where two workgroups of the single-wave kernel share
-  //  a CU and one of the lean kernel fills it: B=512, T=256, S<=64 73.8 against 59.3 us; tools/diag/lean_ab.sh)
-  const bool lean_pays = PPL == 4 || (PPL == 2 && p.B <= 256);
-  if (!no_h1 && !force_single && (kLeanDefault ? lean_pays || force_h1 : force_h1) && h1_supported(p.V, p.Smax, PPL)) {
-    const int rc = launch_fast_h1_chain(p, PPL, stream);
+  static const bool force_f32 = getenv("E2E_F1_F32") != nullptr, force_single = getenv("E2E_F1_SINGLE") != nullptr,
+                    force_halo = getenv("E2E_F1_HALO") != nullptr;
+  const bool wide = PPL == 8 ? long_wide_rows(p.V) : p.V > kMaxSmallV;
+  FastParams q = p;                                                // the segment kernel's parameters
+  Chains c;
+  if (wide) {
+    int rc;
+    if constexpr (PPL == 4) { rc = launch_probs<(kMaxBigV + 63) / 64>(p, stream); c = hf_chains<4, ChainF64W>(p.V); }
+    else if constexpr (PPL == 8) { rc = launch_probs<(kMaxHugeV + 63) / 64>(p, stream); c = hf_chains<8, ChainF64LW>(p.V); }
+    else { set_error("fast CTC path: %d columns need four pairs per lane", p.V); return E2E_ERR_UNSUPPORTED; }
     if (rc != E2E_OK) return rc;
-    return launch_segments<PPL>(p, lds2, stream);
+  } else if constexpr (PPL == 8) {
+    c = hf_chains<8, ChainF64L>(p.V);
+  } else if (force_f32 || (p.chains == E2E_CHAINS_F32 && PPL == 4)) {
+    c = hf_chains<PPL, ChainF32>(p.V);
+    q.ztol = kZTolF32;
+  } else if (!force_single && (PPL == 4 || (PPL == 2 && p.B <= 256)) && h1_supported(p.V, p.Smax, PPL)) {
+    c = h1_chains(PPL, p.V);
+  } else if (!force_single && (PPL == 4 || force_halo) && p.Smax + 1 <= ChainF64::kMaxW * kHfOwn) {
+    c = hf_chains<PPL, ChainF64>(p.V);
+  } else {
+    const size_t lds8 = F1Lds::bytes(p.V), lds4 = F1Lds::bytes(p.V, 4);
+    if (p.B > 256 && lds8 > 80 * 1024 && lds4 <= 80 * 1024) c = Chains{&ctc_fast_chain_kernel<PPL, 4>, 512, lds4};
+    else c = Chains{&ctc_fast_chain_kernel<PPL>, 512, lds8};
+    q.trkA = p.cumA; q.trkB = p.cumB;
   }
-  // f64 halo chains: two waves per direction hold 224 label pairs.  Where they win: the widest rows (158 against 166 us per
-  // step at S <= 200; at S <= 127 the single wave carries two pairs per lane itself and wins, 120 against 131 us).
-  // E2E_F1_SINGLE=1: the single-wave chains everywhere, E2E_F1_HALO=1: the halo chains wherever they fit (A/B, tests)
-  if (!force_single && (PPL == 4 || (force_halo && PPL >= 1)) && p.Smax + 1 <= ChainF64::kMaxW * kHfOwn) {
-    const HfLds hl = HfLds::of<ChainF64>(p.V);
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_hf_kernel<PPL, ChainF64>), hl.total), "hipFuncSetAttribute");
-    hipLaunchKernelGGL((ctc_fast_chain_hf_kernel<PPL, ChainF64>), dim3(p.B), dim3(ChainF64::kWaves * 64), hl.total, stream, p);
-    E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_chain_hf_kernel launch");
-    return launch_segments<PPL>(p, lds2, stream);
+  const int rc = launch_chains(c, p, stream);
+  if (rc != E2E_OK) return rc;
+  if constexpr (PPL >= 4) {
+    if (wide) return launch_segments<PPL, true>(q, F2Lds<PPL>::bytes(p.V), stream);
   }
-  // (the ring at half its depth where the full one keeps a second workgroup off a CU that the batch has work for)
-  static const char* rb_env = getenv("E2E_F1_RING");               // (A/B: 4 / 8 forces the depth)
-  const bool shallow = rb_env ? rb_env[0] == '4' : (p.B > 256 && lds1 > 80 * 1024 && F1Lds::bytes(p.V, 4) <= 80 * 1024);
-  if (shallow) {
-    const size_t lds4 = F1Lds::bytes(p.V, 4);
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&ctc_fast_chain_kernel<PPL, 4>), (int)lds4), "hipFuncSetAttribute");
-    hipLaunchKernelGGL((ctc_fast_chain_kernel<PPL, 4>), dim3(p.B), dim3(512), lds4, stream, p);
-  } else hipLaunchKernelGGL(ctc_fast_chain_kernel<PPL>, dim3(p.B), dim3(512), lds1, stream, p);
-  E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_chain_kernel launch");
-  FastParams q = p; q.trkA = p.cumA; q.trkB = p.cumB;          // (its frame follows the maximum itself)
-  return launch_segments<PPL>(q, lds2, stream);
+  return launch_segments<PPL>(q, F2Lds<PPL>::bytes(p.V), stream);
 }
 
 int ppl_for(int Smax) {
@@ -1983,7 +1911,7 @@ int launch_fast(const LossArgs& a, bool fallback_to_exact) {
     case 1: rc = launch_fast_ppl<1>(p, a.stream); break;
     case 2: rc = launch_fast_ppl<2>(p, a.stream); break;
     case 4: rc = launch_fast_ppl<4>(p, a.stream); break;
-    case 8: rc = launch_fast_long(p, a.stream); break;
+    case 8: rc = launch_fast_ppl<8>(p, a.stream); break;
     default: set_error("fast CTC path: Smax=%d too long", a.Smax); return E2E_ERR_UNSUPPORTED;
   }
   if (rc != E2E_OK) return rc;
@@ -2024,15 +1952,18 @@ extern "C" int e2e_debug_fast_profile(unsigned long long* host, int n) {
 }
 #endif
 
-// Diagnostics (not part of include/e2e_ctc.h): copy the fast path's per-utterance flag words and both log Z
-// values out of a workspace that the last e2e_ctc_loss_fwd_bwd(ALGO_FAST/AUTO) call used.  Synchronises.
+// Diagnostics (not part of include/e2e_ctc.h) that read what the last e2e_ctc_loss_fwd_bwd(ALGO_FAST/AUTO) call left in its
+// workspace: the workspace as that call aligned it and the fast path's layout of it, once the device is idle.
+static int debug_workspace(const void* workspace, int B, int T, int V, int Smax, const char*& ws, e2e::FastLayout& l) {
+  ws = reinterpret_cast<const char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+  l = e2e::fast_layout(B, T, V, Smax);
+  return hipDeviceSynchronize() == hipSuccess ? E2E_OK : E2E_ERR_HIP;
+}
 // Diagnostics: how many flagged utterances of the last AUTO call the f64 redo of the segments could NOT settle (they were
 // recomputed by the exact kernel: ~7 ms for a batch instead of ~1).  Synchronises.
 extern "C" int e2e_debug_fast_redo_failures(const void* workspace, int B, int T, int V, int Smax, int* count_host) {
-  uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
-  const e2e::FastLayout l = e2e::fast_layout(B, T, V, Smax);
-  if (hipDeviceSynchronize() != hipSuccess) return E2E_ERR_HIP;
+  const char* ws; e2e::FastLayout l;
+  if (debug_workspace(workspace, B, T, V, Smax, ws, l) != E2E_OK) return E2E_ERR_HIP;
   int ctl[4];
   if (hipMemcpy(ctl, ws + l.ctl, sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
   *count_host = ctl[1];
@@ -2042,10 +1973,8 @@ extern "C" int e2e_debug_fast_redo_failures(const void* workspace, int B, int T,
 // redos of single segments, of the wait for the other workgroups, of its extended-range chains, of its extended-range segments,
 // and the end of the launch's last workgroup.  Zeros if nothing was flagged.  Synchronises.
 extern "C" int e2e_debug_flagged_phases(const void* workspace, int B, int T, int V, int Smax, double* us_host) {
-  uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
-  const e2e::FastLayout l = e2e::fast_layout(B, T, V, Smax);
-  if (hipDeviceSynchronize() != hipSuccess) return E2E_ERR_HIP;
+  const char* ws; e2e::FastLayout l;
+  if (debug_workspace(workspace, B, T, V, Smax, ws, l) != E2E_OK) return E2E_ERR_HIP;
   unsigned long long st[8];
   if (hipMemcpy(st, ws + l.ctl + 64, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
   for (int k = 1; k <= 4; k++) us_host[k - 1] = st[0] && st[k] ? (double)(long long)(st[k] - st[0]) * 0.01 : 0.0;
@@ -2057,20 +1986,17 @@ extern "C" int e2e_debug_flagged_phases(const void* workspace, int B, int T, int
 // segment for its utterance's chains -- what they left undone was recomputed by the exact kernel) and redos of single segments
 // that failed (ctl[5]).  Both 0 on an idle GPU.  Synchronises.
 extern "C" int e2e_debug_flagged_counters(const void* workspace, int B, int T, int V, int Smax, int* timeouts_host, int* failed_redos_host) {
-  uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
-  const e2e::FastLayout l = e2e::fast_layout(B, T, V, Smax);
-  if (hipDeviceSynchronize() != hipSuccess) return E2E_ERR_HIP;
+  const char* ws; e2e::FastLayout l;
+  if (debug_workspace(workspace, B, T, V, Smax, ws, l) != E2E_OK) return E2E_ERR_HIP;
   int ctl[8];
   if (hipMemcpy(ctl, ws + l.ctl, sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
   *timeouts_host = ctl[4]; *failed_redos_host = ctl[5];
   return E2E_OK;
 }
+// Diagnostics: the fast path's per-utterance flag words and both log Z values.  Synchronises.
 extern "C" int e2e_debug_fast_state(const void* workspace, int B, int T, int V, int Smax, int* flags_host, double* logz_host) {
-  uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
-  const e2e::FastLayout l = e2e::fast_layout(B, T, V, Smax);
-  if (hipDeviceSynchronize() != hipSuccess) return E2E_ERR_HIP;
+  const char* ws; e2e::FastLayout l;
+  if (debug_workspace(workspace, B, T, V, Smax, ws, l) != E2E_OK) return E2E_ERR_HIP;
   if (hipMemcpy(flags_host, ws + l.flags, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
   if (hipMemcpy(logz_host, ws + l.logz, sizeof(double) * 2 * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
   return E2E_OK;

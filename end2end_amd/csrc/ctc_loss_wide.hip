@@ -21,10 +21,7 @@
 namespace e2e {
 namespace {
 
-#ifndef E2E_WIDE_KWAVES
-#define E2E_WIDE_KWAVES 4
-#endif
-constexpr int kWaves = E2E_WIDE_KWAVES;      // frames per workgroup (round 6, one process, B=512 T=256 V=8000: 1 / 2 / 4 / 8 frames -> f32 1825 / 1761 / 1715 / 1726 us,
+constexpr int kWaves = 4;                    // frames per workgroup (round 6, one process, B=512 T=256 V=8000: 1 / 2 / 4 / 8 frames -> f32 1825 / 1761 / 1715 / 1726 us,
                                              //  bf16 982 / 956 / 946 / 1049 us per call)
 
 struct WideParams {
@@ -50,24 +47,15 @@ __device__ __forceinline__ float exp_acc(float x) {        // ~1 ulp, x <= ~88
   return ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
 }
 
-// exp(x) for x <= 0 where 1e-6 relative is plenty (the dense rows' exp(x - max): the result is a probability <= 1 that ends up in
-// a gradient held to 2e-6 absolute, or in a 16-bit number): the product's rounding, |x| log2(e) 2^-24, is the whole error.
-// Two instructions instead of exp_acc's eight.  What it buys, in one process (tools/diag/ab_time.py, B=512, T=256, V=8000): nothing for f32
-// and bf16 rows (1740 / 985 us per call either way: those kernels wait for HBM) and 1535 -> 995 us for f16 rows, whose kernel no longer
-// spills (86 registers instead of 168 + 41 spilled).
-#ifndef E2E_WIDE_FAST_EXP
-#define E2E_WIDE_FAST_EXP 1
-#endif
-// exp(x - M) with mM = -M log2(e) worked out once per row: one multiply-add and v_exp_f32 (exp2(-inf) = 0: padding lanes need no clamp;
-// the rounding of mM is common to the whole row and cancels in the normalisation)
-__device__ __forceinline__ float exp_row(float x, float M, float mM) {
-#if E2E_WIDE_FAST_EXP
-  (void)M;
+// exp(x - M) for x <= M where 1e-6 relative is plenty (the dense rows' exp(x - max): the result is a probability <= 1 that ends up
+// in a gradient held to 2e-6 absolute, or in a 16-bit number): the product's rounding, |x| log2(e) 2^-24, is the whole error.
+// With mM = -M log2(e) worked out once per row: one multiply-add and v_exp_f32 (exp2(-inf) = 0: padding lanes need no clamp; the
+// rounding of mM is common to the whole row and cancels in the normalisation).  Two instructions instead of exp_acc's eight.  What
+// it buys against exp_acc(x - M), in one process (tools/diag/ab_time.py, B=512, T=256, V=8000): nothing for f32 and bf16 rows
+// (1740 / 985 us per call either way: those kernels wait for HBM) and 1535 -> 995 us for f16 rows, whose kernel no longer spills
+// (86 registers instead of 168 + 41 spilled).
+__device__ __forceinline__ float exp_row(float x, float mM) {
   return __builtin_amdgcn_exp2f(fmaf(x, 1.44269504088896340736f, mM));
-#else
-  (void)mM;
-  return exp_acc(x - M);
-#endif
 }
 
 __device__ __forceinline__ float wave_max_f(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64)); return v; }
@@ -315,23 +303,10 @@ typedef float vf4 __attribute__((ext_vector_type(4)));
 // E: the logits' (and the gradient's) element type -- float, or f16_t / bf16_t read and written 16 bytes (8 elements) at a
 // time and converted in registers: 2*V*sizeof(E) bytes per frame.  NV4: float4-equivalents of registers per lane, rows of
 // up to 256*NV4 columns either way.
-// Cache policy of the dense row kernels (bit 0: non-temporal loads, bit 1: non-temporal stores).  Round 6, one process, B=512, T=256,
-// V=8000 (tools/diag/ab_time.py): both non-temporal -- the form until then -- f32 1743 / bf16 990 us per call; neither 1859 / 1037;
-// loads only 2007 / 1162; **stores only 1663 / 912**.  The row is read once, but not only once: the wave's tail gathers the
-// utterance's <= S+1 label columns out of it, and behind a non-temporal load those are a second trip to HBM instead of an L2 hit.
-#ifndef E2E_WIDE_NT
-#define E2E_WIDE_NT 2
-#endif
-#if E2E_WIDE_NT & 1
-#define DENSE_LD(p) __builtin_nontemporal_load(p)
-#else
-#define DENSE_LD(p) (*(p))
-#endif
-#if E2E_WIDE_NT & 2
-#define DENSE_ST(v, p) __builtin_nontemporal_store(v, p)
-#else
-#define DENSE_ST(v, p) (*(p) = (v))
-#endif
+// Cache policy of the dense row kernels: plain loads, non-temporal stores.  Round 6, one process, B=512, T=256, V=8000
+// (tools/diag/ab_time.py): both non-temporal -- the form until then -- f32 1743 / bf16 990 us per call; neither 1859 / 1037; loads
+// only 2007 / 1162; **stores only 1663 / 912**.  The row is read once, but not only once: the wave's tail gathers the utterance's
+// <= S+1 label columns out of it, and behind a non-temporal load those are a second trip to HBM instead of an L2 hit.
 template <int NV4, typename E>
 __device__ __forceinline__ void wide_rows_dense_body(const WideParams& p) {
   constexpr int EPC = 16 / (int)sizeof(E);            // elements per 16-byte chunk
@@ -358,7 +333,7 @@ __device__ __forceinline__ void wide_rows_dense_body(const WideParams& p) {
 #pragma unroll
     for (int e = 0; e < EPC; e++) of[e] = f;
     const ev o = __builtin_convertvector(of, ev);
-    for (int i = lane; i < n4; i += 64) DENSE_ST(o, &g4[i]);
+    for (int i = lane; i < n4; i += 64) __builtin_nontemporal_store(o, &g4[i]);
     return;
   }
   const float ninf = -__builtin_huge_valf();
@@ -383,8 +358,8 @@ __device__ __forceinline__ void wide_rows_dense_body(const WideParams& p) {
   auto to_held = [](const fv& f) -> held { if constexpr (PACKED) return __builtin_convertvector(f, ev); else return f; };
 #pragma unroll
   for (int u = 0; u < NCH; u++) {
-    if (64 * u + 64 <= n4) { const ev r = DENSE_LD(&x4[64 * u + lane]); if constexpr (PACKED) v[u] = r; else v[u] = __builtin_convertvector(r, fv); }
-    else if (64 * u < n4) { const ev r = DENSE_LD(&x4[part_idx]); if constexpr (PACKED) v[u] = r; else v[u] = __builtin_convertvector(r, fv); }
+    if (64 * u + 64 <= n4) { const ev r = x4[64 * u + lane]; if constexpr (PACKED) v[u] = r; else v[u] = __builtin_convertvector(r, fv); }
+    else if (64 * u < n4) { const ev r = x4[part_idx]; if constexpr (PACKED) v[u] = r; else v[u] = __builtin_convertvector(r, fv); }
     else {
       fv none;
 #pragma unroll
@@ -409,7 +384,7 @@ __device__ __forceinline__ void wide_rows_dense_body(const WideParams& p) {
         fv f = as_f32(v[u]);
         float part = 0.f;
 #pragma unroll
-        for (int e = 0; e < EPC; e++) { f[e] = exp_row(f[e], M, mM); part += f[e]; }
+        for (int e = 0; e < EPC; e++) { f[e] = exp_row(f[e], mM); part += f[e]; }
         v[u] = to_held(f * kHeld);
         sum += (64 * u + 64 <= n4 || part_in) ? part : 0.f;
       }
@@ -421,8 +396,8 @@ __device__ __forceinline__ void wide_rows_dense_body(const WideParams& p) {
     lse = M + logf(sum);
 #pragma unroll
     for (int u = 0; u < NCH; u++) {
-      if (64 * u + 64 <= n4) DENSE_ST(__builtin_convertvector(as_f32(v[u]) * invg, ev), &g4[64 * u + lane]);
-      else if (64 * u < n4) DENSE_ST(__builtin_convertvector(as_f32(v[u]) * invg, ev), &g4[part_idx]);
+      if (64 * u + 64 <= n4) __builtin_nontemporal_store(__builtin_convertvector(as_f32(v[u]) * invg, ev), &g4[64 * u + lane]);
+      else if (64 * u < n4) __builtin_nontemporal_store(__builtin_convertvector(as_f32(v[u]) * invg, ev), &g4[part_idx]);
       if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
     if (lane == 0) p.lse[row] = lse;
@@ -434,8 +409,8 @@ __device__ __forceinline__ void wide_rows_dense_body(const WideParams& p) {
         fv o;
 #pragma unroll
         for (int e = 0; e < EPC; e++) o[e] = exp_acc(f[e]);
-        if (64 * u + 64 <= n4) DENSE_ST(__builtin_convertvector(o * p.gscale, ev), &g4[64 * u + lane]);
-        else DENSE_ST(__builtin_convertvector(o * p.gscale, ev), &g4[part_idx]);
+        if (64 * u + 64 <= n4) __builtin_nontemporal_store(__builtin_convertvector(o * p.gscale, ev), &g4[64 * u + lane]);
+        else __builtin_nontemporal_store(__builtin_convertvector(o * p.gscale, ev), &g4[part_idx]);
       }
       if (u & 1) __builtin_amdgcn_sched_barrier(0);
     }

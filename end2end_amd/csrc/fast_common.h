@@ -1,5 +1,5 @@
 // Device code shared by the translation units of the fast CTC path (ctc_loss_fast.hip: single-wave and two-pairs-per-lane
-// chains, segment kernel, launchers; ctc_loss_fast_h1.hip: the one-pair-per-lane chain kernel).  The kernels live in separate
+// chains, segment kernel, launchers; ctc_loss_fast_h1.hip: the lean halo chain kernel).  The kernels live in separate
 // translation units -- i.e. separate code objects -- on purpose: see the note on code placement in DESIGN.md 4.1.
 #pragma once
 #include <stdlib.h>
@@ -13,9 +13,7 @@
 // Every kernel of the fast path starts on a 64 KB boundary of its code object: where a kernel's code lies relative to such
 // boundaries changes its speed by integer factors (the segment kernel: 61 -> 401 us when another kernel's growth moved it
 // across one), and with the alignment pinned no kernel's placement depends on its neighbours' sizes.
-#ifndef E2E_KERNEL_ALIGN
 #define E2E_KERNEL_ALIGN __attribute__((aligned(65536)))
-#endif
 
 namespace e2e {
 namespace fastk {
@@ -751,9 +749,12 @@ __device__ __forceinline__ void halo_frame_wave(const FastParams& p, int b, int 
 }
 
 
-// the one-pair-per-lane chain kernel (ctc_loss_fast_h1.hip); h1_supported: whether it takes the shape
+// a chain kernel's launch: one workgroup of `threads` per utterance, `lds` bytes of dynamic LDS
+struct Chains { void (*kernel)(FastParams); int threads; size_t lds; };
+
+// the lean halo chain kernel (ctc_loss_fast_h1.hip); h1_supported: whether it takes the shape
 bool h1_supported(int V, int Smax, int ppl);
-int launch_fast_h1_chain(const FastParams& p, int ppl, hipStream_t stream);      // (the caller launches the segment kernel behind it)
+Chains h1_chains(int ppl, int V);
 
 }  // namespace fastk
 }  // namespace e2e

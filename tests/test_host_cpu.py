@@ -70,6 +70,42 @@ def test_no_kernel_copies_its_parameter_block_to_scratch():
     assert not bad, "kernels that spill a block of state at their entry (dwords stored to scratch, scratch loads): %s" % bad
 
 
+def test_native_sources_have_no_build_or_environment_switches():
+    """One path per shape: no preprocessor switch or environment variable in end2end_amd/csrc selects alternative code.  An A/B
+    experiment lives on a branch (tools/diag/build_variant.sh, ab_time.py) and is not merged.  What may stay: include guards,
+    the two instrumented builds, and the environment variables the tests use to force a kernel onto a shape the dispatch gives
+    to another (E2E_F1_F32 / _SINGLE / _HALO, E2E_BEAM_GENERAL) or to see the n-gram tables' diagnostics (E2E_LM_DEBUG)."""
+    profile_builds = {"E2E_FAST_PROFILE", "E2E_BEAM_PROFILE"}
+    kept_env = {"E2E_F1_F32", "E2E_F1_SINGLE", "E2E_F1_HALO", "E2E_BEAM_GENERAL", "E2E_LM_DEBUG"}
+    csrc = os.path.join(ROOT, "end2end_amd", "csrc")
+    conds, envs, sources = [], set(), 0
+    for dirpath, _, files in os.walk(csrc):
+        for f in sorted(files):
+            if not f.endswith((".hip", ".h", ".hpp", ".cpp", ".cc", ".c")):
+                continue
+            sources += 1
+            rel = os.path.relpath(os.path.join(dirpath, f), ROOT)
+            text = open(os.path.join(dirpath, f)).read()
+            lines = text.splitlines()
+            for i, line in enumerate(lines):
+                m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*)", line)
+                if not m:
+                    continue
+                cond = re.sub(r"/\*.*?\*/", "", m.group(2).split("//")[0]).strip()
+                name = re.sub(r"^defined\s*\(?\s*(\w+)\s*\)?$", r"\1", cond) if m.group(1) == "if" else cond
+                guard = (m.group(1) == "ifndef" and i + 1 < len(lines)
+                         and re.fullmatch(r"\s*#\s*define\s+%s\s*" % re.escape(cond), lines[i + 1]) is not None)
+                if not guard and name not in profile_builds:
+                    conds.append("%s:%d: %s" % (rel, i + 1, line.strip()))
+            code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+            for m in re.finditer(r"getenv\s*\(\s*([^)]*)\)", code):
+                lit = re.fullmatch(r'"([^"]*)"', m.group(1).strip())
+                envs.add(lit.group(1) if lit else "<not a literal: %s in %s>" % (m.group(1).strip(), rel))
+    assert sources >= 8, "found only %d native sources under %s" % (sources, csrc)
+    assert not conds, "preprocessor conditions other than include guards and %s:\n%s" % (sorted(profile_builds), "\n".join(conds))
+    assert envs <= kept_env, "environment variables read beyond %s: %s" % (sorted(kept_env), sorted(envs - kept_env))
+
+
 def test_pybind_layer_loads_and_reports_errors():
     from end2end_amd import _C, _runtime
     assert _C.abi_version() == _C.ABI_VERSION == _runtime.ABI_VERSION

@@ -1,6 +1,6 @@
 #!/bin/bash
 # builds the instrumented variant of the library (-DE2E_FAST_PROFILE -DE2E_BEAM_PROFILE) as build/diag/prof_lib.so (or
-# build/diag/$PROF_OUT); E2E_EXTRA_DEFS adds -D options (e.g. -DE2E_ZTOL=1e9 switches the segment self-check off);
+# build/diag/$PROF_OUT); E2E_EXTRA_DEFS adds -D options (a switch of an experiment's branch);
 # PROF_FILES limits the sources compiled with the options to the listed ones (the others come from the regular build)
 set -e
 cd "$(dirname "$0")/../../end2end_amd/csrc"; mkdir -p ../../build/diag

@@ -1,5 +1,5 @@
-# per-wave cycle accounts of the one-pair-per-lane chain kernel (instrumented library: tools/diag/build_profile_lib.sh).
-# Classes: waves per direction = min(S // 56 + 1, 4).
+# per-wave cycle accounts of the lean halo chain kernel (instrumented library: tools/diag/build_profile_lib.sh).
+# Classes: waves per direction = min(S // 112 + 1, 2).
 import sys, ctypes as C, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -23,9 +23,9 @@ for it in range(3):
 torch.cuda.synchronize()
 assert L.e2e_debug_fast_profile3_h1(buf, 0) == 0
 a = np.array(buf[:], dtype=np.float64).reshape(256, 2, 8, 4)
-tlc = tl.cpu().numpy(); NPL = 1 if os.environ.get("E2E_F1_NP", "2") == "1" else 2
-for W in range(1, 6):
-    sel = np.minimum(tlc // (56 * NPL) + 1, 4 // NPL) == W
+tlc = tl.cpu().numpy()
+for W in range(1, 3):
+    sel = np.minimum(tlc // 112 + 1, 2) == W
     if not sel.any(): continue
     print("utterances with %d waves per direction: %d" % (W, sel.sum()))
     for dname, dd in (("alpha", 0), ("beta", 1)):

@@ -1,4 +1,4 @@
-"""Time beam 100 with the synthetic 3-gram at BASELINE configs[3] (B=64, T=1500, V=29); E2E_LM_TWO_ROUNDS=1: the id-keyed lookup."""
+"""Time beam 100 with the synthetic 3-gram at BASELINE configs[3] (B=64, T=1500, V=29)."""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -18,4 +18,4 @@ with tempfile.TemporaryDirectory() as td:
     for _ in range(3):
         t0 = time.perf_counter(); r = eng.decode(x, xl); torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
     dt = min(ts)
-    print("two_rounds=%s: %.1f ms, %.0f utt/s [%s]" % (os.environ.get("E2E_LM_TWO_ROUNDS", "0"), dt * 1e3, 64 / dt, r[2][0][:40]))
+    print("%.1f ms, %.0f utt/s [%s]" % (dt * 1e3, 64 / dt, r[2][0][:40]))
