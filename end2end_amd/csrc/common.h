@@ -39,6 +39,16 @@ int hip_fail(hipError_t e, const char* what);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+__device__ __forceinline__ double ninf() { return -__builtin_huge_val(); }
+
+// the reference's two-argument log-sum-exp, src/utils/math_utils.h:8-16 (log(1.0 + x), not log1p)
+__device__ __forceinline__ double lse2(double a, double b) {
+  if (a == ninf()) return b;
+  if (b == ninf()) return a;
+  if (a > b) return a + log(1.0 + exp(b - a));
+  return b + log(1.0 + exp(a - b));
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize = `bytes` for kernel `fn`, raised when a launch needs more than the largest size asked for so far per (kernel, device) --
 // not on every launch: a host call that an entry point meant to be captured into a graph should not repeat.  Returns a hipError_t.
 hipError_t allow_dynamic_lds(const void* fn, int bytes);

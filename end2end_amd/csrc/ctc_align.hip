@@ -28,8 +28,6 @@ struct AlignParams {
   unsigned char* bp;       // [B][T][Lpad]
 };
 
-__device__ __forceinline__ double ninf() { return -__builtin_huge_val(); }
-
 template <typename IO>
 __global__ __launch_bounds__(kThreads) void ctc_align_kernel(AlignParams p) {
   extern __shared__ __align__(16) unsigned char smem[];

@@ -25,418 +25,15 @@
 // destroyed at once, so this is equivalent and saves ~W*V allocations, LM-state writes and frees per step.
 //
 // The language model stands where KenLM stands upstream (src/decoders/ctc_decoder.cpp:60-71,77-88,264-308):
-// host-side ARPA reader (plain or gzip), device-resident open-addressing tables, standard back-off scoring.  A beam
+// host-side ARPA reader (plain or gzip, ctc_lm.hip), device-resident open-addressing tables (ctc_lm.h), standard back-off
+// scoring.  A beam
 // member's V answers are looked up once per LM state when it enters the beam and kept in LDS (see lm_query).
-#include <zlib.h>
-
-#include <algorithm>
-#include <cctype>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
 #include <stdlib.h>
 
-#include "common.h"
-
-namespace e2e {
-
-constexpr int kLmMaxOrder = 6;     // KENLM_MAX_ORDER=6, CMakeLists.txt:36
-constexpr int kCtx = kLmMaxOrder - 1;
-
-struct NgSlot { uint32_t ids[kLmMaxOrder]; int32_t n; float prob; float backoff; };
-// The same tables in the form the kernel probes: one 16-byte load per probe, matched by the n-gram's 64-bit hash
-// (the loader checks that no two n-grams of the model share one; a queried n-gram that is NOT in the model would have
-// to collide in all 64 bits with the entry at its probe position to be mistaken for it).
-struct NgSig {                                                   // sig 0: empty
-  uint64_t sig; float prob; float backoff;
-  // second half, read for CONTEXT lookups only: one bit per continuation word of this n-gram (bit cont_bit(w) is set if the
-  // model lists (this n-gram, w)).  A query's longer n-grams are only looked up when their context says they may exist:
-  // what a beam step asks is bound by the number of distinct cache lines its waves touch, and for most
-  // (context, word) pairs a beam search tries there is no such n-gram.  No false negatives; contexts with many
-  // continuations fill their 64 bits and every lookup is made, as before.
-  uint64_t cont; uint64_t pad;
-};
-// Unigrams are not hashed at all: one 16-byte entry per word id (prob > 0: the model has no such unigram).  A few hundred
-// KB that stay in L2, where the hashed table (megabytes, one slot per random line) is a trip past it for every probe.
-struct UniEntry { float prob; float backoff; uint64_t cont; };
-__host__ __device__ inline int cont_bit(uint32_t w) { return (int)(((uint64_t)w * 0x9E3779B97F4A7C15ULL) >> 58); }
-struct VEntry { uint64_t key; uint32_t val; float prob; };       // key 0: empty; prob: the word's unigram log10 p (> 0: none listed)
-// The kernel's vocabulary table is a TWO-CHOICE (cuckoo) table: a spelling sits in one of the two slots its hash names, so a
-// probe is two loads issued together and never a second round (with linear probing the slowest of a wave's 64 lanes needed
-// three).  It is small -- 64 bytes per word -- and stays in L2, where a second line per probe is cheap.  (The n-gram table
-// keeps linear probing: since the continuation bits its probes are rare or shared by a state's characters.)
-__host__ __device__ inline void two_slots(uint64_t h, uint32_t mask, uint32_t& i1, uint32_t& i2) {
-  // (the second slot from a re-mixed hash: bits 32.. of an FNV hash of a short spelling are far from uniform -- 7 191
-  //  distinct values for the bench model's 10 003 words -- and cuckoo insertion then fails)
-  i1 = (uint32_t)h & mask; i2 = (uint32_t)((h * 0x9E3779B97F4A7C15ULL) >> 32) & mask;
-  if (i2 == i1) i2 = i1 ^ 1u;
-}
-
-struct LmView {                    // what the kernel sees (device pointers) / what the host scorer sees
-  int order;
-  const uint64_t* vkeys; const uint32_t* vvals; uint32_t vmask;
-  const NgSlot* ng; uint32_t ngmask;
-  uint32_t bos;
-  const unsigned char* label_bytes; const int* label_off;   // label c spells bytes [off[c], off[c+1])
-  int fold_case;
-  const NgSig* ngs; const VEntry* vt;                        // device only (null: n-gram hashes collide, use ng / vkeys)
-  const UniEntry* uni; uint32_t nwords;                      // device only, with ngs
-  float unk_prob;                                            // p(<unk>) (KenLM's -100 if the model has none)
-};
-
-__host__ __device__ inline uint64_t fnv_step(uint64_t h, unsigned char b) { return (h ^ b) * 1099511628211ULL; }
-constexpr uint64_t kFnvInit = 1469598103934665603ULL;
-
-// hash of an n-gram of word ids (table placement and signature; internal to this file): one multiply per id
-__host__ __device__ inline uint64_t ng_mix(uint64_t h, uint32_t id) { h = (h ^ id) * 0x9E3779B97F4A7C15ULL; return h ^ (h >> 32); }
-__host__ __device__ inline uint64_t ng_finish(uint64_t h, int n) { h = ng_mix(h, 0x51ED2700u + (uint32_t)n); return h == 0 ? 1 : h; }
-__host__ __device__ inline uint64_t ngram_hash(const uint32_t* ids, int n) {
-  uint64_t h = kFnvInit;
-  for (int i = 0; i < n; i++) h = ng_mix(h, ids[i]);
-  return ng_finish(h, n);
-}
-
-__host__ __device__ inline uint32_t lm_word_lookup(const LmView& lm, uint64_t h) {
-  if (h == 0) h = 1;
-  for (uint32_t i = (uint32_t)h & lm.vmask;; i = (i + 1) & lm.vmask) {
-    const uint64_t k = lm.vkeys[i];
-    if (k == h) return lm.vvals[i];
-    if (k == 0) return 0;                       // NotFound() == <unk> == 0
-  }
-}
-
-__host__ __device__ inline const NgSlot* lm_ngram_find(const LmView& lm, const uint32_t* ids, int n) {
-  for (uint32_t i = (uint32_t)ngram_hash(ids, n) & lm.ngmask;; i = (i + 1) & lm.ngmask) {
-    const NgSlot* s = &lm.ng[i];
-    if (s->n == 0) return nullptr;
-    if (s->n == n) {
-      bool eq = true;
-      for (int k = 0; k < n; k++) eq = eq && s->ids[k] == ids[k];
-      if (eq) return s;
-    }
-  }
-}
-
-// log10 p(word | ctx) with ARPA back-off; ctx is most-recent-first.  Float accumulation in KenLM's order: the prob of
-// the longest listed n-gram, then the back-off weights of the longer contexts, shortest context first.
-__host__ __device__ inline float lm_base_score(const LmView& lm, const uint32_t* ctx, int ctx_len, uint32_t word,
-                                               uint32_t* out_ctx, int* out_len) {
-  int n = ctx_len; if (n > lm.order - 1) n = lm.order - 1;
-  uint32_t ids[kLmMaxOrder];
-  float bo[kLmMaxOrder + 1];
-  float result = 0.f; int found_k = -1;
-  for (int k = n; k >= 0; k--) {
-    for (int i = 0; i < k; i++) ids[i] = ctx[k - 1 - i];
-    ids[k] = word;
-    const NgSlot* s = lm_ngram_find(lm, ids, k + 1);
-    if (s) { result = s->prob; found_k = k; break; }
-    bo[k] = 0.f;
-    if (k > 0) { const NgSlot* c = lm_ngram_find(lm, ids, k); if (c) bo[k] = c->backoff; }
-  }
-  if (found_k < 0) { const uint32_t z = 0; const NgSlot* u = lm_ngram_find(lm, &z, 1); result = u ? u->prob : -100.f; found_k = 0; }
-  for (int k = found_k + 1; k <= n; k++) result += bo[k];
-  if (out_ctx) {
-    int m = n + 1; if (m > lm.order - 1) m = lm.order - 1;
-    uint32_t tmp[kLmMaxOrder];
-    if (m > 0) tmp[0] = word;
-    for (int i = 1; i < m; i++) tmp[i] = ctx[i - 1];
-    for (int i = 0; i < m; i++) out_ctx[i] = tmp[i];
-    *out_len = m;
-  }
-  return result;
-}
-
-}  // namespace e2e
-
-// ------------------------------------------------------------------------------------------------------
-// host side of the LM
-// ------------------------------------------------------------------------------------------------------
-struct e2e_lm {
-  int order = 0;
-  int fold_case = 0;
-  std::vector<uint64_t> vkeys; std::vector<uint32_t> vvals;
-  std::vector<e2e::NgSlot> ng;
-  std::vector<unsigned char> label_bytes; std::vector<int> label_off;
-  std::unordered_map<std::string, uint32_t> exact;       // word -> id, exact case (GetVocabulary().Index)
-  uint32_t bos = 0;
-  // device copies
-  uint64_t* d_vkeys = nullptr; uint32_t* d_vvals = nullptr; e2e::NgSlot* d_ng = nullptr;
-  unsigned char* d_label_bytes = nullptr; int* d_label_off = nullptr;
-  e2e::NgSig* d_ngs = nullptr; e2e::VEntry* d_vt = nullptr;     // (d_ngs stays null if two n-grams share a hash)
-  e2e::UniEntry* d_uni = nullptr; uint32_t nwords = 0;
-  float unk_prob = -100.f;
-  int device = -1;                                       // HIP device that holds the tables (-1: host only)
-  e2e::LmView host_view() const {
-    return {order, vkeys.data(), vvals.data(), (uint32_t)vkeys.size() - 1, ng.data(), (uint32_t)ng.size() - 1, bos,
-            label_bytes.data(), label_off.data(), fold_case, nullptr, nullptr, nullptr, nwords, unk_prob};
-  }
-  e2e::LmView dev_view() const {
-    return {order, d_vkeys, d_vvals, (uint32_t)vkeys.size() - 1, d_ng, (uint32_t)ng.size() - 1, bos,
-            d_label_bytes, d_label_off, fold_case, d_ngs, d_ngs ? d_vt : nullptr, d_ngs ? d_uni : nullptr, nwords, unk_prob};
-  }
-};
-
-namespace e2e {
-namespace {
-
-uint64_t word_hash(const std::string& w) {
-  uint64_t h = kFnvInit;
-  for (unsigned char c : w) h = fnv_step(h, c);
-  return h == 0 ? 1 : h;
-}
-
-size_t pow2_at_least(size_t n) { size_t p = 16; while (p < n) p <<= 1; return p; }
-
-std::string lower(const std::string& s) {
-  std::string r = s;
-  for (auto& c : r) c = (char)::tolower((unsigned char)c);      // str_to_lower, ctc_decoder.cpp:32-36
-  return r;
-}
-
-}  // namespace
-}  // namespace e2e
-
-using namespace e2e;
-
-extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int V, int case_sensitive, e2e_lm** out) {
-  if (out) *out = nullptr;
-  if (!path || !out || V < 0 || (V > 0 && !labels)) { set_error("e2e_lm_load_arpa: bad argument"); return E2E_ERR_ARG; }
-  gzFile f = gzopen(path, "rb");
-  if (!f) { set_error("cannot open language model %s", path); return E2E_ERR_IO; }
-  {
-    // KenLM's own binary format (what `build_binary` writes; upstream's LoadVirtual, ctc_decoder.cpp:64, takes it too)
-    // is not read here: say so instead of failing to find ARPA sections
-    char magic[64] = {0};
-    const int got = gzread(f, magic, sizeof(magic) - 1);
-    if (got > 0 && strncmp(magic, "mmap lm http://kheafield.com/code", 33) == 0) {
-      gzclose(f);
-      set_error("%s is a KenLM binary model; this library reads ARPA (plain or .gz) -- convert it back with KenLM, or "
-                "load the ARPA file it was built from", path);
-      return E2E_ERR_UNSUPPORTED;
-    }
-    gzrewind(f);
-  }
-  e2e_lm* lm = new e2e_lm();
-  lm->fold_case = case_sensitive ? 0 : 1;
-  std::vector<std::string> words;                          // id -> word; id 0 is <unk>
-  auto intern = [&](const std::string& w) -> uint32_t {
-    auto it = lm->exact.find(w);
-    if (it != lm->exact.end()) return it->second;
-    const uint32_t id = (uint32_t)words.size();
-    words.push_back(w); lm->exact.emplace(w, id);
-    return id;
-  };
-  intern("<unk>");
-  struct Entry { uint32_t ids[kLmMaxOrder]; int n; float prob, bo; };
-  std::vector<Entry> entries;
-  std::vector<char> buf(1 << 16);
-  int section = 0; bool saw_data = false;
-  while (gzgets(f, buf.data(), (int)buf.size())) {
-    char* line = buf.data();
-    size_t len = strlen(line);
-    while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
-    if (len == 0) continue;
-    if (line[0] == '\\') {
-      int k;
-      if (strncmp(line, "\\data\\", 6) == 0) saw_data = true;
-      else if (sscanf(line, "\\%d-grams:", &k) == 1) { section = k; if (k > lm->order) lm->order = k; }
-      else if (strncmp(line, "\\end\\", 5) == 0) break;
-      continue;
-    }
-    if (section == 0 || section > kLmMaxOrder) continue;
-    char* save = nullptr;
-    char* tok = strtok_r(line, " \t", &save);
-    if (!tok) continue;
-    Entry e; e.n = section; e.prob = strtof(tok, nullptr); e.bo = 0.f;
-    bool ok = true;
-    for (int i = 0; i < section; i++) { tok = strtok_r(nullptr, " \t", &save); if (!tok) { ok = false; break; } e.ids[i] = intern(tok); }
-    if (!ok) continue;
-    tok = strtok_r(nullptr, " \t", &save);
-    if (tok) e.bo = strtof(tok, nullptr);
-    entries.push_back(e);
-  }
-  gzclose(f);
-  if (!saw_data || lm->order == 0) { delete lm; set_error("%s: not an ARPA file (no \\data\\ / n-gram sections)", path); return E2E_ERR_IO; }
-  if (lm->order > kLmMaxOrder) { delete lm; set_error("%s: order %d > %d", path, lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
-  {  // <unk> absent from the file: KenLM's default unknown_missing_logprob = -100
-    bool has_unk = false;
-    for (const auto& e : entries) if (e.n == 1 && e.ids[0] == 0) { has_unk = true; break; }
-    if (!has_unk) { Entry e; e.n = 1; e.ids[0] = 0; e.prob = -100.f; e.bo = 0.f; entries.push_back(e); }
-  }
-  // n-gram table
-  // (load <= 1/4: most misses end at the first slot.  The table's footprint is not what the kernel's queries cost: 2, 3, 4, 8
-  //  slots per entry -- 2 to 8 MB for the bench's model -- measured 28.0 / 26.6 / 26.6 / 26.1 ms per C4 batch.)
-  lm->ng.assign(pow2_at_least(entries.size() * 4 + 16), NgSlot{{0, 0, 0, 0, 0, 0}, 0, 0.f, 0.f});
-  const uint32_t ngmask = (uint32_t)lm->ng.size() - 1;
-  for (const auto& e : entries) {
-    uint32_t i = (uint32_t)ngram_hash(e.ids, e.n) & ngmask;
-    for (;; i = (i + 1) & ngmask) {
-      NgSlot& s = lm->ng[i];
-      if (s.n == 0) { s.n = e.n; for (int k = 0; k < e.n; k++) s.ids[k] = e.ids[k]; s.prob = e.prob; s.backoff = e.bo; break; }
-      if (s.n == e.n && memcmp(s.ids, e.ids, sizeof(uint32_t) * e.n) == 0) { s.prob = e.prob; s.backoff = e.bo; break; }
-    }
-  }
-  // vocabulary table keyed by the hash of the (optionally lower-cased) spelling; when two words fold to the same
-  // string the reference keeps whichever its unordered_map iteration visits last (unspecified) -- here: lowest id
-  lm->vkeys.assign(pow2_at_least(words.size() * 4 + 16), 0);
-  lm->vvals.assign(lm->vkeys.size(), 0);
-  const uint32_t vmask = (uint32_t)lm->vkeys.size() - 1;
-  for (uint32_t id = 0; id < words.size(); id++) {
-    const uint64_t h = word_hash(lm->fold_case ? lower(words[id]) : words[id]);
-    for (uint32_t i = (uint32_t)h & vmask;; i = (i + 1) & vmask) {
-      if (lm->vkeys[i] == h) break;
-      if (lm->vkeys[i] == 0) { lm->vkeys[i] = h; lm->vvals[i] = id; break; }
-    }
-  }
-  { auto it = lm->exact.find("<s>"); lm->bos = it != lm->exact.end() ? it->second : 0; }
-  lm->label_off.assign(1, 0);
-  for (int c = 0; c < V; c++) {
-    for (const char* s = labels[c]; *s; s++) lm->label_bytes.push_back((unsigned char)*s);
-    lm->label_off.push_back((int)lm->label_bytes.size());
-  }
-  if (lm->label_bytes.empty()) lm->label_bytes.push_back(0);
-  // upload
-  auto up = [](void** d, const void* h, size_t bytes) -> bool {
-    if (hipMalloc(d, bytes) != hipSuccess) return false;
-    return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  // the kernel's 16-byte forms of the two tables (same slots)
-  std::vector<NgSig> ngs(lm->ng.size(), NgSig{0, 0.f, 0.f, 0, 0});
-  std::vector<UniEntry> uni(words.size(), UniEntry{1.f, 0.f, 0});
-  lm->nwords = (uint32_t)words.size();
-  bool sig_ok = true;
-  {
-    std::vector<uint64_t> seen;
-    seen.reserve(entries.size());
-    for (size_t i = 0; i < lm->ng.size(); i++) {
-      const NgSlot& sl = lm->ng[i];
-      if (sl.n == 0) continue;
-      ngs[i].sig = ngram_hash(sl.ids, sl.n); ngs[i].prob = sl.prob; ngs[i].backoff = sl.backoff;
-      seen.push_back(ngs[i].sig);
-      if (sl.n == 1 && sl.ids[0] == 0) lm->unk_prob = sl.prob;
-    }
-    std::sort(seen.begin(), seen.end());
-    sig_ok = std::adjacent_find(seen.begin(), seen.end()) == seen.end();
-    // continuation bits: (w1 .. wn) sets bit cont_bit(wn) of its context (w1 .. wn-1).  The kernel's scorer
-    // (lm_score_parallel) looks an n-gram up only behind a HIT of its context, so a model that lists an n-gram without its
-    // context (SRILM-pruned files do; KenLM inserts blank entries for them) cannot use these tables: the id-keyed walk
-    // (lm_base_score), which probes every order, takes over.
-    bool contexts_listed = true;
-    const LmView hv = lm->host_view();
-    for (size_t i = 0; i < lm->ng.size(); i++) {
-      const NgSlot& sl = lm->ng[i];
-      if (sl.n == 1) { uni[sl.ids[0]].prob = sl.prob; uni[sl.ids[0]].backoff = sl.backoff; }
-    }
-    for (size_t i = 0; i < lm->ng.size() && contexts_listed; i++) {
-      const NgSlot& sl = lm->ng[i];
-      if (sl.n < 2) continue;
-      const NgSlot* c = lm_ngram_find(hv, sl.ids, sl.n - 1);
-      if (!c) { contexts_listed = false; break; }
-      const uint64_t bit = 1ULL << cont_bit(sl.ids[sl.n - 1]);
-      if (sl.n == 2) uni[sl.ids[0]].cont |= bit; else ngs[(size_t)(c - lm->ng.data())].cont |= bit;
-    }
-    if (!contexts_listed) {
-      sig_ok = false;
-      if (getenv("E2E_LM_DEBUG")) fprintf(stderr, "e2e_lm: an n-gram's context is not listed; using the id tables (slower)\n");
-    }
-  }
-  std::vector<VEntry> vt(lm->vkeys.size(), VEntry{0, 0u, 1.f});
-  for (size_t i = 0; i < lm->vkeys.size() && sig_ok; i++) {      // (one entry per distinct folded spelling already)
-    if (lm->vkeys[i] == 0) continue;
-    // cuckoo insertion: a free slot of the item's two, else evict the occupant of one and move that on
-    VEntry item{lm->vkeys[i], lm->vvals[i], uni[lm->vvals[i]].prob};
-    const uint32_t mask = (uint32_t)vt.size() - 1;
-    uint32_t i1, i2;
-    two_slots(item.key, mask, i1, i2);
-    if (vt[i1].key == 0) { vt[i1] = item; continue; }
-    if (vt[i2].key == 0) { vt[i2] = item; continue; }
-    uint32_t pos = i1;
-    bool placed = false;
-    for (int kick = 0; kick < 2000 && !placed; kick++) {
-      std::swap(item, vt[pos]);
-      if (item.key == 0) { placed = true; break; }
-      two_slots(item.key, mask, i1, i2);
-      pos = pos == i1 ? i2 : i1;
-    }
-    if (!placed) sig_ok = false;                                  // (never seen at load <= 1/4; the id-keyed walk takes over)
-  }
-  // Self-check of what the kernel will read, against the id tables it stands for: every spelling is found in one of its two
-  // vocabulary slots with the right id and unigram; every listed n-gram is found by its signature with the right numbers and
-  // its context lists its last word.  (What is NOT listed can only cost a wasted lookup: the filters have no false negatives.)
-  if (sig_ok) {
-    const uint32_t vmask2 = (uint32_t)vt.size() - 1;
-    for (size_t i = 0; i < lm->vkeys.size() && sig_ok; i++) {
-      if (lm->vkeys[i] == 0) continue;
-      uint32_t i1, i2;
-      two_slots(lm->vkeys[i], vmask2, i1, i2);
-      const VEntry* e = vt[i1].key == lm->vkeys[i] ? &vt[i1] : vt[i2].key == lm->vkeys[i] ? &vt[i2] : nullptr;
-      sig_ok = e && e->val == lm->vvals[i] && e->prob == uni[e->val].prob;
-    }
-    const LmView hv = lm->host_view();
-    for (size_t i = 0; i < lm->ng.size() && sig_ok; i++) {
-      const NgSlot& sl = lm->ng[i];
-      if (sl.n == 0) continue;
-      const uint64_t sig = ngram_hash(sl.ids, sl.n);
-      uint32_t j = (uint32_t)sig & ngmask;
-      while (ngs[j].sig != sig && ngs[j].sig != 0) j = (j + 1) & ngmask;
-      sig_ok = ngs[j].sig == sig && ngs[j].prob == sl.prob && ngs[j].backoff == sl.backoff;
-      if (sig_ok && sl.n == 1) sig_ok = uni[sl.ids[0]].prob == sl.prob && uni[sl.ids[0]].backoff == sl.backoff;
-      if (sig_ok && sl.n >= 2) {
-        const uint64_t bit = 1ULL << cont_bit(sl.ids[sl.n - 1]);
-        const NgSlot* c = lm_ngram_find(hv, sl.ids, sl.n - 1);
-        const uint64_t cont = sl.n == 2 ? uni[sl.ids[0]].cont : (c ? ngs[(size_t)(c - lm->ng.data())].cont : 0ULL);
-        sig_ok = (sl.n == 2 || c) && (cont & bit) != 0;         // (an unlisted context fails: the kernel would never probe the n-gram)
-      }
-    }
-    if (!sig_ok) fprintf(stderr, "e2e_lm: the kernel's tables failed their self-check; using the id tables (slower)\n");
-  }
-  if (getenv("E2E_LM_DEBUG")) fprintf(stderr, "e2e_lm: %zu entries, %zu words, signature tables %s\n", entries.size(), words.size(), sig_ok ? "ok" : "NOT usable");
-  bool ok = (!sig_ok || up((void**)&lm->d_ngs, ngs.data(), ngs.size() * sizeof(NgSig))) &&
-            up((void**)&lm->d_vt, vt.data(), vt.size() * sizeof(VEntry)) &&
-            up((void**)&lm->d_uni, uni.data(), uni.size() * sizeof(UniEntry)) &&
-            up((void**)&lm->d_vkeys, lm->vkeys.data(), lm->vkeys.size() * sizeof(uint64_t)) &&
-            up((void**)&lm->d_vvals, lm->vvals.data(), lm->vvals.size() * sizeof(uint32_t)) &&
-            up((void**)&lm->d_ng, lm->ng.data(), lm->ng.size() * sizeof(NgSlot)) &&
-            up((void**)&lm->d_label_bytes, lm->label_bytes.data(), lm->label_bytes.size()) &&
-            up((void**)&lm->d_label_off, lm->label_off.data(), lm->label_off.size() * sizeof(int));
-  if (!ok) {
-    // no usable GPU: keep the host tables (e2e_lm_word_index / e2e_lm_score still work); e2e_ctc_beam refuses it
-    (void)hipGetLastError();
-    (void)hipFree(lm->d_vkeys); (void)hipFree(lm->d_vvals); (void)hipFree(lm->d_ng);
-    (void)hipFree(lm->d_label_bytes); (void)hipFree(lm->d_label_off); (void)hipFree(lm->d_ngs); (void)hipFree(lm->d_vt); (void)hipFree(lm->d_uni);
-    lm->d_vkeys = nullptr; lm->d_vvals = nullptr; lm->d_ng = nullptr; lm->d_label_bytes = nullptr; lm->d_label_off = nullptr;
-    lm->d_ngs = nullptr; lm->d_vt = nullptr; lm->d_uni = nullptr;
-  } else if (hipGetDevice(&lm->device) != hipSuccess) {
-    lm->device = -1;
-  }
-  *out = lm;
-  return E2E_OK;
-}
-
-extern "C" void e2e_lm_free(e2e_lm* lm) {
-  if (!lm) return;
-  (void)hipFree(lm->d_vkeys); (void)hipFree(lm->d_vvals); (void)hipFree(lm->d_ng);
-  (void)hipFree(lm->d_label_bytes); (void)hipFree(lm->d_label_off); (void)hipFree(lm->d_ngs); (void)hipFree(lm->d_vt); (void)hipFree(lm->d_uni);
-  delete lm;
-}
-
-extern "C" int e2e_lm_order(const e2e_lm* lm) { return lm ? lm->order : 0; }
-extern "C" int e2e_lm_device(const e2e_lm* lm) { return lm ? lm->device : -1; }
-
-// get_idx(string), ctc_decoder.cpp:77-82: exact lookup when case sensitive, else lower-cased lookup
-extern "C" uint32_t e2e_lm_word_index(const e2e_lm* lm, const char* word) {
-  if (!lm || !word) return 0;
-  const std::string w = lm->fold_case ? lower(word) : std::string(word);
-  return lm_word_lookup(lm->host_view(), word_hash(w));
-}
-
-extern "C" double e2e_lm_score(const e2e_lm* lm, const uint32_t* ctx, int ctx_len, uint32_t word) {
-  if (!lm || ctx_len < 0 || ctx_len > kCtx || (ctx_len > 0 && !ctx)) return 0.0;
-  return (double)lm_base_score(lm->host_view(), ctx, ctx_len, word, nullptr, nullptr);
-}
+#include "ctc_lm.h"
 
 // ------------------------------------------------------------------------------------------------------
 // the kernel
@@ -444,7 +41,7 @@ extern "C" double e2e_lm_score(const e2e_lm* lm, const uint32_t* ctx, int ctx_le
 namespace e2e {
 namespace {
 
-constexpr int kThreadsNoLm = 1024, kThreadsLm = 1024;   // (with a language model: 512 threads measured 30 % slower)
+constexpr int kThreads = 1024;     // (with a language model: 512 threads measured 30 % slower)
 constexpr int kMaxCand = 8192;     // W*V + W candidates per step (LDS key array)
 constexpr int kLdsBudget = 158 * 1024;
 constexpr int kSelBits = 11, kSelBins = 1 << kSelBits;   // radix-select digit (two alternating histograms in LDS)
@@ -477,16 +74,6 @@ struct BeamParams {
   BeamNode* nodes;                                    // per-utterance workspace
   int NCAP, CMAX, WP2, HS;
 };
-
-__device__ __forceinline__ double ninf() { return -__builtin_huge_val(); }
-
-// src/utils/math_utils.h:8-16
-__device__ __forceinline__ double lse2(double a, double b) {
-  if (a == ninf()) return b;
-  if (b == ninf()) return a;
-  if (a > b) return a + log(1.0 + exp(b - a));
-  return b + log(1.0 + exp(a - b));
-}
 
 // inclusive prefix sum over the 64 lanes, all DPP (row_shr 1/2/4/8 with zero fill, row_bcast 15/31)
 __device__ __forceinline__ int wave_scan_i(int v) {
@@ -788,19 +375,21 @@ struct BeamLds {
   }
 };
 
-// node id -> position in the beam, for the <= W members: open addressing in LDS, one table per member set (the
-// table of the set that is being built is cleared a phase earlier).  Replaces a `slot` field in the HBM nodes that
-// cost a global round trip per step to read.
-struct SlotMap {
+// Open addressing in LDS, int key -> int value, -1 an empty key.  SlotMap: node id -> position in the beam, for the <= W
+// members, one table per member set (the table of the set that is being built is cleared a phase earlier); replaces a
+// `slot` field in the HBM nodes that cost a global round trip per step to read.  ChildMap (the general kernel):
+// (member position * V + character) -> node id of the alive child.
+template <int kShift>
+struct HashMap {
   int* key; int* val; int mask;
   __device__ static unsigned hash(int k) { return (unsigned)k * 2654435761u; }
-  __device__ void insert(int k, int j) const {
-    unsigned h = (hash(k) >> 8) & mask;
+  __device__ void insert(int k, int v) const {
+    unsigned h = (hash(k) >> kShift) & mask;
     while (atomicCAS(&key[h], -1, k) != -1) h = (h + 1) & mask;
-    val[h] = j;
+    val[h] = v;
   }
   __device__ int find(int k) const {
-    unsigned h = (hash(k) >> 8) & mask;
+    unsigned h = (hash(k) >> kShift) & mask;
     for (;;) {
       const int kk = key[h];
       if (kk == k) return val[h];
@@ -809,6 +398,176 @@ struct SlotMap {
     }
   }
 };
+typedef HashMap<8> SlotMap;
+typedef HashMap<7> ChildMap;
+
+// ---- the phases both kernels share ----
+// The barrier a shared phase passes its data through: LDS only in the fast kernel, a full barrier in the general one (whose
+// data crosses threads through global memory as well).
+struct LdsSync { __device__ void operator()() const { lds_barrier(); } };
+struct FullSync { __device__ void operator()() const { __syncthreads(); } };
+
+// the root prefix (get_initial_prefix, :222-230) as member 0 of set 0 and node 0; one thread
+__device__ __forceinline__ void init_root(const BeamParams& p, BeamNode* nodes, const Members& M0) {
+  BeamNode& r = nodes[0];
+  r.parent = -1; r.last_char = -1;
+  LmFields l;
+  l.lm_score = 0.0; l.lm_before = 0.0; l.num_words = 0; l.num_oov = 0; l.num_oov_before = 0; l.word_len = 0;
+  l.word_hash = kFnvInit; l.st_n = 0; l.stb_n = 0;
+  if (p.has_lm) { l.st[0] = p.lm.bos; l.st_n = 1; l.stb[0] = p.lm.bos; l.stb_n = 1; }
+  M0.ppb[0] = 0.0; M0.ppnb[0] = ninf(); M0.full[0] = lse2(ninf(), 0.0); M0.inc[0] = ninf(); M0.kept[0] = 0; M0.node[0] = 0; M0.last[0] = -1; M0.gown[0] = -1; M0.gchar[0] = 0; M0.gnode[0] = 0;
+  M0.lm[0] = l;
+}
+
+// what the score of a member's would-be children needs of its LM state (only these fields are ever loaded)
+template <bool LM>
+__device__ __forceinline__ LmFields score_fields(const LmFields& m) {
+  LmFields pr;
+  pr.num_words = m.num_words;
+  if (LM) { pr.lm_score = m.lm_score; pr.lm_before = m.lm_before; pr.num_oov = m.num_oov; pr.num_oov_before = m.num_oov_before; }
+  return pr;
+}
+// the LM's answer for (member, character) at index i of an answer table (no language model: none)
+template <bool LM, typename Idx>
+__device__ __forceinline__ LmAnswer answer_at(const LmAnswer* lmc, Idx i) {
+  LmAnswer ans; ans.sc = 0.f; ans.wi = 0u;
+  if (LM) ans = lmc[i];
+  return ans;
+}
+// the key of the would-be child (parent pr, char c) whose probability after next_step is prev_pnb = val, prev_pb = -inf
+template <bool LM>
+__device__ __forceinline__ unsigned long long child_key(const BeamParams& p, const LmFields& pr, int parent_last, int c, LmAnswer ans, double val) {
+  LmFields nl;
+  child_score_fields<LM>(p, pr, parent_last, c, ans, nl);
+  return okey(beam_score<LM>(p, val, ninf(), nl));
+}
+
+// members: repeated-character share (:386-387), next_step (:337-342), score; row(c) is this step's log-probability of c.
+// Each member's key goes to keys[i]; key_hi / key_lo collect the high words of the largest and of the smallest.
+template <bool LM, class Row>
+__device__ __forceinline__ void update_members(const BeamParams& p, const Members& A, int n, Row row, unsigned long long* keys,
+                                               unsigned& key_hi, unsigned& key_lo) {
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    const int lc = A.last[i];
+    double pnb = A.inc[i];
+    if (lc >= 0 && lc != p.blank) pnb = lse2(pnb, row(lc) + A.ppnb[i]);
+    A.npnb[i] = pnb;
+    const double nf = lse2(pnb, A.npb[i]);            // the score's log-sum-exp is next step's `full` if the member stays
+    A.nfull[i] = nf;
+    const double sc = beam_score_full<LM>(p, nf, A.lm[i]);
+    const unsigned long long uk = okey(sc);
+    keys[i] = uk;
+    const unsigned h32 = (unsigned)(uk >> 32);
+    key_hi = max(key_hi, h32); key_lo = min(key_lo, h32);
+  }
+}
+
+// One digit of a radix select, once the digit's histogram hcur (kSelBins bins, the largest digit last) is complete: the digit
+// where the running count from the top reaches krem.  Every thread owns kPer adjacent bins (one wave walking 32 bins per lane
+// paid a 64-way bank conflict on every read) and zeroes them in hclear; found(rest, digit, count) is called by the one thread
+// that owns the threshold digit (rest: how many of the digit's `count` keys are still wanted).  Leaves a Sync barrier behind
+// the histogram reads and clears; the caller's barrier has to follow found().
+template <class Sync, class Found>
+__device__ __forceinline__ void select_digit(const int* hcur, int* hclear, int krem, int* s_part, Found found) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  constexpr int kPer = kSelBins / kThreads;
+  static_assert(kPer * kThreads == kSelBins && kPer >= 1, "bins per thread");
+  const int top = kSelBins - 1 - kPer * tid;
+  int cnt[kPer], mine = 0;
+#pragma unroll
+  for (int jj = 0; jj < kPer; jj++) { cnt[jj] = hcur[top - jj]; mine += cnt[jj]; }
+  const int inc = wave_scan_i(mine);
+  if (lane == 63) s_part[wid] = inc;
+#pragma unroll
+  for (int jj = 0; jj < kPer; jj++) hclear[top - jj] = 0;
+  Sync()();
+  int above = inc - mine;                       // candidates with a larger digit than this thread's first
+  {
+    const int wtot = wave_scan_i(lane < kThreads / 64 ? s_part[lane] : 0);
+    if (wid > 0) above += __builtin_amdgcn_readlane(wtot, wid - 1);
+  }
+  if (above < krem && above + mine >= krem) {   // the threshold digit is one of this thread's
+#pragma unroll
+    for (int jj = 0; jj < kPer; jj++) {
+      if (above + cnt[jj] >= krem) { found(krem - above, top - jj, cnt[jj]); break; }
+      above += cnt[jj];
+    }
+  }
+}
+
+// Rank of the M gathered candidates by (score desc, position asc): eight lanes count for one candidate.  emit(rank, e) for
+// every candidate e whose rank -- its place in the new beam -- is below W.  kUnroll: comparisons in flight per lane (4 where
+// emit is a store; where it builds the member, 4 would cost the general kernel two VGPRs spilled to scratch).
+template <int kUnroll, class Emit>
+__device__ __forceinline__ void rank_gathered(const unsigned long long* uskey, int M, int W, Emit emit) {
+  const int tid = threadIdx.x;
+  for (int e0 = 0; e0 < M; e0 += kThreads / 8) {
+    const int e = e0 + (tid >> 3), part = tid & 7;
+    int cnt = 0;
+    if (e < M) {
+      // (the gathered list is in position order within its two parts, and the keys of the first part are all
+      // larger than those of the second: among equal keys the earlier list index is the earlier position)
+      const unsigned long long ke = uskey[e];
+#pragma unroll kUnroll
+      for (int jj = part; jj < M; jj += 8) {
+        const unsigned long long kj = uskey[jj];
+        cnt += (kj > ke || (kj == ke && jj < e)) ? 1 : 0;
+      }
+    }
+    cnt += __builtin_amdgcn_update_dpp(0, cnt, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
+    cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x4E, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
+    cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x141, 0xf, 0xf, true);     // row_half_mirror: the other quad of the 8
+    if (e < M && part == 0 && cnt < W) emit(cnt, e);
+  }
+}
+
+// ---- guards and child tables of the new beam Bm (nsel members) ----
+// A guard whose owner left the beam is inherited from the owner's guard (the next alive prefix up the path whose
+// parent was a member), until an owner that stays is found or the path runs out.  Every alive child of a member is
+// some member's guard: writing the guards into the cleared tables -- store(member position * V + character, node) --
+// reproduces exactly the entries whose weak_ptr has not expired upstream.
+template <class Store>
+__device__ __forceinline__ void rebuild_guards(const Members& A, const Members& Bm, int nsel, int V, Store store) {
+  for (int j = threadIdx.x; j < nsel; j += kThreads) {
+    Bm.inc[j] = ninf(); Bm.kept[j] = 0;                      // (what the next step's pair loop expects to find)
+    int go = Bm.gown[j], gc = Bm.gchar[j], gn = Bm.gnode[j];
+    while (go >= 0 && !A.kept[go]) { const int o = go; go = A.gown[o]; gc = A.gchar[o]; gn = A.gnode[o]; }
+    if (go >= 0) {
+      const int o = A.newpos[go];
+      Bm.gown[j] = o; Bm.gchar[j] = gc; Bm.gnode[j] = gn;
+      store(o * V + gc, gn);
+    } else {
+      Bm.gown[j] = -1;
+    }
+  }
+}
+
+// ---- final sort (:418-424) reduces to the best prefix; its sentence (:232-245) ----
+// A: the n members after the last step; key: n doubles of scratch.  err: the node pool ran out.
+template <bool LM>
+__device__ __forceinline__ void read_out(const BeamParams& p, const Members& A, int n, double* key, const BeamNode* nodes,
+                                         const int& err) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < n; i += kThreads) key[i] = beam_score<LM>(p, A.ppnb[i], A.ppb[i], A.lm[i]);
+  __syncthreads();
+  int64_t* out = p.out + (int64_t)b * p.max_out;
+  for (int64_t i = tid; i < p.max_out; i += kThreads) out[i] = 0;
+  __threadfence_block();
+  __syncthreads();
+  if (tid == 0) {
+    int bi = 0;
+    for (int i = 1; i < n; i++) if (key[i] > key[bi]) bi = i;            // first maximum = (score desc, position asc)
+    const int best = A.node[bi];
+    int64_t m = 0;
+    for (int k = best; k >= 0; k = nodes[k].parent) if (k == best || nodes[k].parent >= 0) m++;
+    int64_t at = m;
+    for (int k = best; k >= 0; k = nodes[k].parent)
+      if (k == best || nodes[k].parent >= 0) { at--; if (at < p.max_out) out[at] = nodes[k].last_char; }
+    // in-band status (include/e2e_ctc.h): a length above max_out says "truncated, m were needed"; -1 = node pool
+    // exhausted (the sentence is then that of the last completed step and must not be used)
+    p.out_len[b] = err ? (int64_t)-1 : m;
+  }
+}
 
 #ifdef E2E_BEAM_PROFILE
 } }  // leave the namespaces for the device symbol
@@ -821,11 +580,9 @@ namespace e2e { namespace {
 #define BPROF(slot) do {} while (0)
 #endif
 
-// NT threads per workgroup
 // LMK: 0 no language model, 1 the general LM walk, 2 the fast one (see lm_query)
-template <typename IO, int LMK, int NT>
-__global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
-  constexpr int kThreads = NT;
+template <typename IO, int LMK>
+__global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   constexpr bool LM = LMK != 0;
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -890,14 +647,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
   if (tid == 0) {
     s_next_node = 1; s_err = 0;                                                     // node 0 is taken
     s_hi2[0] = 0u; s_lo2[0] = 0xffffffffu; s_total_new2[0] = 0; s_nnew2[0] = 0;
-    BeamNode& r = nodes[0];
-    r.parent = -1; r.last_char = -1;
-    LmFields l;
-    l.lm_score = 0.0; l.lm_before = 0.0; l.num_words = 0; l.num_oov = 0; l.num_oov_before = 0; l.word_len = 0;
-    l.word_hash = kFnvInit; l.st_n = 0; l.stb_n = 0;
-    if (p.has_lm) { l.st[0] = p.lm.bos; l.st_n = 1; l.stb[0] = p.lm.bos; l.stb_n = 1; }
-    M0.ppb[0] = 0.0; M0.ppnb[0] = ninf(); M0.full[0] = lse2(ninf(), 0.0); M0.inc[0] = ninf(); M0.kept[0] = 0; M0.node[0] = 0; M0.last[0] = -1; M0.gown[0] = -1; M0.gchar[0] = 0; M0.gnode[0] = 0;
-    M0.lm[0] = l;
+    init_root(p, nodes, M0);
   }
   __syncthreads();
   if (tid == 0) slot_map(0).insert(0, 0);
@@ -958,9 +708,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
     for (int ii = lay_ii0; ii < n; ii += members_per_pass) {
       const double full = A.full[ii], ppb = A.ppb[ii];
       const int last = A.last[ii];
-      LmFields pr;                                              // (only the fields the scores need are ever loaded)
-      pr.num_words = A.lm[ii].num_words;
-      if (LM) { pr.lm_score = A.lm[ii].lm_score; pr.lm_before = A.lm[ii].lm_before; pr.num_oov = A.lm[ii].num_oov; pr.num_oov_before = A.lm[ii].num_oov_before; }
+      const LmFields pr = score_fields<LM>(A.lm[ii]);
       for (int ci = part; ci < V; ci += P) {
         const double curp = srow[ci];
         unsigned long long* const slot = ukey + n + ci * n + ii;
@@ -973,12 +721,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
           if (j >= 0) A.inc[j] = val;            // the child is a beam member: its share from this parent
           // else: alive but pruned (Q7) -- the probability is lost and the slot stays taken
         } else {
-          LmFields nl;
-          LmAnswer ans; ans.sc = 0.f; ans.wi = 0u;
-          if (LM) ans = lmcA[ii * V + ci];
-          child_score_fields<LM>(p, pr, last, ci, ans, nl);
-          const double sc = beam_score<LM>(p, val, ninf(), nl);                  // after next_step: prev_pnb = val, prev_pb = -inf
-          uk = okey(sc);
+          uk = child_key<LM>(p, pr, last, ci, answer_at<LM>(lmcA, ii * V + ci), val);
           key_hi = max(key_hi, (unsigned)(uk >> 32));
           my_new++;
         }
@@ -993,20 +736,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
     if (lane == 0) atomicMax(&s_hi, key_hi);
     lds_barrier();
     BPROF(1);
-    // members: repeated-character share (:386-387), next_step (:337-342), score
-    for (int i = tid; i < n; i += kThreads) {
-      const int lc = A.last[i];
-      double pnb = A.inc[i];
-      if (lc >= 0 && lc != blank) pnb = lse2(pnb, srow[lc] + A.ppnb[i]);
-      A.npnb[i] = pnb;
-      const double nf = lse2(pnb, A.npb[i]);            // the score's log-sum-exp is next step's `full` if the member stays
-      A.nfull[i] = nf;
-      const double sc = beam_score_full<LM>(p, nf, A.lm[i]);
-      const unsigned long long uk = okey(sc);
-      ukey[i] = uk;
-      const unsigned h32 = (unsigned)(uk >> 32);
-      key_hi = max(key_hi, h32); key_lo = min(key_lo, h32);
-    }
+    update_members<LM>(p, A, n, [&](int c) { return srow[c]; }, ukey, key_hi, key_lo);
     if (wid < (n + 63) / 64) {
       key_hi = (unsigned)wave_max_i((int)(key_hi ^ 0x80000000u)) ^ 0x80000000u;
       key_lo = ~((unsigned)wave_max_i((int)((~key_lo) ^ 0x80000000u)) ^ 0x80000000u);
@@ -1071,12 +801,26 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
       } else {
         const int q = d - n;
         const int c = n > 1 ? (int)__umulhi((unsigned)q, lay_nmagic) : q, i = q - c * n;
-        LmAnswer ans; ans.sc = 0.f; ans.wi = 0u;
-        if (LM) ans = lmcA[i * V + c];
-        child_lm<LM>(p, lt, A.lm[i], A.last[i], c, ans, Bm.lm[j]);                 // (straight into LDS: a local LmFields lives in scratch)
+        child_lm<LM>(p, lt, A.lm[i], A.last[i], c, answer_at<LM>(lmcA, i * V + c), Bm.lm[j]);                 // (straight into LDS: a local LmFields lives in scratch)
       }
     };
     auto place = [&](int j, int d) { place_core(j, d); place_lm(j, d); };
+    // The members are built by W threads on two waves, not by the ranking threads (one lane in eight of all sixteen waves:
+    // every wave walked the whole of place() -- with a language model some 400 instructions -- for eight useful lanes,
+    // and the phase was bound by the instructions the four SIMDs had to issue).  (Called at the end of both branches
+    // below: behind their join it would cost the LM instances two VGPRs spilled to scratch.)
+    auto place_all = [&]() {
+      lds_barrier();
+      if (LM) {
+        // blocks of 128 threads alternate between the two halves: waves 0-1 the lattice half of members 0..127, waves 2-3
+        // their LM half, ...
+        const int blk = tid >> 7, j0 = (tid & 127) + 128 * (blk >> 1);
+        if (blk & 1) { for (int j = j0; j < nsel; j += kThreads / 2) place_lm(j, sel[j]); }
+        else { for (int j = j0; j < nsel; j += kThreads / 2) place_core(j, sel[j]); }
+      } else {
+        for (int j = tid; j < nsel; j += kThreads) place(j, sel[j]);
+      }
+    };
     if (nreal > W) {                                                             // :405-415
       // ---- radix select of the W-th largest score on the order-preserving 64-bit key, 11 bits per pass ----
       // Where to start: the threshold lies between the smallest score of a full beam's old members (W candidates are
@@ -1104,38 +848,14 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
           if ((u & mask) == prefix && u != kNoCandKey) atomicAdd(&hcur[(int)((u >> shift) & dmask)], 1);
         }
         lds_barrier();
-        // the digit where the running count (from the top) reaches krem: every thread owns kPer adjacent bins
-        // (one wave walking 32 bins per lane paid a 64-way bank conflict on every read)
-        constexpr int kPer = kSelBins / kThreads;
-        static_assert(kPer * kThreads == kSelBins && kPer >= 1, "bins per thread");
-        const int top = kSelBins - 1 - kPer * tid;
-        int cnt[kPer], mine = 0;
-#pragma unroll
-        for (int jj = 0; jj < kPer; jj++) { cnt[jj] = hcur[top - jj]; mine += cnt[jj]; }
-        const int inc = wave_scan_i(mine);
-        if (lane == 63) s_part[wid] = inc;
-#pragma unroll
-        for (int jj = 0; jj < kPer; jj++) hnext[top - jj] = 0;    // (at pass 0 this is the region that held the previous step's sel)
-        lds_barrier();
-        int above = inc - mine;                       // candidates with a larger digit than this thread's first
-        {
-          const int wtot = wave_scan_i(lane < kThreads / 64 ? s_part[lane] : 0);
-          if (wid > 0) above += __builtin_amdgcn_readlane(wtot, wid - 1);
-        }
+        // (hnext: at pass 0 the region that held the previous step's sel)
         const unsigned long long digit_mask = dmask << shift;
-        if (above < krem && above + mine >= krem) {   // the threshold digit is one of this thread's
-#pragma unroll
-          for (int jj = 0; jj < kPer; jj++) {
-            if (above + cnt[jj] >= krem) {
-              s_krem = krem - above;
-              s_prefix = (prefix & ~digit_mask) | ((unsigned long long)(top - jj) << shift);
-              s_bin = cnt[jj];
-              s_done = cnt[jj] == krem - above ? 1 : 0;     // the whole bin survives: no finer threshold needed
-              break;
-            }
-            above += cnt[jj];
-          }
-        }
+        select_digit<LdsSync>(hcur, hnext, krem, s_part, [&](int rest, int digit, int count) {
+          s_krem = rest;
+          s_prefix = (prefix & ~digit_mask) | ((unsigned long long)digit << shift);
+          s_bin = count;
+          s_done = count == rest ? 1 : 0;     // the whole bin survives: no finer threshold needed
+        });
         mask |= digit_mask;
         lds_barrier();
         krem = s_krem; prefix = s_prefix; bin = s_bin; done = s_done != 0;
@@ -1187,40 +907,11 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
       const int M = tg + take;                      // W <= M <= W - 1 + kSelSmall gathered candidates
       lds_barrier();
       BPROF(8);
-      // ---- rank the gathered candidates by (score desc, position asc): eight lanes count for one candidate; rank < W
-      //      is the candidate's place in the new beam (the surplus of a small threshold bin falls off the end) ----
+      // ---- rank the gathered candidates; rank < W is the candidate's place in the new beam (the surplus of a small
+      //      threshold bin falls off the end) ----
       if (LM) for (int h = tid; h < kStateSlots; h += kThreads) tsig[h] = 0ULL;
-      for (int e0 = 0; e0 < M; e0 += kThreads / 8) {
-        const int e = e0 + (tid >> 3), part = tid & 7;
-        int cnt = 0;
-        if (e < M) {
-          // (the gathered list is in position order within its two parts, and the keys of the first part are all
-          // larger than those of the second: among equal keys the earlier list index is the earlier position)
-          const unsigned long long ke = uskey[e];
-#pragma unroll 4
-          for (int jj = part; jj < M; jj += 8) {
-            const unsigned long long kj = uskey[jj];
-            cnt += (kj > ke || (kj == ke && jj < e)) ? 1 : 0;
-          }
-        }
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x4E, 0xf, 0xf, true);      // quad_perm [2,3,0,1]
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x141, 0xf, 0xf, true);     // row_half_mirror: the other quad of the 8
-        if (e < M && part == 0 && cnt < W) sel[cnt] = sidx[e];
-      }
-      // The members are built by W threads on two waves, not by the ranking threads (one lane in eight of all sixteen waves:
-      // every wave walked the whole of place() -- with a language model some 400 instructions -- for eight useful lanes,
-      // and the phase was bound by the instructions the four SIMDs had to issue).
-      lds_barrier();
-      if (LM) {
-        // blocks of 128 threads alternate between the two halves: waves 0-1 the lattice half of members 0..127, waves 2-3
-        // their LM half, ...
-        const int blk = tid >> 7, j0 = (tid & 127) + 128 * (blk >> 1);
-        if (blk & 1) { for (int j = j0; j < nsel; j += kThreads / 2) place_lm(j, sel[j]); }
-        else { for (int j = j0; j < nsel; j += kThreads / 2) place_core(j, sel[j]); }
-      } else {
-        for (int j = tid; j < nsel; j += kThreads) place(j, sel[j]);
-      }
+      rank_gathered<4>(uskey, M, W, [&](int rank, int e) { sel[rank] = sidx[e]; });
+      place_all();
     } else {
       // nothing is pruned (the first steps of an utterance): old members, then the pairs that exist, in order
       for (int j = tid; j < n; j += kThreads) sel[j] = j;
@@ -1236,36 +927,11 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
       for (int q = q0; q < q1; q++)
         if (ukey[n + q] != kNoCandKey) sel[pos++] = n + q;
       if (LM) for (int h = tid; h < kStateSlots; h += kThreads) tsig[h] = 0ULL;
-      lds_barrier();
-      if (LM) {
-        // blocks of 128 threads alternate between the two halves: waves 0-1 the lattice half of members 0..127, waves 2-3
-        // their LM half, ...
-        const int blk = tid >> 7, j0 = (tid & 127) + 128 * (blk >> 1);
-        if (blk & 1) { for (int j = j0; j < nsel; j += kThreads / 2) place_lm(j, sel[j]); }
-        else { for (int j = j0; j < nsel; j += kThreads / 2) place_core(j, sel[j]); }
-      } else {
-        for (int j = tid; j < nsel; j += kThreads) place(j, sel[j]);
-      }
+      place_all();
     }
     lds_barrier();
     BPROF(3);
-    // ---- guards and child tables of the new beam ----
-    // A guard whose owner left the beam is inherited from the owner's guard (the next alive prefix up the path whose
-    // parent was a member), until an owner that stays is found or the path runs out.  Every alive child of a member is
-    // some member's guard: writing the guards into the cleared tables reproduces exactly the entries whose weak_ptr has
-    // not expired upstream.
-    for (int j = tid; j < nsel; j += kThreads) {
-      Bm.inc[j] = ninf(); Bm.kept[j] = 0;                      // (what the next step's pair loop expects to find)
-      int go = Bm.gown[j], gc = Bm.gchar[j], gn = Bm.gnode[j];
-      while (go >= 0 && !A.kept[go]) { const int o = go; go = A.gown[o]; gc = A.gchar[o]; gn = A.gnode[o]; }
-      if (go >= 0) {
-        const int o = A.newpos[go];
-        Bm.gown[j] = o; Bm.gchar[j] = gc; Bm.gnode[j] = gn;
-        ctabB[o * V + gc] = gn;
-      } else {
-        Bm.gown[j] = -1;
-      }
-    }
+    rebuild_guards(A, Bm, nsel, V, [&](int e, int node) { ctabB[e] = node; });
     if (LM) {
       // The LM's answers for the new beam: carried over with a member that stays, asked for a member that is new -- but
       // only once per LM STATE.  What is asked depends on the member's state only (the word begun, the context, whether
@@ -1349,32 +1015,9 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
     if (s_err) break;
   }
 
-  // ---- final sort (:418-424) reduces to the best prefix; its sentence (:232-245) ----
-  {
-    Members A;
-    A.carve(mem0 + (size_t)cur * mbytes, W);
-    for (int i = tid; i < n; i += kThreads) key[i] = beam_score<LM>(p, A.ppnb[i], A.ppb[i], A.lm[i]);
-    __syncthreads();
-  }
-  int64_t* out = p.out + (int64_t)b * p.max_out;
-  for (int64_t i = tid; i < p.max_out; i += kThreads) out[i] = 0;
-  __threadfence_block();
-  __syncthreads();
-  if (tid == 0) {
-    int bi = 0;
-    for (int i = 1; i < n; i++) if (key[i] > key[bi]) bi = i;            // first maximum = (score desc, position asc)
-    Members A;
-    A.carve(mem0 + (size_t)cur * mbytes, W);
-    const int best = A.node[bi];
-    int64_t m = 0;
-    for (int k = best; k >= 0; k = nodes[k].parent) if (k == best || nodes[k].parent >= 0) m++;
-    int64_t at = m;
-    for (int k = best; k >= 0; k = nodes[k].parent)
-      if (k == best || nodes[k].parent >= 0) { at--; if (at < p.max_out) out[at] = nodes[k].last_char; }
-    // in-band status (include/e2e_ctc.h): a length above max_out says "truncated, m were needed"; -1 = node pool
-    // exhausted (the sentence is then that of the last completed step and must not be used)
-    p.out_len[b] = s_err ? (int64_t)-1 : m;
-  }
+  Members A;
+  A.carve(mem0 + (size_t)cur * mbytes, W);
+  read_out<LM>(p, A, n, key, nodes, s_err);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1396,7 +1039,6 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamParams p) {
 // the same result (tests run the whole beam suite through it: E2E_BEAM_GENERAL=1).  beam_width <= kGenMaxW and what the
 // maps and the selection's arrays leave of one workgroup's LDS (the member sets move to the workspace beyond ~256): 512.
 constexpr int kGenMaxW = 1024;
-constexpr int kGenThreads = 1024;
 
 // Character pre-selection of the general kernel (no language model): capacity of the per-step character list and words of
 // the character bitmap in LDS (alphabets beyond 2^16 columns take every character, as before).
@@ -1415,30 +1057,10 @@ struct GenParams {
   int CH;                        // child map slots (power of two >= 4W)
 };
 
-struct ChildMap {                // (member position * V + character) -> node id of the alive child
-  int* key; int* val; int mask;
-  __device__ static unsigned hash(int k) { return (unsigned)k * 2654435761u; }
-  __device__ void insert(int k, int v) const {
-    unsigned h = (hash(k) >> 7) & mask;
-    while (atomicCAS(&key[h], -1, k) != -1) h = (h + 1) & mask;
-    val[h] = v;
-  }
-  __device__ int find(int k) const {
-    unsigned h = (hash(k) >> 7) & mask;
-    for (;;) {
-      const int kk = key[h];
-      if (kk == k) return val[h];
-      if (kk == -1) return -1;
-      h = (h + 1) & mask;
-    }
-  }
-};
-
 __device__ __forceinline__ void gsync() { __threadfence_block(); __syncthreads(); }
 
 template <typename IO, int LMK>
-__global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParams p, GenParams g) {
-  constexpr int kThreads = kGenThreads;
+__global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p, GenParams g) {
   constexpr bool LM = LMK != 0;
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1479,14 +1101,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
   for (int h = tid; h < 2 * g.CH; h += kThreads) { cm0[h] = -1; cm0[2 * g.CH + h] = -1; }
   if (tid == 0) {
     s_next_node = 1; s_err = 0;                                                     // node 0 is taken
-    BeamNode& r = nodes[0];
-    r.parent = -1; r.last_char = -1;
-    LmFields l;
-    l.lm_score = 0.0; l.lm_before = 0.0; l.num_words = 0; l.num_oov = 0; l.num_oov_before = 0; l.word_len = 0;
-    l.word_hash = kFnvInit; l.st_n = 0; l.stb_n = 0;
-    if (p.has_lm) { l.st[0] = p.lm.bos; l.st_n = 1; l.stb[0] = p.lm.bos; l.stb_n = 1; }
-    M0.ppb[0] = 0.0; M0.ppnb[0] = ninf(); M0.full[0] = lse2(ninf(), 0.0); M0.inc[0] = ninf(); M0.kept[0] = 0; M0.node[0] = 0; M0.last[0] = -1; M0.gown[0] = -1; M0.gchar[0] = 0; M0.gnode[0] = 0;
-    M0.lm[0] = l;
+    init_root(p, nodes, M0);
   }
   gsync();
   if (tid == 0) slot_map(0).insert(0, 0);
@@ -1552,28 +1167,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
           if ((u & maskc) == prefix) atomicAdd(&hist[(int)((u >> shift) & ((1u << width) - 1u))], 1);
         }
         __syncthreads();
-        constexpr int kPer = kSelBins / kThreads;
-        const int top = kSelBins - 1 - kPer * tid;
-        int cnt[kPer], mine = 0;
-#pragma unroll
-        for (int jj = 0; jj < kPer; jj++) { cnt[jj] = hist[top - jj]; mine += cnt[jj]; }
-        const int inc = wave_scan_i(mine);
-        if (lane == 63) s_part[wid] = inc;
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < kPer; jj++) hist[top - jj] = 0;
-        int above = inc - mine;
-        {
-          const int wtot = wave_scan_i(lane < kThreads / 64 ? s_part[lane] : 0);
-          if (wid > 0) above += __builtin_amdgcn_readlane(wtot, wid - 1);
-        }
-        if (above < krem && above + mine >= krem) {
-#pragma unroll
-          for (int jj = 0; jj < kPer; jj++) {
-            if (above + cnt[jj] >= krem) { s_krem = krem - above; s_ckey = prefix | ((unsigned)(top - jj) << shift); break; }
-            above += cnt[jj];
-          }
-        }
+        select_digit<FullSync>(hist, hist, krem, s_part, [&](int rest, int digit, int) { s_krem = rest; s_ckey = prefix | ((unsigned)digit << shift); });
         __syncthreads();
         krem = s_krem; prefix = s_ckey; maskc |= ((1u << width) - 1u) << shift;
         __syncthreads();
@@ -1631,14 +1225,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
         if (j >= 0) A.inc[j] = val;            // the child is a beam member: its share from this parent
         // else: alive but pruned (Q7) -- the probability is lost and the slot stays taken
       } else {
-        LmFields pr, nl;
-        pr.num_words = A.lm[ii].num_words;
-        if (LM) { pr.lm_score = A.lm[ii].lm_score; pr.lm_before = A.lm[ii].lm_before; pr.num_oov = A.lm[ii].num_oov; pr.num_oov_before = A.lm[ii].num_oov_before; }
-        LmAnswer ans; ans.sc = 0.f; ans.wi = 0u;
-        if (LM) ans = lmcA[(size_t)ii * V + ci];
-        child_score_fields<LM>(p, pr, last, ci, ans, nl);
-        const double sc = beam_score<LM>(p, val, ninf(), nl);                  // after next_step: prev_pnb = val, prev_pb = -inf
-        uk = okey(sc);
+        uk = child_key<LM>(p, score_fields<LM>(A.lm[ii]), last, ci, answer_at<LM>(lmcA, (size_t)ii * V + ci), val);
         key_hi = max(key_hi, (unsigned)(uk >> 32));
         my_new++;
       }
@@ -1649,20 +1236,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
       if (lane == 63 && incl) atomicAdd(&s_total_new, incl);
     }
     gsync();
-    // ---- members: repeated-character share (:386-387), next_step (:337-342), score ----
-    for (int i = tid; i < n; i += kThreads) {
-      const int lc = A.last[i];
-      double pnb = A.inc[i];
-      if (lc >= 0 && lc != blank) pnb = lse2(pnb, LP(lc) + A.ppnb[i]);
-      A.npnb[i] = pnb;
-      const double nf = lse2(pnb, A.npb[i]);
-      A.nfull[i] = nf;
-      const double sc = beam_score_full<LM>(p, nf, A.lm[i]);
-      const unsigned long long uk = okey(sc);
-      gkey[i] = uk;
-      const unsigned h32 = (unsigned)(uk >> 32);
-      key_hi = max(key_hi, h32); key_lo = min(key_lo, h32);
-    }
+    update_members<LM>(p, A, n, LP, gkey, key_hi, key_lo);
     key_hi = (unsigned)wave_max_i((int)(key_hi ^ 0x80000000u)) ^ 0x80000000u;
     key_lo = ~((unsigned)wave_max_i((int)((~key_lo) ^ 0x80000000u)) ^ 0x80000000u);
     if (lane == 0) { atomicMax(&s_hi, key_hi); atomicMin(&s_lo, key_lo); }
@@ -1687,9 +1261,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
         const int si = div_n(q), i = q - si * n;
         const int c = CH(si);
         const double val = LP(c) + (c == A.last[i] ? A.ppb[i] : A.full[i]);
-        LmAnswer ans; ans.sc = 0.f; ans.wi = 0u;
-        if (LM) ans = lmcA[(size_t)i * V + c];
-        child_lm<LM>(p, lt, A.lm[i], A.last[i], c, ans, Bm.lm[j]);
+        child_lm<LM>(p, lt, A.lm[i], A.last[i], c, answer_at<LM>(lmcA, (size_t)i * V + c), Bm.lm[j]);
         int k = atomicAdd(&s_next_node, 1);                                       // make_shared<Prefix>, :254
         if (k >= p.NCAP) { s_err = 1; k = 0; }
         else {
@@ -1725,34 +1297,12 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
           if ((u & mask) == prefix && u != kNoCandKey) atomicAdd(&hist[(int)((u >> shift) & dmask)], 1);
         }
         __syncthreads();
-        constexpr int kPer = kSelBins / kThreads;
-        const int top = kSelBins - 1 - kPer * tid;
-        int cnt[kPer], mine = 0;
-#pragma unroll
-        for (int jj = 0; jj < kPer; jj++) { cnt[jj] = hist[top - jj]; mine += cnt[jj]; }
-        const int inc = wave_scan_i(mine);
-        if (lane == 63) s_part[wid] = inc;
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < kPer; jj++) hist[top - jj] = 0;
-        int above = inc - mine;
-        {
-          const int wtot = wave_scan_i(lane < kThreads / 64 ? s_part[lane] : 0);
-          if (wid > 0) above += __builtin_amdgcn_readlane(wtot, wid - 1);
-        }
         const unsigned long long digit_mask = dmask << shift;
-        if (above < krem && above + mine >= krem) {
-#pragma unroll
-          for (int jj = 0; jj < kPer; jj++) {
-            if (above + cnt[jj] >= krem) {
-              s_krem = krem - above;
-              s_prefix = (prefix & ~digit_mask) | ((unsigned long long)(top - jj) << shift);
-              s_done = cnt[jj] == krem - above ? 1 : 0;     // the whole bin survives: no finer threshold needed
-              break;
-            }
-            above += cnt[jj];
-          }
-        }
+        select_digit<FullSync>(hist, hist, krem, s_part, [&](int rest, int digit, int count) {
+          s_krem = rest;
+          s_prefix = (prefix & ~digit_mask) | ((unsigned long long)digit << shift);
+          s_done = count == rest ? 1 : 0;     // the whole bin survives: no finer threshold needed
+        });
         mask |= digit_mask;
         __syncthreads();
         krem = s_krem; prefix = s_prefix; done = s_done != 0;
@@ -1779,22 +1329,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
       }
       const int M = tg + krem;                      // == W
       __syncthreads();
-      // ---- rank by (score desc, position asc): eight lanes count for one candidate ----
-      for (int e0 = 0; e0 < M; e0 += kThreads / 8) {
-        const int e = e0 + (tid >> 3), part = tid & 7;
-        int cnt = 0;
-        if (e < M) {
-          const unsigned long long ke = uskey[e];
-          for (int jj = part; jj < M; jj += 8) {
-            const unsigned long long kj = uskey[jj];
-            cnt += (kj > ke || (kj == ke && jj < e)) ? 1 : 0;
-          }
-        }
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0xB1, 0xf, 0xf, true);
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x4E, 0xf, 0xf, true);
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x141, 0xf, 0xf, true);
-        if (e < M && part == 0 && cnt < W) place(cnt, sidx[e]);
-      }
+      rank_gathered<1>(uskey, M, W, [&](int rank, int e) { place(rank, sidx[e]); });
     } else {
       // nothing is pruned: old members, then the pairs that exist, in order
       int mine = 0;
@@ -1811,19 +1346,7 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
       for (int j = tid; j < nsel; j += kThreads) place(j, sidx[j]);
     }
     gsync();
-    // ---- guards and child map of the new beam (see the fast kernel) ----
-    for (int j = tid; j < nsel; j += kThreads) {
-      Bm.inc[j] = ninf(); Bm.kept[j] = 0;
-      int go = Bm.gown[j], gc = Bm.gchar[j], gn = Bm.gnode[j];
-      while (go >= 0 && !A.kept[go]) { const int o = go; go = A.gown[o]; gc = A.gchar[o]; gn = A.gnode[o]; }
-      if (go >= 0) {
-        const int o = A.newpos[go];
-        Bm.gown[j] = o; Bm.gchar[j] = gc; Bm.gnode[j] = gn;
-        cmB.insert(o * V + gc, gn);
-      } else {
-        Bm.gown[j] = -1;
-      }
-    }
+    rebuild_guards(A, Bm, nsel, V, [&](int e, int node) { cmB.insert(e, node); });
     if (LM) {
       // the LM's answers for the new beam: rows copied with members that stay, asked for members that are new
       for (size_t e = tid; e < (size_t)nsel * V; e += kThreads) {
@@ -1838,29 +1361,9 @@ __global__ __launch_bounds__(kGenThreads) void ctc_beam_general_kernel(BeamParam
     if (s_err) break;
   }
 
-  // ---- final sort (:418-424) reduces to the best prefix; its sentence (:232-245) ----
-  {
-    Members A;
-    A.carve(mem0 + (size_t)cur * mbytes, W);
-    for (int i = tid; i < n; i += kThreads) fkey[i] = beam_score<LM>(p, A.ppnb[i], A.ppb[i], A.lm[i]);
-    __syncthreads();
-  }
-  int64_t* out = p.out + (int64_t)b * p.max_out;
-  for (int64_t i = tid; i < p.max_out; i += kThreads) out[i] = 0;
-  gsync();
-  if (tid == 0) {
-    int bi = 0;
-    for (int i = 1; i < n; i++) if (fkey[i] > fkey[bi]) bi = i;            // first maximum = (score desc, position asc)
-    Members A;
-    A.carve(mem0 + (size_t)cur * mbytes, W);
-    const int best = A.node[bi];
-    int64_t m = 0;
-    for (int k = best; k >= 0; k = nodes[k].parent) if (k == best || nodes[k].parent >= 0) m++;
-    int64_t at = m;
-    for (int k = best; k >= 0; k = nodes[k].parent)
-      if (k == best || nodes[k].parent >= 0) { at--; if (at < p.max_out) out[at] = nodes[k].last_char; }
-    p.out_len[b] = s_err ? (int64_t)-1 : m;
-  }
+  Members A;
+  A.carve(mem0 + (size_t)cur * mbytes, W);
+  read_out<LM>(p, A, n, fkey, nodes, s_err);
 }
 
 struct GenLayout { size_t gkey, lmc, gmem, total, lds; int CH; bool members_in_ws; };
@@ -1897,6 +1400,8 @@ BeamLayout beam_layout(int B, int T, int V, int W, bool lm = false) {
 
 }  // namespace
 }  // namespace e2e
+
+using namespace e2e;
 
 // does one workgroup's LDS hold the beam of this width over this alphabet? (the fast kernel)
 static bool beam_fits(int V, int W, bool lm) {
@@ -2010,17 +1515,16 @@ extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, i
 #undef E2E_GEN_OF
     E2E_HIP_CHECK(allow_dynamic_lds(gfn, (int)gl.lds), "hipFuncSetAttribute");
     void* gargs[] = { &p, &g };
-    E2E_HIP_CHECK(hipLaunchKernel(gfn, dim3(B), dim3(kGenThreads), gargs, gl.lds, s), "ctc_beam_general_kernel launch");
+    E2E_HIP_CHECK(hipLaunchKernel(gfn, dim3(B), dim3(kThreads), gargs, gl.lds, s), "ctc_beam_general_kernel launch");
     E2E_HIP_CHECK(hipGetLastError(), "ctc_beam_general_kernel launch");
     return E2E_OK;
   }
-#define E2E_BEAM_OF(IO) (!lm ? (const void*)&ctc_beam_kernel<IO, 0, kThreadsNoLm> : fast_lm ? (const void*)&ctc_beam_kernel<IO, 2, kThreadsLm> : (const void*)&ctc_beam_kernel<IO, 1, kThreadsLm>)
+#define E2E_BEAM_OF(IO) (!lm ? (const void*)&ctc_beam_kernel<IO, 0> : fast_lm ? (const void*)&ctc_beam_kernel<IO, 2> : (const void*)&ctc_beam_kernel<IO, 1>)
   const void* fn = dtype == E2E_F32 ? E2E_BEAM_OF(float) : dtype == E2E_F64 ? E2E_BEAM_OF(double) : dtype == E2E_F16 ? E2E_BEAM_OF(f16_t) : E2E_BEAM_OF(bf16_t);
 #undef E2E_BEAM_OF
-  const int nthreads = lm ? kThreadsLm : kThreadsNoLm;
   E2E_HIP_CHECK(allow_dynamic_lds(fn, (int)l.lds), "hipFuncSetAttribute");
   void* args[] = { &p };
-  E2E_HIP_CHECK(hipLaunchKernel(fn, dim3(B), dim3(nthreads), args, l.lds, s), "ctc_beam_kernel launch");
+  E2E_HIP_CHECK(hipLaunchKernel(fn, dim3(B), dim3(kThreads), args, l.lds, s), "ctc_beam_kernel launch");
   E2E_HIP_CHECK(hipGetLastError(), "ctc_beam_kernel launch");
   return E2E_OK;
 }

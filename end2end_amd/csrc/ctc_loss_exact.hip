@@ -44,16 +44,6 @@ struct ExactParams {
   int has_ext;        // mode 1: utterances whose numbers -- not whose inputs -- defeated the fast path are redone in extended range (ctc_ext.h)
 };
 
-__device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
-
-// src/utils/math_utils.h:8-16 (log(1.0 + x), not log1p)
-__device__ __forceinline__ double lse2(double a, double b) {
-  if (a == neg_inf()) return b;
-  if (b == neg_inf()) return a;
-  if (a > b) return a + log(1.0 + exp(b - a));
-  return b + log(1.0 + exp(a - b));
-}
-
 __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -438,7 +428,7 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
   if (!p.logprobs) {
     for (int t = wid; t < Tmax; t += kThreads / 64) {
       const IO* row = x + (int64_t)t * p.sT;
-      double m = neg_inf();
+      double m = ninf();
       for (int v = lane; v < V; v += 64) m = fmax(m, (double)row[(int64_t)v * p.sV]);
       m = wave_max(m);
       double s = 0.0;
@@ -695,7 +685,7 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
   }
   // ---- P1: alpha sweep, ctc_loss.cpp:33-61 ----
   for (int j = tid; j < L; j += kThreads) {
-    double a = neg_inf();
+    double a = ninf();
     if (j == 0 && (T > 1 || L == 1)) a = lp(0, ext[0]);
     if (j == 1) a = lp(0, ext[1]);
     buf0[j] = a;
@@ -708,7 +698,7 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
     const int start = max(0, L - 2 * (T - t)), end = min(2 * t + 2, L);
     double* warow = wa + (size_t)t * Lmax;
     for (int j = tid; j < L; j += kThreads) {
-      double a = neg_inf();
+      double a = ninf();
       if (j >= start && j < end) {
         const int cl = ext[j];
         a = prev[j];
@@ -731,7 +721,7 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
   __syncthreads();
 
   const double qnan = __builtin_nan("");
-  const bool infeasible = logZ == neg_inf();
+  const bool infeasible = logZ == ninf();
   if (infeasible && !blank_valued_label) {
     // infeasible alignment: the reference's exp(-inf - (-inf)) poisons the whole slab (Q2)
     for (size_t i = tid; i < (size_t)Tmax * V; i += kThreads) grads[i] = (IO)qnan;
@@ -751,7 +741,7 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
     double blank_part = 0.0;
     for (int j = tid; j < L; j += kThreads) {
       const int cl = ext[j];
-      double bt = neg_inf();
+      double bt = ninf();
       if (t == T - 1) {
         if (j == L - 1 && (T > 1 || L == 1)) bt = 0.0;
         if (j == L - 2) bt = 0.0;
@@ -764,7 +754,7 @@ __device__ __forceinline__ void ctc_exact_one(const ExactParams& p, unsigned cha
       }
       be_cur[j] = bt + lp(t, cl);
       // posterior of cell (j,t); exp(-inf)=0   (infeasible: 1 for a finite cell)
-      const double pj = infeasible ? ((warow[j] + bt > neg_inf()) ? 1.0 : 0.0) : exp(warow[j] + bt - logZ);
+      const double pj = infeasible ? ((warow[j] + bt > ninf()) ? 1.0 : 0.0) : exp(warow[j] + bt - logZ);
       if (j & 1) psorted[rank[j >> 1]] = pj; else blank_part += pj;
     }
     blank_part = wave_sum(blank_part);
