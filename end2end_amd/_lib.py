@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("E2E_CTC_LIB") or os.path.join(_HERE, "csrc", "libe2e_
 
 F32, F64, F16, BF16 = 0, 1, 2, 3
 ALGO_AUTO, ALGO_EXACT, ALGO_FAST = 0, 1, 2
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _lib = None
 _lock = threading.Lock()
@@ -64,6 +64,12 @@ def load():
                                            vp, vp, vp, C.c_size_t, C.c_int, vp]
         L.e2e_ctc_loss_fwd_bwd_opt.restype = C.c_int
         L.e2e_ctc_loss_fwd_bwd_opt.argtypes = L.e2e_ctc_loss_fwd_bwd.argtypes + [C.POINTER(LossOpts)]
+        L.e2e_ctc_noblank_workspace_bytes.restype = C.c_size_t
+        L.e2e_ctc_noblank_workspace_bytes.argtypes = [C.c_int] * 5
+        L.e2e_ctc_noblank_fwd_bwd.restype = C.c_int
+        L.e2e_ctc_noblank_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              vp, vp, vp, C.c_size_t, vp, C.POINTER(LossOpts)]
         L.e2e_ctc_scale_grads.restype = C.c_int
         L.e2e_ctc_scale_grads.argtypes = [vp, C.c_int, vp, C.c_int, i64, vp]
         L.e2e_ctc_greedy.restype = C.c_int

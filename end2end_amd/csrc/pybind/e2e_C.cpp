@@ -105,6 +105,34 @@ PYBIND11_MODULE(_C, m) {
         py::arg("workspace_bytes"), py::arg("algo"), py::arg("stream"), py::arg("grad_scale") = 1.0,
         py::arg("reduced") = 0, py::arg("reduction") = E2E_REDUCE_NONE, py::arg("chains") = E2E_CHAINS_F64);
 
+  m.def("ctc_noblank_workspace_bytes", [](int B, int T, int V, int Smax, int dtype) {
+    return e2e_ctc_noblank_workspace_bytes(B, T, V, Smax, dtype);
+  });
+
+  // (arguments the library would refuse are refused here too, before anything reaches the GPU)
+  m.def("ctc_noblank_fwd_bwd",
+        [](uintptr_t x, int dtype, bool input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
+           int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, int space_idx,
+           uintptr_t losses, uintptr_t grads, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
+           double grad_scale, uintptr_t reduced, int reduction) {
+          if (dtype != E2E_F32 && dtype != E2E_F64) throw py::value_error("ctc_noblank_fwd_bwd: dtype must be F32 or F64");
+          if (V < 1 || (space_idx != -1 && (space_idx < 0 || space_idx >= V)))
+            throw py::value_error("ctc_noblank_fwd_bwd: space_idx " + std::to_string(space_idx) + " is neither -1 nor in [0, " +
+                                  std::to_string(V) + ")");
+          if (reduction < E2E_REDUCE_NONE || reduction > E2E_REDUCE_MEAN || (reduction != E2E_REDUCE_NONE && !reduced))
+            throw py::value_error("ctc_noblank_fwd_bwd: bad reduction");
+          e2e_ctc_loss_opts o{grad_scale, ptr<void>(reduced), reduction, E2E_CHAINS_F64};
+          check(e2e_ctc_noblank_fwd_bwd(ptr<const void>(x), dtype, input_is_logprobs ? 1 : 0, sB, sT, sV,
+                                        ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
+                                        ptr<const int64_t>(t_len), B, T, V, Smax, space_idx, ptr<void>(losses),
+                                        ptr<void>(grads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("input_is_logprobs"), py::arg("sB"), py::arg("sT"), py::arg("sV"),
+        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
+        py::arg("V"), py::arg("Smax"), py::arg("space_idx"), py::arg("losses"), py::arg("grads"), py::arg("workspace"),
+        py::arg("workspace_bytes"), py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0,
+        py::arg("reduction") = E2E_REDUCE_NONE);
+
   m.def("ctc_scale_grads",
         [](uintptr_t grads, int dtype, uintptr_t scale, int B, int64_t row_elems, uintptr_t stream) {
           check(e2e_ctc_scale_grads(ptr<void>(grads), dtype, ptr<const void>(scale), B, row_elems, ptr<void>(stream)));

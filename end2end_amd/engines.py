@@ -3,6 +3,9 @@
 CTCLossEngine    <-> cpp_ctc_loss.CTCLossEngine     (src/losses/ctc_loss_py.cpp:8-16)
 CTCDecoderEngine <-> cpp_ctc_decoder.CTCDecoder     (src/decoders/ctc_decoder_py.cpp:8-38)
 
+and, with the same compute() contract, CTCWithoutBlankLossEngine for the blank-free loss (a numba function upstream,
+pytorch_end2end/functions/ctc_without_blank.py).
+
 Same constructor arguments, keyword names, defaults and results.  The top-level modules `cpp_ctc_loss` and
 `cpp_ctc_decoder` of this repository export them under the reference's names, so that the reference's own callers
 (`import_module("cpp_ctc_loss")`, pytorch_end2end/modules/ctc_loss.py:74; `import cpp_ctc_decoder`,
@@ -155,6 +158,65 @@ class CTCLossEngine:
                 _C.ctc_scale_grads(grads.data_ptr(), R.dtype_code(grads.dtype), scale.data_ptr(), B,
                                    grads.numel() // B, R.stream_handle(grads.device))
         return grads
+
+
+class CTCWithoutBlankLossEngine:
+    """space_idx -> .compute(logits, targets, logits_lengths, targets_lengths) -> (losses[B], grads[B,T,V]) for the
+    blank-free (ASG-style) lattice of pytorch_end2end/functions/ctc_without_blank.py:13-138 upstream, computed by
+    e2e_ctc_noblank_fwd_bwd.  The contract of CTCLossEngine.compute (devices, dtypes, `input_is_logprobs`, `grad_scale`,
+    `reduction`), so that ForwardBackwardLossFunction serves it unchanged; 16-bit inputs are up-cast to f32."""
+
+    def __init__(self, space_idx=-1):
+        self.space_idx = int(space_idx)
+
+    def compute(self, logits, targets, logits_lengths, targets_lengths, input_is_logprobs=True,
+                grad_scale=1.0, reduction=None):
+        if logits.dim() != 3:
+            raise ValueError("logits must be (batch, time, alphabet)")
+        src_device, src_dtype = logits.device, logits.dtype
+        dev = R.compute_device(logits)
+        x = logits.detach().to(dev)
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float32)
+        B, T, V = x.shape
+        if self.space_idx != -1 and not 0 <= self.space_idx < V:
+            raise ValueError("space_idx %d is neither -1 nor a label of the %d-column alphabet" % (self.space_idx, V))
+        targets = _as_long(targets, dev)
+        if targets.dim() != 2 or targets.shape[0] != B:
+            raise ValueError("targets must be (batch, max_target_length)")
+        xl = _as_long(logits_lengths, dev)
+        tl = _as_long(targets_lengths, dev)
+        if xl.numel() != B or tl.numel() != B:
+            raise ValueError("lengths must have one entry per utterance")
+        if reduction not in (None, "sum", "mean"):
+            raise ValueError("reduction must be None, 'sum' or 'mean'")
+        Smax = targets.shape[1]
+        if Smax == 0:
+            targets = torch.zeros((B, 1), dtype=torch.long, device=dev)
+        losses = torch.empty(B, dtype=x.dtype, device=dev)
+        grads = torch.empty((B, T, V), dtype=x.dtype, device=dev)
+        if B == 0:
+            out = (losses.to(src_device, src_dtype), grads.to(src_device, src_dtype))
+            return out if reduction is None else out + (getattr(out[0], reduction)(),)
+        reduced = torch.empty((), dtype=x.dtype, device=dev) if reduction else None
+        code = R.dtype_code(x.dtype)
+        with _on_device(dev):
+            ws = R.workspace(dev, _C.ctc_noblank_workspace_bytes(B, T, V, Smax, code))
+            sB, sT, sV = x.stride()
+            _C.ctc_noblank_fwd_bwd(x.data_ptr(), code, bool(input_is_logprobs), sB, sT, sV,
+                                   targets.data_ptr(), targets.stride(0), xl.data_ptr(), tl.data_ptr(),
+                                   B, T, V, Smax, self.space_idx, losses.data_ptr(), grads.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), R.stream_handle(dev), float(grad_scale),
+                                   reduced.data_ptr() if reduction else 0, _REDUCTIONS[reduction])
+        if src_device != dev or src_dtype != losses.dtype:
+            losses = losses.to(src_device, src_dtype)
+            if reduction:
+                reduced = reduced.to(src_device, src_dtype)
+        if src_device != dev or src_dtype != grads.dtype:
+            grads = grads.to(src_device, src_dtype)
+        return (losses, grads) if reduction is None else (losses, grads, reduced)
+
+    scale_grads_ = staticmethod(CTCLossEngine.scale_grads_)
 
 
 class LanguageModel:

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define E2E_CTC_ABI_VERSION 3
+#define E2E_CTC_ABI_VERSION 4
 
 /* element types of the logits / log-prob tensor (losses and grads use the same) */
 #define E2E_F32 0
@@ -140,6 +140,43 @@ int e2e_ctc_loss_fwd_bwd_opt(const void* x, int dtype, int input_is_logprobs,
  * (pytorch_end2end/functions/forward_backward.py:33) without a second (B,T,V) tensor. */
 int e2e_ctc_scale_grads(void* grads, int dtype, const void* scale /* (B) same dtype */,
                         int B, int64_t row_elems /* T*V */, void* stream);
+
+/* ------------------------------------------------------------------------
+ * CTC without blank (ASG-style) loss forward + backward (since ABI 4).
+ * Replaces pytorch_end2end.functions.ctc_without_blank.CTCWithoutBlankLossFunction
+ *   pytorch_end2end/functions/ctc_without_blank.py:13-138 (a numba lattice on host copies upstream).
+ *   x            (B,T,V) tensor with element strides sB,sT,sV (any strides); dtype E2E_F32 or E2E_F64 only -- the Python
+ *                engine up-casts 16-bit inputs to f32 before the call
+ *   input_is_logprobs
+ *                1: x holds log-probabilities -- upstream's function: grads = exp(x) - posterior on rows t < x_len[b];
+ *                0: x holds raw logits; log_softmax(dim=V) is fused in and grads are d loss / d logits
+ *                   (= softmax - posterior).
+ *                Either way padded rows t >= x_len[b] are 0 (upstream fills only rows t < x_len, np.zeros_like).
+ *   targets      (B,*) int64, row stride tgt_stride, first t_len[b] entries used
+ *   space_idx    -1 (none) or a label in [0,V) wrapped around the target: ext = [sp] + target + [sp]; an empty target or
+ *                the target [sp] gives ext = [space_idx].  Quirk Q10: space_idx = -1 with an empty target gives ext = [-1],
+ *                which upstream's numpy indexing reads as column V-1 -- reproduced.  Anything else: E2E_ERR_ARG.
+ *   lattice      from cell j a frame stays at j or moves to j+1 (no blank, no skip, repeats allowed); start cell 0
+ *                (and 1 with spaces), end cell L'-1 (and L'-2 with spaces)
+ *   x_len,t_len  (B) int64 (1 <= x_len[b] <= T, 0 <= t_len[b] <= Smax); lengths outside these ranges or a target outside
+ *                [0,V) give loss = NaN and a NaN gradient slab for that utterance only
+ *   losses       (B) same dtype as x (upstream always returns float32: a deliberate difference, as Q3, so that f64
+ *                gradcheck works); +inf for an infeasible utterance, whose rows t < x_len[b] are then NaN (as Q2)
+ *   grads        (B,T,V) contiguous, same dtype as x
+ *   workspace    >= e2e_ctc_noblank_workspace_bytes(...) bytes: per-frame row statistics and alpha checkpoints every
+ *                16 frames (B=256, T=1000, Smax=200: 29 MB)
+ *   opts         NULL, or e2e_ctc_loss_opts: grad_scale and reduced / reduction as for e2e_ctc_loss_fwd_bwd_opt; `chains`
+ *                is ignored
+ * f32 inputs run a rescaled probability-domain lattice with f64 cells; an utterance it cannot settle is redone in the f64
+ * log domain in the same call.  f64 inputs run the reference's log-domain arithmetic.  Targets of up to ~2 900 labels
+ * (the lattice rows live in one workgroup's LDS); beyond that E2E_ERR_UNSUPPORTED (workspace_bytes then returns 0).
+ */
+size_t e2e_ctc_noblank_workspace_bytes(int B, int T, int V, int Smax, int dtype);
+
+int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_logprobs, int64_t sB, int64_t sT, int64_t sV,
+                            const int64_t* targets, int64_t tgt_stride, const int64_t* x_len, const int64_t* t_len,
+                            int B, int T, int V, int Smax, int space_idx, void* losses, void* grads,
+                            void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_loss_opts* opts);
 
 /* ------------------------------------------------------------------------
  * Greedy decode.  Replaces cpp_ctc_decoder.CTCDecoder.decode_greedy

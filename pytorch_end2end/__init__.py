@@ -4,8 +4,10 @@
 
 works unchanged (pytorch_end2end/__init__.py:1-6 upstream), and so do the sub-module paths the reference's users and
 tests import (`pytorch_end2end.modules.ctc_loss`, `.decoders.ctc_decoder`, `.encoders.text_encoders`,
-`.functions.forward_backward`).  Only the CTC hot path exists here; the numba back-ends, Gram-CTC, CTC-without-blank
-and the alignment losses of the upstream package are out of scope.
+`.functions.forward_backward`, `.modules.ctc_without_blank`, `.functions.ctc_without_blank`,
+`.modules.alignment_loss`, `.utils.alignment`).  The numba back-ends of CTC without blank and of the alignment run as HIP
+kernels here; Gram-CTC (an empty stub upstream) and segmented CTC (not importable upstream) are out of scope (DESIGN.md
+section 7).
 """
 from end2end_amd import CTCDecoder, CTCDecoderError, CTCEncoder, CTCLoss, DecoderResults
 
