@@ -9,8 +9,8 @@ by hand-written HIP kernels (end2end_amd/csrc, C ABI in include/e2e_ctc.h).
 from .decoders.ctc_decoder import CTCDecoder, CTCDecoderError, DecoderResults
 from .encoders.text_encoders import CTCEncoder
 from .modules.alignment_loss import AlignedTargetsLoss
-from .modules.ctc_loss import CTCLoss
+from .modules.ctc_loss import CTCLoss, GramCTCLoss
 from .modules.ctc_without_blank import CTCWithoutBlankLoss
 
 __all__ = ["CTCLoss", "CTCDecoder", "CTCEncoder", "CTCDecoderError", "DecoderResults", "CTCWithoutBlankLoss",
-           "AlignedTargetsLoss"]
+           "AlignedTargetsLoss", "GramCTCLoss"]

@@ -70,6 +70,12 @@ def load():
         L.e2e_ctc_noblank_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               vp, vp, vp, C.c_size_t, vp, C.POINTER(LossOpts)]
+        L.e2e_gram_ctc_workspace_bytes.restype = C.c_size_t
+        L.e2e_gram_ctc_workspace_bytes.argtypes = [C.c_int] * 6
+        L.e2e_gram_ctc_fwd_bwd.restype = C.c_int
+        L.e2e_gram_ctc_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, i64p, vp, C.c_int, C.c_int, C.c_int,
+                                           vp, vp, vp, C.c_size_t, vp, C.POINTER(LossOpts)]
         L.e2e_ctc_scale_grads.restype = C.c_int
         L.e2e_ctc_scale_grads.argtypes = [vp, C.c_int, vp, C.c_int, i64, vp]
         L.e2e_ctc_greedy.restype = C.c_int
@@ -101,6 +107,8 @@ def load():
         L.e2e_ctc_align.restype = C.c_int
         L.e2e_ctc_align.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64, vp, C.c_size_t, vp]
+        L.e2e_debug_gram_redo_flags.restype = C.c_int
+        L.e2e_debug_gram_redo_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.e2e_debug_stream_copy.restype = C.c_int
         L.e2e_debug_stream_copy.argtypes = [vp, vp, C.c_size_t, vp]
         # (the dtype codes above are include/e2e_ctc.h's: the pybind layer, which is compiled against the header, carries them)

@@ -26,6 +26,7 @@
 // row that under/overflows, a final total of 0 or non-finite although the lattice is structurally feasible -- is redone
 // in the log domain by the same workgroup.  f64 input: the log domain throughout, upstream's log(1 + exp) and order.
 #include "common.h"
+#include "loss_rows.h"
 
 namespace e2e {
 namespace {
@@ -61,32 +62,7 @@ __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcn
 
 template <typename IO>
 __global__ __launch_bounds__(256) void noblank_rows_kernel(NbParams p, double* lse_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (int64_t)p.B * p.T) return;
-  const int b = (int)(row / p.T), t = (int)(row - (int64_t)b * p.T);
-  const int V = p.V;
-  IO* g = reinterpret_cast<IO*>(p.grads) + row * V;
-  const int64_t xl = p.x_len[b];
-  if (t >= xl) {                              // padded frame (and every frame of a bad length: the lattice writes its NaN slab)
-    for (int v = lane; v < V; v += 64) g[v] = (IO)0;
-    return;
-  }
-  const IO* x = reinterpret_cast<const IO*>(p.x) + (int64_t)b * p.sB + (int64_t)t * p.sT;
-  double lse = 0.0;
-  if (p.logits) {
-    double m = ninf();
-    for (int v = lane; v < V; v += 64) m = fmax(m, (double)x[(int64_t)v * p.sV]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    double s = 0.0;
-    for (int v = lane; v < V; v += 64) s += exp((double)x[(int64_t)v * p.sV] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    lse = m + log(s);
-    if (lane == 0) lse_out[row] = lse;
-  }
-  for (int v = lane; v < V; v += 64) g[v] = (IO)(p.gscale * exp((double)x[(int64_t)v * p.sV] - lse));
+  loss_rows<IO>(p, lse_out);
 }
 
 template <typename IO>

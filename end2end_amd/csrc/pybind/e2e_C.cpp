@@ -133,6 +133,36 @@ PYBIND11_MODULE(_C, m) {
         py::arg("workspace_bytes"), py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0,
         py::arg("reduction") = E2E_REDUCE_NONE);
 
+  m.def("gram_ctc_workspace_bytes", [](int B, int T, int V, int Smax, int max_order, int dtype) {
+    return e2e_gram_ctc_workspace_bytes(B, T, V, Smax, max_order, dtype);
+  });
+
+  m.def("gram_ctc_fwd_bwd",
+        [](uintptr_t x, int dtype, bool input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
+           int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, uintptr_t keys,
+           uintptr_t cols, int n_grams, int radix, int max_order, uintptr_t losses, uintptr_t grads, uintptr_t workspace,
+           size_t workspace_bytes, uintptr_t stream, double grad_scale, uintptr_t reduced, int reduction) {
+          if (dtype != E2E_F32 && dtype != E2E_F64) throw py::value_error("gram_ctc_fwd_bwd: dtype must be F32 or F64");
+          if (radix < 1 || radix > V)
+            throw py::value_error("gram_ctc_fwd_bwd: radix " + std::to_string(radix) + " is not in [1, " + std::to_string(V) + "]");
+          if (max_order < 1 || max_order > 8)
+            throw py::value_error("gram_ctc_fwd_bwd: max_order " + std::to_string(max_order) + " is not in [1, 8]");
+          if (n_grams < 0 || (n_grams > 0 && (!keys || !cols))) throw py::value_error("gram_ctc_fwd_bwd: bad gram table");
+          if (reduction < E2E_REDUCE_NONE || reduction > E2E_REDUCE_MEAN || (reduction != E2E_REDUCE_NONE && !reduced))
+            throw py::value_error("gram_ctc_fwd_bwd: bad reduction");
+          e2e_ctc_loss_opts o{grad_scale, ptr<void>(reduced), reduction, E2E_CHAINS_F64};
+          check(e2e_gram_ctc_fwd_bwd(ptr<const void>(x), dtype, input_is_logprobs ? 1 : 0, sB, sT, sV,
+                                     ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
+                                     ptr<const int64_t>(t_len), B, T, V, Smax, ptr<const int64_t>(keys),
+                                     ptr<const int32_t>(cols), n_grams, radix, max_order, ptr<void>(losses),
+                                     ptr<void>(grads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("input_is_logprobs"), py::arg("sB"), py::arg("sT"), py::arg("sV"),
+        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
+        py::arg("V"), py::arg("Smax"), py::arg("keys"), py::arg("cols"), py::arg("n_grams"), py::arg("radix"),
+        py::arg("max_order"), py::arg("losses"), py::arg("grads"), py::arg("workspace"), py::arg("workspace_bytes"),
+        py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0, py::arg("reduction") = E2E_REDUCE_NONE);
+
   m.def("ctc_scale_grads",
         [](uintptr_t grads, int dtype, uintptr_t scale, int B, int64_t row_elems, uintptr_t stream) {
           check(e2e_ctc_scale_grads(ptr<void>(grads), dtype, ptr<const void>(scale), B, row_elems, ptr<void>(stream)));

@@ -4,7 +4,8 @@ CTCLossEngine    <-> cpp_ctc_loss.CTCLossEngine     (src/losses/ctc_loss_py.cpp:
 CTCDecoderEngine <-> cpp_ctc_decoder.CTCDecoder     (src/decoders/ctc_decoder_py.cpp:8-38)
 
 and, with the same compute() contract, CTCWithoutBlankLossEngine for the blank-free loss (a numba function upstream,
-pytorch_end2end/functions/ctc_without_blank.py).
+pytorch_end2end/functions/ctc_without_blank.py) and GramCTCLossEngine <-> cpp_gram_ctc_loss.GramCTCLossEngine
+(src/losses/gram_ctc_loss_py.cpp; its compute_2d is empty upstream).
 
 Same constructor arguments, keyword names, defaults and results.  The top-level modules `cpp_ctc_loss` and
 `cpp_ctc_decoder` of this repository export them under the reference's names, so that the reference's own callers
@@ -208,6 +209,153 @@ class CTCWithoutBlankLossEngine:
                                    B, T, V, Smax, self.space_idx, losses.data_ptr(), grads.data_ptr(),
                                    ws.data_ptr(), ws.numel(), R.stream_handle(dev), float(grad_scale),
                                    reduced.data_ptr() if reduction else 0, _REDUCTIONS[reduction])
+        if src_device != dev or src_dtype != losses.dtype:
+            losses = losses.to(src_device, src_dtype)
+            if reduction:
+                reduced = reduced.to(src_device, src_dtype)
+        if src_device != dev or src_dtype != grads.dtype:
+            grads = grads.to(src_device, src_dtype)
+        return (losses, grads) if reduction is None else (losses, grads, reduced)
+
+    scale_grads_ = staticmethod(CTCLossEngine.scale_grads_)
+
+
+GRAM_MAX_ORDER = 8
+
+
+def gram_table(num_base_labels, total_labels, label2ids):
+    """Check upstream's (num_base_labels, total_labels, label2ids) and return the gram table of e2e_gram_ctc_fwd_bwd:
+    (keys int64 sorted ascending, their columns int32, max_order), host arrays.  Column 0 is the blank, columns
+    1 .. R-1 the unigrams, every column R .. V-1 a gram of label2ids (a sequence of 1..8 base ids in [1, R)); the key of
+    a gram is its sequence read as a number in radix R (upstream's get_hash, src/losses/gram_ctc_loss.cpp:22-28)."""
+    R, V = int(num_base_labels), int(total_labels)
+    if not 1 <= R <= V:
+        raise ValueError("num_base_labels %d and total_labels %d: need 1 <= num_base_labels <= total_labels" % (R, V))
+    grams = {c: (c,) for c in range(1, R)}
+    for key, ids in dict(label2ids).items():
+        c = int(key)
+        if c != key or not 1 <= c < V:
+            raise ValueError("label2ids key %r is not a column in [1, %d)" % (key, V))
+        seq = tuple(int(i) for i in ids)
+        if not 1 <= len(seq) <= GRAM_MAX_ORDER:
+            raise ValueError("column %d: a gram has 1 to %d base labels, not %d" % (c, GRAM_MAX_ORDER, len(seq)))
+        if any(not 1 <= i < R for i in seq):
+            raise ValueError("column %d: base label ids must be in [1, %d): %r" % (c, R, list(ids)))
+        if c < R and seq != (c,):
+            raise ValueError("column %d is the unigram [%d], not %r" % (c, c, list(ids)))
+        grams[c] = seq
+    missing = [c for c in range(R, V) if c not in grams]
+    if missing:
+        raise ValueError("label2ids has no entry for the gram columns %s" % missing[:10])
+    order = max((len(g) for g in grams.values()), default=1)
+    if R ** order > 2 ** 63 - 1:
+        raise ValueError("num_base_labels %d ** max_order %d overflows int64 keys" % (R, order))
+    keys = {}
+    for c in sorted(grams):
+        k = 0
+        for i in grams[c]:
+            k = k * R + i
+        if k in keys:
+            raise ValueError("columns %d and %d spell the same gram %r" % (keys[k], c, list(grams[c])))
+        keys[k] = c
+    ks = sorted(keys)
+    return np.array(ks, dtype=np.int64), np.array([keys[k] for k in ks], dtype=np.int32), order
+
+
+class GramCTCLossEngine:
+    """(blank_idx, num_base_labels, total_labels, label2ids) -> .compute(logits, targets, logits_lengths,
+    targets_lengths) -> (losses[B], grads[B,T,V]) for Gram-CTC, computed by e2e_gram_ctc_fwd_bwd (the definition:
+    include/e2e_ctc.h).  The contract of CTCLossEngine.compute, so that ForwardBackwardLossFunction serves it unchanged;
+    16-bit inputs are up-cast to f32.  Construction checks the table on the host; the device copy is made on first use
+    and kept per device."""
+
+    def __init__(self, blank_idx, num_base_labels, total_labels, label2ids):
+        if int(blank_idx) != 0:
+            raise NotImplementedError("Gram-CTC supports blank_idx=0 only (as upstream)")
+        self.blank_idx = 0
+        self.num_base_labels = int(num_base_labels)
+        self.total_labels = int(total_labels)
+        self._keys, self._cols, self.max_order = gram_table(num_base_labels, total_labels, label2ids)
+        self._per_device = {}
+        self._last = None
+
+    def redo_flags(self):
+        """Diagnostics (synchronises): per utterance of the last compute(), why it was redone in the f64 log domain -- 0 not
+        (or f64 input), 1 the probability-domain forward could not settle it (infeasible utterances included), 2 the backward
+        found a frame whose posteriors do not sum to 1 (e2e_debug_gram_redo_flags).  Read before another call on the stream
+        reuses the workspace."""
+        import ctypes
+        from . import _lib
+        ws, B, T, Smax = self._last
+        out = (ctypes.c_int * B)()
+        _lib.check(_lib.load().e2e_debug_gram_redo_flags(ctypes.c_void_p(ws.data_ptr()), B, T, Smax, self.max_order, out))
+        return np.array(out[:], dtype=np.int32)
+
+    def _table(self, dev):
+        t = self._per_device.get(dev.index)
+        if t is None:
+            t = (torch.from_numpy(self._keys).to(dev), torch.from_numpy(self._cols).to(dev))
+            self._per_device[dev.index] = t
+        return t
+
+    def max_target_length(self):
+        """The longest target the kernel serves at this table's max_order (its rows live in one workgroup's LDS)."""
+        lo, hi = 0, 1 << 16
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if _C.gram_ctc_workspace_bytes(1, 1, self.total_labels, mid, self.max_order, _C.F32) > 0:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    def compute(self, logits, targets, logits_lengths, targets_lengths, input_is_logprobs=True,
+                grad_scale=1.0, reduction=None):
+        if logits.dim() != 3:
+            raise ValueError("logits must be (batch, time, alphabet)")
+        if logits.shape[2] != self.total_labels:
+            raise ValueError("logits have %d columns; this Gram-CTC table has total_labels=%d"
+                             % (logits.shape[2], self.total_labels))
+        src_device, src_dtype = logits.device, logits.dtype
+        dev = R.compute_device(logits)
+        x = logits.detach().to(dev)
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float32)
+        B, T, V = x.shape
+        targets = _as_long(targets, dev)
+        if targets.dim() != 2 or targets.shape[0] != B:
+            raise ValueError("targets must be (batch, max_target_length)")
+        xl = _as_long(logits_lengths, dev)
+        tl = _as_long(targets_lengths, dev)
+        if xl.numel() != B or tl.numel() != B:
+            raise ValueError("lengths must have one entry per utterance")
+        if reduction not in (None, "sum", "mean"):
+            raise ValueError("reduction must be None, 'sum' or 'mean'")
+        Smax = targets.shape[1]
+        if Smax == 0:
+            targets = torch.zeros((B, 1), dtype=torch.long, device=dev)
+        losses = torch.empty(B, dtype=x.dtype, device=dev)
+        grads = torch.empty((B, T, V), dtype=x.dtype, device=dev)
+        if B == 0:
+            out = (losses.to(src_device, src_dtype), grads.to(src_device, src_dtype))
+            return out if reduction is None else out + (getattr(out[0], reduction)(),)
+        code = R.dtype_code(x.dtype)
+        nbytes = _C.gram_ctc_workspace_bytes(B, T, V, Smax, self.max_order, code)
+        if nbytes == 0:
+            raise ValueError("Gram-CTC: targets of %d labels exceed the %d the kernel serves at max_order %d"
+                             % (Smax, self.max_target_length(), self.max_order))
+        reduced = torch.empty((), dtype=x.dtype, device=dev) if reduction else None
+        keys, cols = self._table(dev)
+        with _on_device(dev):
+            ws = R.workspace(dev, nbytes)
+            sB, sT, sV = x.stride()
+            _C.gram_ctc_fwd_bwd(x.data_ptr(), code, bool(input_is_logprobs), sB, sT, sV,
+                                targets.data_ptr(), targets.stride(0), xl.data_ptr(), tl.data_ptr(),
+                                B, T, V, Smax, keys.data_ptr(), cols.data_ptr(), keys.numel(), self.num_base_labels,
+                                self.max_order, losses.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws.numel(),
+                                R.stream_handle(dev), float(grad_scale), reduced.data_ptr() if reduction else 0,
+                                _REDUCTIONS[reduction])
+        self._last = (ws, B, T, Smax)
         if src_device != dev or src_dtype != losses.dtype:
             losses = losses.to(src_device, src_dtype)
             if reduction:

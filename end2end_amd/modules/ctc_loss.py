@@ -10,7 +10,7 @@ Differences that do not change results:
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..engines import CTCLossEngine
+from ..engines import CTCLossEngine, GramCTCLossEngine
 from ..functions.forward_backward import ForwardBackwardLossFunction
 
 
@@ -69,8 +69,31 @@ class CTCLoss(ForwardBackwardLossBase):
 
 
 class GramCTCLoss(CTCLoss):
-    """Gram-CTC is an unfinished stub upstream (empty compute_2d, src/losses/gram_ctc_loss.cpp:30-37;
-    the module raises, pytorch_end2end/modules/ctc_loss.py:94-106) and is out of scope here."""
+    """
+    Gram-CTC loss (Liu et al., ICML 2017, `<https://arxiv.org/abs/1703.00096>`_): the model may emit whole n-grams of
+    base labels as single columns.  A path's labelling collapses runs of one column, drops blanks and concatenates the
+    grams' base sequences; the loss is -log of the total probability of the paths that spell the target.  Computed by
+    e2e_gram_ctc_fwd_bwd (definition and limits: include/e2e_ctc.h).
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("Gram-CTC is not implemented (neither is it upstream)")
+    :param blank_idx: id of the blank label, only ``0`` supported
+    :param num_base_labels: R, the base labels with the blank counted: targets hold ids ``1 .. R-1``
+    :param total_labels: V, the columns of the logits: ``1 .. R-1`` the unigrams, ``R .. V-1`` the grams
+    :param label2ids: ``{column: [base ids]}`` for every column ``>= R`` (1 to 8 ids each); entries for ``c < R`` must be
+        ``[c]``
+    :param size_average: average (instead of sum) over the batch; only with ``reduce``
+    :param reduce: reduce to a scalar; ``None`` returns the ``(batch,)`` vector
+    :param after_logsoftmax: inputs are already log-probabilities
+    :param time_major: inputs are ``(time, batch, alphabet)``
+    :param fused: (extension) fuse log-softmax into the kernel when ``after_logsoftmax`` is False
+    """
+
+    def __init__(self, blank_idx, num_base_labels, total_labels, label2ids,
+                 size_average=None, reduce=None, after_logsoftmax=False, time_major=False, fused=True):
+        ForwardBackwardLossBase.__init__(self, size_average, reduce, after_logsoftmax, time_major, blank_idx)
+        if self._blank_idx != 0:
+            raise NotImplementedError("Gram-CTC supports blank_idx=0 only (as upstream)")
+        self._fused = fused
+        self._num_base_labels = num_base_labels
+        self._total_labels = total_labels
+        self._label2ids = label2ids
+        self._engine = GramCTCLossEngine(self._blank_idx, self._num_base_labels, self._total_labels, self._label2ids)

@@ -179,6 +179,49 @@ int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_logprobs, int
                             void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_loss_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * Gram-CTC loss forward + backward (since ABI 4; Liu et al., ICML 2017, arXiv:1703.00096).
+ * Replaces cpp_gram_ctc_loss.GramCTCLossEngine(blank_idx, num_base_labels, total_labels, label2ids).compute(...), whose
+ *   compute_2d is empty upstream (src/losses/gram_ctc_loss.cpp:30-37).  The definition (upstream never fixed one):
+ *   columns      0 the blank; c in [1, radix) the unigram (c); c in [radix, V) a gram, a sequence of 1..8 base labels
+ *   labelling    of a path (one column per frame): collapse runs of one column, drop blanks, concatenate the grams'
+ *                base sequences.  The loss is -log of the total probability of the paths whose labelling is the target.
+ *                Two identical grams in a row need a blank between them; different grams do not.
+ *   lattice      boundaries j = 0..S of the target: a blank state at each, a gram state (j, k) wherever y[j-k..j-1] is a
+ *                gram (k <= max_order).  blank(j) <- itself, every gram state ending at j; gram(j, k) <- itself,
+ *                blank(j-k), every gram state ending at j-k but one of the same column.  Start blank(0), gram(k, k); end
+ *                blank(S), every gram(S, k).  With unigrams only (V = radix) this is CTC with blank 0.
+ * Parameters as e2e_ctc_noblank_fwd_bwd, without space_idx, and:
+ *   targets      (B,*) int64 base-label ids in [1, radix); a target outside that range, or x_len / t_len outside
+ *                1 <= x_len[b] <= T, 0 <= t_len[b] <= Smax, gives loss = NaN and a NaN gradient slab for that utterance
+ *   keys, cols   the gram table, device: n_grams int64 keys sorted ascending and the int32 column of each.  The key of a
+ *                gram (y_1 .. y_k) is the polynomial y_1 * radix^(k-1) + ... + y_k (ids >= 1: keys of different orders
+ *                never collide).  It holds every column in [1, V): the unigram c has the key c.  Keys must be distinct.
+ *   n_grams      entries of the table (>= 0; keys / cols may be NULL when 0)
+ *   radix        R = number of base labels, the blank counted: base ids are 1 .. R-1; 1 <= R <= V
+ *   max_order    the longest gram, 1..8; radix ** max_order must fit in int64
+ *   losses       (B) same dtype as x; +inf for an infeasible utterance (no path spells the target in x_len[b] frames, or
+ *                every such path has probability 0), whose rows t < x_len[b] are then NaN
+ *   grads        (B,T,V) contiguous, same dtype as x: softmax - posterior (input_is_logprobs = 0) or exp(x) - posterior
+ *                (1) on rows t < x_len[b], 0 beyond
+ *   workspace    >= e2e_gram_ctc_workspace_bytes(...) bytes: per-frame row statistics and alpha checkpoints every 16
+ *                frames, B*T*8 + B*ceil(T/16)*((Smax+1)*(max_order+1)*8 + 4) + B*4 bytes (B=256, T=1000, Smax=200,
+ *                max_order=3: 106 MB)
+ *   opts         NULL, or e2e_ctc_loss_opts: grad_scale and reduced / reduction as for e2e_ctc_loss_fwd_bwd_opt; `chains`
+ *                is ignored
+ * f32 inputs run a rescaled probability-domain lattice with f64 cells; an utterance it cannot settle is redone in the f64
+ * log domain in the same call.  f64 inputs run the log domain throughout.  The lattice rows live in one workgroup's LDS:
+ * targets of up to Smax = 668 labels at max_order 3 (1 316 at 1, 887 at 2, 536 at 4, 299 at 8); beyond that the call
+ * returns E2E_ERR_UNSUPPORTED and e2e_gram_ctc_workspace_bytes returns 0.
+ */
+size_t e2e_gram_ctc_workspace_bytes(int B, int T, int V, int Smax, int max_order, int dtype);
+
+int e2e_gram_ctc_fwd_bwd(const void* x, int dtype, int input_is_logprobs, int64_t sB, int64_t sT, int64_t sV,
+                         const int64_t* targets, int64_t tgt_stride, const int64_t* x_len, const int64_t* t_len,
+                         int B, int T, int V, int Smax, const int64_t* keys, const int32_t* cols, int n_grams,
+                         int radix, int max_order, void* losses, void* grads,
+                         void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_loss_opts* opts);
+
+/* ------------------------------------------------------------------------
  * Greedy decode.  Replaces cpp_ctc_decoder.CTCDecoder.decode_greedy
  *   src/decoders/ctc_decoder.cpp:443-490 (argmax + blank/repeat collapse).
  *   x        (B,T,V) logits or log-probs, strides sB,sT,sV, f32/f64

@@ -34,6 +34,11 @@ int e2e_debug_fast_state(const void* workspace, int B, int T, int V, int Smax, i
  * recomputed by the exact kernel).  Synchronises. */
 int e2e_debug_fast_redo_failures(const void* workspace, int B, int T, int V, int Smax, int* count_host);
 
+/* After an e2e_gram_ctc_fwd_bwd call with this workspace and these sizes: per utterance, why it was redone in the f64 log
+ * domain (0 it was not, or the input was f64; 1 the probability-domain forward could not settle it, an infeasible utterance
+ * included; 2 the backward found a frame whose posteriors do not sum to 1, or a beta row out of range).  Synchronises. */
+int e2e_debug_gram_redo_flags(const void* workspace, int B, int T, int Smax, int max_order, int* flags_host);
+
 /* The flagged-utterance launch of that call as its workgroup 0 saw it, microseconds since the launch's start (100 MHz clock):
  * us[0] end of its f64 redos of single segments, [1] of the wait for the other workgroups, [2] of its extended-range chains,
  * [3] of its extended-range segments, [4] end of the launch's last workgroup, [5] when that workgroup learnt it was the last

@@ -6,8 +6,8 @@ works unchanged (pytorch_end2end/__init__.py:1-6 upstream), and so do the sub-mo
 tests import (`pytorch_end2end.modules.ctc_loss`, `.decoders.ctc_decoder`, `.encoders.text_encoders`,
 `.functions.forward_backward`, `.modules.ctc_without_blank`, `.functions.ctc_without_blank`,
 `.modules.alignment_loss`, `.utils.alignment`).  The numba back-ends of CTC without blank and of the alignment run as HIP
-kernels here; Gram-CTC (an empty stub upstream) and segmented CTC (not importable upstream) are out of scope (DESIGN.md
-section 7).
+kernels here, and so does Gram-CTC (`.modules.ctc_loss.GramCTCLoss`, an empty stub upstream).
+Segmented CTC (not importable upstream) is out of scope.
 """
 from end2end_amd import CTCDecoder, CTCDecoderError, CTCEncoder, CTCLoss, DecoderResults
 
