@@ -109,6 +109,8 @@ def load():
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64, vp, C.c_size_t, vp]
         L.e2e_debug_gram_redo_flags.restype = C.c_int
         L.e2e_debug_gram_redo_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.e2e_debug_noblank_redo_flags.restype = C.c_int
+        L.e2e_debug_noblank_redo_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.e2e_debug_stream_copy.restype = C.c_int
         L.e2e_debug_stream_copy.argtypes = [vp, vp, C.c_size_t, vp]
         # (the dtype codes above are include/e2e_ctc.h's: the pybind layer, which is compiled against the header, carries them)

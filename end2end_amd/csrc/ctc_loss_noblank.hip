@@ -32,8 +32,10 @@ namespace e2e {
 namespace {
 
 constexpr int kNbThreads = 256;
-constexpr int kNbBlk = 16;                   // frames per block = checkpoint interval (fewer when a row is very long)
-constexpr size_t kNbLdsMax = 160 * 1024 - 256;   // LDS of one gfx950 workgroup, less the kernel's own words
+constexpr int kNbBlk = 16;                   // frames per block = checkpoint interval (fewer from Smax 236 on: nb_block)
+// LDS of one gfx950 workgroup, less the lattice kernel's static LDS: 288 bytes (f32; 272 f64), its own words and
+// __syncthreads_or's; tests/test_noblank_cpu.py checks the built kernels against it
+constexpr size_t kNbLdsMax = 160 * 1024 - 288;
 constexpr double kLowLp = -700.0;            // a finite log-probability below this sends an f32 utterance to the log domain
 
 struct NbParams {
@@ -65,8 +67,9 @@ __global__ __launch_bounds__(256) void noblank_rows_kernel(NbParams p, double* l
   loss_rows<IO>(p, lse_out);
 }
 
+// redo: [B] 0, or why the utterance was redone in the log domain (1 forward, 2 backward)
 template <typename IO>
-__global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p) {
+__global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p, int* redo) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Tmax = p.T, V = p.V, K = p.K, Lm = p.Lmax;
@@ -87,6 +90,7 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p)
   const int T = bad_len ? 0 : (int)Tq, S = bad_len ? 0 : (int)Sq;
   const int64_t* tg = p.targets + (int64_t)b * p.tgt_stride;
   const int sp = p.space;
+  if (tid == 0) redo[b] = 0;
 
   // ---- the extended target ----
   int bad = bad_len;
@@ -244,7 +248,11 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p)
       zm = two ? Q[L - 1] + Q[L - 2] : Q[L - 1];
       const int fail = __syncthreads_or(range_bad || s_flag || !(zm > 0.0) || !(zm < INFINITY));
       cend = s_cend;
-      if (fail) { logd = true; continue; }           // this utterance goes to the log domain
+      if (fail) {                                    // this utterance goes to the log domain
+        if (tid == 0) redo[b] = 1;
+        logd = true;
+        continue;
+      }
       logz = log(zm) + (double)cend * 0.69314718055994530942;
     }
     __syncthreads();                                 // (the last alpha row is read; beta takes its buffer)
@@ -342,6 +350,7 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p)
     }
     finish(0, 0, kNbThreads);
     if (logd || !__syncthreads_or(lost)) break;
+    if (tid == 0) redo[b] = 2;
     logd = true;
   }
 }
@@ -358,7 +367,7 @@ int nb_block(int Lmax) {
   return 0;
 }
 
-struct NbLayout { size_t lse, ck, ckc, total; int K, NB, Lmax; };
+struct NbLayout { size_t lse, ck, ckc, redo, total; int K, NB, Lmax; };
 NbLayout nb_layout(int B, int T, int Smax) {
   NbLayout l{};
   l.Lmax = nb_lmax(Smax);
@@ -368,7 +377,8 @@ NbLayout nb_layout(int B, int T, int Smax) {
   l.lse = 0;
   l.ck = align_up((size_t)B * T * sizeof(double), 256);
   l.ckc = l.ck + align_up((size_t)B * l.NB * l.Lmax * sizeof(double), 256);
-  l.total = l.ckc + align_up((size_t)B * l.NB * sizeof(int), 256);
+  l.redo = l.ckc + align_up((size_t)B * l.NB * sizeof(int), 256);
+  l.total = l.redo + align_up((size_t)B * sizeof(int), 256);
   return l;
 }
 
@@ -410,6 +420,7 @@ extern "C" int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_lo
   p.K = l.K; p.NB = l.NB; p.Lmax = l.Lmax; p.gscale = opts ? opts->grad_scale : 1.0;
   p.losses = losses; p.grads = grads;
   p.lse = reinterpret_cast<const double*>(ws + l.lse); p.ck = reinterpret_cast<double*>(ws + l.ck); p.ckc = reinterpret_cast<int*>(ws + l.ckc);
+  int* redo = reinterpret_cast<int*>(ws + l.redo);
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = nb_lds_bytes(l.K, l.Lmax);
   const unsigned rows_grid = (unsigned)(((int64_t)B * T + 3) / 4);
@@ -418,12 +429,12 @@ extern "C" int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_lo
     hipLaunchKernelGGL(noblank_rows_kernel<float>, dim3(rows_grid), dim3(256), 0, s, p, lse_out);
     E2E_HIP_CHECK(hipGetLastError(), "noblank_rows_kernel launch");
     E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&noblank_lattice_kernel<float>), (int)lds), "hipFuncSetAttribute");
-    hipLaunchKernelGGL(noblank_lattice_kernel<float>, dim3(B), dim3(kNbThreads), lds, s, p);
+    hipLaunchKernelGGL(noblank_lattice_kernel<float>, dim3(B), dim3(kNbThreads), lds, s, p, redo);
   } else {
     hipLaunchKernelGGL(noblank_rows_kernel<double>, dim3(rows_grid), dim3(256), 0, s, p, lse_out);
     E2E_HIP_CHECK(hipGetLastError(), "noblank_rows_kernel launch");
     E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&noblank_lattice_kernel<double>), (int)lds), "hipFuncSetAttribute");
-    hipLaunchKernelGGL(noblank_lattice_kernel<double>, dim3(B), dim3(kNbThreads), lds, s, p);
+    hipLaunchKernelGGL(noblank_lattice_kernel<double>, dim3(B), dim3(kNbThreads), lds, s, p, redo);
   }
   E2E_HIP_CHECK(hipGetLastError(), "noblank_lattice_kernel launch");
   if (opts && opts->reduced && opts->reduction != E2E_REDUCE_NONE) {
@@ -432,5 +443,19 @@ extern "C" int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_lo
     a.reduced = opts->reduced; a.reduction = opts->reduction;
     return launch_reduce_losses(a);
   }
+  return E2E_OK;
+}
+
+// Diagnostics: after an e2e_ctc_noblank_fwd_bwd call with this workspace, why each utterance was redone in the log domain
+// (0 not redone, f64 input, or no lattice run; 1 the forward could not settle it, 2 the backward lost mass or range).
+// Synchronises.
+extern "C" int e2e_debug_noblank_redo_flags(const void* workspace, int B, int T, int Smax, int* flags_host) {
+  if (!workspace || !flags_host || B < 1 || T < 1 || Smax < 0) { set_error("bad arguments"); return E2E_ERR_ARG; }
+  const NbLayout l = nb_layout(B, T, Smax);
+  if (l.K == 0) { set_error("no such layout"); return E2E_ERR_UNSUPPORTED; }
+  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
+  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
+  E2E_HIP_CHECK(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  E2E_HIP_CHECK(hipMemcpy(flags_host, ws + l.redo, sizeof(int) * B, hipMemcpyDeviceToHost), "hipMemcpy");
   return E2E_OK;
 }

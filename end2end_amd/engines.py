@@ -169,6 +169,19 @@ class CTCWithoutBlankLossEngine:
 
     def __init__(self, space_idx=-1):
         self.space_idx = int(space_idx)
+        self._last = None
+
+    def redo_flags(self):
+        """Diagnostics (synchronises): per utterance of the last compute(), why it was redone in the f64 log domain -- 0 not
+        (or f64 input, or no lattice to run: bad lengths or labels, more labels than frames), 1 the probability-domain
+        forward could not settle it, 2 the backward found a frame whose posteriors do not sum to 1
+        (e2e_debug_noblank_redo_flags).  Read before another call on the stream reuses the workspace."""
+        import ctypes
+        from . import _lib
+        ws, B, T, Smax = self._last
+        out = (ctypes.c_int * B)()
+        _lib.check(_lib.load().e2e_debug_noblank_redo_flags(ctypes.c_void_p(ws.data_ptr()), B, T, Smax, out))
+        return np.array(out[:], dtype=np.int32)
 
     def compute(self, logits, targets, logits_lengths, targets_lengths, input_is_logprobs=True,
                 grad_scale=1.0, reduction=None):
@@ -209,6 +222,7 @@ class CTCWithoutBlankLossEngine:
                                    B, T, V, Smax, self.space_idx, losses.data_ptr(), grads.data_ptr(),
                                    ws.data_ptr(), ws.numel(), R.stream_handle(dev), float(grad_scale),
                                    reduced.data_ptr() if reduction else 0, _REDUCTIONS[reduction])
+        self._last = (ws, B, T, Smax)
         if src_device != dev or src_dtype != losses.dtype:
             losses = losses.to(src_device, src_dtype)
             if reduction:

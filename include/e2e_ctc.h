@@ -163,13 +163,15 @@ int e2e_ctc_scale_grads(void* grads, int dtype, const void* scale /* (B) same dt
  *   losses       (B) same dtype as x (upstream always returns float32: a deliberate difference, as Q3, so that f64
  *                gradcheck works); +inf for an infeasible utterance, whose rows t < x_len[b] are then NaN (as Q2)
  *   grads        (B,T,V) contiguous, same dtype as x
- *   workspace    >= e2e_ctc_noblank_workspace_bytes(...) bytes: per-frame row statistics and alpha checkpoints every
- *                16 frames (B=256, T=1000, Smax=200: 29 MB)
+ *   workspace    >= e2e_ctc_noblank_workspace_bytes(...) bytes: per-frame row statistics, alpha checkpoints every K
+ *                frames (K below) and a per-utterance redo flag (B=256, T=1000, Smax=200: 29 MB)
  *   opts         NULL, or e2e_ctc_loss_opts: grad_scale and reduced / reduction as for e2e_ctc_loss_fwd_bwd_opt; `chains`
  *                is ignored
  * f32 inputs run a rescaled probability-domain lattice with f64 cells; an utterance it cannot settle is redone in the f64
- * log domain in the same call.  f64 inputs run the reference's log-domain arithmetic.  Targets of up to ~2 900 labels
- * (the lattice rows live in one workgroup's LDS); beyond that E2E_ERR_UNSUPPORTED (workspace_bytes then returns 0).
+ * log domain in the same call.  f64 inputs run the reference's log-domain arithmetic.  The lattice rows live in one
+ * workgroup's LDS, in blocks of K frames, K the checkpoint interval: K = 16 up to Smax = 235, then fewer (15 from 236, 11
+ * from 308, 8 from 399, 5 from 566, 3 from 784, 2 from 972, 1 from 1 276).  Targets of up to Smax = 1 855 labels; beyond
+ * that E2E_ERR_UNSUPPORTED (workspace_bytes then returns 0).
  */
 size_t e2e_ctc_noblank_workspace_bytes(int B, int T, int V, int Smax, int dtype);
 

@@ -39,6 +39,11 @@ int e2e_debug_fast_redo_failures(const void* workspace, int B, int T, int V, int
  * included; 2 the backward found a frame whose posteriors do not sum to 1, or a beta row out of range).  Synchronises. */
 int e2e_debug_gram_redo_flags(const void* workspace, int B, int T, int Smax, int max_order, int* flags_host);
 
+/* The same after an e2e_ctc_noblank_fwd_bwd call with this workspace and these sizes (0 also for an utterance with no lattice
+ * to run: bad lengths or labels, or more labels than frames; 1 the probability-domain forward could not settle it; 2 the
+ * backward found a frame whose posteriors do not sum to 1, or a beta row out of range).  Synchronises. */
+int e2e_debug_noblank_redo_flags(const void* workspace, int B, int T, int Smax, int* flags_host);
+
 /* The flagged-utterance launch of that call as its workgroup 0 saw it, microseconds since the launch's start (100 MHz clock):
  * us[0] end of its f64 redos of single segments, [1] of the wait for the other workgroups, [2] of its extended-range chains,
  * [3] of its extended-range segments, [4] end of the launch's last workgroup, [5] when that workgroup learnt it was the last

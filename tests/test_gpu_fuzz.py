@@ -13,6 +13,10 @@ Families (cases; what they drive):
   exact    120                          E2E_ALGO_EXACT, f32 and f64, log domain
   fastauto 120                          unit-noise / trained-model emissions: the fast path proper (AUTO), ragged, any blank
   align    60                           e2e_ctc_align, bit-exact
+  noblank  98 (f32 + f64, x 2 widths)   CTC without blank against tests/noblank_ref.py: every LDS block size K = 16..1
+  gram     98 (f32 + f64, x 2 widths)   Gram-CTC against tests/gram_ref.py: every (max_order, K) of orders 1..8
+(noblank and gram compare with the f64 test-side references, not the oracle: each case runs with targets exactly max(t_len)
+wide and padded wider with garbage, and both runs must match; the tests assert the block sizes and redo reasons they reach.)
 The beam search's slice of the same kind lives in tests/test_gpu_beam.py::test_fuzz_slice_equals_the_oracle_or_is_a_proven_tie
 (220 cases, run through both kernels).  The counts are printed in pytest's summary (tests/conftest.py).
 """
@@ -23,10 +27,14 @@ import numpy as np
 import pytest
 import torch
 
+import gram_ref as GR
+import noblank_ref as NR
 import oracle_lib as O
 import gpu_util as U
 from end2end_amd import _lib
 from test_gpu_align import c_abi_align
+from test_gpu_gram import gc_block
+from test_gpu_noblank import nb_block
 
 pytestmark = pytest.mark.gpu
 
@@ -405,3 +413,344 @@ def test_batches_beyond_the_cu_count_take_the_shallow_probability_ring(shape):
     U.assert_same(ga, g_o, 1e-4, 2e-6, "grads")
     lf, _ = U.c_abi_loss(torch.from_numpy(x), tg, xl, tl, 0, False, _lib.ALGO_FAST)
     assert not np.isnan(lf).any(), "the fast path gave up on %s" % np.nonzero(np.isnan(lf))[0].tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# noblank / gram: CTC without blank (ctc_loss_noblank.hip) and Gram-CTC (ctc_loss_gram.hip) against the f64 test-side
+# references on exactly the log-probabilities the kernel sees.  The padded target width picks the LDS block K and the row
+# layout, so every case runs twice: targets exactly max(t_len) wide, then wider (within capacity) with garbage beyond t_len.
+# ---------------------------------------------------------------------------------------------------------------------
+DEV = torch.device("cuda", 0)
+
+
+def _bands(block, last):
+    """{K: (first, last width)} of a block-size function over the widths 0..last"""
+    out = {}
+    for s in range(last + 1):
+        k = block(s)
+        out[k] = (out.get(k, (s, s))[0], s)
+    return out
+
+
+NB_LAST = 1855                                       # the longest target the no-blank kernel serves
+NB_BANDS = _bands(nb_block, NB_LAST)
+GC_LAST = {M: max(s for s in range(1400) if gc_block(s, M)) for M in range(1, 9)}
+GC_BANDS = {M: _bands(lambda s: gc_block(s, M), GC_LAST[M]) for M in range(1, 9)}
+GC_PAIRS = sorted((M, K) for M in GC_BANDS for K in GC_BANDS[M])
+
+
+def _wider(bands, W, rng):
+    """a padded width beyond W, in a random block-size band that has one"""
+    ks = sorted(k for k, (lo, hi) in bands.items() if hi > W)
+    lo, hi = bands[int(rng.choice(ks))]
+    return int(rng.integers(max(lo, W + 1), hi + 1))
+
+
+def _lengths(rng, need, K, T):
+    """x_len >= need: exactly need, ending on the first or the last frame of a block, anywhere; one frame short (infeasible)
+    now and then"""
+    kind = int(rng.integers(0, 6))
+    if kind == 5 and need >= 2:
+        return min(need - 1, T)
+    x = [need, -(-(need - 1) // K) * K + 1, -(-need // K) * K, int(rng.integers(need, max(need, T) + 1))][min(kind, 3)]
+    return min(max(x, need), T)
+
+
+def _on_gpu(x, view):
+    """x (B, T, V) on the GPU as it is, as a time-major view (a permuted copy) or column-strided (sV = 2)"""
+    if view == "time_major":
+        return x.permute(1, 0, 2).contiguous().to(DEV).permute(1, 0, 2)
+    if view == "strided":
+        w = torch.zeros(x.shape[0], x.shape[1], 2 * x.shape[2], dtype=x.dtype, device=DEV)
+        w[:, :, ::2] = x.to(DEV)
+        return w[:, :, ::2]
+    return x.to(DEV)
+
+
+def _padded(tg, tl, width, V, rng):
+    """targets `width` wide: row b holds tg[b, :tl[b]], then garbage (-1, V or 2**40)"""
+    out = np.empty((len(tl), width), dtype=np.int64)
+    for b in range(len(tl)):
+        out[b] = [-1, V, 1 << 40][int(rng.integers(0, 3))]
+        out[b, :tl[b]] = tg[b, :tl[b]]
+    return torch.from_numpy(out)
+
+
+def _differs(got_l, got_g, want_l, want_g, tol):
+    """None, or what differs: the inf/NaN pattern exactly, losses within tol * max(1, |want|), gradients within tol"""
+    inf = np.isinf(want_l)
+    if not (np.array_equal(np.isinf(got_l), inf) and np.array_equal(np.isnan(got_l), np.isnan(want_l))
+            and np.array_equal(got_l[inf], want_l[inf])):
+        return "losses %s, want %s" % (got_l.tolist(), want_l.tolist())
+    fin = np.isfinite(want_l)
+    dl = np.abs(got_l[fin] - want_l[fin]) / np.maximum(1.0, np.abs(want_l[fin]))
+    if (dl > tol).any():
+        return "losses off by %.3g (relative) at %s" % (dl.max(), np.flatnonzero(fin)[dl > tol].tolist())
+    if not np.array_equal(np.isnan(got_g), np.isnan(want_g)):
+        return "NaN pattern of the gradient, utterances %s" % sorted(set(np.nonzero(np.isnan(got_g) != np.isnan(want_g))[0].tolist()))
+    ok = ~np.isnan(want_g)
+    dg = np.max(np.abs(got_g[ok] - want_g[ok]), initial=0.0)
+    return None if dg <= tol else "gradient off by %.3g" % dg
+
+
+def _run_twice(family, c, eng, want_l, want_g, rng, block, reached, reasons):
+    """c's call at its exact and its padded width -> [(run, width, what differs)]; adds the block sizes reached and, for f32,
+    the redo reasons reported.  The backward must not redo an f32 'plain' utterance (unit-scale noise): its mass check fails
+    only when the forward's rows lost cells that carry paths.  (The forward may redo one: with a long target and few spare
+    frames the end cells fall 2**-1074 below their row's largest, and the probability-domain total is 0.)"""
+    bad = []
+    tol = 1e-9 if c["x"].dtype == torch.float64 else 1e-5
+    xl, tl = torch.from_numpy(c["xl"]).to(DEV), torch.from_numpy(c["tl"]).to(DEV)
+    for run, width in (("exact", int(c["tl"].max())), ("padded", c["pad"])):
+        out = eng.compute(_on_gpu(c["x"], c["view"]), _padded(c["tg"], c["tl"], width, c["V"], rng).to(DEV), xl, tl,
+                          input_is_logprobs=c["logprobs"], grad_scale=c["scale"], reduction=c["reduction"])
+        flags = eng.redo_flags() if c["x"].dtype == torch.float32 else None
+        reached.add(block(width))
+        r = _differs(out[0].cpu().double().numpy(), out[1].cpu().double().numpy(), want_l, want_g * c["scale"], tol)
+        if r is None and c["reduction"]:
+            want = want_l.sum() if c["reduction"] == "sum" else want_l.mean()
+            got = float(out[2].item())
+            if not (got == want or (np.isnan(got) and np.isnan(want)) or
+                    (np.isfinite(want) and abs(got - want) <= tol * max(1.0, abs(want)))):
+                r = "reduced (%s) %r, want %r" % (c["reduction"], got, want)
+        if r is None and flags is not None:
+            reasons.update(flags.tolist())
+            if not set(flags.tolist()) <= {0, 1, 2}:
+                r = "redo flags %s" % flags.tolist()
+            elif c["mode"] == "plain" and (flags == 2).any():
+                r = "the backward redid unit-noise utterances: flags %s" % flags.tolist()
+        if r is not None:
+            bad.append((run, width, r))
+    _count(family, len(c["tl"]))
+    return bad
+
+
+def _common(rng, c, B):
+    c["view"] = str(rng.choice(["contiguous", "contiguous", "time_major", "strided"]))
+    c["scale"] = float(rng.choice([1.0, 0.37, 1.0 / B]))
+    c["reduction"] = [None, "sum", "mean"][int(rng.integers(0, 3))]
+    return c
+
+
+def _inputs(rng, B, T, V, mode, dtype):
+    """(x as the call gets it, logprobs): 'plain' unit-scale noise, 'sharp' logits at scale 8-20, 'low' log-probabilities
+    below -700 (logits at scale 150-250, or log-probabilities given so)"""
+    logprobs = False
+    if mode == "sharp":
+        x = torch.from_numpy(rng.standard_normal((B, T, V)) * float(rng.choice([8.0, 12.0, 16.0, 20.0])))
+    elif mode == "low" and rng.random() < 0.5:
+        x = torch.from_numpy(rng.standard_normal((B, T, V)) * float(rng.integers(150, 251)))
+    else:
+        x = torch.from_numpy(rng.standard_normal((B, T, V)) * float(rng.choice([0.5, 1.0, 2.0, 3.0])))
+        logprobs = mode == "low" or rng.random() < 0.4
+        if logprobs:
+            x = torch.log_softmax(x, -1)
+            if mode == "low":
+                x[rng.random((B, T, V)) < 0.05] = -750.0 - 100.0 * float(rng.random())
+    return x.to(dtype), logprobs
+
+
+# ---- noblank ----
+NB_V = [1, 2, 3, 5, 29, 29, 64, 300, 2000, 32000]
+
+
+def _nb_case(rng, case, dtype, big=False):
+    """The exact width in the band of K = 16 - case % 16 (case % 16 == 0: sharp logits, == 8: log-probabilities below -700)"""
+    K = 16 - case % 16
+    mode = "plain" if big else {0: "sharp", 8: "low"}.get(case % 16, "plain")
+    lo, hi = NB_BANDS[K]
+    if big:                                          # more utterances than the 256 CUs
+        B, W, T = 300, int(rng.integers(0, 21)), int(rng.integers(20, 61))
+    elif mode == "sharp":
+        B, W, T = int(rng.integers(4, 7)), int(rng.integers(20, 41)), int(rng.integers(300, 601))
+    else:
+        W = int(rng.integers(lo, min(hi, NB_LAST - 1) + 1)) if K < 16 or rng.random() < 0.5 else int(rng.integers(0, 49))
+        B = int(rng.integers(1, 7 if W < 300 else 3))
+        T = max(W, 1) + int(rng.choice([0, 0, 1, K - 1, K, K + 1, int(rng.integers(0, 3 * K + 1))]))
+    V = 29 if mode == "sharp" or big else int(rng.choice([v for v in NB_V if B * T * v <= 4_000_000]))
+    sp = int(rng.choice(sorted({-1, 0, V - 1, V // 2})))
+    style = str(rng.choice(["random", "runs", "distinct", "space"]))
+    if style == "runs":                              # long runs of one label
+        tg = np.repeat(rng.integers(0, V, size=(B, W + 1)), int(rng.integers(4, 61)), axis=1)[:, :W]
+    elif style == "distinct":                        # all-distinct labels (distinct within every V of them)
+        tg = np.stack([np.tile(rng.permutation(V), W // V + 1)[:W] for _ in range(B)]) if W else np.zeros((B, 0), np.int64)
+    else:
+        tg = rng.integers(0, V, size=(B, W))
+        if style == "space" and sp >= 0:
+            tg[rng.random((B, W)) < 0.2] = sp
+    tl = rng.integers(0, W + 1, size=B)
+    tl[0] = W
+    if B > 1 and rng.random() < 0.4:                 # the target [sp] (Q10's neighbour) or the empty target
+        tl[1] = 1 if sp >= 0 and W >= 1 else 0
+        if W >= 1:
+            tg[1, 0] = sp if sp >= 0 else tg[1, 0]
+    xl = np.array([T] + [_lengths(rng, max(int(tl[b]), 1), K, T) for b in range(1, B)], dtype=np.int64)
+    if mode == "sharp":
+        xl[1:] = rng.integers(80, T + 1, size=B - 1)
+    x, logprobs = _inputs(rng, B, T, V, mode, dtype)
+    c = dict(x=x, logprobs=logprobs, tg=tg.astype(np.int64), tl=tl.astype(np.int64), xl=xl, V=V, sp=sp, mode=mode,
+             pad=_wider(NB_BANDS, W, rng))
+    return _common(rng, c, B)
+
+
+def _nb_want(c):
+    lp = (c["x"].double() if c["logprobs"] else torch.log_softmax(c["x"].double(), -1)).numpy()
+    B, T, V = lp.shape
+    want_l, want_g = np.zeros(B), np.zeros((B, T, V))
+    for b in range(B):
+        n, s = int(c["xl"][b]), int(c["tl"][b])
+        want_l[b], want_g[b, :n] = NR.utterance(lp[b, :n], c["tg"][b, :s], c["sp"])
+    return want_l, want_g
+
+
+@pytest.mark.parametrize("dtype,seed,n", [(torch.float32, 20, 48), (torch.float64, 21, 48)], ids=["f32_seed20", "f64_seed21"])
+def test_noblank_family_against_the_f64_restatement(dtype, seed, n):
+    from end2end_amd.engines import CTCWithoutBlankLossEngine
+    rng = np.random.default_rng(seed)
+    bad, reached, reasons = [], set(), set()
+    for case in range(n + 1):
+        c = _nb_case(rng, case, dtype, big=case == n)
+        want_l, want_g = _nb_want(c)
+        r = _run_twice("noblank", c, CTCWithoutBlankLossEngine(c["sp"]), want_l, want_g, rng, nb_block, reached, reasons)
+        if r:
+            bad.append((case, c["mode"], tuple(c["x"].shape), int(c["tl"].max()), c["pad"], c["sp"], c["view"],
+                        c["logprobs"], r))
+    assert not bad, "mismatching cases of seed %d: %s" % (seed, bad)
+    assert reached == set(range(1, 17)), "block sizes not reached: %s" % sorted(set(range(1, 17)) - reached)
+    if dtype == torch.float32:
+        assert {1, 2} <= reasons, "redo reasons reported: %s" % sorted(reasons)
+
+
+# ---- gram ----
+GC_MODES = {(2, 16): "sharp", (6, 16): "sharp", (3, 16): "low", (7, 16): "low", (8, 16): "one_gram"}
+
+
+def _gc_table(rng, R, M):
+    """{column: base ids} of max_order M over radix R: grams of every order 2..M, the prefix and the suffix of a longest one,
+    'aa' and 'aaa'; R = 2 has only the runs of its one label; R = 234 holds the largest key, eight 233s"""
+    seqs = set()
+    if R == 2:
+        seqs = {(1,) * k for k in range(2, M + 1)}
+    elif M >= 2:
+        a = int(rng.integers(1, R))
+        seqs |= {(a, a), (a, a, a)} if M >= 3 else {(a, a)}
+        for k in range(2, M + 1):
+            seqs |= {tuple(int(v) for v in rng.integers(1, R, size=k)) for _ in range(int(rng.integers(1, 4)))}
+        g = max(sorted(seqs), key=len)
+        if len(g) >= 3:
+            seqs |= {g[:-1], g[1:]}
+        if R == 234:
+            seqs.add((R - 1,) * M)
+    return {R + i: list(s) for i, s in enumerate(sorted(seqs))}
+
+
+def _gc_frames(tgt, l2i, M):
+    """the fewest frames that spell tgt (every unigram is a column; two equal grams in a row need a blank between them)"""
+    key = {tuple(v): c for c, v in l2i.items()}
+    best = [dict() for _ in range(len(tgt) + 1)]     # boundary -> {column of the last gram: frames}
+    best[0][0] = 0
+    for j in range(len(tgt)):
+        for last, f in best[j].items():
+            for k in range(1, min(M, len(tgt) - j) + 1):
+                c = tgt[j] if k == 1 else key.get(tuple(tgt[j:j + k]))
+                if c is not None:
+                    n = f + (2 if c == last else 1)
+                    best[j + k][c] = min(n, best[j + k].get(c, n))
+    return min(best[-1].values()) if len(tgt) else 1
+
+
+def _gc_case(rng, case, dtype, big=False):
+    """The exact width in the band of the (max_order, K) pair GC_PAIRS[case % 40]"""
+    M, K = (1, 16) if big else GC_PAIRS[case % len(GC_PAIRS)]
+    mode = "plain" if big else GC_MODES.get((M, K), "plain")
+    lo, hi = GC_BANDS[M][K]
+    if M == 1:
+        R = int(rng.choice([1, 2, 5, 29])) if K == 16 and not big else int(rng.choice([2, 5, 29]))
+    else:
+        R = 234 if M == 8 and K in (4, 1) else int(rng.choice([2, 3, 5, 8, 29]))
+    l2i = _gc_table(rng, R, M)
+    V = R + len(l2i)
+    grams = [g for g in l2i.values()]
+    if R == 1:
+        W = 0
+    elif big:
+        W = int(rng.integers(1, 21))
+    elif mode in ("sharp", "low"):
+        W = 30 if mode == "sharp" else 20
+    elif mode == "one_gram":
+        W = 8
+    else:
+        W = int(rng.integers(lo, (hi if K > 1 else hi - 1) + 1))
+    B = 300 if big else int(rng.integers(4, 7)) if mode in ("sharp", "low") else int(rng.integers(1, 7 if W < 200 else 3))
+
+    def spell(S):
+        t = []
+        while len(t) < S:
+            g = grams[int(rng.integers(len(grams)))] if grams and rng.random() < 0.7 else [int(rng.integers(1, R))]
+            t += list(g) * int(rng.integers(1, 3))   # the same gram twice in a row, often
+        return t[:S]
+
+    tg = np.zeros((B, W), dtype=np.int64)
+    for b in range(B):
+        eights = [g for g in grams if len(g) == 8]
+        tg[b] = spell(W) if mode != "one_gram" else eights[b % len(eights)]
+    tl = rng.integers(0, W + 1, size=B)
+    tl[0] = W
+    if mode == "one_gram":
+        tl[:] = 8
+    need = [_gc_frames(tg[b, :tl[b]].tolist(), l2i, M) for b in range(B)]
+    if mode == "sharp":
+        T = 600
+    elif mode == "low":
+        T = 120
+    elif mode == "one_gram":
+        T = 1
+    else:
+        T = need[0] + int(rng.choice([0, 0, 1, K - 1, K, K + 1, int(rng.integers(0, W + 3))]))
+    xl = np.array([T] + [_lengths(rng, need[b], K, T) for b in range(1, B)], dtype=np.int64)
+    if mode in ("sharp", "low"):
+        xl[1:] = rng.integers(min(80, T), T + 1, size=B - 1)
+    for b in range(1, B):                            # a bad target now and then: 0, or an id >= R
+        if tl[b] >= 1 and rng.random() < 0.1:
+            tg[b, int(rng.integers(0, tl[b]))] = int(rng.choice([0, R, V + 5]))
+    x, logprobs = _inputs(rng, B, T, V, "plain" if mode == "one_gram" else mode, dtype)
+    c = dict(x=x, logprobs=logprobs, tg=tg, tl=tl.astype(np.int64), xl=xl, V=V, R=R, M=M, l2i=l2i, mode=mode,
+             pad=_wider(GC_BANDS[M], W, rng))
+    return _common(rng, c, B)
+
+
+def _gc_want(c):
+    lp = (c["x"].double() if c["logprobs"] else torch.log_softmax(c["x"].double(), -1)).numpy()
+    B, T, V = lp.shape
+    grams = GR.grams_of(c["R"], V, c["l2i"])
+    want_l, want_g = np.zeros(B), np.zeros((B, T, V))
+    for b in range(B):
+        n, s = int(c["xl"][b]), int(c["tl"][b])
+        t = c["tg"][b, :s]
+        if ((t < 1) | (t >= c["R"])).any():          # a bad target: NaN loss and slab
+            want_l[b], want_g[b] = np.nan, np.nan
+            continue
+        want_l[b], post = GR.lattice(lp[b, :n], t, grams)
+        with np.errstate(invalid="ignore"):
+            want_g[b, :n] = np.exp(lp[b, :n]) - post
+    return want_l, want_g
+
+
+@pytest.mark.parametrize("dtype,seed,n", [(torch.float32, 30, 48), (torch.float64, 31, 48)], ids=["f32_seed30", "f64_seed31"])
+def test_gram_family_against_the_f64_lattice(dtype, seed, n):
+    from end2end_amd.engines import GramCTCLossEngine
+    rng = np.random.default_rng(seed)
+    bad, reached, reasons = [], set(), set()
+    for case in range(n + 1):
+        c = _gc_case(rng, case, dtype, big=case == n)
+        want_l, want_g = _gc_want(c)
+        eng = GramCTCLossEngine(0, c["R"], c["V"], c["l2i"])
+        assert eng.max_order == c["M"]
+        r = _run_twice("gram", c, eng, want_l, want_g, rng, lambda w: (c["M"], gc_block(w, c["M"])), reached, reasons)
+        if r:
+            bad.append((case, c["mode"], tuple(c["x"].shape), c["R"], c["M"], int(c["tl"].max()), c["pad"], c["view"],
+                        c["logprobs"], r))
+    assert not bad, "mismatching cases of seed %d: %s" % (seed, bad)
+    assert reached == set(GC_PAIRS), "(max_order, K) not reached: %s" % sorted(set(GC_PAIRS) - reached)
+    if dtype == torch.float32:
+        assert {1, 2} <= reasons, "redo reasons reported: %s" % sorted(reasons)

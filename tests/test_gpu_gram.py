@@ -86,9 +86,10 @@ def test_unigrams_only_equal_ctc_with_blank_0(B, T, S, seed):
         assert (grad[b, n:] == 0).all()
 
 
-def gram_table(rng, R, n2, n3, n4=0):
+def gram_table(rng, R, *counts):
+    """counts[i] random grams of order i + 2 over the base labels 1..R-1 -> (label2ids, V)"""
     l2i, seen, c = {}, set(), R
-    for k, n in ((2, n2), (3, n3), (4, n4)):
+    for k, n in enumerate(counts, start=2):
         while sum(len(v) == k for v in l2i.values()) < n:
             s = tuple(int(v) for v in rng.integers(1, R, size=k))
             if s not in seen:
@@ -265,14 +266,18 @@ def test_infeasible_and_bad_utterances_poison_only_themselves(dt):
     vs_ref(4, 6, l2i, x[ok], tg[ok], xl[ok], tl[ok])
 
 
-@pytest.mark.parametrize("scale,T,why", [(8.0, 600, 2), (14.0, 600, 2), (20.0, 600, 2), (300.0, 120, 1)])
-def test_sharp_logits_take_the_log_domain_redo_and_still_match(scale, T, why):
+@pytest.mark.parametrize("scale,T,why,order", [
+    pytest.param(8.0, 600, 2, 3, id="8.0-600-2"), pytest.param(14.0, 600, 2, 3, id="14.0-600-2"),
+    pytest.param(20.0, 600, 2, 3, id="20.0-600-2"), pytest.param(300.0, 120, 1, 3, id="300.0-120-1"),
+    pytest.param(14.0, 600, 2, 6, id="order6-14.0-600-2"), pytest.param(300.0, 120, 1, 6, id="order6-300.0-120-1")])
+def test_sharp_logits_take_the_log_domain_redo_and_still_match(scale, T, why, order):
     # Sharp logits unrelated to the targets: at scale 8-20 over 600 frames cells that carry paths flush to zero under their
     # row's scale, the backward finds frames whose posteriors do not sum to 1 and redoes the utterance (flag 2); at scale
-    # 300 log-probabilities fall below -700 and the forward sends every utterance to the log domain (flag 1).
+    # 300 log-probabilities fall below -700 and the forward sends every utterance to the log domain (flag 1).  Tables of
+    # max_order 3 and 6.
     rng = np.random.default_rng(15)
     R = 8
-    l2i, V = gram_table(rng, R, 10, 5)
+    l2i, V = gram_table(rng, R, 10, 5, *([3] * (order - 3)))
     B, S = 8, 30
     x, _, xl, tl = _ragged(48, B, T, V, S, R=R, scale=scale, min_t=80)
     tg = dense_targets(rng, l2i, R, B, S)
@@ -298,21 +303,50 @@ def gc_block(S, M):
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.float64])
-@pytest.mark.parametrize("S,T,K", [(200, 437, 8), (300, 650, 4), (500, 1013, 2), (668, 1341, 1)])
-def test_blocks_shorter_than_the_checkpoint_interval_against_the_lattice(dt, S, T, K):
+@pytest.mark.parametrize("S,T,K,M", [
+    pytest.param(200, 437, 8, 3, id="200-437-8"), pytest.param(300, 650, 4, 3, id="300-650-4"),
+    pytest.param(500, 1013, 2, 3, id="500-1013-2"), pytest.param(668, 1341, 1, 3, id="668-1341-1"),
+    pytest.param(200, 437, 4, 5, id="order5-200-437-4"), pytest.param(447, 931, 1, 5, id="order5-447-931-1"),
+    pytest.param(250, 537, 2, 6, id="order6-250-537-2"), pytest.param(336, 709, 1, 7, id="order7-336-709-1"),
+    pytest.param(50, 137, 16, 8, id="order8-50-137-16"), pytest.param(80, 197, 8, 8, id="order8-80-197-8"),
+    pytest.param(120, 277, 4, 8, id="order8-120-277-4"), pytest.param(200, 437, 2, 8, id="order8-200-437-2"),
+    pytest.param(290, 617, 1, 8, id="order8-290-617-1")])
+def test_blocks_shorter_than_the_checkpoint_interval_against_the_lattice(dt, S, T, K, M):
     # Targets long enough that the LDS block K is below the 16-frame checkpoint interval: the backward recomputes every
     # block from its checkpoint through the blocks ahead of it.  Ragged lengths end utterances inside a block and away
-    # from a checkpoint.
-    assert gc_block(S, 3) == K
+    # from a checkpoint.  Tables of max_order M: grams of every order 2..M, spelled into the targets.
+    assert gc_block(S, M) == K
     rng = np.random.default_rng(S)
     R = 29
-    l2i, V = gram_table(rng, R, 60, 20)
+    l2i, V = gram_table(rng, R, 60, 20, *([8] * (M - 3)))
     B = 3
     tg = dense_targets(rng, l2i, R, B, S)
     tl = torch.tensor([S, S - 5, S - 13])
     xl = torch.tensor([T, T - 7, T - 26])
     x = torch.randn(B, T, V, generator=torch.Generator().manual_seed(S)).to(dt)
     vs_ref(R, V, l2i, x, tg, xl, tl)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+def test_radix_234_order_8_keys_near_the_int64_limit_against_the_lattice(dt):
+    # 234 ** 8 - 1 = 0.975 * INT64_MAX: the largest key a table can hold is the gram of eight 233s.  The table mixes it with
+    # other order-8 grams of high labels, its own prefix and suffix, and grams of every lower order; the targets spell them.
+    rng = np.random.default_rng(234)
+    R = 234
+    top = [R - 1] * 8
+    assert (R ** 8 - 1) / (2 ** 63 - 1) > 0.97
+    l2i, V = gram_table(rng, R, 6, 4, 3, 3, 3, 3, 3)
+    for g in (top, top[:-1], [R - 2] + top[1:], [R - 1, R - 2] * 4):
+        if g not in l2i.values():
+            l2i[V] = g
+            V += 1
+    B, T, S = 4, 160, 120
+    assert gc_block(S, 8) == 4
+    tg = dense_targets(rng, l2i, R, B, S)
+    tg[0, :16] = torch.tensor(top + top)                  # the top key twice in a row (a blank between them)
+    x, _, xl, tl = _ragged(50, B, T, V, S, R=R, min_t=100)
+    xl[1:] = torch.tensor([T - 1, 99, 120])
+    vs_ref(R, V, l2i, x.to(dt), tg, xl, tl)
 
 
 def test_one_label_past_the_documented_limit_raises():

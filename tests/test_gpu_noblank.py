@@ -187,11 +187,13 @@ def _engine_vs_ref(x, tg, xl, tl, space_idx, logprobs=False):
     from end2end_amd.engines import CTCWithoutBlankLossEngine
     eng = CTCWithoutBlankLossEngine(space_idx)
     loss, grad = eng.compute(x.to(DEV), tg.to(DEV), xl.to(DEV), tl.to(DEV), input_is_logprobs=logprobs)
+    flags = eng.redo_flags()
     lp = x.double() if logprobs else torch.log_softmax(x.double(), -1)
     want_l, want_g = NR.noblank_loss_grad(lp.numpy(), tg.numpy(), xl.numpy(), tl.numpy(), space_idx)
     tol = 1e-9 if x.dtype == torch.float64 else 1e-5
     check_losses(loss.cpu().numpy(), want_l, tol)
     check_grads(grad.cpu().numpy(), want_g, tol)
+    return flags
 
 
 @pytest.mark.parametrize("space_idx", [-1, 28])
@@ -230,8 +232,58 @@ def test_log_probs_below_minus_700_take_the_log_domain():
     x, tg, xl, tl = _ragged(25, 8, 80, 10, 20, 2, scale=200.0)
     lp = torch.log_softmax(x.double(), -1)
     assert ((lp > -np.inf) & (lp < -700)).any()
-    _engine_vs_ref(x, tg, xl, tl, 2)
+    flags = _engine_vs_ref(x, tg, xl, tl, 2)
+    assert (flags == 1).all(), flags                        # (the forward's redo: e2e_debug_noblank_redo_flags)
     _engine_vs_ref(x * 0.3, tg, xl, tl, -1)                 # (scale x60)
+
+
+def nb_block(Smax):
+    """The LDS block K of the lattice kernel (ctc_loss_noblank.hip nb_lds_bytes / nb_block), restated; 0: not served."""
+    Lm = Smax + 2
+    for K in range(16, 0, -1):
+        if 8 * (3 * (K + 1) * Lm + 2 * K * Lm + 2 * Lm) + 4 * (2 * Lm + 2 * K) + 64 <= 160 * 1024 - 288:
+            return K
+    return 0
+
+
+@pytest.mark.parametrize("space_idx", [-1, 3])
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+@pytest.mark.parametrize("S,K", [(240, 15), (320, 11), (420, 8), (600, 5), (900, 3), (1100, 2), (1500, 1), (1855, 1)])
+def test_blocks_shorter_than_16_frames_against_restatement(S, K, dt, space_idx):
+    # Targets long enough that the LDS block K -- the checkpoint interval -- drops below 16 frames; most of these K do not
+    # divide 16, and the backward hands the blocks through its three-slot ring.  Smax = 1855 is the last width served.
+    # Ragged lengths end utterances on the first frame of a block (a checkpoint), on its last frame and in between.
+    assert nb_block(S) == K and nb_block(1855) == 1 and nb_block(1856) == 0
+    g = torch.Generator().manual_seed(S + K)
+    B, T, V = 3, S + 2 * K + 5, 29
+    x = torch.randn(B, T, V, generator=g).to(dt)
+    tg = torch.randint(0, V, (B, S), generator=g)
+    tl = torch.tensor([S, S - 5, S - 13])
+    first = -(-(S - 6) // K) * K + 1                 # x_len - 1 a multiple of K, x_len >= t_len
+    last = -(-(S - 13) // K) * K                     # x_len a multiple of K
+    xl = torch.tensor([T, first, last])
+    assert (xl >= tl).all() and (xl <= T).all() and (first - 1) % K == 0 and last % K == 0
+    _engine_vs_ref(x, tg, xl, tl, space_idx)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+def test_the_widest_row_of_every_block_size_launches(dt):
+    # Regression: the LDS limit left less room than the kernel's static LDS takes, and the two widths whose blocks filled
+    # it (Smax 784 and 1856) failed to launch.  784 (now K = 3) and the last width of every block size, short targets
+    # padded to it; 1856 is refused with the documented error.
+    from end2end_amd.engines import CTCWithoutBlankLossEngine
+    g = torch.Generator().manual_seed(31)
+    B, T, V = 3, 40, 29
+    widths = [784] + [max(s for s in range(1856) if nb_block(s) == K) for K in range(1, 17)]
+    assert nb_block(784) == 3 and widths[1] == 1855
+    with pytest.raises(Exception, match="Smax=1856"):
+        CTCWithoutBlankLossEngine(5).compute(torch.randn(B, T, V, device=DEV), torch.zeros(B, 1856, dtype=torch.long),
+                                             torch.tensor([40, 33, 17]), torch.tensor([30, 12, 0]))
+    for W in widths:
+        x = torch.randn(B, T, V, generator=g).to(dt)
+        tg = torch.full((B, W), -1, dtype=torch.long)
+        tg[:, :30] = torch.randint(0, V, (B, 30), generator=g)
+        _engine_vs_ref(x, tg, torch.tensor([40, 33, 17]), torch.tensor([30, 12, 0]), 5)
 
 
 def test_reduce_and_weighted_backward():

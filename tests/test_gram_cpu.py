@@ -45,6 +45,56 @@ def test_named_repeat_cases_against_brute_force():
         assert np.isfinite(bl) and abs(ll - bl) <= 1e-10 * abs(bl) and np.max(np.abs(lpst - bp)) <= 1e-10
 
 
+def test_lattice_equals_brute_force_with_grams_of_order_4_to_8():
+    # the orders the GPU tests trust gram_ref.lattice for: tiny tables (R = 2-3, V**T <= 4096) whose grams have 4..8 base
+    # labels, overlapping ('aaaa' beside 'aaaaa', one gram a prefix of another), targets spelled from them with repeats
+    rng = np.random.default_rng(48)
+    n_fin = n_long = 0
+    for case in range(120):
+        R = int(rng.integers(2, 4))
+        seqs = set()
+        while len(seqs) < int(rng.integers(1, 4)):
+            k = int(rng.integers(4, 9))
+            g = tuple(int(v) for v in rng.integers(1, R, size=k))
+            seqs |= {g, g[:-1]} if rng.random() < 0.3 and len(seqs) < 2 else {g}
+        l2i = {R + i: list(s) for i, s in enumerate(sorted(seqs))}
+        V = R + len(l2i)
+        T = int(rng.integers(1, 8))
+        while V ** T > 4096:
+            T -= 1
+        grams = GR.grams_of(R, V, l2i)
+        tgt = []
+        for _ in range(int(rng.integers(0, T + 2))):
+            tgt += list(l2i[int(rng.choice(list(l2i)))]) if rng.random() < 0.7 else [int(rng.integers(1, R))]
+        x = rng.normal(size=(T, V)) * float(rng.choice([0.5, 1.0, 3.0]))
+        lp = x - np.log(np.sum(np.exp(x), axis=1, keepdims=True))
+        bl, bp = GR.brute_force(lp, tgt, grams)
+        ll, lpst = GR.lattice(lp, tgt, grams)
+        if np.isinf(bl):
+            assert np.isinf(ll) and ll > 0 and np.isnan(lpst).all(), (tgt, l2i, ll)
+            continue
+        n_fin += 1
+        n_long += len(tgt) > T                       # (more labels than frames: only grams spell it)
+        assert abs(ll - bl) <= 1e-10 * max(1.0, abs(bl)), (tgt, l2i, ll, bl)
+        assert np.max(np.abs(lpst - bp)) <= 1e-10, (tgt, l2i)
+    assert n_fin >= 50 and n_long >= 20, (n_fin, n_long)
+
+
+@pytest.mark.parametrize("R", [2, 3])
+def test_one_order_8_gram_spells_the_whole_target_in_one_frame(R):
+    l2i = {R: [1] * 8, R + 1: [1] * 4} if R == 2 else {R: [1, 2, 2, 1, 2, 1, 1, 2], R + 1: [2, 2, 1]}
+    grams = GR.grams_of(R, R + 2, l2i)
+    lp = np.log(np.array([[0.1] * R + [0.5, 0.4 - 0.1 * (R - 1)]]))
+    for tgt in (l2i[R], l2i[R] + [1]):
+        bl, bp = GR.brute_force(lp, tgt, grams)
+        ll, lpst = GR.lattice(lp, tgt, grams)
+        if len(tgt) == 8:
+            assert abs(bl + np.log(0.5)) < 1e-12 and bp[0, R] == 1.0      # the one path: the gram's column
+            assert abs(ll - bl) <= 1e-12 and np.max(np.abs(lpst - bp)) <= 1e-12
+        else:
+            assert np.isinf(bl) and np.isinf(ll)                        # one label more: no path in one frame
+
+
 def test_a_gram_needs_fewer_frames_than_ctc():
     # "aa" needs three frames under CTC (a, blank, a) but one with the gram "aa"
     grams = GR.grams_of(2, 3, {2: [1, 1]})

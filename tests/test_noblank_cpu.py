@@ -91,3 +91,66 @@ def test_workspace_of_the_headline_shape_stays_under_128_megabytes():
     L = _lib.load()
     n = L.e2e_ctc_noblank_workspace_bytes(256, 1000, 29, 200, _lib.F32)
     assert 0 < n <= 128e6, n
+
+
+def test_documented_capacity():
+    # include/e2e_ctc.h and DESIGN 4.5: targets of up to Smax = 1 855 labels (LDS blocks of one frame), the workspace query
+    # 0 one label beyond, whatever the batch, the frames and the dtype
+    from end2end_amd import _lib
+    L = _lib.load()
+    for B, T, dtype in [(1, 1, _lib.F32), (2, 100, _lib.F32), (4, 3000, _lib.F64)]:
+        assert L.e2e_ctc_noblank_workspace_bytes(B, T, 29, 1855, dtype) > 0
+        assert L.e2e_ctc_noblank_workspace_bytes(B, T, 29, 1856, dtype) == 0
+    hdr = open(os.path.join(ROOT, "include", "e2e_ctc.h")).read()
+    assert "Smax = 1 855" in hdr and "2 900" not in hdr
+
+
+def _static_lds():
+    """{kernel name: static LDS bytes (group_segment_fixed_size)} of the built library's lattice kernels"""
+    import sys
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tools", "perf"))
+    import entry_audit
+    from end2end_amd import _lib
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in entry_audit.code_objects(_lib.LIB_PATH, tmp):
+            notes = subprocess.run([entry_audit.LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
+                                   text=True).stdout
+            for blk in re.split(r"\n\s*- \.", notes):
+                name = re.search(r"\.name:\s*(\S+)", blk)
+                size = re.search(r"\.group_segment_fixed_size:\s*(\d+)", blk)
+                if name and size and "lattice_kernel" in name.group(1):
+                    out[name.group(1)] = int(size.group(1))
+    return out
+
+
+def test_the_lds_of_every_served_width_fits_beside_the_static_lds():
+    # The dynamic LDS a width asks for (nb_lds_bytes of its block K, restated as in test_gpu_noblank.py::nb_block) plus the
+    # kernel's static LDS must fit the 160 KiB of a gfx950 workgroup, or the launch fails (it did at Smax 784 and 1856 while
+    # the limit assumed 256 bytes of static LDS).  Gram-CTC's lattice kernel against its own widths, the same way.
+    static = _static_lds()
+    nb = [v for k, v in static.items() if "noblank" in k]
+    gc = [v for k, v in static.items() if "gram" in k]
+    assert len(nb) == 2 and len(gc) == 2, static
+
+    def nb_lds(S):
+        Lm = S + 2
+        for K in range(16, 0, -1):
+            n = 8 * (3 * (K + 1) * Lm + 2 * K * Lm + 2 * Lm) + 4 * (2 * Lm + 2 * K) + 64
+            if n <= 160 * 1024 - 288:
+                return n
+        return 0
+
+    def gc_lds(S, M):
+        NC = (S + 1) * (M + 1)
+        for K in (16, 8, 4, 2, 1):
+            n = 8 * (2 * K * NC + 4 * NC + 4 * K) + 4 * (3 * NC + S + 1 + K + 16) + 64
+            if n <= 160 * 1024 - 256:
+                return n
+        return 0
+
+    assert nb_lds(1855) and not nb_lds(1856)
+    assert max(nb_lds(S) for S in range(1856)) + max(nb) <= 160 * 1024, (static, max(nb_lds(S) for S in range(1856)))
+    widest = max(gc_lds(S, M) for M in range(1, 9) for S in range(1400))
+    assert widest + max(gc) <= 160 * 1024, (static, widest)
