@@ -207,6 +207,23 @@ int e2e_ctc_loss_takes_dtype(int dtype, int algo, int T, int V, int Smax, int64_
   return 1;
 }
 
+// Diagnostics (include/e2e_ctc_debug.h): which kernels e2e_ctc_loss_fwd_bwd_opt below gives a call of this shape, by the functions
+// it and the launchers dispatch with (resolve_algo, use_wide, wide_takes_fast_lattice, wide_row_form, fast_route).  Host only.
+int e2e_debug_loss_route(int dtype, int algo, int B, int T, int V, int Smax, int chains,
+                         int64_t sB, int64_t sT, int64_t sV, const void* x, const void* grads) {
+  if ((dtype != E2E_F32 && dtype != E2E_F64 && !dtype_is_16bit(dtype)) || B < 0 || T < 1 || V < 1 || Smax < 0 ||
+      (algo != E2E_ALGO_AUTO && algo != E2E_ALGO_EXACT && algo != E2E_ALGO_FAST)) return -1;
+  const int r = resolve_algo(algo, dtype, T, V, Smax);
+  if (r == E2E_ALGO_EXACT) return dtype_is_16bit(dtype) ? -1 : 1000;
+  if (use_wide(dtype, T, V, Smax)) {
+    const int rows = 100 * wide_row_form(dtype, V, sB, sT, sV, x, grads);
+    if (!wide_takes_fast_lattice(T, V, Smax, dtype)) return r == E2E_ALGO_FAST ? -1 : 4000 + rows;
+    return 3000 + rows + fast_route(B, Smax + 1, Smax, chains);
+  }
+  if (!fast_supported(T, V, Smax, dtype)) return -1;
+  return 2000 + fast_route(B, V, Smax, chains);
+}
+
 int e2e_ctc_loss_fwd_bwd(const void* x, int dtype, int input_is_logprobs,
                          int64_t sB, int64_t sT, int64_t sV,
                          const int64_t* targets, int64_t tgt_stride,

@@ -33,6 +33,11 @@ __device__ __forceinline__ void store_elem(void* base, size_t idx, float v, int 
   else reinterpret_cast<f16_t*>(base)[idx] = (f16_t)v;
 }
 
+// A target as the lattice kernels hold it, an int: -1 (outside every alphabet) unless the int64 lies in [0, 2^32) -- its upper
+// word is tested BEFORE it is narrowed, so that 2^32 + 3 or 3 - 2^32 never becomes label 3 (values of 2^31 .. 2^32 - 1 come out
+// negative, outside the alphabet as well).  One compare and one select per label read.
+__device__ __forceinline__ int label_of(int64_t v) { return (v >> 32) != 0 ? -1 : (int)v; }
+
 // thread-local error text behind e2e_last_error()
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
@@ -111,11 +116,17 @@ int launch_exact(const LossArgs& a);
 size_t fast_workspace_bytes(int B, int T, int V, int Smax);
 int launch_fast(const LossArgs& a, bool fallback_to_exact);
 bool fast_supported(int T, int V, int Smax, int dtype);
+// what a fast-path call of this shape runs, for e2e_debug_loss_route: 10 * pairs per lane + the number of the rule of
+// launch_fast_ppl's list that picks its chains (computed by the function the launch follows); 0: not a shape of the fast path
+int fast_route(int B, int V, int Smax, int chains);
 // wide alphabets: per-utterance compaction around the fast path (ctc_loss_wide.hip)
 bool wide_supported(int T, int V, int Smax, int dtype);
 bool wide_takes_fast_lattice(int T, int V, int Smax, int dtype);   // (false: the compact lattice is the exact kernel's)
 size_t wide_workspace_bytes(int B, int T, int V, int Smax, bool with_exact);
 int launch_wide(const LossArgs& a, bool fallback_to_exact);
+// the wide path's row kernels for these logits (launch_wide follows it): 0 element by element in two passes, 1 the same by
+// 16-byte accesses, 2 / 3 / 4 the single-read kernels of 8 / 16 / 32 accesses per lane (rows of up to 2048 / 4096 / 8192 columns)
+int wide_row_form(int dtype, int V, int64_t sB, int64_t sT, int64_t sV, const void* x, const void* grads);
 
 }  // namespace e2e
 

@@ -167,13 +167,13 @@ __device__ __forceinline__ void ext_chain_wave(const ExactParams& p, unsigned ch
   for (int r = 0; r < NP; r++) {
     const int g = g0 + r, li = DIR == 0 ? g : g - 1;
     lvalid[r] = li >= 0 && li < S;
-    const int lv = lvalid[r] ? (int)tg[li] : 0;
+    const int lv = lvalid[r] ? label_of(tg[li]) : 0;
     lab[r] = min(max(lv, 0), V - 1);
     if (DIR == 0) {
-      const int lpv = li >= 1 && li < S ? (int)tg[li - 1] : -1;
+      const int lpv = li >= 1 && li < S ? label_of(tg[li - 1]) : -1;
       sk[r] = (lvalid[r] && li >= 1 && lv != blank && lpv != lv) ? 1.0 : 0.0;                 // ctc_loss.cpp:53-57
     } else {
-      const int lnv = li >= 0 && li + 1 < S ? (int)tg[li + 1] : -1;                          // P = label li + 1
+      const int lnv = li >= 0 && li + 1 < S ? label_of(tg[li + 1]) : -1;                          // P = label li + 1
       sk[r] = (lvalid[r] && li + 1 < S && lv != blank && lnv != lv) ? 1.0 : 0.0;              // ctc_loss.cpp:91-96
     }
   }
@@ -424,9 +424,9 @@ __device__ __forceinline__ void ext_segment_setup(const ExactParams& p, int b, X
     q.g = 32 * c - 16 + lane;
     q.own = lane >= 16 && lane < 48 && q.g <= S;
     q.lvalid = q.g >= 0 && q.g < S;
-    const int lv = q.lvalid ? (int)tg[q.g] : 0;
+    const int lv = q.lvalid ? label_of(tg[q.g]) : 0;
     q.lab = min(max(lv, 0), V - 1);
-    const int lpv = q.g >= 1 && q.g < S ? (int)tg[q.g - 1] : -1, lnv = q.g >= 0 && q.g + 1 < S ? (int)tg[q.g + 1] : -1;
+    const int lpv = q.g >= 1 && q.g < S ? label_of(tg[q.g - 1]) : -1, lnv = q.g >= 0 && q.g + 1 < S ? label_of(tg[q.g + 1]) : -1;
     q.skp = (q.lvalid && q.g >= 1 && lv != blank && lpv != lv) ? 1.0 : 0.0;           // ctc_loss.cpp:53-57
     q.skn = (q.lvalid && q.g + 1 < S && lv != blank && lnv != lv) ? 1.0 : 0.0;         // ctc_loss.cpp:91-96
   }

@@ -125,9 +125,9 @@ __device__ __forceinline__ bool retry_segment_f64(const ExactParams& p, unsigned
 #pragma unroll
   for (int r = 0; r < PPL; r++) {
     const int i = PPL * lane + r;
-    const int li = i < S ? (int)tg[i] : -1;
-    const int lp_ = (i >= 1 && i - 1 < S) ? (int)tg[i - 1] : -1;
-    const int ln = (i + 1 < S) ? (int)tg[i + 1] : -1;
+    const int li = i < S ? label_of(tg[i]) : -1;
+    const int lp_ = (i >= 1 && i - 1 < S) ? label_of(tg[i - 1]) : -1;
+    const int ln = (i + 1 < S) ? label_of(tg[i + 1]) : -1;
     lab[r] = (i < S && li >= 0 && li < V) ? li : -1;
     skp[r] = (i < S && i >= 1 && li != blank && lp_ != li) ? 1.f : 0.f;
     skn[r] = (i + 1 < S && li != blank && ln != li) ? 1.f : 0.f;

@@ -471,8 +471,8 @@ __device__ __forceinline__ void hf_chain_wave(const FastParams& p, int b, int T,
   for (int r = 0; r < 2; r++) {
     const int pr = p0 + r;
     const bool in = pr >= 0 && pr < S;
-    const int li = in ? (int)tg[pr] : -1;
-    const int lpv = (pr >= 1 && pr - 1 < S) ? (int)tg[pr - 1] : -1;
+    const int li = in ? label_of(tg[pr]) : -1;
+    const int lpv = (pr >= 1 && pr - 1 < S) ? label_of(tg[pr - 1]) : -1;
     lab[r] = (in && li >= 0 && li < V) ? li : V;           // V: the always-zero row
     // alpha: the skip (pr-1) -> pr as pair pr sees it; beta: the same skip as pair pr-1 sees it (this pair prepares what
     // the label cell of the pair below takes from it)
@@ -1775,11 +1775,28 @@ bool long_wide_rows(int V) { return V > kMaxSmallV || HfLds::of<ChainF64L>(V).to
 //      of eight where B > 256 and eight blocks need more than 80 KB of LDS and four do not (eight would keep a second
 //      workgroup off a CU that the batch has work for).
 // E2E_F1_F32 / _SINGLE / _HALO are for the tests: they force kernels onto shapes that the rule gives to others.
+// The number of the rule above that picks a call's chains (rule 6 with the ring of four blocks: 7); `force`: bit 0 E2E_F1_F32,
+// 1 _SINGLE, 2 _HALO.  launch_fast_ppl follows it, and e2e_debug_loss_route reports it.
+int chain_rule(int ppl, int B, int V, int Smax, int chains, int force) {
+  const bool force_f32 = force & 1, force_single = force & 2, force_halo = force & 4;
+  if (ppl == 8 ? long_wide_rows(V) : V > kMaxSmallV) return 1;
+  if (ppl == 8) return 2;
+  if (force_f32 || (chains == E2E_CHAINS_F32 && ppl == 4)) return 3;
+  if (!force_single && (ppl == 4 || (ppl == 2 && B <= 256)) && h1_supported(V, Smax, ppl)) return 4;
+  if (!force_single && (ppl == 4 || force_halo) && Smax + 1 <= ChainF64::kMaxW * kHfOwn) return 5;
+  return (B > 256 && F1Lds::bytes(V) > 80 * 1024 && F1Lds::bytes(V, 4) <= 80 * 1024) ? 7 : 6;
+}
+
+int forced_chains() {
+  static const int force = (getenv("E2E_F1_F32") != nullptr ? 1 : 0) | (getenv("E2E_F1_SINGLE") != nullptr ? 2 : 0) |
+                           (getenv("E2E_F1_HALO") != nullptr ? 4 : 0);
+  return force;
+}
+
 template <int PPL>
 int launch_fast_ppl(const FastParams& p, hipStream_t stream) {
-  static const bool force_f32 = getenv("E2E_F1_F32") != nullptr, force_single = getenv("E2E_F1_SINGLE") != nullptr,
-                    force_halo = getenv("E2E_F1_HALO") != nullptr;
-  const bool wide = PPL == 8 ? long_wide_rows(p.V) : p.V > kMaxSmallV;
+  const int rule = chain_rule(PPL, p.B, p.V, p.Smax, p.chains, forced_chains());
+  const bool wide = rule == 1;
   FastParams q = p;                                                // the segment kernel's parameters
   Chains c;
   if (wide) {
@@ -1790,17 +1807,16 @@ int launch_fast_ppl(const FastParams& p, hipStream_t stream) {
     if (rc != E2E_OK) return rc;
   } else if constexpr (PPL == 8) {
     c = hf_chains<8, ChainF64L>(p.V);
-  } else if (force_f32 || (p.chains == E2E_CHAINS_F32 && PPL == 4)) {
+  } else if (rule == 3) {
     c = hf_chains<PPL, ChainF32>(p.V);
     q.ztol = kZTolF32;
-  } else if (!force_single && (PPL == 4 || (PPL == 2 && p.B <= 256)) && h1_supported(p.V, p.Smax, PPL)) {
+  } else if (rule == 4) {
     c = h1_chains(PPL, p.V);
-  } else if (!force_single && (PPL == 4 || force_halo) && p.Smax + 1 <= ChainF64::kMaxW * kHfOwn) {
+  } else if (rule == 5) {
     c = hf_chains<PPL, ChainF64>(p.V);
   } else {
-    const size_t lds8 = F1Lds::bytes(p.V), lds4 = F1Lds::bytes(p.V, 4);
-    if (p.B > 256 && lds8 > 80 * 1024 && lds4 <= 80 * 1024) c = Chains{&ctc_fast_chain_kernel<PPL, 4>, 512, lds4};
-    else c = Chains{&ctc_fast_chain_kernel<PPL>, 512, lds8};
+    if (rule == 7) c = Chains{&ctc_fast_chain_kernel<PPL, 4>, 512, F1Lds::bytes(p.V, 4)};
+    else c = Chains{&ctc_fast_chain_kernel<PPL>, 512, F1Lds::bytes(p.V)};
     q.trkA = p.cumA; q.trkB = p.cumB;
   }
   const int rc = launch_chains(c, p, stream);
@@ -1876,6 +1892,11 @@ bool fast_supported(int T, int V, int Smax, int dtype) {
 
 size_t fast_workspace_bytes(int B, int T, int V, int Smax) {
   return fast_layout(B, T, V, Smax).total;
+}
+
+int fast_route(int B, int V, int Smax, int chains) {
+  const int ppl = ppl_of(V, Smax);
+  return ppl == 0 ? 0 : 10 * ppl + chain_rule(ppl, B, V, Smax, chains, forced_chains());
 }
 
 int launch_exact_flagged(const LossArgs& a, int* flags, int mode, const FastRetry* retry);

@@ -110,14 +110,14 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
   for (int r = 0; r < kHxNP; r++) {
     const int gi = g0 + r, li = DIR == 0 ? gi : gi - 1;
     const bool lin = li >= 0 && li < S;
-    const int lv = lin ? (int)tg[li] : -1;
+    const int lv = lin ? label_of(tg[li]) : -1;
     lab[r] = (lin && lv >= 0 && lv < V) ? lv : V;          // V: the always-zero row
     if (DIR == 0) {
-      const int lpv = (li >= 1 && li - 1 < S) ? (int)tg[li - 1] : -1;
+      const int lpv = (li >= 1 && li - 1 < S) ? label_of(tg[li - 1]) : -1;
       sk[r] = (lin && li >= 1 && lv != blank && lpv != lv) ? skip_w : 0.0;              // ctc_loss.cpp:53-57
       badlab |= !halo && lin && (lv == blank || lv < 0 || lv >= V);
     } else {
-      const int tj = (gi >= 1 && gi < S) ? (int)tg[gi] : -1;                            // the skip label gi-1 -> label gi
+      const int tj = (gi >= 1 && gi < S) ? label_of(tg[gi]) : -1;                            // the skip label gi-1 -> label gi
       sk[r] = (gi >= 1 && gi < S && lv != blank && tj != lv) ? skip_w : 0.0;            // ctc_loss.cpp:91-96
     }
   }

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void wide_compact_kernel(WideParams p) {
   const int64_t Sq = p.t_len[b];
   const int S = Sq < 0 ? 0 : (Sq > p.Smax ? p.Smax : (int)Sq);
   const int64_t* tg = p.targets + (int64_t)b * p.tgt_stride;
-  for (int i = tid; i < S; i += 256) lab[i] = (int)tg[i];
+  for (int i = tid; i < S; i += 256) lab[i] = label_of(tg[i]);
   for (int k = tid; k < p.VC; k += 256) p.clabel[(size_t)b * p.VC + k] = (k == p.VC - 1) ? p.blank : -1;
   __syncthreads();
   for (int i = tid; i < S; i += 256) {
@@ -552,6 +552,15 @@ bool wide_takes_fast_lattice(int T, int V, int Smax, int dtype) {
   return wide_supported(T, V, Smax, dtype) && !wide_inner_exact(T, Smax);
 }
 
+int wide_row_form(int dtype, int V, int64_t sB, int64_t sT, int64_t sV, const void* x, const void* grads) {
+  const int epc = dtype_is_16bit(dtype) ? 8 : 4;   // elements per 16-byte access
+  const bool vec4 = sV == 1 && (sT % epc == 0) && (sB % epc == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
+                    (V % epc == 0) && (reinterpret_cast<uintptr_t>(grads) % 16 == 0);
+  if (!vec4) return 0;
+  if (V > 8192) return 1;                          // beyond what a wave's registers hold: logits read twice
+  return V <= 2048 ? 2 : V <= 4096 ? 3 : 4;
+}
+
 size_t wide_workspace_bytes(int B, int T, int V, int Smax, bool with_exact) {
   return wide_layout(B, T, V, Smax, with_exact).total;
 }
@@ -571,11 +580,9 @@ int launch_wide(const LossArgs& a, bool fallback_to_exact) {
   p.lse = reinterpret_cast<float*>(ws + l.lse); p.shift = reinterpret_cast<float*>(ws + l.shift);
   p.xc = reinterpret_cast<float*>(ws + l.xc);
   p.gc = reinterpret_cast<const float*>(ws + l.gc);
-  const bool io16 = dtype_is_16bit(a.dtype);
-  const int esz = io16 ? 2 : 4, epc = 16 / esz;    // element size, elements per 16-byte access
-  const bool vec4 = a.sV == 1 && (a.sT % epc == 0) && (a.sB % epc == 0) && (reinterpret_cast<uintptr_t>(a.x) % 16 == 0) &&
-                    (a.V % epc == 0) && (reinterpret_cast<uintptr_t>(a.grads) % 16 == 0);
-  const bool dense = vec4 && a.V <= 8192;          // the row fits a wave's registers: logits read once
+  const int esz = dtype_is_16bit(a.dtype) ? 2 : 4;             // element size
+  const int form = wide_row_form(a.dtype, a.V, a.sB, a.sT, a.sV, a.x, a.grads);
+  const bool vec4 = form >= 1, dense = form >= 2;
   hipLaunchKernelGGL(wide_compact_kernel, dim3(a.B), dim3(256), sizeof(int) * 3 * (a.Smax > 0 ? a.Smax : 1), a.stream, p);
   E2E_HIP_CHECK(hipGetLastError(), "wide_compact_kernel launch");
 

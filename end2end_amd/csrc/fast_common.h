@@ -339,9 +339,9 @@ struct LaneCells {
 #pragma unroll
     for (int q = 0; q < PPL; q++) {
       const int i = PPL * lane + q;
-      const int li = i < S ? (int)tg[i] : -1;
-      const int lp = (i >= 1 && i - 1 < S) ? (int)tg[i - 1] : -1;
-      const int ln = (i + 1 < S) ? (int)tg[i + 1] : -1;
+      const int li = i < S ? label_of(tg[i]) : -1;
+      const int lp = (i >= 1 && i - 1 < S) ? label_of(tg[i - 1]) : -1;
+      const int ln = (i + 1 < S) ? label_of(tg[i + 1]) : -1;
       lab[q] = i < S ? li : V;
       skp[q] = (i < S && i >= 1 && li != blank && lp != li) ? r * r : 0.f;
       skn[q] = (i + 1 < S && li != blank && ln != li) ? r * r : 0.f;

@@ -72,7 +72,10 @@ const char* e2e_last_error(void);
  *                   grads are d loss / d logits (= softmax - posterior for
  *                   t < x_len[b], 0 for padded rows), i.e. what
  *                   pytorch_end2end/modules/ctc_loss.py:37-40 + autograd give.
- *   targets      (B,*) int64, row stride tgt_stride, first t_len[b] entries used
+ *   targets      (B,Smax) int64, row stride tgt_stride (>= Smax), first t_len[b] entries used; what lies beyond them is never read
+ *   Smax         the WIDTH of the targets tensor.  It, not the longest target in the batch, selects the kernels (and sizes the
+ *                workspace): a batch padded to 300 columns runs other kernels than the same batch at 200, with the same results
+ *                (e2e_debug_loss_route in e2e_ctc_debug.h tells which).  A target is compared with [0,V) as the int64 it is.
  *   x_len,t_len  (B) int64 (1 <= x_len[b] <= T, 0 <= t_len[b] <= Smax).  An utterance whose lengths are
  *                outside these ranges, or whose first t_len[b] targets contain a value outside [0,V), gets
  *                loss = NaN and a NaN gradient slab (the reference reads out of bounds there); the other

@@ -10,6 +10,7 @@
 #define E2E_CTC_DEBUG_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -24,10 +25,35 @@ int e2e_debug_stream_copy(void* dst, const void* src, size_t bytes, void* stream
  * right results whether they run out or not). */
 int e2e_debug_occupy(int workgroups, int threads, int lds_bytes, long long nanoseconds, void* stream);
 
+/* Which kernels e2e_ctc_loss_fwd_bwd_opt gives a call of these sizes, strides and pointers (`chains`: e2e_ctc_loss_opts.chains),
+ * computed on the host by the functions the call itself dispatches with; no GPU is touched.  -1: the call is refused (bad
+ * sizes, a shape E2E_ALGO_FAST does not take, 16-bit logits the caller has to up-cast).  Otherwise 1000 * path + 100 * rows +
+ * 10 * pairs + rule:
+ *   path   1 the exact kernel (rows, pairs, rule 0); 2 the fast path; 3 the wide path (per-utterance compact alphabet of Smax + 1
+ *          columns) with the fast path's lattice on it; 4 the wide path with the exact kernel's lattice (rows only)
+ *   rows   the wide path's row kernels: 0 element by element in two passes, 1 the same by 16-byte accesses, 2 / 3 / 4 the
+ *          single-read kernels for up to 2048 / 4096 / 8192 columns; 0 on the other paths
+ *   pairs  label pairs per lane of the lattice kernels: 1, 2, 4, 8 (targets tensors of up to 63 / 127 / 255 / 447 columns;
+ *          alphabets of 97..224 columns 4 up to 223 labels, 8 beyond; of 225..448 columns always 8)
+ *   rule   what picks the chain kernel, as listed at launch_fast_ppl (end2end_amd/csrc/ctc_loss_fast.hip): 1 the wide-row forms
+ *          behind a probability table, 2 ChainF64L (eight pairs), 3 ChainF32, 4 the lean halo chains, 5 ChainF64, 6 the single-wave
+ *          chains, 7 the same with the ring of four blocks (B > 256)
+ * It is the WIDTH of the targets tensor, Smax, that selects all this -- not the longest target in it. */
+int e2e_debug_loss_route(int dtype, int algo, int B, int T, int V, int Smax, int chains,
+                         int64_t sB, int64_t sT, int64_t sV, const void* x, const void* grads);
+
 /* After an e2e_ctc_loss_fwd_bwd(ALGO_AUTO / ALGO_FAST) call that took the fast path: the per-utterance
  * flag words (0 = served by the fast path; bits: 1 bad lengths, 2 blank in targets, 4 infeasible,
  * 8 range / self-check, 16 non-finite, 32 log Z mismatch, 64 emissions near the end of f32) and the
- * alpha-side / beta-side log Z of the chains, read out of `workspace`.  Synchronises. */
+ * alpha-side / beta-side log Z of the chains, read out of `workspace`.  Synchronises.
+ * The words carry three more bits, which send the utterance to the full recomputation like 1 and 2: 128 a bounded wait
+ * inside a chain kernel ran out, 256 a probability below f32's smallest normal number (the fast path's table holds a marker in
+ * its place), 512 set by the flagged launch itself: an f64 redo of one of the utterance's segments failed (settled by the
+ * extended-range redo's second round).  What the flagged launch does with a word f: nothing for 0; f & (1 | 2 | 128 | 256):
+ * full recomputation by the exact kernel; else f & (4 | 32 | 64): the extended-range redo; else (8 / 16 only): the f64 redo of
+ * the flagged segments -- unless another utterance of the call takes the extended-range redo, which these then join.
+ * The extended-range redo leaves its own marks in the word: 2048 it ran the utterance's chains, 4096 and could not settle it
+ * (the exact kernel recomputes it), 8192 / 16384 the alpha / the beta chains have finished on a workgroup of their own. */
 int e2e_debug_fast_state(const void* workspace, int B, int T, int V, int Smax, int* flags_host, double* logz_host);
 
 /* How many flagged utterances of that call the f64 redo of the segments could not settle (they were

@@ -9,10 +9,33 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def c_abi_loss(x, targets, x_len, t_len, blank=0, logprobs=True, algo=_lib.ALGO_AUTO, keep=None, opts=None, chains=None):
+def padded_targets(targets, t_len, width, padding, row_stride=None):
+    """(B, width) int64 device view: row b holds targets[b, :t_len[b]], then padding[b] (one value per row, or one for all) up to
+    `width` columns.  row_stride > width: the view is buf[:, k:k + width] of a (B, row_stride) buffer whose other columns
+    hold the same padding values."""
+    tg = np.asarray(targets).astype(np.int64)
+    tl = np.asarray(t_len).astype(np.int64)
+    B = len(tl)
+    tg = tg.reshape(B, -1)
+    row_stride = width if row_stride is None else int(row_stride)
+    assert width >= 1 and row_stride >= width and (tl <= min(width, tg.shape[1])).all()
+    buf = np.empty((B, row_stride), dtype=np.int64)
+    buf[:] = np.broadcast_to(np.asarray(padding, dtype=np.int64).reshape(-1, 1), (B, 1))
+    k = (row_stride - width) // 2
+    for b in range(B):
+        buf[b, k:k + max(int(tl[b]), 0)] = tg[b, :max(int(tl[b]), 0)]
+    return torch.from_numpy(buf).to(dev())[:, k:k + width]
+
+
+def c_abi_loss(x, targets, x_len, t_len, blank=0, logprobs=True, algo=_lib.ALGO_AUTO, keep=None, opts=None, chains=None,
+               width=None, padding=-1, row_stride=None):
     """x: torch tensor (B,T,V) on any device with any strides (moved to the GPU keeping its layout).
     opts = (grad_scale, reduction): call e2e_ctc_loss_fwd_bwd_opt and return (losses, grads, reduced).
-    chains = _lib.CHAINS_F32: the same entry point with e2e_ctc_loss_opts.chains set (returns (losses, grads))."""
+    chains = _lib.CHAINS_F32: the same entry point with e2e_ctc_loss_opts.chains set (returns (losses, grads) without opts).
+    width / padding / row_stride: the targets tensor the call gets is padded_targets(...) -- `width` columns (that is Smax),
+    garbage beyond t_len[b], rows `row_stride` elements apart.
+    keep: receives the call's workspace, and under "route" what e2e_debug_loss_route says of exactly this call."""
+    import ctypes
     L = _lib.load()
     d = dev()
     if not x.is_cuda:
@@ -21,9 +44,12 @@ def c_abi_loss(x, targets, x_len, t_len, blank=0, logprobs=True, algo=_lib.ALGO_
         x = torch.empty_strided(base.shape, base.stride(), dtype=base.dtype, device=d)
         x.copy_(base)
     B, T, V = x.shape
-    targets = torch.as_tensor(np.asarray(targets)).to(d, torch.long).reshape(B, -1).contiguous()
-    if targets.shape[1] == 0:
-        targets = torch.zeros((B, 1), dtype=torch.long, device=d)
+    if width is not None:
+        targets = padded_targets(targets, t_len, width, padding, row_stride)
+    else:
+        targets = torch.as_tensor(np.asarray(targets)).to(d, torch.long).reshape(B, -1).contiguous()
+        if targets.shape[1] == 0:
+            targets = torch.zeros((B, 1), dtype=torch.long, device=d)
     xl = torch.as_tensor(np.asarray(x_len)).to(d, torch.long)
     tl = torch.as_tensor(np.asarray(t_len)).to(d, torch.long)
     Smax = targets.shape[1]
@@ -40,23 +66,33 @@ def c_abi_loss(x, targets, x_len, t_len, blank=0, logprobs=True, algo=_lib.ALGO_
             ws.data_ptr(), ws.numel(), algo, _lib.stream_ptr(d))
     if opts is None and chains is None:
         _lib.check(L.e2e_ctc_loss_fwd_bwd(*args))
-    elif opts is None:
-        import ctypes
-        o = _lib.LossOpts(1.0, None, _lib.REDUCE_NONE, int(chains))
-        _lib.check(L.e2e_ctc_loss_fwd_bwd_opt(*args, ctypes.byref(o)))
     else:
         reduced = torch.full((1,), 7.0, dtype=loss_dtype, device=d)
-        o = _lib.LossOpts(float(opts[0]), reduced.data_ptr() if opts[1] else None, int(opts[1]))
-        import ctypes
+        scale, reduction = (1.0, _lib.REDUCE_NONE) if opts is None else opts
+        o = _lib.LossOpts(float(scale), reduced.data_ptr() if reduction else None, int(reduction),
+                          int(chains) if chains is not None else _lib.CHAINS_F64)
         _lib.check(L.e2e_ctc_loss_fwd_bwd_opt(*args, ctypes.byref(o)))
     torch.cuda.synchronize()
     if keep is not None:
         keep["workspace"] = ws              # (diagnostics read the fast path's flag words out of it)
+        keep["Smax"] = Smax
+        keep["route"] = loss_route(code, algo, B, T, V, Smax, chains or 0, sB, sT, sV, x.data_ptr(), grads.data_ptr())
     if grads.dtype in (torch.float16, torch.bfloat16):
         grads = grads.float()                                # (numpy has no bf16)
     if opts is not None:
         return losses.cpu().numpy(), grads.cpu().numpy(), reduced.cpu().numpy()[0]
     return losses.cpu().numpy(), grads.cpu().numpy()
+
+
+def loss_route(dtype_code, algo, B, T, V, Smax, chains=0, sB=None, sT=None, sV=1, x=256, grads=256):
+    """e2e_debug_loss_route (include/e2e_ctc_debug.h); by default for contiguous, aligned tensors.  Needs no GPU."""
+    import ctypes
+    L = _lib.load()
+    L.e2e_debug_loss_route.restype = ctypes.c_int
+    L.e2e_debug_loss_route.argtypes = [ctypes.c_int] * 7 + [ctypes.c_longlong] * 3 + [ctypes.c_void_p] * 2
+    sT = V * sV if sT is None else sT
+    sB = T * sT if sB is None else sB
+    return L.e2e_debug_loss_route(dtype_code, algo, B, T, V, Smax, chains, sB, sT, sV, x, grads)
 
 
 def c_abi_greedy(x, x_len, blank=0):

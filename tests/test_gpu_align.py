@@ -20,9 +20,12 @@ def c_abi_align(lp, targets, x_len, t_len, blank=0, is_ctc=True, pad=-100):
         lp = torch.empty_strided(base.shape, base.stride(), dtype=base.dtype, device=d)
         lp.copy_(base)
     B, T, V = lp.shape
-    tg = torch.as_tensor(np.asarray(targets)).to(d, torch.long).reshape(B, -1).contiguous()
-    if tg.shape[1] == 0:
-        tg = torch.zeros((B, 1), dtype=torch.long, device=d)
+    if torch.is_tensor(targets) and targets.is_cuda:
+        tg = targets                   # a device tensor goes in as it is: (B, width) int64, rows tg.stride(0) apart
+    else:
+        tg = torch.as_tensor(np.asarray(targets)).to(d, torch.long).reshape(B, -1).contiguous()
+        if tg.shape[1] == 0:
+            tg = torch.zeros((B, 1), dtype=torch.long, device=d)
     xl = torch.as_tensor(np.asarray(x_len)).to(d, torch.long)
     tl = torch.as_tensor(np.asarray(t_len)).to(d, torch.long)
     out = torch.full((B, T), 7, dtype=torch.long, device=d)

@@ -15,6 +15,12 @@ Families (cases; what they drive):
   align    60                           e2e_ctc_align, bit-exact
   noblank  98 (f32 + f64, x 2 widths)   CTC without blank against tests/noblank_ref.py: every LDS block size K = 16..1
   gram     98 (f32 + f64, x 2 widths)   Gram-CTC against tests/gram_ref.py: every (max_order, K) of orders 1..8
+  callshape 393 random + 156 sweep     cases of the ext (120 f32 + 40 bf16 + 40 f16 drawn), fastauto (120), scaled (60) and exact (40)
+            + 7 flag-route batches     generators under a randomised CALL SHAPE: targets padded into another dispatch band with garbage
+                                        beyond t_len, tgt_stride beyond the width, strided logits, grad_scale, fused reduction; asserts
+                                        the routes (e2e_debug_loss_route) and flag routes it reached.  16-bit cases that the engine
+                                        would up-cast are counted as callshape_upcast.  The align family runs each case a second
+                                        time with padded targets.
 (noblank and gram compare with the f64 test-side references, not the oracle: each case runs with targets exactly max(t_len)
 wide and padded wider with garbage, and both runs must match; the tests assert the block sizes and redo reasons they reach.)
 The beam search's slice of the same kind lives in tests/test_gpu_beam.py::test_fuzz_slice_equals_the_oracle_or_is_a_proven_tie
@@ -274,6 +280,7 @@ def test_fast_path_family_against_the_oracle(seed, n):
 # ---------------------------------------------------------------------------------------------------------------------
 def test_align_family_is_bit_exact_against_the_oracle():
     rng = np.random.default_rng(0)
+    rp = np.random.default_rng(100)                      # the padded second run's draws
     bad = []
     for case in range(60):
         B = int(rng.integers(1, 6)); T = int(rng.integers(1, 300)); V = int(rng.integers(2, 40))
@@ -305,6 +312,14 @@ def test_align_family_is_bit_exact_against_the_oracle():
         _count("align", B)
         if not np.array_equal(got, want):
             bad.append((case, dict(B=B, T=T, V=V, S=S, is_ctc=is_ctc, blank=blank, style=style)))
+        # the same call with the targets padded wider with garbage beyond t_len and handed over as a column slice of a wider
+        # buffer (tgt_stride > width): the same labelling (the draws come from a generator of their own)
+        fill = [[-1, V, blank, int(pool[0]), 1 << 40, -(1 << 63)][int(rp.integers(0, 6))] for _ in range(B)]
+        width = tg.shape[1] + int(rp.integers(1, 200))
+        wide = U.padded_targets(tg.numpy(), tl, width, fill, width + int(rp.integers(1, 41)))
+        got = c_abi_align(lp, wide, xl, tl, blank, is_ctc)
+        if not np.array_equal(got, want):
+            bad.append((case, "padded to %d with %s" % (width, sorted(set(fill))), dict(B=B, T=T, V=V, S=S, is_ctc=is_ctc, blank=blank, style=style)))
     assert not bad, bad
 
 
@@ -754,3 +769,433 @@ def test_gram_family_against_the_f64_lattice(dtype, seed, n):
     assert reached == set(GC_PAIRS), "(max_order, K) not reached: %s" % sorted(set(GC_PAIRS) - reached)
     if dtype == torch.float32:
         assert {1, 2} <= reasons, "redo reasons reported: %s" % sorted(reasons)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# callshape: cases of the generators above (new seeds) under a randomised CALL SHAPE -- what the families above never vary.
+# The library picks its kernels from the targets tensor's width (Smax), not from the lengths, so a padded batch runs other
+# kernels than the same batch at its exact width; grad_scale is applied by whichever kernel writes a gradient element and the
+# reduction by whichever workgroup ends the call.  Expected values: the oracle on the exact-width targets, times the scale in
+# f64.  Every draw of the shape comes from a generator of its own, so the case generators keep their streams.
+# ---------------------------------------------------------------------------------------------------------------------
+# around every edge of the dispatch (95/96: the compact alphabet of Smax + 1 columns reaches the lattice kernels' 96/97), one well beyond
+CS_WIDTHS = [63, 64, 95, 96, 127, 128, 223, 224, 255, 256, 447, 448, 600]
+CS_BANDS = [(0, 63), (64, 95), (96, 127), (128, 223), (224, 255), (256, 447), (448, 1 << 30)]
+CS_PAD_KINDS = ["-1", "V", "blank", "valid", "2**40", "-2**63"]
+CS_LAYOUTS = ["contiguous", "time_major", "strided", "pitch"]
+CS_SCALES = [1.0, 0.37, None, -3.0]                                   # (None: 1 / B)
+CS_REDUCTIONS = [None, "sum", "mean"]
+# flag routes of a fast-path call (include/e2e_ctc_debug.h, e2e_debug_fast_state): what the flagged launch had to do
+CS_FLAG_ROUTES = ["none", "segments4", "segments8", "extended", "full"]
+
+
+def _cs_band(width):
+    return next(i for i, (lo, hi) in enumerate(CS_BANDS) if lo <= width <= hi)
+
+
+def _cs_shape(rs, tl, B, V, blank):
+    """the call shape of one case, drawn from `rs`"""
+    W = max(int(np.max(tl)), 1)
+    wider = [w for w in CS_WIDTHS if w > W and _cs_band(w) != _cs_band(W)]
+    width = W if (not wider or rs.random() < 0.2) else int(rs.choice(wider))
+    labels = [v for v in range(V) if v != blank] or [blank]
+    fill = {"-1": -1, "V": V, "blank": blank, "2**40": 1 << 40, "-2**63": -(1 << 63)}
+    kinds = [str(rs.choice(CS_PAD_KINDS)) for _ in range(B)]
+    padding = [fill[k] if k != "valid" else int(rs.choice(labels)) for k in kinds]
+    row_stride = width if rs.random() < 0.5 else width + int(rs.integers(1, 41))
+    scale = CS_SCALES[int(rs.integers(0, 4))]
+    return dict(width=width, padded=width > W, half=2 * W <= width, padding=padding, row_stride=row_stride,
+                layout=str(rs.choice(CS_LAYOUTS)), scale=1.0 / B if scale is None else scale,
+                reduction=CS_REDUCTIONS[int(rs.integers(0, 3))])
+
+
+def _cs_layout(x, layout):
+    """x (B, T, V) on the host as the call gets it: contiguous, a time-major view, column-strided (sV = 2), or with a gap
+    between the utterances (c_abi_loss keeps the strides on its way to the GPU)"""
+    B, T, V = x.shape
+    if layout == "time_major":
+        return x.permute(1, 0, 2).contiguous().permute(1, 0, 2)
+    if layout == "strided":
+        w = torch.zeros(B, T, 2 * V, dtype=x.dtype)
+        w[:, :, ::2] = x
+        return w[:, :, ::2]
+    if layout == "pitch":
+        w = torch.zeros(B, T + 3, V, dtype=x.dtype)
+        w[:, :T] = x
+        return w[:, :T]
+    return x.contiguous()
+
+
+def _cs_flag_routes(keep, B, T, V):
+    """what the flagged launch of a fast-path AUTO call did, from the flag words the chains and the segment kernel left
+    (masked to the bits include/e2e_ctc_debug.h documents; 512 is the launch's own)"""
+    L = _lib.load()
+    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
+    flags, logz = (ctypes.c_int * B)(), (ctypes.c_double * (2 * B))()
+    assert L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], flags, logz) == 0
+    raw = np.array(flags[:], dtype=np.int64)
+    f = raw & 511                                                  # what the chains and the segment kernel reported
+    took_ext = (raw & 2048) != 0                                   # the extended-range redo ran this utterance's chains (round 0 or 1)
+    full = ((f & (1 | 2 | 128 | 256)) != 0) | ((raw & 4096) != 0)
+    rng_only = (f != 0) & ((f & ~(8 | 16)) == 0) & ~took_ext
+    out = set()
+    if not f.any():
+        out.add("none")
+    if full.any():
+        out.add("full")
+    if took_ext.any():
+        out.add("extended")
+    pairs = keep["route"] // 10 % 10
+    if rng_only.any() and pairs in (4, 8):                         # settled by the f64 redo of their flagged segments
+        out.add("segments%d" % pairs)
+    return out
+
+
+class _CsLog:
+    """what the family reached: route code -> set of marks ('padded', 'scale', 'reduction'), the same per flag route,
+    the bands in which a genuinely padded case (max(t_len) at most half the width) ran"""
+    def __init__(self):
+        self.routes, self.flag_routes, self.half_bands, self.row_forms = {}, {}, set(), {}
+
+    def add(self, sh, keep, flag_routes):
+        marks = {"any"} | ({"padded"} if sh["padded"] else set())
+        if sh["padded"] and sh["scale"] != 1.0:
+            marks.add("scale")
+        if sh["padded"] and sh["reduction"]:
+            marks.add("reduction")
+        self.routes.setdefault(keep["route"], set()).update(marks)
+        for fr in flag_routes:
+            m = self.flag_routes.setdefault(fr, set())
+            m.update(({"scale"} if sh["scale"] != 1.0 else set()) | ({"reduction"} if sh["reduction"] else set()))
+            if sh["scale"] != 1.0 and sh["reduction"]:
+                m.add("both")
+        if sh["padded"] and sh["half"]:
+            self.half_bands.add(_cs_band(sh["width"]))
+
+
+CS_LOG = _CsLog()
+CS_SEEN = []          # (style, seed) of the slices that ran: the coverage test below needs all of them
+
+
+def _cs_run(c_x, logprobs, tg, xl, tl, blank, algo, sh, tol, log, io16=None):
+    """One call under the shape `sh` against the oracle -> None, or the first difference.  c_x: what the call is given (a host
+    tensor of the call's dtype).  tol = (loss rtol, loss atol, grad rtol, grad atol before the scale)."""
+    tg, xl, tl = np.asarray(tg), np.asarray(xl), np.asarray(tl)
+    B, T, V = c_x.shape
+    lp = c_x.double() if logprobs else torch.log_softmax(c_x.double(), -1)
+    l_o, g_o = O.ctc_loss(lp.numpy(), tg, xl, tl, blank)                  # (the exact-width targets)
+    if not logprobs:
+        for b in range(B):
+            if np.isfinite(l_o[b]):
+                g_o[b, int(xl[b]):] = 0.0                                  # (an infeasible utterance stays NaN everywhere, quirk Q2)
+    g_o = g_o * sh["scale"]
+    red = {None: _lib.REDUCE_NONE, "sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN}[sh["reduction"]]
+    keep = {}
+    la, ga, got_red = U.c_abi_loss(_cs_layout(c_x, sh["layout"]), tg, xl, tl, blank, logprobs, algo, keep=keep,
+                                   opts=(sh["scale"], red), width=sh["width"], padding=sh["padding"], row_stride=sh["row_stride"])
+    assert keep["route"] > 0, "the route diagnostic refuses a call that ran: %d" % keep["route"]
+    flag_routes = _cs_flag_routes(keep, B, T, V) if (keep["route"] // 1000 == 2 and algo == _lib.ALGO_AUTO) else set()
+    log.add(sh, keep, flag_routes)
+    if io16 is not None:
+        ga = torch.from_numpy(ga).to(io16).float().numpy()                 # (an up-cast call: the engine rounds the gradient back)
+    lr, la_, gr, ga_ = tol
+    try:
+        U.assert_same(la, l_o, lr, la_, "losses")
+        U.assert_same(ga, g_o, gr, ga_ * abs(sh["scale"]), "grads")
+        if sh["reduction"]:
+            # 1. against the oracle: the per-loss tolerance summed over the batch
+            want = l_o.sum() if sh["reduction"] == "sum" else l_o.mean()
+            if np.isnan(l_o).any():
+                assert np.isnan(got_red), "reduced %r, want NaN" % got_red
+            elif np.isinf(l_o).any():
+                assert got_red == np.inf, "reduced %r, want +inf" % got_red
+            else:
+                bound = (lr * np.abs(l_o) + la_).sum() / (B if sh["reduction"] == "mean" else 1)
+                assert abs(float(got_red) - want) <= bound, "reduced %r, oracle %r" % (got_red, want)
+                # 2. against the f64 sum of the losses this call returned.  Every writer of the reduced loss accumulates in f64 and
+                # rounds once to the result's type: the flagged launch (write_reduction in ctc_exact_kernel) and, behind the exact
+                # kernel and the wide path (after its loss correction), reduce_losses_kernel.  So the bound is one rounding of the
+                # result's type, plus B roundings of the f64 accumulation in whatever order
+                l64 = la.astype(np.float64)
+                own = l64.sum() / (B if sh["reduction"] == "mean" else 1)
+                eps = 2.0 ** -53 if c_x.dtype == torch.float64 else 2.0 ** -24
+                assert abs(float(got_red) - own) <= eps * abs(own) + (B + 1) * 2.0 ** -53 * np.abs(l64).sum(), \
+                    "reduced %r, the call's own losses give %r" % (got_red, own)
+        return None
+    except AssertionError as e:
+        return ["route %d %s" % (keep["route"], sorted(flag_routes))] + str(e).strip().splitlines()[:5]
+
+
+def _cs_describe(sh):
+    return "width %d stride %d %s scale %g %s pad %s" % (sh["width"], sh["row_stride"], sh["layout"], sh["scale"], sh["reduction"],
+                                                         sorted(set(sh["padding"])))
+
+
+def _takes_dtype(x, algo, width):
+    """e2e_ctc_loss_takes_dtype as CTCLossEngine.compute asks it"""
+    B, T, V = x.shape
+    sB, sT, sV = x.stride()
+    return bool(_lib.load().e2e_ctc_loss_takes_dtype(_lib.dtype_code(x.dtype), algo, T, V, width, sB, sT, sV, None, None))
+
+
+G16 = {None: (1e-4, 2e-6), torch.bfloat16: (2.0 ** -7, 2.0 ** -8), torch.float16: (2.0 ** -10, 2.0 ** -11)}
+
+
+@pytest.mark.parametrize("style,seed,n,dtype", [("ext", 40, 120, None), ("ext", 41, 40, torch.bfloat16), ("ext", 42, 40, torch.float16),
+                                                ("fastauto", 43, 120, None), ("scaled", 44, 60, None), ("exact", 45, 40, None)],
+                         ids=["ext_f32_seed40", "ext_bf16_seed41", "ext_f16_seed42", "fastauto_seed43", "scaled_seed44", "exact_seed45"])
+def test_callshape_family_against_the_oracle(style, seed, n, dtype):
+    rng = np.random.default_rng(seed)                   # the cases: the generators' own stream
+    rs = np.random.default_rng(1000 + seed)             # the call shapes
+    bad, marginal, done = [], [], 0
+    for case in range(n):
+        algo, io16, up16 = _lib.ALGO_AUTO, dtype, None
+        if style == "ext":
+            c = _ext_case(rng)
+            if c["logprobs"] and dtype is not None:
+                continue                                 # (16-bit log-probabilities cannot hold these: logits only)
+            xt, logprobs, blank = torch.from_numpy(c["x"]), c["logprobs"], c["blank"]
+            x = torch.log_softmax(xt, -1).float() if logprobs else (xt.float() if io16 is None else xt.to(io16))
+            tg, xl, tl = c["tg"], c["xl"], c["tl"]
+        elif style == "fastauto":
+            c = _fast_case(rng)
+            xt, logprobs, blank = torch.from_numpy(c["x"]), c["logprobs"], c["blank"]
+            io16 = None if logprobs else [None, None, torch.bfloat16, torch.float16][case % 4]
+            x = xt.float() if io16 is None else xt.to(io16)
+            if logprobs:
+                x = torch.log_softmax(x.double(), -1).float()
+            tg, xl, tl = c["tg"], c["xl"], c["tl"]
+        else:
+            c = _small_case(rng, case, style, wide=(style == "scaled" and case % 3 == 0))
+            x, logprobs, blank = c["inp"], not c["fused"], c["blank"]
+            tg, xl, tl = c["tg"].numpy(), c["xl"].numpy(), c["tl"].numpy()
+            algo = _lib.ALGO_AUTO if style == "scaled" else _lib.ALGO_EXACT
+        B, T, V = x.shape
+        sh = _cs_shape(rs, tl, B, V, blank)
+        if io16 is not None and not _takes_dtype(_cs_layout(x, sh["layout"]), algo, sh["width"]):
+            x, up16 = x.float(), io16                    # as CTCLossEngine.compute: up-cast, the gradient rounded back
+        if style in ("scaled", "exact"):
+            tol = (1e-9, 1e-12, 1e-9, 1e-12) if c["f64"] else (1e-4, 2e-6, 1e-4, 2e-6)
+        else:
+            tol = (1e-4, 2e-5) + G16[io16]
+        r = _cs_run(x, logprobs, tg, xl, tl, blank, algo, sh, tol, CS_LOG, io16=up16)
+        if r is not None and style == "ext":
+            # the ext family's marginal rule, unchanged: single elements within 1e-5 (times |scale|), at most max(1, done // 50) cases
+            r2 = _cs_run(x, logprobs, tg, xl, tl, blank, algo, sh, tol[:3] + (max(1e-5, 2 * tol[3]),), _CsLog(), io16=up16)
+            if r2 is None:
+                marginal.append(case)
+                r = None
+        done += 1
+        _count("callshape_upcast" if up16 is not None else "callshape", B)
+        if r is not None:
+            bad.append((case, tuple(x.shape), str(x.dtype), int(np.max(tl)), blank, logprobs, _cs_describe(sh), r))
+    CS_SEEN.append((style, seed))
+    assert not bad, "mismatching cases of %s seed %d: %s" % (style, seed, bad)
+    assert len(marginal) <= max(1, done // 50), "marginal cases (one element within 1e-5) of seed %d: %s" % (seed, marginal)
+
+
+def _cs_key(route):
+    """a route code without its row-kernel digit: (path, 10 * pairs + rule)"""
+    return route // 1000, route % 100
+
+
+# what the generators' alphabets and the widths above reach (B <= 8: not the ring of four blocks; no f32 chains; rows of
+# 2049..4096 and of more than 8192 columns are in no generator)
+CS_ROUTES = {(1, 0), (2, 16), (2, 24), (2, 26), (2, 44), (2, 45), (2, 46), (2, 41), (2, 81), (2, 82),
+             (3, 16), (3, 24), (3, 26), (3, 41), (3, 81), (4, 0)}
+CS_ROW_FORMS = {0, 2, 4}
+
+
+def test_callshape_family_reached_every_route_padded_scaled_and_reduced():
+    """A fuzz that never leaves one route proves little.  Runs a deterministic sweep -- unit noise, targets of at most 30 labels,
+    every alphabet class at EVERY width of CS_WIDTHS, scale and reduction alternating -- and four batches built like
+    tests/test_gpu_regimes.py's for the flag routes, then asserts over them and the random slices above: every route the
+    generators can reach was reached by a padded case, with grad_scale != 1 and with a reduction; every flag route was seen with
+    grad_scale != 1 and with a reduction; every band had a batch padded to at least twice its longest target."""
+    for params in [("ext", 40, 120, None), ("ext", 41, 40, torch.bfloat16), ("ext", 42, 40, torch.float16),
+                   ("fastauto", 43, 120, None), ("scaled", 44, 60, None), ("exact", 45, 40, None)]:
+        if params[:2] not in CS_SEEN:                    # (this test selected alone: the slices run here)
+            test_callshape_family_against_the_oracle(*params)
+    bad = []
+    rng = np.random.default_rng(50)
+    combos = [(0.37, "sum"), (-3.0, "mean"), (0.125, None), (1.0, "sum")]
+    k = 0
+    for V in (29, 80, 150, 300, 1000, 8000):
+        B, T, S = 3, 120, 30
+        for width in CS_WIDTHS:
+            x = torch.from_numpy(rng.standard_normal((B, T, V))).float()
+            tg = rng.integers(1, V, size=(B, S)); tl = rng.integers(1, S + 1, size=B); tl[0] = S
+            xl = np.array([T, T - 9, T // 2 + 20])
+            for scale, reduction in (combos[k % 4], combos[(k + 1) % 4]):
+                sh = dict(width=width, padded=True, half=True, padding=[-1, V, 1 << 40], row_stride=width + 5 * (k % 2),
+                          layout=CS_LAYOUTS[k % 4], scale=scale, reduction=reduction)
+                r = _cs_run(x, False, tg, xl, tl, 0, _lib.ALGO_AUTO, sh, (1e-4, 2e-5, 1e-4, 2e-6), CS_LOG)
+                _count("callshape", B)
+                if r is not None:
+                    bad.append(("sweep", V, _cs_describe(sh), r))
+            k += 1
+    # flag routes, deterministic: (a) a trained model's batch with mislabelled utterances (extended range), sharp unrelated ones
+    # (range flags: they join the extended-range redo) and a blank-valued target (full recomputation); (b) sharp unrelated
+    # emissions at scale 3, flagged for range only: the f64 redo of single segments, in the four-pairs instance at the exact
+    # width and, padded to 300 columns, in the eight-pairs instance
+    from test_gpu_regimes import aligned
+    rng = np.random.default_rng(77)
+    x, tg, xl, tl = aligned(rng, 12, 1000, 29, 200, 10.0, short=[(5, 933)])
+    tg[1], tl[1] = tg[2].copy(), tl[2]
+    tg[5], tl[5] = tg[6].copy(), tl[6]
+    x[7] = rng.standard_normal(x[7].shape) * 3.0
+    x[8] = rng.standard_normal(x[8].shape) * 3.0
+    tg[9, 3] = 0
+    want = {}
+    for width, scale, reduction in ((200, -3.0, "mean"), (224, 0.37, "sum")):
+        sh = dict(width=width, padded=width > 200, half=False, padding=[-1] * 12, row_stride=width + 7, layout="contiguous",
+                  scale=scale, reduction=reduction)
+        log = _CsLog()
+        r = _cs_run(torch.from_numpy(x), False, tg, xl, tl, 0, _lib.ALGO_AUTO, sh, (1e-4, 2e-5, 1e-4, 2e-6), log)
+        _count("callshape", 12)
+        want["a%d" % width] = ({"full"}, set(log.flag_routes))
+        CS_LOG.add(sh, {"route": next(iter(log.routes))}, set(log.flag_routes))
+        if r is not None:
+            bad.append(("flags a", _cs_describe(sh), r))
+    rng = np.random.default_rng(504)                     # (c) sharp unrelated emissions at scale 8: the extended-range redo
+    B, T, V, S = 4, 500, 29, 100
+    x = (rng.standard_normal((B, T, V)) * 8.0).astype(np.float32)
+    tg = rng.integers(1, V, size=(B, S)); tl = rng.integers(S // 2, S + 1, size=B); xl = np.array([T, T - 21, T, T])
+    for width, scale, reduction in ((100, 0.37, "sum"), (128, -3.0, "mean")):
+        sh = dict(width=width, padded=width > 100, half=False, padding=[1 << 40] * B, row_stride=width + 1, layout="time_major",
+                  scale=scale, reduction=reduction)
+        log = _CsLog()
+        r = _cs_run(torch.from_numpy(x), False, tg, xl, tl, 0, _lib.ALGO_AUTO, sh, (1e-4, 2e-5, 1e-4, 2e-6), log)
+        _count("callshape", B)
+        want["c%d" % width] = ({"extended"}, set(log.flag_routes))
+        CS_LOG.add(sh, {"route": next(iter(log.routes))}, set(log.flag_routes))
+        if r is not None:
+            bad.append(("flags c", _cs_describe(sh), r))
+    rng = np.random.default_rng(5)
+    B, T, V, S = 8, 1000, 29, 200
+    x = (rng.standard_normal((B, T, V)) * 3.0).astype(np.float32)
+    tg = rng.integers(1, V, size=(B, S)); tl = rng.integers(S // 2, S + 1, size=B); xl = np.full(B, T)
+    for width, scale, reduction in ((200, -3.0, "mean"), (300, 0.37, "sum"), (300, -3.0, "mean")):
+        sh = dict(width=width, padded=width > 200, half=False, padding=[V] * B, row_stride=width, layout="pitch",
+                  scale=scale, reduction=reduction)
+        log = _CsLog()
+        r = _cs_run(torch.from_numpy(x), False, tg, xl, tl, 0, _lib.ALGO_AUTO, sh, (1e-4, 2e-5, 1e-4, 2e-6), log)
+        _count("callshape", B)
+        want["b%d" % width] = ({"segments%d" % (4 if width == 200 else 8)}, set(log.flag_routes))
+        CS_LOG.add(sh, {"route": next(iter(log.routes))}, set(log.flag_routes))
+        if r is not None:
+            bad.append(("flags b", _cs_describe(sh), r))
+    L = CS_LOG
+    print("callshape routes:", {r: sorted(m) for r, m in sorted(L.routes.items())})
+    print("callshape flag routes:", {r: sorted(m) for r, m in sorted(L.flag_routes.items())}, {k: sorted(v[1]) for k, v in want.items()})
+    assert not bad, "mismatching cases: %s" % bad
+    for name, (need, got) in want.items():
+        assert need <= got, "batch %s no longer takes the flag route it was built for: %s, not %s" % (name, sorted(got), sorted(need))
+
+    keys = {}
+    for route, marks in L.routes.items():
+        keys.setdefault(_cs_key(route), set()).update(marks)
+    need = CS_ROUTES | set(keys)
+    missing = {k: sorted({"padded", "scale", "reduction"} - keys.get(k, set())) for k in sorted(need)
+               if not {"padded", "scale", "reduction"} <= keys.get(k, set())}
+    assert not missing, "routes (path, 10 * pairs + rule) not reached by a padded case / with grad_scale != 1 / with a reduction: %s" % missing
+    rows = {r // 100 % 10 for r, m in L.routes.items() if r // 1000 in (3, 4) and {"padded", "scale", "reduction"} <= m}
+    assert CS_ROW_FORMS <= rows, "row kernels of the wide path reached padded, scaled and reduced: %s" % sorted(rows)
+    fmiss = {f: sorted({"scale", "reduction"} - L.flag_routes.get(f, set())) for f in CS_FLAG_ROUTES
+             if not {"scale", "reduction"} <= L.flag_routes.get(f, set())}
+    assert not fmiss, "flag routes not seen with grad_scale != 1 / with a reduction: %s" % fmiss
+    assert set(range(1, len(CS_BANDS))) <= L.half_bands, "bands with a batch padded to twice its longest target: %s" % sorted(L.half_bands)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Labels that only fit in 64 bits.  include/e2e_ctc.h promises NaN for an utterance whose first t_len[b] targets hold a value
+# outside [0, V).  Until this family was written the fast and wide paths narrowed a target to 32 bits BEFORE that test, so
+# 2**32 + 3 or 3 - 2**32 inside t_len was computed as label 3: a finite loss under AUTO / FAST, NaN under EXACT.
+# One shape per reader of the targets.
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,B,T,V,S,scale,algo,chains", [
+    ("one_pair_LaneCells_load", 5, 200, 29, 60, 1.0, _lib.ALGO_AUTO, None),
+    ("two_pairs_lean_halo", 5, 400, 29, 100, 1.0, _lib.ALGO_AUTO, None),
+    ("four_pairs_lean_halo", 5, 600, 29, 200, 1.0, _lib.ALGO_AUTO, None),
+    ("four_pairs_f32_chains", 5, 600, 29, 200, 1.0, _lib.ALGO_AUTO, _lib.CHAINS_F32),
+    ("four_pairs_f64_halo_V80", 5, 600, 80, 200, 1.0, _lib.ALGO_AUTO, None),
+    ("eight_pairs", 5, 800, 29, 300, 1.0, _lib.ALGO_AUTO, None),
+    ("wide_rows_V150", 5, 400, 150, 100, 1.0, _lib.ALGO_AUTO, None),
+    ("compaction_V8000", 5, 150, 8000, 50, 1.0, _lib.ALGO_AUTO, None),
+    ("extended_range_redo", 5, 500, 29, 100, 8.0, _lib.ALGO_AUTO, None),
+    ("f64_segment_redo", 8, 1000, 29, 200, 3.0, _lib.ALGO_AUTO, None),
+    ("fast_only", 5, 400, 29, 100, 1.0, _lib.ALGO_FAST, None),
+    ("exact", 5, 100, 29, 40, 1.0, _lib.ALGO_EXACT, None),
+], ids=lambda v: v if isinstance(v, str) else "")
+def test_a_label_beyond_32_bits_inside_t_len_poisons_its_utterance_only(name, B, T, V, S, scale, algo, chains):
+    redo = name == "f64_segment_redo"          # (the batch of test_gpu_regimes.py's range-flag tests: seed 5, every utterance T frames long)
+    rng = np.random.default_rng(5 if redo else len(name) + T)
+    x = (rng.standard_normal((B, T, V)) * scale).astype(np.float32)
+    tg = rng.integers(1, V, size=(B, S)).astype(np.int64)
+    tl = rng.integers(S // 2, S + 1, size=B)
+    xl = np.full(B, T)
+    if not redo:
+        tl[0], xl[B - 1] = S, T - 11
+    lp = torch.log_softmax(torch.from_numpy(x).double(), -1).numpy()
+    l_o, g_o = O.ctc_loss(lp, tg, xl, tl, 0)                                   # (before the labels are spoilt)
+    for b in range(B):
+        g_o[b, xl[b]:] = 0.0
+    assert np.isfinite(l_o).all()
+    bad = tg.copy()
+    where = {1: (int(tl[1]) - 1, 1 << 32), 2: (0, -(1 << 32)), 3: (int(tl[3]) // 2, 1 << 40)}    # utterance: (position, offset)
+    for b, (i, off) in where.items():
+        bad[b, i] += off                                                       # the low 32 bits stay a valid non-blank label
+        l_o[b], g_o[b] = np.nan, np.nan
+    keep = {}
+    la, ga = U.c_abi_loss(torch.from_numpy(x), bad, xl, tl, 0, False, algo, keep=keep, chains=chains)
+    if algo == _lib.ALGO_FAST:                                                 # (FAST poisons whatever leaves the f32 lattice, too)
+        assert np.isnan(la[[1, 2, 3]]).all() and np.isnan(ga[[1, 2, 3]]).all(), la
+        return
+    U.assert_same(la, l_o, 1e-4, 2e-5, "losses (route %d)" % keep["route"])
+    U.assert_same(ga, g_o, 1e-4, 2e-5 if chains else 2e-6, "grads (route %d)" % keep["route"])
+    want_route = {"one_pair_LaneCells_load": 2016, "two_pairs_lean_halo": 2024, "four_pairs_lean_halo": 2044, "four_pairs_f32_chains": 2043,
+                  "four_pairs_f64_halo_V80": 2045, "eight_pairs": 2082, "wide_rows_V150": 2041, "compaction_V8000": 3416,
+                  "extended_range_redo": 2024, "f64_segment_redo": 2044, "exact": 1000}[name]
+    assert keep["route"] == want_route, (keep["route"], want_route)
+    if name in ("extended_range_redo", "f64_segment_redo"):
+        got = _cs_flag_routes(keep, B, T, V)
+        assert {"extended_range_redo": "extended", "f64_segment_redo": "segments4"}[name] in got and "full" in got, got
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The module on a headline-like batch whose targets tensor is padded, as a collate function pads it
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_module_on_a_padded_headline_like_batch(dtype):
+    """CTCLoss(reduce=True, size_average=True / False) and reduce=False with a weighted backward on B=8, T=1000, V=29, S<=120,
+    the targets padded with -1 to 129, 224, 300, 448 and 600 columns: four pairs per lane on the lean halo chains, the
+    single-wave chains, eight pairs per lane, and -- from 448 columns on -- the exact kernel (16-bit logits up-cast by the
+    engine).  Loss and input gradient against the oracle at every width."""
+    from end2end_amd import CTCLoss
+    rng = np.random.default_rng(8)
+    B, T, V, S = 8, 1000, 29, 120
+    x = torch.from_numpy(rng.standard_normal((B, T, V))).float().to(dtype)
+    tg = rng.integers(1, V, size=(B, S)); tl = rng.integers(S // 2, S + 1, size=B); tl[0] = S
+    xl = rng.integers(T // 2, T + 1, size=B); xl[0] = T
+    l_o, g_o = O.ctc_loss(torch.log_softmax(x.double(), -1).numpy(), tg, xl, tl, 0)
+    for b in range(B):
+        g_o[b, xl[b]:] = 0.0
+    w = np.array([1.0, -2.0, 0.5, 4.0, -1.0, 0.25, 2.0, -0.5])                 # the weights of the reduce=False backward: powers of two,
+                                                                               # so that a 16-bit gradient is rounded once, by the kernel
+    g_rtol, g_atol = G16[None if dtype == torch.float32 else dtype]
+    for width in (129, 224, 300, 448, 600):
+        pad = U.padded_targets(tg, tl, width, -1)
+        for mode, want_l, want_g in (("mean", l_o.mean(), g_o / B), ("sum", l_o.sum(), g_o), ("none", l_o, g_o * w[:, None, None])):
+            xd = x.to(DEV).requires_grad_()
+            mod = CTCLoss(reduce=mode != "none", size_average=mode == "mean")
+            loss = mod(xd, pad, torch.from_numpy(xl).to(DEV), torch.from_numpy(tl).to(DEV))
+            if mode == "none":
+                loss.backward(torch.from_numpy(w).to(DEV, loss.dtype))
+            else:
+                loss.backward()
+            what = "%s, %d columns" % (mode, width)
+            # (a 16-bit module returns its loss in the logits' dtype: one rounding of that type on top of the f32 bound)
+            l_rtol = 1e-4 if dtype == torch.float32 else 1e-4 + 2.0 ** -8
+            U.assert_same(loss.detach().double().cpu().numpy(), want_l, l_rtol, 2e-5, "loss (%s)" % what)
+            wmax = 1.0 if mode != "none" else float(np.abs(w).max())
+            U.assert_same(xd.grad.double().cpu().numpy(), want_g, g_rtol, g_atol * wmax, "gradient (%s)" % what)

@@ -312,3 +312,52 @@ def test_one_character_labels_that_are_lone_surrogates_still_spell():
     assert eng._strings(torch.tensor([[1, 2, 0], [2, 2, 2]]), [2, 3]) == ["\ud800a", "aaa"]
     plain = DecoderEngine(0, 1, ["_", "b", "a"])
     assert plain._codes is not None and plain._strings(torch.tensor([[1, 2, 0], [2, 2, 2]]), [2, 3]) == ["ba", "aaa"]
+
+
+def test_loss_route_at_the_band_edges():
+    """e2e_debug_loss_route -- computed by the functions the loss call dispatches with (resolve_algo, use_wide, wide_row_form,
+    ppl_of, chain_rule), on the host -- at the edges README / DESIGN name.  It is the WIDTH of the targets tensor that moves a
+    call from band to band: tests/test_gpu_fuzz.py's callshape family pads its way through all of them."""
+    import gpu_util as U
+    from end2end_amd import _lib
+    f32, f64, bf16 = _lib.F32, _lib.F64, _lib.BF16
+    AUTO, EXACT, FAST = _lib.ALGO_AUTO, _lib.ALGO_EXACT, _lib.ALGO_FAST
+
+    def route(B, T, V, S, dtype=f32, algo=AUTO, **kw):
+        return U.loss_route(dtype, algo, B, T, V, S, **kw)
+
+    # widths 63/64, 127/128, 223/224, 255/256, 447/448 at 29 columns: pairs per lane 1, 2, 4, 4, 8; the lean halo chains (rule 4)
+    # up to 223 labels, the single-wave chains (6) for one pair per lane and for 224..255 labels, ChainF64L (2) for eight pairs
+    got = [route(8, 1000, 29, S) for S in (1, 63, 64, 127, 128, 223, 224, 255, 256, 447, 448, 600)]
+    assert got == [2016, 2016, 2024, 2024, 2044, 2044, 2046, 2046, 2082, 2082, 1000, 1000], got
+    assert route(8, 1000, 29, 200, chains=_lib.CHAINS_F32) == 2043 and route(8, 1000, 29, 100, chains=_lib.CHAINS_F32) == 2024
+    # B 256/257 at two pairs per lane: beyond one utterance per CU the single-wave chains; their ring of four blocks (7)
+    # where eight need more than 80 KB of LDS (63..96 columns).  The lean halo chains hold up to 78 columns: beyond, ChainF64 (5)
+    # at four pairs per lane and the single-wave chains at two
+    assert [route(B, 1000, 29, 100) for B in (256, 257)] == [2024, 2026]
+    assert [route(B, 256, V, 64) for B, V in ((512, 62), (512, 63), (512, 96), (256, 78), (256, 79))] == [2026, 2027, 2027, 2024, 2026]
+    assert [route(8, 1000, V, 200) for V in (78, 79, 96)] == [2044, 2045, 2045]
+    # 96/97, 224/225, 448/449 columns: the wide-row forms (rule 1) with four, then eight pairs per lane, then the compaction
+    got = [route(8, 1000, V, 100) for V in (96, 97, 224, 225, 448, 449, 452)]
+    assert got == [2026, 2041, 2041, 2081, 2081, 3041, 3241], got
+    # eight pairs per lane: ChainF64L's ring fits the LDS up to 73 columns, the wide-row form beyond
+    assert [route(8, 1000, V, 300) for V in (29, 73, 74, 96, 150, 224)] == [2082, 2082, 2081, 2081, 2081, 2081]
+    assert route(8, 1000, 150, 223) == 2041 and route(8, 1000, 150, 224) == 2081
+    # the compaction: its lattice has Smax + 1 columns, so the WIDTH picks the inner kernels as well; the row kernels follow
+    # the alphabet, the strides and the alignment
+    got = [route(8, 1000, 8000, S) for S in (63, 64, 77, 78, 95, 96, 223, 224, 447, 448)]
+    assert got == [3416, 3424, 3424, 3426, 3426, 3441, 3441, 3481, 3481, 4400], got
+    assert [route(8, 1000, V, 50) for V in (1000, 1001, 2048, 2052, 4096, 4100, 8192, 8196)] == [3216, 3016, 3216, 3316, 3316, 3416, 3416, 3116]
+    assert route(8, 1000, 8000, 50, sV=2) == 3016 and route(8, 1000, 8000, 50, x=260) == 3016
+    assert route(8, 1000, 8000, 50, dtype=bf16) == 3416 and route(8, 1000, 8004, 50, dtype=bf16) == 3016
+    assert route(8, 1000, 1000, 600) == 1000 and route(8, 1000, 1204, 600) == 4200        # (the compaction must halve the columns)
+    # what is refused, and what is the exact kernel's
+    assert route(8, 1000, 29, 100, dtype=f64) == 1000 and route(8, 1000, 29, 100, algo=EXACT) == 1000
+    assert route(8, 1000, 29, 448, algo=FAST) == -1 and route(8, 1000, 8000, 448, algo=FAST) == -1
+    assert route(8, 1000, 29, 448, dtype=bf16) == -1 and route(8, 1000, 29, 100, dtype=bf16, algo=EXACT) == -1
+    assert route(8, 1000, 29, 100, algo=FAST) == 2024 and route(8, 0, 29, 100) == -1
+    # the workspace steps where the route does (its layout follows the same ppl_of: 128 checkpoint cells per pair per lane)
+    L = _lib.load()
+    ws = lambda S: L.e2e_ctc_loss_workspace_bytes(8, 1000, 29, S, f32, AUTO)
+    for S in (63, 127, 255):
+        assert ws(S + 1) - ws(S) > 8 * (ws(S) - ws(S - 1)) > 0, S
