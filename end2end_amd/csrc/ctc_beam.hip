@@ -28,6 +28,10 @@
 // host-side ARPA reader (plain or gzip, ctc_lm.hip), device-resident open-addressing tables (ctc_lm.h), standard back-off
 // scoring.  A beam
 // member's V answers are looked up once per LM state when it enters the beam and kept in LDS (see lm_query).
+//
+// Two read-outs end the search: read_out() -- the best prefix's sentence, what upstream's sort + [0] keeps (e2e_ctc_beam) -- and
+// read_out_nbest() -- the first `nbest` of the ranked final beam with their scores, counts and, if asked for, the frame at which
+// each label's prefix was created (e2e_ctc_beam_nbest; no counterpart upstream).
 #include <cstdio>
 #include <cstring>
 
@@ -57,7 +61,7 @@ struct LmFields {
   int st_n, stb_n;
 };
 
-// tree node in HBM: the structure only (16 bytes).  Everything a prefix needs while it is in the beam -- the four
+// tree node in HBM: the structure only (8 bytes).  Everything a prefix needs while it is in the beam -- the four
 // log-probabilities, the LM state, its child table, its parent's id -- lives in LDS; a pruned-but-alive prefix still
 // "receives" probability upstream, but nothing ever reads it: quirk Q7 reduces to "its (parent, char) slot stays
 // occupied".  Nodes are never reused: at most W prefixes are created per step, so W*(T+3) nodes cover an utterance
@@ -73,6 +77,12 @@ struct BeamParams {
   int64_t* out; int64_t max_out; int64_t* out_len;
   BeamNode* nodes;                                    // per-utterance workspace
   int NCAP, CMAX, WP2, HS;
+  // The n-best read-out (e2e_ctc_beam_nbest).  nbest == 0 is the plain call: read_out() runs and none of the rest is read.
+  int nbest;
+  int64_t* n_hyp; double* scores; int* counts;        // (B), (B,nbest,3), (B,nbest,2); out / out_len are (B,nbest,max_out) / (B,nbest)
+  int64_t* ts_out;                                    // (B,nbest,max_out) frames of the output ids, or null
+  int* node_t;                                        // [B][NCAP] beside `nodes`: the frame at which a node was created.  Null unless
+                                                      // timestamps were asked for: the step loop then stores nothing more
 };
 
 // inclusive prefix sum over the 64 lanes, all DPP (row_shr 1/2/4/8 with zero fill, row_bcast 15/31)
@@ -569,6 +579,69 @@ __device__ __forceinline__ void read_out(const BeamParams& p, const Members& A, 
   }
 }
 
+// ---- the n-best read-out: the final sort (:418-424) kept whole ----
+// All n members of the last step are ranked by (score descending, position ascending) on the ordered key, as the search ranks
+// its candidates; read_out()'s first maximum is rank 0.  The first N = min(nbest, n) get their sentence -- one lane per
+// hypothesis, spread over the waves, so that the N chains of dependent loads run side by side and the tail of the call is one
+// parent walk long, not N -- their scores and counts, and (node_t given) for every id the frame at which its node was created:
+// a node is created exactly once and never reused, so this is the frame at which the label entered the beam on this path.
+// ukey (n), order (n), lens (nbest): scratch in LDS that is dead after the last step.  Every element of every output row is
+// written exactly once: by its walker up to the length, by the fill behind it.
+template <bool LM>
+__device__ __forceinline__ void read_out_nbest(const BeamParams& p, const Members& A, int n, unsigned long long* ukey, int* order,
+                                               int* lens, const BeamNode* nodes, const int* node_t, const int& err) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int N = p.nbest, nh = n < N ? n : N;
+  for (int i = tid; i < n; i += kThreads) ukey[i] = okey(beam_score<LM>(p, A.ppnb[i], A.ppb[i], A.lm[i]));
+  __syncthreads();
+  rank_gathered<4>(ukey, n, nh, [&](int rank, int e) { order[rank] = e; });
+  __syncthreads();
+  int64_t* const out = p.out + (int64_t)b * N * p.max_out;
+  int64_t* const ts = p.ts_out ? p.ts_out + (int64_t)b * N * p.max_out : nullptr;
+  int64_t* const out_len = p.out_len + (int64_t)b * N;
+  double* const scores = p.scores + (int64_t)b * N * 3;
+  int* const counts = p.counts + (int64_t)b * N * 2;
+  const int every = kThreads / nh, h = tid / every;               // hypothesis h on thread h * every (nh <= W <= kThreads)
+  if (h * every == tid && h < nh) {
+    const int i = order[h], best = A.node[i];
+    int m = 0;
+    for (int k = best; k >= 0;) { const int par = nodes[k].parent; if (k == best || par >= 0) m++; k = par; }
+    int64_t* const o = out + (int64_t)h * p.max_out;
+    int64_t* const to = ts ? ts + (int64_t)h * p.max_out : nullptr;
+    int at = m;
+    for (int k = best; k >= 0;) {
+      const BeamNode nd = nodes[k];
+      if (k == best || nd.parent >= 0) {
+        at--;
+        if (at < p.max_out) {
+          o[at] = nd.last_char;
+          if (to) to[at] = nd.parent >= 0 ? node_t[k] : -1;        // (the root, an empty winner's -1, entered at no frame)
+        }
+      }
+      k = nd.parent;
+    }
+    lens[h] = m;
+    out_len[h] = m;                                                // (in-band status as in read_out: > max_out = truncated)
+    const double ctc = lse2(A.ppnb[i], A.ppb[i]);
+    scores[3 * h] = beam_score<LM>(p, A.ppnb[i], A.ppb[i], A.lm[i]);
+    scores[3 * h + 1] = ctc;
+    scores[3 * h + 2] = LM ? A.lm[i].lm_score : 0.0;
+    counts[2 * h] = A.lm[i].num_words;
+    counts[2 * h + 1] = LM ? A.lm[i].num_oov : 0;
+  }
+  for (int e = nh + tid; e < N; e += kThreads) {                   // fewer members than asked for
+    out_len[e] = 0; lens[e] = 0;
+    scores[3 * e] = ninf(); scores[3 * e + 1] = ninf(); scores[3 * e + 2] = 0.0;
+    counts[2 * e] = 0; counts[2 * e + 1] = 0;
+  }
+  if (tid == 0) p.n_hyp[b] = err ? (int64_t)-1 : (int64_t)nh;      // -1: node pool exhausted, nothing of this utterance may be used
+  __syncthreads();
+  for (int e = 0; e < N; e++) {
+    const int64_t from = lens[e] < p.max_out ? lens[e] : p.max_out;
+    for (int64_t i = from + tid; i < p.max_out; i += kThreads) { out[e * p.max_out + i] = 0; if (ts) ts[e * p.max_out + i] = -1; }
+  }
+}
+
 #ifdef E2E_BEAM_PROFILE
 } }  // leave the namespaces for the device symbol
 __device__ unsigned long long g_beam_prof[16];
@@ -618,6 +691,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   __shared__ unsigned long long s_prefix;
 
   BeamNode* nodes = p.nodes + (size_t)b * p.NCAP;
+  int* const node_t = p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;     // (uniform: null in the plain call)
   const IO* lp = reinterpret_cast<const IO*>(p.lp) + (int64_t)b * p.sB;
   int64_t Tq = p.x_len[b];
   const int T = Tq < 0 ? 0 : (Tq > p.T ? p.T : (int)Tq);
@@ -788,6 +862,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
           BeamNode nn;
           nn.parent = A.node[i]; nn.last_char = c;
           nodes[k] = nn;                                                          // (fire and forget)
+          if (node_t) node_t[k] = t;
           mapB.insert(k, j);
         }
         Bm.ppb[j] = ninf(); Bm.ppnb[j] = val; Bm.full[j] = lse2(val, ninf()); Bm.node[j] = k; Bm.last[j] = c;
@@ -1017,7 +1092,9 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
 
   Members A;
   A.carve(mem0 + (size_t)cur * mbytes, W);
-  read_out<LM>(p, A, n, key, nodes, s_err);
+  // (the n-best read-out's scratch: the candidate keys and the selection's two histograms, dead after the last step)
+  if (p.nbest) read_out_nbest<LM>(p, A, n, reinterpret_cast<unsigned long long*>(key), hist, hist + kSelBins, nodes, node_t, s_err);
+  else read_out<LM>(p, A, n, key, nodes, s_err);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1090,6 +1167,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
   LabelTab lt; lt.off = p.lm.label_off; lt.bytes = p.lm.label_bytes; lt.one = nullptr;
 
   BeamNode* nodes = p.nodes + (size_t)b * p.NCAP;
+  int* const node_t = p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;     // (uniform: null in the plain call)
   const IO* lp = reinterpret_cast<const IO*>(p.lp) + (int64_t)b * p.sB;
   unsigned long long* const gkey = g.gkey + (size_t)b * ((size_t)W + (size_t)W * V);
   LmAnswer* const lmc0 = LM ? g.lmc + (size_t)b * 2 * (size_t)W * V : nullptr;
@@ -1268,6 +1346,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
           BeamNode nn;
           nn.parent = A.node[i]; nn.last_char = c;
           nodes[k] = nn;
+          if (node_t) node_t[k] = t;
           mapB.insert(k, j);
         }
         Bm.ppb[j] = ninf(); Bm.ppnb[j] = val; Bm.full[j] = lse2(val, ninf()); Bm.node[j] = k; Bm.last[j] = c;
@@ -1363,7 +1442,8 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
 
   Members A;
   A.carve(mem0 + (size_t)cur * mbytes, W);
-  read_out<LM>(p, A, n, fkey, nodes, s_err);
+  if (p.nbest) read_out_nbest<LM>(p, A, n, reinterpret_cast<unsigned long long*>(fkey), sidx, hist, nodes, node_t, s_err);
+  else read_out<LM>(p, A, n, fkey, nodes, s_err);
 }
 
 struct GenLayout { size_t gkey, lmc, gmem, total, lds; int CH; bool members_in_ws; };
@@ -1450,12 +1530,24 @@ extern "C" size_t e2e_ctc_beam_workspace_bytes(int B, int T, int V, int beam_wid
   return a > b ? a : b;
 }
 
-extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
-                            const int64_t* x_len, int B, int T, int V, int blank,
-                            int beam_width, int space_id, const e2e_lm* lm,
-                            double lmwt, double wip, double oov_penalty,
-                            int64_t* out, int64_t max_out, int64_t* out_len,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+// the frames of the nodes, one int per node beside the node pool (e2e_ctc_beam_nbest with timestamps)
+static size_t node_frames_bytes(int B, int NCAP) { return align_up((size_t)B * NCAP * sizeof(int), 256); }
+
+extern "C" size_t e2e_ctc_beam_nbest_workspace_bytes(int B, int T, int V, int beam_width, int with_lm, int with_timesteps) {
+  const size_t base = e2e_ctc_beam_workspace_bytes_lm(B, T, V, beam_width, with_lm);
+  if (!base || !with_timesteps) return base;
+  return base + node_frames_bytes(B, beam_layout(B, T, V, beam_width, with_lm != 0).NCAP);
+}
+
+// what e2e_ctc_beam_nbest adds to the arguments of e2e_ctc_beam (null: the plain call)
+struct NBestOut { int nbest; int64_t* n_hyp; double* scores; int32_t* counts; int64_t* timesteps; };
+
+static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                     const int64_t* x_len, int B, int T, int V, int blank,
+                     int beam_width, int space_id, const e2e_lm* lm,
+                     double lmwt, double wip, double oov_penalty,
+                     int64_t* out, int64_t max_out, int64_t* out_len, const NBestOut* nb,
+                     void* workspace, size_t workspace_bytes, void* stream) {
   if (dtype != E2E_F32 && dtype != E2E_F64 && !dtype_is_16bit(dtype)) { set_error("dtype must be E2E_F32, E2E_F64, E2E_F16 or E2E_BF16"); return E2E_ERR_ARG; }
   if (B < 0 || T < 1 || V < 1 || beam_width < 1 || max_out < 1) { set_error("bad sizes"); return E2E_ERR_ARG; }
   if (blank < 0 || blank >= V) { set_error("blank=%d outside [0,%d)", blank, V); return E2E_ERR_ARG; }
@@ -1487,7 +1579,8 @@ extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, i
   const GenLayout gl = gen_layout(B, V, beam_width, l.WP2, l.HS, lm != nullptr);
   uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
   const uintptr_t aligned = (base + 255) & ~(uintptr_t)255;
-  const size_t need = l.total + (general ? gl.total : 0);
+  const size_t frames_at = l.total + (general ? gl.total : 0);
+  const size_t need = frames_at + (nb && nb->timesteps ? node_frames_bytes(B, l.NCAP) : 0);
   if (!workspace || workspace_bytes < need + (aligned - base)) { set_error("workspace too small: need %zu", need + 256); return E2E_ERR_WORKSPACE; }
   if (B == 0) return E2E_OK;
   char* ws = reinterpret_cast<char*>(aligned);
@@ -1501,6 +1594,10 @@ extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, i
   p.out = out; p.max_out = max_out; p.out_len = out_len;
   p.nodes = reinterpret_cast<BeamNode*>(ws + l.nodes);
   p.NCAP = l.NCAP; p.CMAX = l.CMAX; p.WP2 = l.WP2; p.HS = l.HS;
+  p.nbest = nb ? nb->nbest : 0;
+  p.n_hyp = nb ? nb->n_hyp : nullptr; p.scores = nb ? nb->scores : nullptr; p.counts = nb ? nb->counts : nullptr;
+  p.ts_out = nb ? nb->timesteps : nullptr;
+  p.node_t = nb && nb->timesteps ? reinterpret_cast<int*>(ws + frames_at) : nullptr;
   hipStream_t s = (hipStream_t)stream;
   const bool fast_lm = lm && lm->d_ngs && lm->order - 1 <= kParCtx;
   if (general) {
@@ -1527,6 +1624,35 @@ extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, i
   E2E_HIP_CHECK(hipLaunchKernel(fn, dim3(B), dim3(kThreads), args, l.lds, s), "ctc_beam_kernel launch");
   E2E_HIP_CHECK(hipGetLastError(), "ctc_beam_kernel launch");
   return E2E_OK;
+}
+
+extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                            const int64_t* x_len, int B, int T, int V, int blank,
+                            int beam_width, int space_id, const e2e_lm* lm,
+                            double lmwt, double wip, double oov_penalty,
+                            int64_t* out, int64_t max_out, int64_t* out_len,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return beam_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
+                   out, max_out, out_len, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2e_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                                  const int64_t* x_len, int B, int T, int V, int blank,
+                                  int beam_width, int space_id, const e2e_lm* lm,
+                                  double lmwt, double wip, double oov_penalty,
+                                  int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                                  double* scores, int32_t* counts, int64_t* timesteps,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (beam_width < 1 || nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (B > 0 && (!n_hyp || !scores || !counts || !out || !out_len)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  if (V >= 1 && beam_width > e2e_ctc_beam_max_width(V, lm != nullptr)) {
+    set_error("beam_width = %d over an alphabet of %d%s: at most %d", beam_width, V, lm ? " with a language model" : "",
+              e2e_ctc_beam_max_width(V, lm != nullptr));
+    return E2E_ERR_ARG;
+  }
+  const NBestOut nb = { nbest, n_hyp, scores, counts, timesteps };
+  return beam_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
+                   out, max_out, out_len, &nb, workspace, workspace_bytes, stream);
 }
 
 #ifdef E2E_BEAM_PROFILE

@@ -17,6 +17,12 @@ class CTCDecoderError(Exception):
 
 DecoderResults = namedtuple("DecoderResults", ["decoded_targets", "decoded_targets_lengths", "decoded_sentences"])
 
+# decode_nbest(): (B, N, ...) per utterance and hypothesis, ranked by `scores`; `decoded_sentences[b]` lists the
+# num_hypotheses[b] sentences of utterance b; `timesteps` is None unless asked for
+NBestResults = namedtuple("NBestResults", ["decoded_targets", "decoded_targets_lengths", "decoded_sentences", "scores",
+                                           "ctc_scores", "lm_scores", "num_words", "num_oov_words", "num_hypotheses",
+                                           "timesteps"])
+
 
 class CTCDecoder:
     """
@@ -78,6 +84,26 @@ class CTCDecoder:
                 logits = torch.log_softmax(logits, -1)
         logits, logits_lengths = self._batch_major(logits, logits_lengths)
         return DecoderResults(*self._decoder.decode(logits_=logits, logits_lengths_=logits_lengths))
+
+    def decode_nbest(self, logits, logits_lengths=None, nbest=None, timesteps=False):
+        """The hypotheses the beam search ends with, best first (an extension: upstream returns the first only).
+
+        :param nbest: how many to return per utterance, at most ``beam_width`` (the default)
+        :param timesteps: also return, for every decoded label, the frame at which it entered the beam
+        :return: ``NBestResults(decoded_targets (batch, nbest, longest), decoded_targets_lengths (batch, nbest),
+            decoded_sentences (a list per utterance), scores, ctc_scores, lm_scores, num_words, num_oov_words
+            (batch, nbest), num_hypotheses (batch), timesteps (batch, nbest, longest) or None)``;
+            ``scores = ctc_scores + lmwt * lm_scores - wip * num_words + oov_penalty * num_oov_words``, hypothesis 0 is
+            what ``decode`` returns, slots beyond ``num_hypotheses[b]`` are empty (length 0, score -inf).
+        """
+        if self._beam_width == 1:
+            raise CTCDecoderError("decode_nbest needs beam_width > 1: greedy decoding has no beam")
+        with torch.no_grad():
+            if not self._after_logsoftmax:
+                logits = torch.log_softmax(logits, -1)
+        logits, logits_lengths = self._batch_major(logits, logits_lengths)
+        return NBestResults(*self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest,
+                                                        timesteps=timesteps))
 
     def _print_scores_for_sentence(self, words):
         self._decoder.print_scores_for_sentence(words)

@@ -534,6 +534,53 @@ class CTCDecoderEngine:
         ids, out_len = self._result(ids), self._result(out_len)
         return ids, out_len, self._strings(ids.cpu(), lens)
 
+    def decode_nbest(self, logits_, logits_lengths_, nbest=None, timesteps=False):
+        """The same search read out as an n-best list, on LOG-PROBABILITIES (e2e_ctc_beam_nbest, include/e2e_ctc.h) ->
+        (indices (B,N,maxlen) int64, lengths (B,N), sentences [B][n_hyp], scores (B,N) f64, ctc_scores, lm_scores,
+        num_words (B,N) int32, num_oov (B,N), num_hypotheses (B), timesteps (B,N,maxlen) int64 or None).  Hypotheses are
+        ranked by total score, hypothesis 0 is decode()'s result; slots beyond num_hypotheses[b] are empty (length 0, -inf)."""
+        N = self.beam_width if nbest is None else int(nbest)
+        if not 1 <= N <= self.beam_width:
+            raise ValueError("nbest=%d outside [1, beam_width=%d]" % (N, self.beam_width))
+        x, xl, dev = self._prep(logits_, logits_lengths_)
+        B, T, V = x.shape
+        max_out = T + 1
+        out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
+        out_len = torch.empty((B, N), dtype=torch.long, device=dev)
+        n_hyp = torch.empty(B, dtype=torch.long, device=dev)
+        scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
+        counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+        ts = torch.empty((B, N, max_out), dtype=torch.long, device=dev) if timesteps else None
+        if B:
+            with torch.cuda.device(dev):
+                lm = self.lm.on(dev).handle if self.lm is not None else 0
+                nbytes = _C.ctc_beam_nbest_workspace_bytes(B, T, V, self.beam_width, self.lm is not None, bool(timesteps))
+                ws = R.workspace(dev, nbytes)
+                sB, sT, sV = x.stride()
+                _C.ctc_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(),
+                                  B, T, V, self.blank_idx, self.beam_width, self.space_id, lm,
+                                  self.lmwt, self.wip, self.oov_penalty, N,
+                                  out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                                  counts.data_ptr(), ts.data_ptr() if timesteps else 0,
+                                  ws.data_ptr(), ws.numel(), R.stream_handle(dev))
+        nh = n_hyp.tolist()
+        lens = out_len.tolist()
+        # per-utterance and per-hypothesis status ride on the counts and lengths, as in decode()
+        for b in range(B):
+            if nh[b] < 0:
+                raise R.E2EError("beam search: utterance %d ran out of prefix-tree nodes" % b)
+            if max(lens[b]) > max_out:
+                raise R.E2EError("beam search: utterance %d needs %d output ids, %d provided" % (b, max(lens[b]), max_out))
+        width = max((max(row) for row in lens), default=0)
+        ids = out[:, :, :width].contiguous()       # packed to the longest hypothesis of the batch
+        ids_host = ids.cpu()
+        flat = self._strings(ids_host.reshape(B * N, width), [n for row in lens for n in row])   # one lookup per batch
+        sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+        r = self._result
+        return (ids if self.keep_on_device else ids_host, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
+                r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
+                r(counts[:, :, 1].contiguous()), r(n_hyp), r(ts[:, :, :width].contiguous()) if timesteps else None)
+
     def print_scores_for_sentence(self, words):
         """src/decoders/ctc_decoder.cpp:141-151: word, decoder index, vocabulary index, log10 score."""
         if self.lm is None:

@@ -311,6 +311,39 @@ int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The same search, read out as an n-best list (additive, ABI 4: nothing above changes meaning).
+ * The search ends with up to beam_width ranked hypotheses; e2e_ctc_beam returns the first, this call the first `nbest`,
+ * ranked as the search ranks its own candidates: total score descending, ties (and -inf scores) by position in the final
+ * beam.  Hypothesis 0 is e2e_ctc_beam's result, bit for bit.  Arguments up to oov_penalty, dtypes, strides, width limits
+ * and language-model rules are e2e_ctc_beam's; asynchronous, allocates nothing, capturable.
+ *   nbest      1 <= nbest <= beam_width, else E2E_ERR_ARG (as is a beam_width above e2e_ctc_beam_max_width(): every
+ *              argument error is found on the host before any launch)
+ *   out        (B,nbest,max_out) int64, zero-filled behind each sentence
+ *   out_len    (B,nbest) int64: 0 for slots >= n_hyp[b]; > max_out = truncated, that many ids were needed and the first
+ *              max_out were written (the in-band status of e2e_ctc_beam, per hypothesis)
+ *   n_hyp      (B) int64: min(nbest, members of the final beam); -1 = the node pool ran out (nothing of the utterance may
+ *              be used)
+ *   scores     (B,nbest,3) f64: total (what the search ranks by), its CTC part log(p_blank + p_non_blank), the
+ *              language model's score (0 without a model); total = ctc + lmwt * lm - wip * num_words + oov_penalty *
+ *              num_oov.  Slots >= n_hyp[b]: -inf, -inf, 0.
+ *   counts     (B,nbest,2) int32: num_words, num_oov (0 without a model)
+ *   timesteps  NULL, or (B,nbest,max_out) int64: for every id written to `out` the frame at which the prefix ending in
+ *              that label was created, i.e. entered the beam on this path (a prefix is created once and never re-created);
+ *              strictly increasing along a sentence; -1 behind the sentence and for the -1 id of an empty winner.
+ *              Only a call with timesteps records the frames: one int32 per prefix-tree node more workspace.
+ *   workspace >= e2e_ctc_beam_nbest_workspace_bytes(...); with_timesteps = 0: exactly e2e_ctc_beam_workspace_bytes_lm().
+ */
+size_t e2e_ctc_beam_nbest_workspace_bytes(int B, int T, int V, int beam_width, int with_lm, int with_timesteps);
+
+int e2e_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                       const int64_t* x_len, int B, int T, int V, int blank,
+                       int beam_width, int space_id, const e2e_lm* lm,
+                       double lmwt, double wip, double oov_penalty,
+                       int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                       double* scores, int32_t* counts, int64_t* timesteps,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Viterbi forced alignment on the same lattice (max-plus instead of sum).
  * Replaces pytorch_end2end/utils/alignment.py:50-106 (_get_alignment_ctc_1d), :10-47
  * (_get_alignment_asg_1d, is_ctc = 0: no blanks) and the batch driver :109-138
