@@ -59,9 +59,10 @@ def dtype_code(dt):
 _workspaces = {}
 
 
-def workspace(device, nbytes):
-    """A cached per-(device, stream) scratch buffer of at least nbytes (grown geometrically)."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+def workspace(device, nbytes, stream=None):
+    """A cached per-(device, stream) scratch buffer of at least nbytes (grown geometrically).  `stream`: the device's current
+    stream as stream_handle() gives it, for a caller that has asked already (the query costs over a microsecond)."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream if stream is None else stream)
     buf = _workspaces.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)

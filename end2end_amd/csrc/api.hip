@@ -244,10 +244,7 @@ int e2e_ctc_loss_fwd_bwd_opt(const void* x, int dtype, int input_is_logprobs,
                              void* losses, void* grads,
                              void* workspace, size_t workspace_bytes,
                              int algo, void* stream, const e2e_ctc_loss_opts* opts) {
-  if (opts && (opts->reduction < E2E_REDUCE_NONE || opts->reduction > E2E_REDUCE_MEAN ||
-               (opts->reduction != E2E_REDUCE_NONE && !opts->reduced))) {
-    set_error("bad e2e_ctc_loss_opts: reduction %d, reduced %p", opts->reduction, opts->reduced); return E2E_ERR_ARG;
-  }
+  if (!loss_opts_ok(opts)) return E2E_ERR_ARG;
   if (opts && opts->chains != E2E_CHAINS_F64 && opts->chains != E2E_CHAINS_F32) {
     set_error("bad e2e_ctc_loss_opts: chains %d", opts->chains); return E2E_ERR_ARG;
   }
@@ -258,10 +255,7 @@ int e2e_ctc_loss_fwd_bwd_opt(const void* x, int dtype, int input_is_logprobs,
     set_error("null pointer argument"); return E2E_ERR_ARG;
   }
   if (algo != E2E_ALGO_AUTO && algo != E2E_ALGO_EXACT && algo != E2E_ALGO_FAST) { set_error("bad algo %d", algo); return E2E_ERR_ARG; }
-  // 256-B align the workspace base
-  uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const uintptr_t aligned = (base + 255) & ~(uintptr_t)255;
-  if (workspace && workspace_bytes >= (aligned - base)) { workspace_bytes -= (aligned - base); workspace = reinterpret_cast<void*>(aligned); }
+  align_workspace(workspace, workspace_bytes);
   LossArgs a{x, dtype, input_is_logprobs ? 1 : 0, sB, sT, sV, targets, tgt_stride, x_len, t_len,
              B, T, V, Smax, blank, losses, grads, workspace, workspace_bytes, (hipStream_t)stream};
   if (opts) { a.grad_scale = opts->grad_scale; a.reduced = opts->reduced; a.reduction = opts->reduction; a.chains = opts->chains; }

@@ -43,6 +43,24 @@ void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// A caller's workspace starts at any address; the kernels' buffers at the first 256-byte boundary in it.
+inline unsigned char* aligned_256(const void* p) {
+  return reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255);
+}
+// `ws` to that boundary and `bytes` to what is left behind it; false (both unchanged) for no workspace or one that ends before it
+inline bool align_workspace(void*& ws, size_t& bytes) {
+  const size_t pad = aligned_256(ws) - reinterpret_cast<unsigned char*>(ws);
+  if (!ws || bytes < pad) return false;
+  ws = aligned_256(ws); bytes -= pad;
+  return true;
+}
+// the reduction of an e2e_ctc_loss_opts (null: defaults) is one of E2E_REDUCE_* and has somewhere to go; else sets the error
+inline bool loss_opts_ok(const e2e_ctc_loss_opts* opts) {
+  if (!opts || (opts->reduction >= E2E_REDUCE_NONE && opts->reduction <= E2E_REDUCE_MEAN &&
+                (opts->reduction == E2E_REDUCE_NONE || opts->reduced))) return true;
+  set_error("bad e2e_ctc_loss_opts: reduction %d, reduced %p", opts->reduction, opts->reduced);
+  return false;
+}
 
 __device__ __forceinline__ double ninf() { return -__builtin_huge_val(); }
 

@@ -12,30 +12,28 @@
 // Two launches per call.
 //   gram_rows_kernel     one wave per frame: the row's log-sum-exp (logits in: log-softmax fused; kept in the workspace)
 //                        and the dense part of the gradient, grad[t, v] = scale * exp(lp[t, v]) (0 on padded frames):
-//                        loss_rows.h, shared with ctc_loss_noblank.hip.
+//                        lattice_common.h, shared with ctc_loss_noblank.hip.
 //   gram_lattice_kernel  one 256-thread workgroup per utterance.  Prologue: every cell (j, k) of the target is matched
 //                        against the gram table (binary search), repeated grams are marked, and the gram cells are sorted
 //                        by (column, cell).  Rows of (S+1) * (max_order+1) cells, one boundary per thread, all four waves
 //                        on the serial recurrence with one barrier per frame; each block of K frames has its emissions
 //                        gathered into LDS first.  The backward sweep writes one posterior per column present.
-// Arithmetic: ctc_loss_noblank.hip's.  f32 input: probability domain, f64 cells, every row divided by the power of two of
+// Arithmetic: ctc_loss_noblank.hip's, its helpers and the host call in lattice_common.h.  f32 input: probability domain, f64 cells, every row divided by the power of two of
 // its largest cell (a workgroup-wide max, carried to the next frame through LDS), alpha rows checkpointed every kCk frames;
 // the backward recomputes each block's rows from its checkpoint (bit-identical to the forward's) and runs beta over them.
 // An utterance the probability domain cannot settle -- a finite log-probability below -700, a row that under/overflows, a
 // total of 0 or non-finite, a frame whose posteriors do not sum to 1 -- is redone by the same workgroup in the log domain,
 // which f64 input always uses.
 #include "common.h"
-#include "loss_rows.h"
+#include "lattice_common.h"
 
 namespace e2e {
 namespace {
 
-constexpr int kGcThreads = 256;
-constexpr int kGcWaves = kGcThreads / 64;
+constexpr int kGcWaves = kLatticeThreads / 64;
 constexpr int kCk = 16;                      // checkpoint interval (frames); the LDS block K divides it
 constexpr int kGcMaxOrder = 8;
 constexpr size_t kGcLdsMax = 160 * 1024 - 256;   // LDS of one gfx950 workgroup, less the kernel's own words
-constexpr double kGcLowLp = -700.0;          // a finite log-probability below this sends an f32 utterance to the log domain
 
 struct GcParams {
   const void* x; int64_t sB, sT, sV;
@@ -51,26 +49,6 @@ struct GcParams {
   int* redo;                                 // [B] 0, or why the utterance was redone in the log domain (1 forward, 2 backward)
 };
 
-__device__ __forceinline__ int gc_wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double gc_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double gc_wave_lse(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = lse2(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// biased exponent of a non-negative double (0: zero or subnormal, 2047: inf / NaN)
-__device__ __forceinline__ int gc_expo(double a) { return (__double2hiint(a) >> 20) & 0x7ff; }
-// 2^(1023 - m): divides a row whose largest biased exponent is m into [1, 2)
-__device__ __forceinline__ double gc_inv_pow2(int m) { return __hiloint2double((2046 - m) << 20, 0); }
-
 template <typename IO>
 __global__ __launch_bounds__(256) void gram_rows_kernel(GcParams p, double* lse_out) {
   loss_rows<IO>(p, lse_out);
@@ -79,7 +57,7 @@ __global__ __launch_bounds__(256) void gram_rows_kernel(GcParams p, double* lse_
 // cell (j, k) of a row is j * M1 + k: k = 0 the blank of boundary j, k >= 1 the gram y[j-k..j-1] (if it is one).
 // flag: bit 0 the cell is a state, bit 1 (gram cells) the gram state (j-k, k) exists and has the same column.
 template <typename IO>
-__global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
+__global__ __launch_bounds__(kLatticeThreads) void gram_lattice_kernel(GcParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Tmax = p.T, V = p.V, K = p.K, M = p.M, M1 = p.M + 1;
@@ -109,19 +87,19 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
 
   // ---- prologue: the target, the states, the column order ----
   int bad = bad_len;
-  for (int i = tid; i < S; i += kGcThreads) {
+  for (int i = tid; i < S; i += kLatticeThreads) {
     const int64_t y = tgg[i];
     bad |= y < 1 || y >= p.R;
     tg[i] = (int)y;
   }
   bad = __syncthreads_or(bad);
   if (bad) {
-    for (size_t i = tid; i < (size_t)Tmax * V; i += kGcThreads) grads[i] = (IO)NAN;
+    for (size_t i = tid; i < (size_t)Tmax * V; i += kLatticeThreads) grads[i] = (IO)NAN;
     if (tid == 0) *loss = (LT)NAN;
     return;
   }
   const int NCu = (S + 1) * M1;
-  for (int c = tid; c < NCu; c += kGcThreads) {
+  for (int c = tid; c < NCu; c += kLatticeThreads) {
     const int j = c / M1, k = c - j * M1;
     int u = k == 0 ? 0 : -1;
     if (k > 0 && j >= k) {
@@ -142,7 +120,7 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
   if (tid == 0) { s_flag = 0; s_lost = 0; s_ng = 0; }
   __syncthreads();
   int ng = 0;
-  for (int c = tid; c < NCu; c += kGcThreads) {
+  for (int c = tid; c < NCu; c += kLatticeThreads) {
     const int j = c / M1, k = c - j * M1, u = col[c];
     int f = u >= 0;
     if (k > 0 && u >= 0 && j >= 2 * k && col[c - k * M1] == u) f |= 2;
@@ -171,11 +149,11 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
   auto gather = [&](int t0, int nk) __attribute__((always_inline)) {
     const int tot = nk * NCu;
     int low = 0;
-    for (int base = tid; base < tot; base += 16 * kGcThreads) {
+    for (int base = tid; base < tot; base += 16 * kLatticeThreads) {
       double v[16];
 #pragma unroll
       for (int u = 0; u < 16; u++) {
-        const int e = base + u * kGcThreads;
+        const int e = base + u * kLatticeThreads;
         v[u] = ninf();
         if (e < tot) {
           const int k = e / NCu, c = e - k * NCu, cu = col[c];
@@ -184,11 +162,11 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
       }
 #pragma unroll
       for (int u = 0; u < 16; u++) {
-        const int e = base + u * kGcThreads;
+        const int e = base + u * kLatticeThreads;
         if (e < tot) {
           const int k = e / NCu, c = e - k * NCu;
           const double lp = v[u];
-          low |= lp < kGcLowLp && lp > ninf();
+          low |= lp < kLowLp && lp > ninf();
           pbuf[(size_t)k * NC + c] = logd ? lp : exp(lp);
         }
       }
@@ -199,7 +177,7 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
   // thread's largest exponent
   auto alpha_row = [&](const double* P, double* Q, const double* pr, double sc, bool first) __attribute__((always_inline)) {
     int mx = 0;
-    for (int j = tid; j <= S; j += kGcThreads) {
+    for (int j = tid; j <= S; j += kLatticeThreads) {
       const double* Pj = P + j * M1;
       for (int k = 0; k <= M; k++) {
         const int c = j * M1 + k, f = flag[c];
@@ -221,14 +199,14 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
           a = logd ? s + pr[c] : s * (pr[c] * sc);
         }
         Q[c] = a;
-        mx = max(mx, gc_expo(a));
+        mx = max(mx, expo(a));
       }
     }
     return mx;
   };
   // a row's largest exponent through LDS: each wave's max into wm[par], read after the barrier that follows
   auto put_max = [&](int mx, int par, int* w) __attribute__((always_inline)) {
-    mx = gc_wave_max_i(mx);
+    mx = wave_max_i(mx);
     if (lane == 0) w[par * kGcWaves + wave] = mx;
   };
   auto get_max = [&](int par, const int* wv) __attribute__((always_inline)) {
@@ -239,9 +217,8 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
   double zm = 0.0, logz = 0.0;
   int cend = 0;
   // grad[t, u] for the columns u of the frames [t0, t0 + nk) (alpha * beta in ab, emissions in pbuf); the frames' mass
-  constexpr double kMassTol = 1e-9;
   auto finish = [&](int t0, int nk) __attribute__((always_inline)) {
-    for (int it = tid; it < nk * NG; it += kGcThreads) {
+    for (int it = tid; it < nk * NG; it += kLatticeThreads) {
       const int k = it / NG, q = it - k * NG;
       const int c0 = perm[q], u = col[c0];
       if (q > 0 && col[perm[q - 1]] == u) continue;
@@ -256,7 +233,7 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
       const double* a = ab + (size_t)k * NC;
       double acc = logd ? ninf() : 0.0;
       for (int j = lane; j <= S; j += 64) acc = logd ? lse2(acc, a[j * M1]) : acc + a[j * M1];
-      acc = logd ? gc_wave_lse(acc) : gc_wave_sum(acc);
+      acc = logd ? wave_lse(acc) : wave_sum(acc);
       if (lane == 0) {
         const double post = logd ? exp(acc - logz) : ldexp(acc, cb[k] - cend) / zm;
         const double pv = logd ? exp(pbuf[(size_t)k * NC]) : pbuf[(size_t)k * NC];
@@ -284,15 +261,15 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
         double sc = 1.0;
         if (t > 0 && !logd) {
           const int m = get_max((t - 1) & 1, wm);
-          range_bad |= m == 0 || m >= 2046;
+          range_bad |= expo_out_of_range(m);
           C += m - 1023;
-          sc = gc_inv_pow2(m);
+          sc = inv_pow2(m);
         }
         double* Q = rows + (size_t)(t & 1) * NC;
         const int mx = alpha_row(rows + (size_t)((t + 1) & 1) * NC, Q, pbuf + (size_t)k * NC, sc, t == 0);
         if (!logd) put_max(mx, t & 1, wm);
         if (t % kCk == 0) {                          // (each thread stores the cells it wrote: no barrier needed)
-          for (int j = tid; j <= S; j += kGcThreads)
+          for (int j = tid; j <= S; j += kLatticeThreads)
             for (int k2 = 0; k2 <= M; k2++) ck[(size_t)(t / kCk) * NC + j * M1 + k2] = Q[j * M1 + k2];
           if (tid == 0) ckc[t / kCk] = C;
         }
@@ -306,21 +283,20 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
       logz = z;
     } else {
       const int m = get_max((T - 1) & 1, wm);
-      range_bad |= m == 0 || m >= 2046;
+      range_bad |= expo_out_of_range(m);
       zm = z;
       cend = C;
-      const int fail = __syncthreads_or(range_bad || s_flag || !(zm > 0.0) || !(zm < INFINITY));
-      if (fail) {                                    // this utterance goes to the log domain
+      if (prob_unsettled(range_bad, s_flag, zm)) {                                    // this utterance goes to the log domain
         if (tid == 0) p.redo[b] = 1;
         logd = true;
         continue;
       }
-      logz = log(zm) + (double)cend * 0.69314718055994530942;
+      logz = prob_log_z(zm, cend);
     }
     __syncthreads();                                 // (the last alpha row is read; beta takes its buffer)
     if (tid == 0) *loss = (LT)(-logz);
     if (logd && logz == ninf()) {                    // no path through the emissions: +inf, NaN rows
-      for (size_t i = tid; i < (size_t)T * V; i += kGcThreads) grads[i] = (IO)NAN;
+      for (size_t i = tid; i < (size_t)T * V; i += kLatticeThreads) grads[i] = (IO)NAN;
       return;
     }
 
@@ -332,9 +308,9 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
       // the checkpoint row of frame ts: into ab row 0 when it is the block's first frame, else into pre
       double* R0 = ts == t0 ? ab : pre;
       int C = ckc[ts / kCk], mx = 0;
-      for (int c = tid; c < NCu; c += kGcThreads) {
+      for (int c = tid; c < NCu; c += kLatticeThreads) {
         const double a = ck[(size_t)(ts / kCk) * NC + c];
-        R0[c] = a; mx = max(mx, gc_expo(a));
+        R0[c] = a; mx = max(mx, expo(a));
       }
       if (!logd) put_max(mx, ts & 1, wm);
       if (tid == 0) cb[0] = C;
@@ -348,7 +324,7 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
           if (!logd) {
             const int m = get_max((t - 1) & 1, wm);
             C += m - 1023;
-            sc = gc_inv_pow2(m);
+            sc = inv_pow2(m);
           }
           double* Qr = t >= t0 ? ab + (size_t)(t - t0) * NC : pre + (size_t)((t - ts) & 1) * NC;
           const int m2 = alpha_row(P, Qr, pbuf + (size_t)(t - c0) * NC, sc, false);
@@ -368,14 +344,14 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
         double sc = 1.0;
         if (t < T - 1 && !logd) {
           f = get_max((t + 1) & 1, wmb);
-          lost |= f == 0 || f >= 2046;
+          lost |= expo_out_of_range(f);
           f = min(max(f, 1), 2045);
           D += f - 1023;
-          sc = gc_inv_pow2(f);
+          sc = inv_pow2(f);
         }
         int gx = 0;
         double mass = 0.0;
-        for (int j = tid; j <= S; j += kGcThreads) {
+        for (int j = tid; j <= S; j += kLatticeThreads) {
           for (int k2 = 0; k2 <= M; k2++) {
             const int c = j * M1 + k2;
             double s;
@@ -398,12 +374,12 @@ __global__ __launch_bounds__(kGcThreads) void gram_lattice_kernel(GcParams p) {
             a[c] = as;
             H[c] = h;
             mass += logd ? 0.0 : as;
-            gx = max(gx, gc_expo(h));
+            gx = max(gx, expo(h));
           }
         }
         if (!logd) {
           put_max(gx, t & 1, wmb);
-          mass = gc_wave_sum(mass);
+          mass = wave_sum(mass);
           if (lane == 0) wsum[(size_t)k * kGcWaves + wave] = mass;
         }
         if (tid == 0) cb[k] += D;
@@ -430,20 +406,10 @@ int gc_block(int NC, int Smax) {
   return 0;
 }
 
-struct GcLayout { size_t lse, ck, ckc, redo, total; int K, NB, NC; };
-GcLayout gc_layout(int B, int T, int Smax, int max_order) {
-  GcLayout l{};
-  if ((int64_t)(Smax + 1) * (max_order + 1) > (1 << 20)) return l;
-  l.NC = (Smax + 1) * (max_order + 1);
-  l.K = gc_block(l.NC, Smax);
-  if (l.K == 0) return l;
-  l.NB = (T + kCk - 1) / kCk;
-  l.lse = 0;
-  l.ck = align_up((size_t)B * T * sizeof(double), 256);
-  l.ckc = l.ck + align_up((size_t)B * l.NB * l.NC * sizeof(double), 256);
-  l.redo = l.ckc + align_up((size_t)B * l.NB * sizeof(int), 256);
-  l.total = l.redo + align_up((size_t)B * sizeof(int), 256);
-  return l;
+LatticeLayout gc_layout(int B, int T, int Smax, int max_order) {
+  if ((int64_t)(Smax + 1) * (max_order + 1) > (1 << 20)) return LatticeLayout{};
+  const int NC = (Smax + 1) * (max_order + 1);
+  return lattice_layout(B, T, NC, gc_block(NC, Smax), kCk);
 }
 
 }  // namespace
@@ -454,7 +420,7 @@ using namespace e2e;
 extern "C" size_t e2e_gram_ctc_workspace_bytes(int B, int T, int V, int Smax, int max_order, int dtype) {
   (void)V; (void)dtype;
   if (B < 0 || T < 1 || Smax < 0 || max_order < 1 || max_order > kGcMaxOrder) return 0;
-  const GcLayout l = gc_layout(B, T, Smax, max_order);
+  const LatticeLayout l = gc_layout(B, T, Smax, max_order);
   return l.K ? l.total + 256 : 0;
 }
 
@@ -464,8 +430,10 @@ extern "C" int e2e_gram_ctc_fwd_bwd(const void* x, int dtype, int input_is_logpr
                                     const int32_t* cols, int n_grams, int radix, int max_order, void* losses,
                                     void* grads, void* workspace, size_t workspace_bytes, void* stream,
                                     const e2e_ctc_loss_opts* opts) {
-  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64 (up-cast 16-bit inputs)"); return E2E_ERR_ARG; }
-  if (B < 0 || T < 1 || V < 1 || Smax < 0) { set_error("bad sizes B=%d T=%d V=%d Smax=%d", B, T, V, Smax); return E2E_ERR_ARG; }
+  LossArgs a{x, dtype, input_is_logprobs ? 1 : 0, sB, sT, sV, targets, tgt_stride, x_len, t_len,
+             B, T, V, Smax, 0, losses, grads, workspace, workspace_bytes, (hipStream_t)stream};
+  int rc = lattice_check_args(a, opts);
+  if (rc != E2E_OK) return rc;
   if (radix < 1 || radix > V) { set_error("radix=%d is not in [1, V=%d]", radix, V); return E2E_ERR_ARG; }
   if (max_order < 1 || max_order > kGcMaxOrder) { set_error("max_order=%d is not in [1, %d]", max_order, kGcMaxOrder); return E2E_ERR_ARG; }
   {
@@ -476,52 +444,21 @@ extern "C" int e2e_gram_ctc_fwd_bwd(const void* x, int dtype, int input_is_logpr
     }
   }
   if (n_grams < 0 || (n_grams > 0 && (!keys || !cols))) { set_error("bad gram table: n_grams=%d", n_grams); return E2E_ERR_ARG; }
-  if (opts && (opts->reduction < E2E_REDUCE_NONE || opts->reduction > E2E_REDUCE_MEAN ||
-               (opts->reduction != E2E_REDUCE_NONE && !opts->reduced))) {
-    set_error("bad e2e_ctc_loss_opts: reduction %d, reduced %p", opts->reduction, opts->reduced); return E2E_ERR_ARG;
-  }
-  if (B > 0 && (!x || !x_len || !t_len || !losses || !grads || !targets)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
-  const GcLayout l = gc_layout(B, T, Smax, max_order);
+  const LatticeLayout l = gc_layout(B, T, Smax, max_order);
   if (l.K == 0) {
     set_error("Gram-CTC: Smax=%d at max_order=%d needs more than %zu B of LDS", Smax, max_order, kGcLdsMax);
     return E2E_ERR_UNSUPPORTED;
   }
-  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const uintptr_t aligned = (base + 255) & ~(uintptr_t)255;
-  if (!workspace || workspace_bytes < l.total + (aligned - base)) { set_error("workspace too small: need %zu", l.total + 256); return E2E_ERR_WORKSPACE; }
-  if (B == 0) return E2E_OK;
-  unsigned char* ws = reinterpret_cast<unsigned char*>(aligned);
+  rc = lattice_workspace(a, l);
+  if (rc != E2E_OK || B == 0) return rc;
   GcParams p;
-  p.x = x; p.sB = sB; p.sT = sT; p.sV = sV; p.targets = targets; p.tgt_stride = tgt_stride; p.x_len = x_len; p.t_len = t_len;
-  p.keys = keys; p.cols = cols;
-  p.B = B; p.T = T; p.V = V; p.Smax = Smax; p.R = radix; p.M = max_order; p.n_grams = n_grams;
-  p.logits = input_is_logprobs ? 0 : 1; p.K = l.K; p.NB = l.NB; p.gscale = opts ? opts->grad_scale : 1.0;
-  p.losses = losses; p.grads = grads;
-  p.lse = reinterpret_cast<const double*>(ws + l.lse); p.ck = reinterpret_cast<double*>(ws + l.ck); p.ckc = reinterpret_cast<int*>(ws + l.ckc);
-  p.redo = reinterpret_cast<int*>(ws + l.redo);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = gc_lds_bytes(l.K, l.NC, Smax);
-  const unsigned rows_grid = (unsigned)(((int64_t)B * T + 3) / 4);
-  double* lse_out = reinterpret_cast<double*>(ws + l.lse);
-  if (dtype == E2E_F32) {
-    hipLaunchKernelGGL(gram_rows_kernel<float>, dim3(rows_grid), dim3(256), 0, s, p, lse_out);
-    E2E_HIP_CHECK(hipGetLastError(), "gram_rows_kernel launch");
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&gram_lattice_kernel<float>), (int)lds), "hipFuncSetAttribute");
-    hipLaunchKernelGGL(gram_lattice_kernel<float>, dim3(B), dim3(kGcThreads), lds, s, p);
-  } else {
-    hipLaunchKernelGGL(gram_rows_kernel<double>, dim3(rows_grid), dim3(256), 0, s, p, lse_out);
-    E2E_HIP_CHECK(hipGetLastError(), "gram_rows_kernel launch");
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&gram_lattice_kernel<double>), (int)lds), "hipFuncSetAttribute");
-    hipLaunchKernelGGL(gram_lattice_kernel<double>, dim3(B), dim3(kGcThreads), lds, s, p);
-  }
-  E2E_HIP_CHECK(hipGetLastError(), "gram_lattice_kernel launch");
-  if (opts && opts->reduced && opts->reduction != E2E_REDUCE_NONE) {
-    LossArgs a{x, dtype, input_is_logprobs ? 1 : 0, sB, sT, sV, targets, tgt_stride, x_len, t_len,
-               B, T, V, Smax, 0, losses, grads, ws, workspace_bytes, s};
-    a.reduced = opts->reduced; a.reduction = opts->reduction;
-    return launch_reduce_losses(a);
-  }
-  return E2E_OK;
+  lattice_params(p, a, l);
+  p.keys = keys; p.cols = cols; p.R = radix; p.M = max_order; p.n_grams = n_grams;
+  p.redo = reinterpret_cast<int*>(aligned_256(workspace) + l.redo);
+  static const LatticeKernels<GcParams> kernels = {
+      gram_rows_kernel<float>, gram_rows_kernel<double>, "gram_rows_kernel launch",
+      gram_lattice_kernel<float>, gram_lattice_kernel<double>, "gram_lattice_kernel launch"};
+  return lattice_launch(a, kernels, p, gc_lds_bytes(l.K, l.cells, Smax));
 }
 
 // Diagnostics: after an e2e_gram_ctc_fwd_bwd call with this workspace, why each utterance was redone in the log domain
@@ -530,11 +467,5 @@ extern "C" int e2e_debug_gram_redo_flags(const void* workspace, int B, int T, in
   if (!workspace || !flags_host || B < 1 || T < 1 || Smax < 0 || max_order < 1 || max_order > kGcMaxOrder) {
     set_error("bad arguments"); return E2E_ERR_ARG;
   }
-  const GcLayout l = gc_layout(B, T, Smax, max_order);
-  if (l.K == 0) { set_error("no such layout"); return E2E_ERR_UNSUPPORTED; }
-  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
-  E2E_HIP_CHECK(hipDeviceSynchronize(), "hipDeviceSynchronize");
-  E2E_HIP_CHECK(hipMemcpy(flags_host, ws + l.redo, sizeof(int) * B, hipMemcpyDeviceToHost), "hipMemcpy");
-  return E2E_OK;
+  return lattice_redo_flags(workspace, gc_layout(B, T, Smax, max_order), B, flags_host);
 }

@@ -25,18 +25,17 @@
 // runs beta over them.  An utterance the probability domain cannot settle -- a finite log-probability below -700, a
 // row that under/overflows, a final total of 0 or non-finite although the lattice is structurally feasible -- is redone
 // in the log domain by the same workgroup.  f64 input: the log domain throughout, upstream's log(1 + exp) and order.
+// lattice_common.h holds what this file shares with ctc_loss_gram.hip: the row pass, the numeric helpers, the host call.
 #include "common.h"
-#include "loss_rows.h"
+#include "lattice_common.h"
 
 namespace e2e {
 namespace {
 
-constexpr int kNbThreads = 256;
 constexpr int kNbBlk = 16;                   // frames per block = checkpoint interval (fewer from Smax 236 on: nb_block)
 // LDS of one gfx950 workgroup, less the lattice kernel's static LDS: 288 bytes (f32; 272 f64), its own words and
 // __syncthreads_or's; tests/test_noblank_cpu.py checks the built kernels against it
 constexpr size_t kNbLdsMax = 160 * 1024 - 288;
-constexpr double kLowLp = -700.0;            // a finite log-probability below this sends an f32 utterance to the log domain
 
 struct NbParams {
   const void* x; int64_t sB, sT, sV;
@@ -50,15 +49,6 @@ struct NbParams {
   int* ckc;                                  // [B][NB] their power-of-two exponents
 };
 
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// biased exponent of a non-negative double (0: zero or subnormal, 2047: inf / NaN)
-__device__ __forceinline__ int expo(double a) { return (__double2hiint(a) >> 20) & 0x7ff; }
-// 2^(1023 - m): divides a row whose largest biased exponent is m into [1, 2)
-__device__ __forceinline__ double inv_pow2(int m) { return __hiloint2double((2046 - m) << 20, 0); }
 // order of a wave's LDS operations across steps (the LDS runs one wave's operations in order; this keeps the compiler's)
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
@@ -69,7 +59,7 @@ __global__ __launch_bounds__(256) void noblank_rows_kernel(NbParams p, double* l
 
 // redo: [B] 0, or why the utterance was redone in the log domain (1 forward, 2 backward)
 template <typename IO>
-__global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p, int* redo) {
+__global__ __launch_bounds__(kLatticeThreads) void noblank_lattice_kernel(NbParams p, int* redo) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Tmax = p.T, V = p.V, K = p.K, Lm = p.Lmax;
@@ -94,17 +84,17 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
 
   // ---- the extended target ----
   int bad = bad_len;
-  for (int i = tid; i < S; i += kNbThreads) bad |= tg[i] < 0 || tg[i] >= V;
+  for (int i = tid; i < S; i += kLatticeThreads) bad |= tg[i] < 0 || tg[i] >= V;
   bad = __syncthreads_or(bad);
   const bool single = S == 0 || (S == 1 && tg[0] == sp);
   const bool two = !single && sp >= 0;
   const int L = single ? 1 : two ? S + 2 : S;
   if (bad || L > Lm) {
-    for (size_t i = tid; i < (size_t)Tmax * V; i += kNbThreads) grads[i] = (IO)NAN;
+    for (size_t i = tid; i < (size_t)Tmax * V; i += kLatticeThreads) grads[i] = (IO)NAN;
     if (tid == 0) *loss = (LT)NAN;
     return;
   }
-  for (int i = tid; i < L; i += kNbThreads) {
+  for (int i = tid; i < L; i += kLatticeThreads) {
     int lab;
     if (single) lab = sp < 0 ? V - 1 : sp;                           // ext = [space_idx]; [-1] is column V-1 (Q10)
     else if (two) lab = (i == 0 || i == L - 1) ? sp : (int)tg[i - 1];
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
   }
   if (tid == 0) s_flag = 0;
   __syncthreads();
-  for (int j = tid; j < L; j += kNbThreads) {                        // rank sort by (label, j)
+  for (int j = tid; j < L; j += kLatticeThreads) {                   // rank sort by (label, j)
     const int u = ext[j];
     int r = 0;
     for (int i = 0; i < L; i++) { const int w = ext[i]; r += (w < u) | ((w == u) & (i < j)); }
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
   }
   const bool feasible = two ? S <= T : L <= T;
   if (!feasible) {                                                   // no path: +inf, NaN rows (Q2's rule)
-    for (size_t i = tid; i < (size_t)T * V; i += kNbThreads) grads[i] = (IO)NAN;
+    for (size_t i = tid; i < (size_t)T * V; i += kLatticeThreads) grads[i] = (IO)NAN;
     if (tid == 0) *loss = (LT)INFINITY;
     return;
   }
@@ -192,15 +182,10 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
       grads[(size_t)(t0 + k) * V + u] = (IO)(scale * (pv - post));
     }
   };
-  // Every frame's posteriors sum to 1.  A row is scaled by its LARGEST cell, and a cell far below it that still carries
-  // paths can flush to zero; the mass it carried is then missing from its frame's sum.  Beta checks every frame's sum;
-  // an utterance whose sum is off by more than kMassTol is redone in the log domain after the backward sweep (the redo
-  // rewrites every label column it wrote).
-  constexpr double kMassTol = 1e-9;
   for (int pass = 0; pass < 2; pass++) {
     // ---- forward: alpha, checkpoint at the first frame of every block ----
     if (pass) __syncthreads();
-    gather(0, logd, 0, kNbThreads, false);
+    gather(0, logd, 0, kLatticeThreads, false);
     __syncthreads();
     int C = 0, m = 0, range_bad = 0;
     for (int n = 0; n < NB; n++) {
@@ -229,14 +214,14 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
             }
           }
           wave_lds_sync();
-          if (!logd) { m = wave_max_i(mx); range_bad |= m == 0 || m >= 2046; }
+          if (!logd) { m = wave_max_i(mx); range_bad |= expo_out_of_range(m); }
           if (k == 0) {                                  // checkpoint: to the workspace and into the slot's last row
             for (int j = lane; j < L; j += 64) { ck[(size_t)n * Lm + j] = Q[j]; pb[(size_t)K * Lm + j] = Q[j]; }
             if (lane == 0) { ckc[n] = C; s_ckc[n % 3] = C; }
           }
         }
       } else if (n + 1 < NB) {
-        gather(n + 1, logd, 64, kNbThreads - 64, false);
+        gather(n + 1, logd, 64, kLatticeThreads - 64, false);
       }
       __syncthreads();
     }
@@ -246,19 +231,19 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
     } else {
       if (tid == 0) s_cend = C;
       zm = two ? Q[L - 1] + Q[L - 2] : Q[L - 1];
-      const int fail = __syncthreads_or(range_bad || s_flag || !(zm > 0.0) || !(zm < INFINITY));
+      const int fail = prob_unsettled(range_bad, s_flag, zm);
       cend = s_cend;
       if (fail) {                                    // this utterance goes to the log domain
         if (tid == 0) redo[b] = 1;
         logd = true;
         continue;
       }
-      logz = log(zm) + (double)cend * 0.69314718055994530942;
+      logz = prob_log_z(zm, cend);
     }
     __syncthreads();                                 // (the last alpha row is read; beta takes its buffer)
     if (tid == 0) *loss = (LT)(-logz);
     if (logd && logz == ninf()) {                    // no path through the emissions: +inf, NaN rows
-      for (size_t i = tid; i < (size_t)T * V; i += kNbThreads) grads[i] = (IO)NAN;
+      for (size_t i = tid; i < (size_t)T * V; i += kLatticeThreads) grads[i] = (IO)NAN;
       return;
     }
 
@@ -334,21 +319,20 @@ __global__ __launch_bounds__(kNbThreads) void noblank_lattice_kernel(NbParams p,
           wave_lds_sync();
           if (!logd) {
             f = wave_max_i(gx);
-            lost |= f == 0 || f >= 2046;
+            lost |= expo_out_of_range(f);
             f = min(max(f, 1), 2045);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mass += __shfl_xor(mass, o, 64);
+            mass = wave_sum(mass);
             lost |= !(fabs(ldexp(mass, ek - cend) / zm - 1.0) <= kMassTol);
           }
         }
       } else {
-        if (n + 1 < NB) finish(n + 1, 64, kNbThreads - 64);
+        if (n + 1 < NB) finish(n + 1, 64, kLatticeThreads - 64);
         // blocks NB-1 and NB-2 are still in their slots from the forward sweep
-        if (n >= 1 && n - 1 < NB - 2) gather(n - 1, logd, 64, kNbThreads - 64, true);
+        if (n >= 1 && n - 1 < NB - 2) gather(n - 1, logd, 64, kLatticeThreads - 64, true);
       }
       __syncthreads();
     }
-    finish(0, 0, kNbThreads);
+    finish(0, 0, kLatticeThreads);
     if (logd || !__syncthreads_or(lost)) break;
     if (tid == 0) redo[b] = 2;
     logd = true;
@@ -367,19 +351,9 @@ int nb_block(int Lmax) {
   return 0;
 }
 
-struct NbLayout { size_t lse, ck, ckc, redo, total; int K, NB, Lmax; };
-NbLayout nb_layout(int B, int T, int Smax) {
-  NbLayout l{};
-  l.Lmax = nb_lmax(Smax);
-  l.K = nb_block(l.Lmax);
-  if (l.K == 0) return l;
-  l.NB = (T + l.K - 1) / l.K;
-  l.lse = 0;
-  l.ck = align_up((size_t)B * T * sizeof(double), 256);
-  l.ckc = l.ck + align_up((size_t)B * l.NB * l.Lmax * sizeof(double), 256);
-  l.redo = l.ckc + align_up((size_t)B * l.NB * sizeof(int), 256);
-  l.total = l.redo + align_up((size_t)B * sizeof(int), 256);
-  return l;
+LatticeLayout nb_layout(int B, int T, int Smax) {
+  const int K = nb_block(nb_lmax(Smax));
+  return lattice_layout(B, T, nb_lmax(Smax), K, K);                   // a checkpoint per block
 }
 
 }  // namespace
@@ -390,7 +364,7 @@ using namespace e2e;
 extern "C" size_t e2e_ctc_noblank_workspace_bytes(int B, int T, int V, int Smax, int dtype) {
   (void)V; (void)dtype;
   if (B < 0 || T < 1 || Smax < 0) return 0;
-  const NbLayout l = nb_layout(B, T, Smax);
+  const LatticeLayout l = nb_layout(B, T, Smax);
   return l.K ? l.total + 256 : 0;
 }
 
@@ -399,51 +373,22 @@ extern "C" int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_lo
                                        const int64_t* t_len, int B, int T, int V, int Smax, int space_idx, void* losses,
                                        void* grads, void* workspace, size_t workspace_bytes, void* stream,
                                        const e2e_ctc_loss_opts* opts) {
-  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64 (up-cast 16-bit inputs)"); return E2E_ERR_ARG; }
-  if (B < 0 || T < 1 || V < 1 || Smax < 0) { set_error("bad sizes B=%d T=%d V=%d Smax=%d", B, T, V, Smax); return E2E_ERR_ARG; }
+  LossArgs a{x, dtype, input_is_logprobs ? 1 : 0, sB, sT, sV, targets, tgt_stride, x_len, t_len,
+             B, T, V, Smax, 0, losses, grads, workspace, workspace_bytes, (hipStream_t)stream};
+  int rc = lattice_check_args(a, opts);
+  if (rc != E2E_OK) return rc;
   if (space_idx != -1 && (space_idx < 0 || space_idx >= V)) { set_error("space_idx=%d is neither -1 nor in [0,%d)", space_idx, V); return E2E_ERR_ARG; }
-  if (opts && (opts->reduction < E2E_REDUCE_NONE || opts->reduction > E2E_REDUCE_MEAN ||
-               (opts->reduction != E2E_REDUCE_NONE && !opts->reduced))) {
-    set_error("bad e2e_ctc_loss_opts: reduction %d, reduced %p", opts->reduction, opts->reduced); return E2E_ERR_ARG;
-  }
-  if (B > 0 && (!x || !x_len || !t_len || !losses || !grads || !targets)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
-  const NbLayout l = nb_layout(B, T, Smax);
+  const LatticeLayout l = nb_layout(B, T, Smax);
   if (l.K == 0) { set_error("CTC without blank: Smax=%d needs more than %zu B of LDS", Smax, kNbLdsMax); return E2E_ERR_UNSUPPORTED; }
-  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const uintptr_t aligned = (base + 255) & ~(uintptr_t)255;
-  if (!workspace || workspace_bytes < l.total + (aligned - base)) { set_error("workspace too small: need %zu", l.total + 256); return E2E_ERR_WORKSPACE; }
-  if (B == 0) return E2E_OK;
-  unsigned char* ws = reinterpret_cast<unsigned char*>(aligned);
+  rc = lattice_workspace(a, l);
+  if (rc != E2E_OK || B == 0) return rc;
   NbParams p;
-  p.x = x; p.sB = sB; p.sT = sT; p.sV = sV; p.targets = targets; p.tgt_stride = tgt_stride; p.x_len = x_len; p.t_len = t_len;
-  p.B = B; p.T = T; p.V = V; p.Smax = Smax; p.space = space_idx; p.logits = input_is_logprobs ? 0 : 1;
-  p.K = l.K; p.NB = l.NB; p.Lmax = l.Lmax; p.gscale = opts ? opts->grad_scale : 1.0;
-  p.losses = losses; p.grads = grads;
-  p.lse = reinterpret_cast<const double*>(ws + l.lse); p.ck = reinterpret_cast<double*>(ws + l.ck); p.ckc = reinterpret_cast<int*>(ws + l.ckc);
-  int* redo = reinterpret_cast<int*>(ws + l.redo);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = nb_lds_bytes(l.K, l.Lmax);
-  const unsigned rows_grid = (unsigned)(((int64_t)B * T + 3) / 4);
-  double* lse_out = reinterpret_cast<double*>(ws + l.lse);
-  if (dtype == E2E_F32) {
-    hipLaunchKernelGGL(noblank_rows_kernel<float>, dim3(rows_grid), dim3(256), 0, s, p, lse_out);
-    E2E_HIP_CHECK(hipGetLastError(), "noblank_rows_kernel launch");
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&noblank_lattice_kernel<float>), (int)lds), "hipFuncSetAttribute");
-    hipLaunchKernelGGL(noblank_lattice_kernel<float>, dim3(B), dim3(kNbThreads), lds, s, p, redo);
-  } else {
-    hipLaunchKernelGGL(noblank_rows_kernel<double>, dim3(rows_grid), dim3(256), 0, s, p, lse_out);
-    E2E_HIP_CHECK(hipGetLastError(), "noblank_rows_kernel launch");
-    E2E_HIP_CHECK(allow_dynamic_lds(reinterpret_cast<const void*>(&noblank_lattice_kernel<double>), (int)lds), "hipFuncSetAttribute");
-    hipLaunchKernelGGL(noblank_lattice_kernel<double>, dim3(B), dim3(kNbThreads), lds, s, p, redo);
-  }
-  E2E_HIP_CHECK(hipGetLastError(), "noblank_lattice_kernel launch");
-  if (opts && opts->reduced && opts->reduction != E2E_REDUCE_NONE) {
-    LossArgs a{x, dtype, input_is_logprobs ? 1 : 0, sB, sT, sV, targets, tgt_stride, x_len, t_len,
-               B, T, V, Smax, 0, losses, grads, ws, workspace_bytes, s};
-    a.reduced = opts->reduced; a.reduction = opts->reduction;
-    return launch_reduce_losses(a);
-  }
-  return E2E_OK;
+  lattice_params(p, a, l);
+  p.space = space_idx; p.Lmax = l.cells;
+  static const LatticeKernels<NbParams, int*> kernels = {
+      noblank_rows_kernel<float>, noblank_rows_kernel<double>, "noblank_rows_kernel launch",
+      noblank_lattice_kernel<float>, noblank_lattice_kernel<double>, "noblank_lattice_kernel launch"};
+  return lattice_launch(a, kernels, p, nb_lds_bytes(l.K, l.cells), reinterpret_cast<int*>(aligned_256(workspace) + l.redo));
 }
 
 // Diagnostics: after an e2e_ctc_noblank_fwd_bwd call with this workspace, why each utterance was redone in the log domain
@@ -451,11 +396,5 @@ extern "C" int e2e_ctc_noblank_fwd_bwd(const void* x, int dtype, int input_is_lo
 // Synchronises.
 extern "C" int e2e_debug_noblank_redo_flags(const void* workspace, int B, int T, int Smax, int* flags_host) {
   if (!workspace || !flags_host || B < 1 || T < 1 || Smax < 0) { set_error("bad arguments"); return E2E_ERR_ARG; }
-  const NbLayout l = nb_layout(B, T, Smax);
-  if (l.K == 0) { set_error("no such layout"); return E2E_ERR_UNSUPPORTED; }
-  const uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
-  const char* ws = reinterpret_cast<const char*>((base + 255) & ~(uintptr_t)255);
-  E2E_HIP_CHECK(hipDeviceSynchronize(), "hipDeviceSynchronize");
-  E2E_HIP_CHECK(hipMemcpy(flags_host, ws + l.redo, sizeof(int) * B, hipMemcpyDeviceToHost), "hipMemcpy");
-  return E2E_OK;
+  return lattice_redo_flags(workspace, nb_layout(B, T, Smax), B, flags_host);
 }

@@ -33,6 +33,8 @@ def _as_long(t, device):
     return t.to(device=device, dtype=torch.long).contiguous()
 
 
+_F32_F64 = (torch.float32, torch.float64)
+_16BIT = (torch.float16, torch.bfloat16)
 _REDUCTIONS = {None: _C.REDUCE_NONE, "sum": _C.REDUCE_SUM, "mean": _C.REDUCE_MEAN}
 _ws_bytes = {}                           # (B, T, V, Smax, dtype code, algo) -> e2e_ctc_loss_workspace_bytes
 
@@ -56,15 +58,22 @@ class _NullCtx:
 _NULL_CTX = _NullCtx()
 
 
-class CTCLossEngine:
-    """blank_idx -> .compute(logits, targets, logits_lengths, targets_lengths) -> (losses[B], grads[B,T,V])."""
+class _ForwardBackwardEngine:
+    """compute() of the loss engines: one (B,T,V) tensor of logits or log-probabilities, padded targets and the two
+    lengths in; (losses[B], grads[B,T,V]) out, on the device and in the dtype the logits came in.  A subclass says
+    whether its kernels read 16-bit logits (`_takes_16bit`), what else it checks (`_check`), how large a workspace it needs
+    (`_workspace_bytes`) and makes its one C call (`_launch`)."""
 
-    def __init__(self, blank_idx, algo=R.ALGO_AUTO, f32_chains=False):
-        """`f32_chains` (extension, e2e_ctc_loss_opts.chains): let the lattice chains run in packed f32 where that is
-        faster (long targets, small alphabets): gradient elements within 2e-5 absolute of the reference instead of 2e-6."""
-        self.blank_idx = int(blank_idx)
-        self.algo = algo
-        self.f32_chains = bool(f32_chains)
+    _redo_flags = None                   # name of the e2e_debug_*_redo_flags entry point, if the kernels keep such flags
+    _last = None                         # then: (workspace, B, T, Smax) of the last launch
+
+    def _check(self, V):
+        pass
+
+    def _takes_16bit(self, x, targets):
+        """Do the kernels read these f16 / bf16 logits as they are?  If not they are up-cast to f32, as every dtype but f32
+        and f64 is."""
+        return False
 
     def compute(self, logits, targets, logits_lengths, targets_lengths, input_is_logprobs=True,
                 grad_scale=1.0, reduction=None):
@@ -77,63 +86,46 @@ class CTCLossEngine:
         kernel: the result is then (losses, grads, reduced)."""
         if logits.dim() != 3:
             raise ValueError("logits must be (batch, time, alphabet)")
+        self._check(logits.shape[2])
         src_device, src_dtype = logits.device, logits.dtype
         dev = R.compute_device(logits)
-        x = logits.detach().to(dev)
-        if x.dtype in (torch.float16, torch.bfloat16) and self.algo != R.ALGO_EXACT:
-            # 16-bit logits (raw autocast outputs): the fast and wide paths read them as they are and write the gradient in
-            # the same dtype -- no f32 copy of the (B,T,V) tensors (the reference converts once to double,
-            # src/losses/forward_backward.cpp:15,55-56).  Shapes those paths do not take (the library says which:
-            # e2e_ctc_loss_takes_dtype) are up-cast below.  The gradient of a fresh allocation is 256-byte aligned.
-            B, T, V = x.shape
-            targets = _as_long(targets, dev)
-            Smax = targets.shape[1] if targets.dim() == 2 else 0
-            sB, sT, sV = x.stride()
-            if _C.ctc_loss_takes_dtype(R.dtype_code(x.dtype), self.algo, T, V, Smax, sB, sT, sV, x.data_ptr(), 0):
-                return self._compute_on_device(x, src_device, src_dtype, dev, targets, logits_lengths, targets_lengths,
-                                               input_is_logprobs, grad_scale, reduction)
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.to(torch.float32)
-        return self._compute_on_device(x, src_device, src_dtype, dev, targets, logits_lengths, targets_lengths,
-                                       input_is_logprobs, grad_scale, reduction)
-
-    def _compute_on_device(self, x, src_device, src_dtype, dev, targets, logits_lengths, targets_lengths,
-                           input_is_logprobs, grad_scale, reduction):
-        B, T, V = x.shape
-        half = x.dtype in (torch.float16, torch.bfloat16)
-        loss_dtype = torch.float32 if half else x.dtype        # (16-bit I/O: the library keeps losses in f32)
         targets = _as_long(targets, dev)
+        x = logits.detach().to(dev)
+        if x.dtype not in _F32_F64 and not (x.dtype in _16BIT and self._takes_16bit(x, targets)):
+            x = x.to(torch.float32)
+        B, T, V = x.shape
         if targets.dim() != 2 or targets.shape[0] != B:
             raise ValueError("targets must be (batch, max_target_length)")
         xl = _as_long(logits_lengths, dev)
         tl = _as_long(targets_lengths, dev)
         if xl.numel() != B or tl.numel() != B:
             raise ValueError("lengths must have one entry per utterance")
-        Smax = targets.shape[1]
-        losses = torch.empty(B, dtype=loss_dtype, device=dev)
-        grads = torch.empty((B, T, V), dtype=x.dtype, device=dev)
         if reduction not in (None, "sum", "mean"):
             raise ValueError("reduction must be None, 'sum' or 'mean'")
+        Smax = targets.shape[1]
+        if Smax == 0:
+            targets = torch.zeros((B, 1), dtype=torch.long, device=dev)    # (an address to hand over; never read)
+        loss_dtype = torch.float32 if x.dtype in _16BIT else x.dtype       # (16-bit I/O: the library keeps losses in f32)
+        losses = torch.empty(B, dtype=loss_dtype, device=dev)
+        grads = torch.empty((B, T, V), dtype=x.dtype, device=dev)
         if B == 0:
             out = (losses.to(src_device, src_dtype), grads.to(src_device, src_dtype))
             return out if reduction is None else out + (getattr(out[0], reduction)(),)
-        reduced = torch.empty((), dtype=loss_dtype, device=dev) if reduction else None
         code = R.dtype_code(x.dtype)
+        nbytes = self._workspace_bytes(B, T, V, Smax, code)
+        reduced = torch.empty((), dtype=loss_dtype, device=dev) if reduction else None
+        stream = R.stream_handle(dev)
         with _on_device(dev):
-            key = (B, T, V, Smax, code, self.algo)
-            nbytes = _ws_bytes.get(key)
-            if nbytes is None:
-                nbytes = _ws_bytes[key] = _C.ctc_loss_workspace_bytes(B, T, V, Smax, code, self.algo)
-            ws = R.workspace(dev, nbytes)
+            ws = R.workspace(dev, nbytes, stream)
             sB, sT, sV = x.stride()
-            _C.ctc_loss_fwd_bwd(x.data_ptr(), code, bool(input_is_logprobs), sB, sT, sV,
-                                targets.data_ptr(), targets.stride(0), xl.data_ptr(), tl.data_ptr(),
-                                B, T, V, Smax, self.blank_idx,
-                                losses.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws.numel(),
-                                self.algo, R.stream_handle(dev), float(grad_scale),
-                                reduced.data_ptr() if reduction else 0,
-                                _REDUCTIONS[reduction],
-                                _C.CHAINS_F32 if self.f32_chains else _C.CHAINS_F64)
+            self._launch(dev,
+                         (x.data_ptr(), code, bool(input_is_logprobs), sB, sT, sV, targets.data_ptr(), targets.stride(0),
+                          xl.data_ptr(), tl.data_ptr(), B, T, V, Smax),
+                         (losses.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws.numel()),
+                         (stream, float(grad_scale), reduced.data_ptr() if reduction else 0,
+                          _REDUCTIONS[reduction]))
+        if self._redo_flags:
+            self._last = (ws, B, T, Smax)
         if src_device != dev or src_dtype != losses.dtype:
             losses = losses.to(src_device, src_dtype)
             if reduction:
@@ -161,77 +153,80 @@ class CTCLossEngine:
         return grads
 
 
-class CTCWithoutBlankLossEngine:
+class CTCLossEngine(_ForwardBackwardEngine):
+    """blank_idx -> .compute(logits, targets, logits_lengths, targets_lengths) -> (losses[B], grads[B,T,V])."""
+
+    def __init__(self, blank_idx, algo=R.ALGO_AUTO, f32_chains=False):
+        """`f32_chains` (extension, e2e_ctc_loss_opts.chains): let the lattice chains run in packed f32 where that is
+        faster (long targets, small alphabets): gradient elements within 2e-5 absolute of the reference instead of 2e-6."""
+        self.blank_idx = int(blank_idx)
+        self.algo = algo
+        self.f32_chains = bool(f32_chains)
+
+    def _takes_16bit(self, x, targets):
+        # 16-bit logits (raw autocast outputs): the fast and wide paths read them as they are and write the gradient in
+        # the same dtype -- no f32 copy of the (B,T,V) tensors (the reference converts once to double,
+        # src/losses/forward_backward.cpp:15,55-56).  Shapes those paths do not take (the library says which:
+        # e2e_ctc_loss_takes_dtype) are up-cast.  The gradient of a fresh allocation is 256-byte aligned.
+        if self.algo == R.ALGO_EXACT:
+            return False
+        B, T, V = x.shape
+        Smax = targets.shape[1] if targets.dim() == 2 else 0
+        sB, sT, sV = x.stride()
+        return _C.ctc_loss_takes_dtype(R.dtype_code(x.dtype), self.algo, T, V, Smax, sB, sT, sV, x.data_ptr(), 0)
+
+    def _workspace_bytes(self, B, T, V, Smax, code):
+        key = (B, T, V, Smax, code, self.algo)
+        nbytes = _ws_bytes.get(key)
+        if nbytes is None:
+            nbytes = _ws_bytes[key] = _C.ctc_loss_workspace_bytes(B, T, V, Smax, code, self.algo)
+        return nbytes
+
+    def _launch(self, dev, call, out, opts):
+        _C.ctc_loss_fwd_bwd(*call, self.blank_idx, *out, self.algo, *opts,
+                            _C.CHAINS_F32 if self.f32_chains else _C.CHAINS_F64)
+
+
+class _LatticeLossEngine(_ForwardBackwardEngine):
+    """The engines of the one-workgroup-per-utterance lattice kernels (csrc/lattice_common.h): f32 and f64 only, and a
+    probability-domain f32 pass that redoes in the f64 log domain the utterances it cannot settle."""
+
+    def _redo_args(self):
+        return ()
+
+    def redo_flags(self):
+        """Diagnostics (synchronises): per utterance of the last compute(), why it was redone in the f64 log domain -- 0 not
+        (or f64 input, or no lattice to run: bad lengths or labels, more labels than frames without blank), 1 the
+        probability-domain forward could not settle it (Gram-CTC: infeasible utterances included), 2 the backward found a
+        frame whose posteriors do not sum to 1.  Read before another call on the stream reuses the workspace."""
+        import ctypes
+        from . import _lib
+        ws, B, T, Smax = self._last
+        out = (ctypes.c_int * B)()
+        _lib.check(getattr(_lib.load(), self._redo_flags)(ctypes.c_void_p(ws.data_ptr()), B, T, Smax, *self._redo_args(), out))
+        return np.array(out[:], dtype=np.int32)
+
+
+class CTCWithoutBlankLossEngine(_LatticeLossEngine):
     """space_idx -> .compute(logits, targets, logits_lengths, targets_lengths) -> (losses[B], grads[B,T,V]) for the
     blank-free (ASG-style) lattice of pytorch_end2end/functions/ctc_without_blank.py:13-138 upstream, computed by
     e2e_ctc_noblank_fwd_bwd.  The contract of CTCLossEngine.compute (devices, dtypes, `input_is_logprobs`, `grad_scale`,
     `reduction`), so that ForwardBackwardLossFunction serves it unchanged; 16-bit inputs are up-cast to f32."""
 
+    _redo_flags = "e2e_debug_noblank_redo_flags"
+
     def __init__(self, space_idx=-1):
         self.space_idx = int(space_idx)
-        self._last = None
 
-    def redo_flags(self):
-        """Diagnostics (synchronises): per utterance of the last compute(), why it was redone in the f64 log domain -- 0 not
-        (or f64 input, or no lattice to run: bad lengths or labels, more labels than frames), 1 the probability-domain
-        forward could not settle it, 2 the backward found a frame whose posteriors do not sum to 1
-        (e2e_debug_noblank_redo_flags).  Read before another call on the stream reuses the workspace."""
-        import ctypes
-        from . import _lib
-        ws, B, T, Smax = self._last
-        out = (ctypes.c_int * B)()
-        _lib.check(_lib.load().e2e_debug_noblank_redo_flags(ctypes.c_void_p(ws.data_ptr()), B, T, Smax, out))
-        return np.array(out[:], dtype=np.int32)
-
-    def compute(self, logits, targets, logits_lengths, targets_lengths, input_is_logprobs=True,
-                grad_scale=1.0, reduction=None):
-        if logits.dim() != 3:
-            raise ValueError("logits must be (batch, time, alphabet)")
-        src_device, src_dtype = logits.device, logits.dtype
-        dev = R.compute_device(logits)
-        x = logits.detach().to(dev)
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.to(torch.float32)
-        B, T, V = x.shape
+    def _check(self, V):
         if self.space_idx != -1 and not 0 <= self.space_idx < V:
             raise ValueError("space_idx %d is neither -1 nor a label of the %d-column alphabet" % (self.space_idx, V))
-        targets = _as_long(targets, dev)
-        if targets.dim() != 2 or targets.shape[0] != B:
-            raise ValueError("targets must be (batch, max_target_length)")
-        xl = _as_long(logits_lengths, dev)
-        tl = _as_long(targets_lengths, dev)
-        if xl.numel() != B or tl.numel() != B:
-            raise ValueError("lengths must have one entry per utterance")
-        if reduction not in (None, "sum", "mean"):
-            raise ValueError("reduction must be None, 'sum' or 'mean'")
-        Smax = targets.shape[1]
-        if Smax == 0:
-            targets = torch.zeros((B, 1), dtype=torch.long, device=dev)
-        losses = torch.empty(B, dtype=x.dtype, device=dev)
-        grads = torch.empty((B, T, V), dtype=x.dtype, device=dev)
-        if B == 0:
-            out = (losses.to(src_device, src_dtype), grads.to(src_device, src_dtype))
-            return out if reduction is None else out + (getattr(out[0], reduction)(),)
-        reduced = torch.empty((), dtype=x.dtype, device=dev) if reduction else None
-        code = R.dtype_code(x.dtype)
-        with _on_device(dev):
-            ws = R.workspace(dev, _C.ctc_noblank_workspace_bytes(B, T, V, Smax, code))
-            sB, sT, sV = x.stride()
-            _C.ctc_noblank_fwd_bwd(x.data_ptr(), code, bool(input_is_logprobs), sB, sT, sV,
-                                   targets.data_ptr(), targets.stride(0), xl.data_ptr(), tl.data_ptr(),
-                                   B, T, V, Smax, self.space_idx, losses.data_ptr(), grads.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), R.stream_handle(dev), float(grad_scale),
-                                   reduced.data_ptr() if reduction else 0, _REDUCTIONS[reduction])
-        self._last = (ws, B, T, Smax)
-        if src_device != dev or src_dtype != losses.dtype:
-            losses = losses.to(src_device, src_dtype)
-            if reduction:
-                reduced = reduced.to(src_device, src_dtype)
-        if src_device != dev or src_dtype != grads.dtype:
-            grads = grads.to(src_device, src_dtype)
-        return (losses, grads) if reduction is None else (losses, grads, reduced)
 
-    scale_grads_ = staticmethod(CTCLossEngine.scale_grads_)
+    def _workspace_bytes(self, B, T, V, Smax, code):
+        return _C.ctc_noblank_workspace_bytes(B, T, V, Smax, code)
+
+    def _launch(self, dev, call, out, opts):
+        _C.ctc_noblank_fwd_bwd(*call, self.space_idx, *out, *opts)
 
 
 GRAM_MAX_ORDER = 8
@@ -276,12 +271,14 @@ def gram_table(num_base_labels, total_labels, label2ids):
     return np.array(ks, dtype=np.int64), np.array([keys[k] for k in ks], dtype=np.int32), order
 
 
-class GramCTCLossEngine:
+class GramCTCLossEngine(_LatticeLossEngine):
     """(blank_idx, num_base_labels, total_labels, label2ids) -> .compute(logits, targets, logits_lengths,
     targets_lengths) -> (losses[B], grads[B,T,V]) for Gram-CTC, computed by e2e_gram_ctc_fwd_bwd (the definition:
     include/e2e_ctc.h).  The contract of CTCLossEngine.compute, so that ForwardBackwardLossFunction serves it unchanged;
     16-bit inputs are up-cast to f32.  Construction checks the table on the host; the device copy is made on first use
     and kept per device."""
+
+    _redo_flags = "e2e_debug_gram_redo_flags"
 
     def __init__(self, blank_idx, num_base_labels, total_labels, label2ids):
         if int(blank_idx) != 0:
@@ -291,19 +288,9 @@ class GramCTCLossEngine:
         self.total_labels = int(total_labels)
         self._keys, self._cols, self.max_order = gram_table(num_base_labels, total_labels, label2ids)
         self._per_device = {}
-        self._last = None
 
-    def redo_flags(self):
-        """Diagnostics (synchronises): per utterance of the last compute(), why it was redone in the f64 log domain -- 0 not
-        (or f64 input), 1 the probability-domain forward could not settle it (infeasible utterances included), 2 the backward
-        found a frame whose posteriors do not sum to 1 (e2e_debug_gram_redo_flags).  Read before another call on the stream
-        reuses the workspace."""
-        import ctypes
-        from . import _lib
-        ws, B, T, Smax = self._last
-        out = (ctypes.c_int * B)()
-        _lib.check(_lib.load().e2e_debug_gram_redo_flags(ctypes.c_void_p(ws.data_ptr()), B, T, Smax, self.max_order, out))
-        return np.array(out[:], dtype=np.int32)
+    def _redo_args(self):
+        return (self.max_order,)
 
     def _table(self, dev):
         t = self._per_device.get(dev.index)
@@ -323,62 +310,21 @@ class GramCTCLossEngine:
                 hi = mid - 1
         return lo
 
-    def compute(self, logits, targets, logits_lengths, targets_lengths, input_is_logprobs=True,
-                grad_scale=1.0, reduction=None):
-        if logits.dim() != 3:
-            raise ValueError("logits must be (batch, time, alphabet)")
-        if logits.shape[2] != self.total_labels:
-            raise ValueError("logits have %d columns; this Gram-CTC table has total_labels=%d"
-                             % (logits.shape[2], self.total_labels))
-        src_device, src_dtype = logits.device, logits.dtype
-        dev = R.compute_device(logits)
-        x = logits.detach().to(dev)
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.to(torch.float32)
-        B, T, V = x.shape
-        targets = _as_long(targets, dev)
-        if targets.dim() != 2 or targets.shape[0] != B:
-            raise ValueError("targets must be (batch, max_target_length)")
-        xl = _as_long(logits_lengths, dev)
-        tl = _as_long(targets_lengths, dev)
-        if xl.numel() != B or tl.numel() != B:
-            raise ValueError("lengths must have one entry per utterance")
-        if reduction not in (None, "sum", "mean"):
-            raise ValueError("reduction must be None, 'sum' or 'mean'")
-        Smax = targets.shape[1]
-        if Smax == 0:
-            targets = torch.zeros((B, 1), dtype=torch.long, device=dev)
-        losses = torch.empty(B, dtype=x.dtype, device=dev)
-        grads = torch.empty((B, T, V), dtype=x.dtype, device=dev)
-        if B == 0:
-            out = (losses.to(src_device, src_dtype), grads.to(src_device, src_dtype))
-            return out if reduction is None else out + (getattr(out[0], reduction)(),)
-        code = R.dtype_code(x.dtype)
+    def _check(self, V):
+        if V != self.total_labels:
+            raise ValueError("logits have %d columns; this Gram-CTC table has total_labels=%d" % (V, self.total_labels))
+
+    def _workspace_bytes(self, B, T, V, Smax, code):
         nbytes = _C.gram_ctc_workspace_bytes(B, T, V, Smax, self.max_order, code)
         if nbytes == 0:
             raise ValueError("Gram-CTC: targets of %d labels exceed the %d the kernel serves at max_order %d"
                              % (Smax, self.max_target_length(), self.max_order))
-        reduced = torch.empty((), dtype=x.dtype, device=dev) if reduction else None
-        keys, cols = self._table(dev)
-        with _on_device(dev):
-            ws = R.workspace(dev, nbytes)
-            sB, sT, sV = x.stride()
-            _C.gram_ctc_fwd_bwd(x.data_ptr(), code, bool(input_is_logprobs), sB, sT, sV,
-                                targets.data_ptr(), targets.stride(0), xl.data_ptr(), tl.data_ptr(),
-                                B, T, V, Smax, keys.data_ptr(), cols.data_ptr(), keys.numel(), self.num_base_labels,
-                                self.max_order, losses.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws.numel(),
-                                R.stream_handle(dev), float(grad_scale), reduced.data_ptr() if reduction else 0,
-                                _REDUCTIONS[reduction])
-        self._last = (ws, B, T, Smax)
-        if src_device != dev or src_dtype != losses.dtype:
-            losses = losses.to(src_device, src_dtype)
-            if reduction:
-                reduced = reduced.to(src_device, src_dtype)
-        if src_device != dev or src_dtype != grads.dtype:
-            grads = grads.to(src_device, src_dtype)
-        return (losses, grads) if reduction is None else (losses, grads, reduced)
+        return nbytes
 
-    scale_grads_ = staticmethod(CTCLossEngine.scale_grads_)
+    def _launch(self, dev, call, out, opts):
+        keys, cols = self._table(dev)
+        _C.gram_ctc_fwd_bwd(*call, keys.data_ptr(), cols.data_ptr(), keys.numel(), self.num_base_labels, self.max_order,
+                            *out, *opts)
 
 
 class LanguageModel:
