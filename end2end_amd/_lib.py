@@ -31,6 +31,11 @@ class LossOpts(C.Structure):
     _fields_ = [("grad_scale", C.c_double), ("reduced", C.c_void_p), ("reduction", C.c_int), ("chains", C.c_int)]
 
 
+class BeamOpts(C.Structure):
+    """e2e_ctc_beam_opts (include/e2e_ctc.h)."""
+    _fields_ = [("restrict_to_lexicon", C.c_int)]
+
+
 class E2EError(RuntimeError):
     """An error reported by the native library (message from e2e_last_error())."""
 
@@ -108,6 +113,16 @@ def load():
         L.e2e_ctc_beam_nbest.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
                                          C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p, vp, C.c_size_t, vp]
+        L.e2e_ctc_beam_nbest_opt.restype = C.c_int
+        L.e2e_ctc_beam_nbest_opt.argtypes = L.e2e_ctc_beam_nbest.argtypes + [C.POINTER(BeamOpts)]
+        L.e2e_lm_load_words.restype = C.c_int
+        L.e2e_lm_load_words.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(vp)]
+        L.e2e_lm_enable_lexicon.restype = C.c_int
+        L.e2e_lm_enable_lexicon.argtypes = [vp]
+        L.e2e_lm_has_lexicon.restype = C.c_int
+        L.e2e_lm_has_lexicon.argtypes = [vp]
+        L.e2e_lm_spelling_class.restype = C.c_int
+        L.e2e_lm_spelling_class.argtypes = [vp, C.c_char_p]
         L.e2e_ctc_align_workspace_bytes.restype = C.c_size_t
         L.e2e_ctc_align_workspace_bytes.argtypes = [C.c_int] * 5
         L.e2e_ctc_align.restype = C.c_int

@@ -227,9 +227,19 @@ __device__ __forceinline__ float lm_score_parallel(const LmView& lm, const LmCon
     if (k > found_k && k <= n && (cx.hit >> k & 1u)) result += cx.backoff[k];
   return result;
 }
+// The search restricted to the model's lexicon (e2e_ctc_beam_opts.restrict_to_lexicon; the definition is in DESIGN.md 4.4):
+// a child is created only if its word's spelling is a word of the lexicon or a prefix of one, and a space only behind a
+// whole word.  The vocabulary tables of a model with a lexicon list the prefixes that are no words with id 0, so the probe
+// that finds the word's id also answers the first question: a spelling that is not in the table at all gets kNoChildWord
+// for an answer, and the pair loop creates no candidate for it.  The second follows from what a member holds already.
+constexpr uint32_t kNoChildWord = 0xFFFFFFFFu;
+// LMK, the kernels' template argument: 0 no language model, 1 the general LM walk, 2 the fast one (see lm_query); 3 and 4 are
+// 1 and 2 restricted to the lexicon (instances of their own: the unrestricted ones carry nothing of the rule)
+__host__ __device__ constexpr bool lmk_fast(int lmk) { return lmk == 2 || lmk == 4; }
+__host__ __device__ constexpr bool lmk_restricted(int lmk) { return lmk >= 3; }
 // FAST: the model has signature tables and at most kParCtx words of context (checked by the host): only the round-probed
 // walk is compiled in.  Otherwise: the general walk over the id tables (any order up to 6).
-template <bool FAST>
+template <bool FAST, bool RS>
 __device__ __forceinline__ LmAnswer lm_query(const BeamParams& p, const LabelTab& lt, const LmFields& pr, int parent_last, int c) {
   const bool new_word = pr.num_words == 0 || parent_last == p.space_id;                           // :258-259 (c != space)
   LmAnswer a;
@@ -248,14 +258,26 @@ __device__ __forceinline__ LmAnswer lm_query(const BeamParams& p, const LabelTab
     LmContexts cx;
     lm_contexts(p.lm, ctx, cn, cx);
     const bool in1 = (((uint64_t)e1.y << 32) | e1.x) == h, in2 = (((uint64_t)e2.y << 32) | e2.x) == h;
+    if (RS && !in1 && !in2) { a.wi = kNoChildWord; a.sc = 0.f; return a; }
     a.wi = in1 ? e1.z : in2 ? e2.z : 0u;                             // NotFound() == <unk> == 0
     const float uni_prob = in1 ? __uint_as_float(e1.w) : in2 ? __uint_as_float(e2.w) : p.lm.unk_prob;
     a.sc = lm_score_parallel(p.lm, cx, cn, a.wi, uni_prob);
   } else {
-    a.wi = lm_word_lookup(p.lm, h);
+    if (RS) {
+      if (!lm_word_find(p.lm, h, a.wi)) { a.wi = kNoChildWord; a.sc = 0.f; return a; }
+    } else {
+      a.wi = lm_word_lookup(p.lm, h);
+    }
     a.sc = lm_base_score(p.lm, new_word ? pr.st : pr.stb, cn, a.wi, nullptr, nullptr);
   }
   return a;
+}
+
+// restricted to the lexicon: is the child (member pr, character c) one that may not be created?  (pr: score_fields)
+__device__ __forceinline__ bool lexicon_forbids(const BeamParams& p, const LmFields& pr, int parent_last, int c, LmAnswer ans) {
+  // a space: only behind a whole word -- the member ends inside a word, and that word is not out of vocabulary
+  if (c == p.space_id) return parent_last >= 0 && parent_last != p.space_id && pr.num_oov != pr.num_oov_before;
+  return ans.wi == kNoChildWord;
 }
 
 // Quirk Q8's division, (double)score / ln 10, without the division: for every float whose magnitude lies in [2^-60, 2^20)
@@ -653,10 +675,9 @@ namespace e2e { namespace {
 #define BPROF(slot) do {} while (0)
 #endif
 
-// LMK: 0 no language model, 1 the general LM walk, 2 the fast one (see lm_query)
 template <typename IO, int LMK>
 __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
-  constexpr bool LM = LMK != 0;
+  constexpr bool LM = LMK != 0, RS = lmk_restricted(LMK);
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int V = p.V, W = p.W, blank = p.blank;
@@ -725,7 +746,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   }
   __syncthreads();
   if (tid == 0) slot_map(0).insert(0, 0);
-  if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<LMK == 2>(p, lt, M0.lm[0], -1, c);
+  if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
   __syncthreads();
   int n = 1, cur = 0;
   // the pair loop's thread layout depends on n alone, and n is W for all but an utterance's first steps: worked out when n
@@ -795,9 +816,12 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
           if (j >= 0) A.inc[j] = val;            // the child is a beam member: its share from this parent
           // else: alive but pruned (Q7) -- the probability is lost and the slot stays taken
         } else {
-          uk = child_key<LM>(p, pr, last, ci, answer_at<LM>(lmcA, ii * V + ci), val);
-          key_hi = max(key_hi, (unsigned)(uk >> 32));
-          my_new++;
+          const LmAnswer ans = answer_at<LM>(lmcA, ii * V + ci);
+          if (!RS || !lexicon_forbids(p, pr, last, ci, ans)) {   // (forbidden: no child, no candidate; the member's own
+            uk = child_key<LM>(p, pr, last, ci, ans, val);       //  repeated-character share is update_members' either way)
+            key_hi = max(key_hi, (unsigned)(uk >> 32));
+            my_new++;
+          }
         }
         *slot = uk;
       }
@@ -1073,7 +1097,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
       for (int t2 = tid; t2 < nnew * V; t2 += kThreads) {
         const int r = div_v(t2), c = t2 - r * V, j2 = newlist[r];
         if (c == blank || c == p.space_id) continue;
-        lmcB[j2 * V + c] = lm_query<LMK == 2>(p, lt, Bm.lm[j2], Bm.last[j2], c);
+        lmcB[j2 * V + c] = lm_query<lmk_fast(LMK), RS>(p, lt, Bm.lm[j2], Bm.last[j2], c);
       }
       lds_barrier();
       BPROF(14);
@@ -1138,7 +1162,7 @@ __device__ __forceinline__ void gsync() { __threadfence_block(); __syncthreads()
 
 template <typename IO, int LMK>
 __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p, GenParams g) {
-  constexpr bool LM = LMK != 0;
+  constexpr bool LM = LMK != 0, RS = lmk_restricted(LMK);
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int V = p.V, W = p.W, blank = p.blank;
@@ -1183,7 +1207,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
   }
   gsync();
   if (tid == 0) slot_map(0).insert(0, 0);
-  if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<LMK == 2>(p, lt, M0.lm[0], -1, c);
+  if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
   gsync();
   int n = 1, cur = 0;
   // q / n for the candidate numbers of a step (q < n * V, q * n < 2^32) by one multiplication: ceil(2^32 / n), worked out when
@@ -1303,9 +1327,13 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
         if (j >= 0) A.inc[j] = val;            // the child is a beam member: its share from this parent
         // else: alive but pruned (Q7) -- the probability is lost and the slot stays taken
       } else {
-        uk = child_key<LM>(p, score_fields<LM>(A.lm[ii]), last, ci, answer_at<LM>(lmcA, (size_t)ii * V + ci), val);
-        key_hi = max(key_hi, (unsigned)(uk >> 32));
-        my_new++;
+        const LmFields pr = score_fields<LM>(A.lm[ii]);
+        const LmAnswer ans = answer_at<LM>(lmcA, (size_t)ii * V + ci);
+        if (!RS || !lexicon_forbids(p, pr, last, ci, ans)) {
+          uk = child_key<LM>(p, pr, last, ci, ans, val);
+          key_hi = max(key_hi, (unsigned)(uk >> 32));
+          my_new++;
+        }
       }
       *slot = uk;
     }
@@ -1432,7 +1460,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
         const int j2 = (int)(e / V), c = (int)(e - (size_t)j2 * V);
         const int f = Bm.from[j2];
         if (f >= 0) lmcB[e] = lmcA[(size_t)f * V + c];
-        else if (c != blank && c != p.space_id) lmcB[e] = lm_query<LMK == 2>(p, lt, Bm.lm[j2], Bm.last[j2], c);
+        else if (c != blank && c != p.space_id) lmcB[e] = lm_query<lmk_fast(LMK), RS>(p, lt, Bm.lm[j2], Bm.last[j2], c);
       }
     }
     gsync();
@@ -1546,7 +1574,7 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
                      const int64_t* x_len, int B, int T, int V, int blank,
                      int beam_width, int space_id, const e2e_lm* lm,
                      double lmwt, double wip, double oov_penalty,
-                     int64_t* out, int64_t max_out, int64_t* out_len, const NBestOut* nb,
+                     int64_t* out, int64_t max_out, int64_t* out_len, const NBestOut* nb, bool restricted,
                      void* workspace, size_t workspace_bytes, void* stream) {
   if (dtype != E2E_F32 && dtype != E2E_F64 && !dtype_is_16bit(dtype)) { set_error("dtype must be E2E_F32, E2E_F64, E2E_F16 or E2E_BF16"); return E2E_ERR_ARG; }
   if (B < 0 || T < 1 || V < 1 || beam_width < 1 || max_out < 1) { set_error("bad sizes"); return E2E_ERR_ARG; }
@@ -1600,6 +1628,7 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
   p.node_t = nb && nb->timesteps ? reinterpret_cast<int*>(ws + frames_at) : nullptr;
   hipStream_t s = (hipStream_t)stream;
   const bool fast_lm = lm && lm->d_ngs && lm->order - 1 <= kParCtx;
+  const bool rs = lm && restricted;
   if (general) {
     GenParams g;
     g.gkey = reinterpret_cast<unsigned long long*>(ws + l.total + gl.gkey);
@@ -1607,7 +1636,8 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
     g.gmem = gl.members_in_ws ? reinterpret_cast<unsigned char*>(ws + l.total + gl.gmem) : nullptr;
     g.CH = gl.CH;
     // (16-bit log-probabilities are read as they are -- every one of them is an f32 number, so the search is the f32 one's, bit for bit)
-#define E2E_GEN_OF(IO) (!lm ? (const void*)&ctc_beam_general_kernel<IO, 0> : fast_lm ? (const void*)&ctc_beam_general_kernel<IO, 2> : (const void*)&ctc_beam_general_kernel<IO, 1>)
+#define E2E_GEN_OF(IO) (!lm ? (const void*)&ctc_beam_general_kernel<IO, 0> : fast_lm ? (rs ? (const void*)&ctc_beam_general_kernel<IO, 4> : (const void*)&ctc_beam_general_kernel<IO, 2>) \
+                            : (rs ? (const void*)&ctc_beam_general_kernel<IO, 3> : (const void*)&ctc_beam_general_kernel<IO, 1>))
     const void* gfn = dtype == E2E_F32 ? E2E_GEN_OF(float) : dtype == E2E_F64 ? E2E_GEN_OF(double) : dtype == E2E_F16 ? E2E_GEN_OF(f16_t) : E2E_GEN_OF(bf16_t);
 #undef E2E_GEN_OF
     E2E_HIP_CHECK(allow_dynamic_lds(gfn, (int)gl.lds), "hipFuncSetAttribute");
@@ -1616,7 +1646,8 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
     E2E_HIP_CHECK(hipGetLastError(), "ctc_beam_general_kernel launch");
     return E2E_OK;
   }
-#define E2E_BEAM_OF(IO) (!lm ? (const void*)&ctc_beam_kernel<IO, 0> : fast_lm ? (const void*)&ctc_beam_kernel<IO, 2> : (const void*)&ctc_beam_kernel<IO, 1>)
+#define E2E_BEAM_OF(IO) (!lm ? (const void*)&ctc_beam_kernel<IO, 0> : fast_lm ? (rs ? (const void*)&ctc_beam_kernel<IO, 4> : (const void*)&ctc_beam_kernel<IO, 2>) \
+                             : (rs ? (const void*)&ctc_beam_kernel<IO, 3> : (const void*)&ctc_beam_kernel<IO, 1>))
   const void* fn = dtype == E2E_F32 ? E2E_BEAM_OF(float) : dtype == E2E_F64 ? E2E_BEAM_OF(double) : dtype == E2E_F16 ? E2E_BEAM_OF(f16_t) : E2E_BEAM_OF(bf16_t);
 #undef E2E_BEAM_OF
   E2E_HIP_CHECK(allow_dynamic_lds(fn, (int)l.lds), "hipFuncSetAttribute");
@@ -1633,16 +1664,16 @@ extern "C" int e2e_ctc_beam(const void* lp, int dtype, int64_t sB, int64_t sT, i
                             int64_t* out, int64_t max_out, int64_t* out_len,
                             void* workspace, size_t workspace_bytes, void* stream) {
   return beam_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
-                   out, max_out, out_len, nullptr, workspace, workspace_bytes, stream);
+                   out, max_out, out_len, nullptr, false, workspace, workspace_bytes, stream);
 }
 
-extern "C" int e2e_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
-                                  const int64_t* x_len, int B, int T, int V, int blank,
-                                  int beam_width, int space_id, const e2e_lm* lm,
-                                  double lmwt, double wip, double oov_penalty,
-                                  int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
-                                  double* scores, int32_t* counts, int64_t* timesteps,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
+static int nbest_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                      const int64_t* x_len, int B, int T, int V, int blank,
+                      int beam_width, int space_id, const e2e_lm* lm,
+                      double lmwt, double wip, double oov_penalty,
+                      int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                      double* scores, int32_t* counts, int64_t* timesteps, bool restricted,
+                      void* workspace, size_t workspace_bytes, void* stream) {
   if (beam_width < 1 || nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
   if (B > 0 && (!n_hyp || !scores || !counts || !out || !out_len)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
   if (V >= 1 && beam_width > e2e_ctc_beam_max_width(V, lm != nullptr)) {
@@ -1652,7 +1683,34 @@ extern "C" int e2e_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t
   }
   const NBestOut nb = { nbest, n_hyp, scores, counts, timesteps };
   return beam_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
-                   out, max_out, out_len, &nb, workspace, workspace_bytes, stream);
+                   out, max_out, out_len, &nb, restricted, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2e_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                                  const int64_t* x_len, int B, int T, int V, int blank,
+                                  int beam_width, int space_id, const e2e_lm* lm,
+                                  double lmwt, double wip, double oov_penalty,
+                                  int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                                  double* scores, int32_t* counts, int64_t* timesteps,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return nbest_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
+                    nbest, out, max_out, out_len, n_hyp, scores, counts, timesteps, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2e_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                                      const int64_t* x_len, int B, int T, int V, int blank,
+                                      int beam_width, int space_id, const e2e_lm* lm,
+                                      double lmwt, double wip, double oov_penalty,
+                                      int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                                      double* scores, int32_t* counts, int64_t* timesteps,
+                                      void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts) {
+  const bool restricted = opts && opts->restrict_to_lexicon != 0;
+  if (restricted && (!lm || !lm->has_lexicon)) {
+    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+    return E2E_ERR_ARG;
+  }
+  return nbest_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
+                    nbest, out, max_out, out_len, n_hyp, scores, counts, timesteps, restricted, workspace, workspace_bytes, stream);
 }
 
 #ifdef E2E_BEAM_PROFILE

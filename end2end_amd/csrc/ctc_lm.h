@@ -74,6 +74,18 @@ __host__ __device__ inline uint32_t lm_word_lookup(const LmView& lm, uint64_t h)
   }
 }
 
+// ... and whether the spelling is in the table at all.  A model with a lexicon (e2e_lm_enable_lexicon) also lists every proper
+// prefix of a word that is no word itself, with id 0: to an unrestricted lookup such an entry is the miss it always was, to a
+// search restricted to the lexicon it says "this spelling may go on".
+__host__ __device__ inline bool lm_word_find(const LmView& lm, uint64_t h, uint32_t& id) {
+  if (h == 0) h = 1;
+  for (uint32_t i = (uint32_t)h & lm.vmask;; i = (i + 1) & lm.vmask) {
+    const uint64_t k = lm.vkeys[i];
+    if (k == h) { id = lm.vvals[i]; return true; }
+    if (k == 0) { id = 0; return false; }
+  }
+}
+
 __host__ __device__ inline const NgSlot* lm_ngram_find(const LmView& lm, const uint32_t* ids, int n) {
   for (uint32_t i = (uint32_t)ngram_hash(ids, n) & lm.ngmask;; i = (i + 1) & lm.ngmask) {
     const NgSlot* s = &lm.ng[i];
@@ -134,6 +146,10 @@ struct e2e_lm {
   e2e::NgSig* d_ngs = nullptr; e2e::VEntry* d_vt = nullptr;     // (d_ngs stays null if two n-grams share a hash)
   e2e::UniEntry* d_uni = nullptr; uint32_t nwords = 0;
   float unk_prob = -100.f;
+  // the lexicon (e2e_lm_enable_lexicon): folded spelling -> bit 0 a word, bit 1 a proper prefix of a longer word.  Once it is
+  // built, the vocabulary tables above also hold the prefixes that are no words, with id 0.
+  bool has_lexicon = false;
+  std::unordered_map<std::string, unsigned char> lex_class;
   int device = -1;                                       // HIP device that holds the tables (-1: host only)
   e2e::LmView host_view() const {
     return {order, vkeys.data(), vvals.data(), (uint32_t)vkeys.size() - 1, ng.data(), (uint32_t)ng.size() - 1, bos,

@@ -31,10 +31,40 @@ std::string lower(const std::string& s) {
   return r;
 }
 
+struct Entry { uint32_t ids[kLmMaxOrder]; int n; float prob, bo; };
+
+// cuckoo insertion into the kernel's two-choice vocabulary table: a free slot of the item's two, else evict the occupant of
+// one and move that on
+bool cuckoo_insert(std::vector<VEntry>& vt, VEntry item) {
+  const uint32_t mask = (uint32_t)vt.size() - 1;
+  uint32_t i1, i2;
+  two_slots(item.key, mask, i1, i2);
+  if (vt[i1].key == 0) { vt[i1] = item; return true; }
+  if (vt[i2].key == 0) { vt[i2] = item; return true; }
+  uint32_t pos = i1;
+  for (int kick = 0; kick < 2000; kick++) {
+    std::swap(item, vt[pos]);
+    if (item.key == 0) return true;
+    two_slots(item.key, mask, i1, i2);
+    pos = pos == i1 ? i2 : i1;
+  }
+  return false;
+}
+
+bool upload(void** d, const void* h, size_t bytes) {
+  if (hipMalloc(d, bytes) != hipSuccess) return false;
+  return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+bool is_special(const std::string& w) { return w == "<unk>" || w == "<s>" || w == "</s>"; }
+
 }  // namespace
 }  // namespace e2e
 
 using namespace e2e;
+
+static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::vector<Entry>& entries,
+                        const char* const* labels, int V);
 
 extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int V, int case_sensitive, e2e_lm** out) {
   if (out) *out = nullptr;
@@ -65,7 +95,6 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
     return id;
   };
   intern("<unk>");
-  struct Entry { uint32_t ids[kLmMaxOrder]; int n; float prob, bo; };
   std::vector<Entry> entries;
   std::vector<char> buf(1 << 16);
   int section = 0; bool saw_data = false;
@@ -96,6 +125,15 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
   gzclose(f);
   if (!saw_data || lm->order == 0) { delete lm; set_error("%s: not an ARPA file (no \\data\\ / n-gram sections)", path); return E2E_ERR_IO; }
   if (lm->order > kLmMaxOrder) { delete lm; set_error("%s: order %d > %d", path, lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
+  build_model(lm, words, entries, labels, V);
+  *out = lm;
+  return E2E_OK;
+}
+
+// The tables of a model whose words (id -> word, lm->exact filled) and n-grams have been read: the id-keyed host tables, the
+// kernel's forms of them, their self-check and their upload to the current device.
+static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::vector<Entry>& entries,
+                        const char* const* labels, int V) {
   {  // <unk> absent from the file: KenLM's default unknown_missing_logprob = -100
     bool has_unk = false;
     for (const auto& e : entries) if (e.n == 1 && e.ids[0] == 0) { has_unk = true; break; }
@@ -133,11 +171,7 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
     lm->label_off.push_back((int)lm->label_bytes.size());
   }
   if (lm->label_bytes.empty()) lm->label_bytes.push_back(0);
-  // upload
-  auto up = [](void** d, const void* h, size_t bytes) -> bool {
-    if (hipMalloc(d, bytes) != hipSuccess) return false;
-    return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
+  auto up = upload;
   // the kernel's 16-byte forms of the two tables (same slots)
   std::vector<NgSig> ngs(lm->ng.size(), NgSig{0, 0.f, 0.f, 0, 0});
   std::vector<UniEntry> uni(words.size(), UniEntry{1.f, 0.f, 0});
@@ -181,22 +215,8 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
   std::vector<VEntry> vt(lm->vkeys.size(), VEntry{0, 0u, 1.f});
   for (size_t i = 0; i < lm->vkeys.size() && sig_ok; i++) {      // (one entry per distinct folded spelling already)
     if (lm->vkeys[i] == 0) continue;
-    // cuckoo insertion: a free slot of the item's two, else evict the occupant of one and move that on
-    VEntry item{lm->vkeys[i], lm->vvals[i], uni[lm->vvals[i]].prob};
-    const uint32_t mask = (uint32_t)vt.size() - 1;
-    uint32_t i1, i2;
-    two_slots(item.key, mask, i1, i2);
-    if (vt[i1].key == 0) { vt[i1] = item; continue; }
-    if (vt[i2].key == 0) { vt[i2] = item; continue; }
-    uint32_t pos = i1;
-    bool placed = false;
-    for (int kick = 0; kick < 2000 && !placed; kick++) {
-      std::swap(item, vt[pos]);
-      if (item.key == 0) { placed = true; break; }
-      two_slots(item.key, mask, i1, i2);
-      pos = pos == i1 ? i2 : i1;
-    }
-    if (!placed) sig_ok = false;                                  // (never seen at load <= 1/4; the id-keyed walk takes over)
+    if (!cuckoo_insert(vt, VEntry{lm->vkeys[i], lm->vvals[i], uni[lm->vvals[i]].prob}))
+      sig_ok = false;                                               // (never seen at load <= 1/4; the id-keyed walk takes over)
   }
   // Self-check of what the kernel will read, against the id tables it stands for: every spelling is found in one of its two
   // vocabulary slots with the right id and unigram; every listed n-gram is found by its signature with the right numbers and
@@ -247,8 +267,6 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
   } else if (hipGetDevice(&lm->device) != hipSuccess) {
     lm->device = -1;
   }
-  *out = lm;
-  return E2E_OK;
 }
 
 extern "C" void e2e_lm_free(e2e_lm* lm) {
@@ -271,4 +289,154 @@ extern "C" uint32_t e2e_lm_word_index(const e2e_lm* lm, const char* word) {
 extern "C" double e2e_lm_score(const e2e_lm* lm, const uint32_t* ctx, int ctx_len, uint32_t word) {
   if (!lm || ctx_len < 0 || ctx_len > kCtx || (ctx_len > 0 && !ctx)) return 0.0;
   return (double)lm_base_score(lm->host_view(), ctx, ctx_len, word, nullptr, nullptr);
+}
+
+// A model that scores nothing, from a word list: order 1, every word and <unk> at log10 p = 0.  It exists so that a search can
+// be restricted to a lexicon without a language model (e2e_lm_enable_lexicon): with the restriction off, lmwt anything and
+// oov_penalty = 0, its search is the search without a model.
+extern "C" int e2e_lm_load_words(const char* const* words_in, int n_words, const char* const* labels, int V, int case_sensitive,
+                                 e2e_lm** out) {
+  if (out) *out = nullptr;
+  if (!out || n_words < 0 || (n_words > 0 && !words_in) || V < 0 || (V > 0 && !labels)) { set_error("e2e_lm_load_words: bad argument"); return E2E_ERR_ARG; }
+  for (int i = 0; i < n_words; i++) {
+    const char* w = words_in[i];
+    if (!w || !*w || strpbrk(w, " \t\r\n")) { set_error("e2e_lm_load_words: entry %d is empty or holds white space", i); return E2E_ERR_ARG; }
+  }
+  e2e_lm* lm = new e2e_lm();
+  lm->fold_case = case_sensitive ? 0 : 1;
+  lm->order = 1;
+  std::vector<std::string> words;
+  std::vector<Entry> entries;
+  auto add = [&](const std::string& w) {
+    if (!lm->exact.emplace(w, (uint32_t)words.size()).second) return;        // (listed twice: once)
+    Entry e; e.n = 1; e.ids[0] = (uint32_t)words.size(); e.prob = 0.f; e.bo = 0.f;
+    words.push_back(w); entries.push_back(e);
+  };
+  add("<unk>"); add("<s>"); add("</s>");
+  for (int i = 0; i < n_words; i++) add(words_in[i]);
+  build_model(lm, words, entries, labels, V);
+  *out = lm;
+  return E2E_OK;
+}
+
+extern "C" int e2e_lm_has_lexicon(const e2e_lm* lm) { return lm && lm->has_lexicon ? 1 : 0; }
+
+// bit 0: the spelling is a word of the lexicon; bit 1: it is a proper prefix of a longer word.  0 without a lexicon.
+extern "C" int e2e_lm_spelling_class(const e2e_lm* lm, const char* spelling) {
+  if (!lm || !spelling || !lm->has_lexicon) return 0;
+  auto it = lm->lex_class.find(lm->fold_case ? lower(spelling) : std::string(spelling));
+  return it == lm->lex_class.end() ? 0 : it->second;
+}
+
+// The lexicon of a model: its words (the unigrams but <unk>, <s>, </s>) as the LM lookup spells them, and their prefixes.  The
+// prefixes that are no words enter the vocabulary tables -- the id table and the kernel's two-choice table -- with id 0 and
+// <unk>'s unigram: every lookup that is not restricted reads them as the miss they were, and the one probe a restricted search
+// makes for a word's id also tells it whether the spelling may go on.  Allocates and synchronises, like the loader.
+extern "C" int e2e_lm_enable_lexicon(e2e_lm* lm) {
+  if (!lm) { set_error("e2e_lm_enable_lexicon: no model"); return E2E_ERR_ARG; }
+  if (lm->has_lexicon) return E2E_OK;
+  const LmView hv = lm->host_view();
+  std::unordered_map<std::string, unsigned char> cls;
+  std::vector<std::string> prefixes;                       // proper prefixes that are no words
+  for (const auto& kv : lm->exact) {
+    if (is_special(kv.first)) continue;
+    cls[lm->fold_case ? lower(kv.first) : kv.first] |= 1;
+  }
+  {
+    std::vector<std::string> ws;
+    for (const auto& kv : cls) ws.push_back(kv.first);
+    for (const auto& w : ws)
+      for (size_t n = 1; n < w.size(); n++) {
+        unsigned char& c = cls[w.substr(0, n)];
+        if (c == 0) prefixes.push_back(w.substr(0, n));
+        c |= 2;
+      }
+  }
+  // <unk>, <s> and </s> stay in the tables (an unrestricted search may spell and find them) but are no words of the lexicon.
+  // The tables cannot say so, so a model whose labels can spell one of them inside the lexicon is refused: some chain of
+  // labels spells it with every label boundary on the way at an allowed spelling.
+  const int V = (int)lm->label_off.size() - 1;
+  auto label = [&](int c) {
+    std::string s((const char*)lm->label_bytes.data() + lm->label_off[c], (size_t)(lm->label_off[c + 1] - lm->label_off[c]));
+    return lm->fold_case ? lower(s) : s;
+  };
+  for (const char* sp : {"<unk>", "<s>", "</s>"}) {
+    const std::string s = sp;
+    if (!lm->exact.count(s) && !(lm->fold_case && lm_word_lookup(hv, word_hash(s)))) continue;
+    std::vector<char> reach(s.size() + 1, 0);
+    reach[0] = 1;
+    for (size_t o = 0; o < s.size(); o++) {
+      if (!reach[o] || (o > 0 && !cls.count(s.substr(0, o)))) continue;
+      for (int c = 0; c < V; c++) {
+        const std::string l = label(c);
+        if (!l.empty() && s.compare(o, l.size(), l) == 0 && o + l.size() <= s.size()) reach[o + l.size()] = 1;
+      }
+    }
+    if (reach[s.size()]) {
+      set_error("e2e_lm_enable_lexicon: the labels can spell %s, which the tables could not tell from a word", sp);
+      return E2E_ERR_UNSUPPORTED;
+    }
+  }
+  // the id table again, with room for the prefixes; then the kernel's table of the same size (they share vmask)
+  std::vector<uint64_t> vkeys; std::vector<uint32_t> vvals; std::vector<VEntry> vt;
+  const bool want_vt = lm->d_ngs != nullptr || lm->device < 0;
+  size_t old_n = 0;
+  for (uint64_t k : lm->vkeys) old_n += k != 0;
+  bool built = false;
+  for (size_t size = pow2_at_least((old_n + prefixes.size()) * 4 + 16), tries = 0; tries < 4 && !built; size *= 2, tries++) {
+    if (size < lm->vkeys.size()) size = lm->vkeys.size();
+    vkeys.assign(size, 0); vvals.assign(size, 0);
+    const uint32_t vmask = (uint32_t)size - 1;
+    auto put = [&](uint64_t h, uint32_t id) {
+      for (uint32_t i = (uint32_t)h & vmask;; i = (i + 1) & vmask) {
+        if (vkeys[i] == h) return;                         // (a word's entry stands: words go in first)
+        if (vkeys[i] == 0) { vkeys[i] = h; vvals[i] = id; return; }
+      }
+    };
+    for (size_t i = 0; i < lm->vkeys.size(); i++) if (lm->vkeys[i]) put(lm->vkeys[i], lm->vvals[i]);
+    for (const auto& s : prefixes) put(word_hash(s), 0u);
+    built = true;
+    if (!want_vt) break;
+    vt.assign(size, VEntry{0, 0u, 1.f});
+    for (size_t i = 0; i < size && built; i++) {
+      if (vkeys[i] == 0) continue;
+      const NgSlot* u = lm_ngram_find(hv, &vvals[i], 1);
+      built = cuckoo_insert(vt, VEntry{vkeys[i], vvals[i], u ? u->prob : 1.f});
+    }
+    for (size_t i = 0; i < size && built; i++) {           // self-check, as the loader's
+      if (vkeys[i] == 0) continue;
+      uint32_t i1, i2;
+      two_slots(vkeys[i], vmask, i1, i2);
+      const VEntry* e = vt[i1].key == vkeys[i] ? &vt[i1] : vt[i2].key == vkeys[i] ? &vt[i2] : nullptr;
+      built = e && e->val == vvals[i];
+    }
+  }
+  if (!built) { set_error("e2e_lm_enable_lexicon: the two-choice vocabulary table could not be built"); return E2E_ERR_UNSUPPORTED; }
+  if (getenv("E2E_LM_DEBUG"))
+    fprintf(stderr, "e2e_lm lexicon: %zu spellings, %zu of them prefixes only; vocabulary tables %zu -> %zu bytes\n", cls.size(),
+            prefixes.size(), lm->vkeys.size() * (12 + sizeof(VEntry)), vkeys.size() * (12 + sizeof(VEntry)));
+  if (lm->device >= 0) {
+    int cur = -1;
+    E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
+    E2E_HIP_CHECK(hipSetDevice(lm->device), "hipSetDevice");
+    uint64_t* dk = nullptr; uint32_t* dv = nullptr; VEntry* dt = nullptr;
+    const bool ok = upload((void**)&dk, vkeys.data(), vkeys.size() * sizeof(uint64_t)) &&
+                    upload((void**)&dv, vvals.data(), vvals.size() * sizeof(uint32_t)) &&
+                    upload((void**)&dt, vt.data(), vt.size() * sizeof(VEntry)) &&
+                    hipDeviceSynchronize() == hipSuccess;       // (nothing in flight reads the tables that are freed below)
+    if (!ok) {
+      (void)hipGetLastError();
+      (void)hipFree(dk); (void)hipFree(dv); (void)hipFree(dt);
+      (void)hipSetDevice(cur);
+      set_error("e2e_lm_enable_lexicon: the tables could not be uploaded");
+      return E2E_ERR_HIP;
+    }
+    (void)hipFree(lm->d_vkeys); (void)hipFree(lm->d_vvals); (void)hipFree(lm->d_vt);
+    lm->d_vkeys = dk; lm->d_vvals = dv; lm->d_vt = dt;
+    (void)hipSetDevice(cur);
+  }
+  lm->vkeys.swap(vkeys); lm->vvals.swap(vvals);
+  lm->lex_class.swap(cls);
+  lm->has_lexicon = true;
+  return E2E_OK;
 }

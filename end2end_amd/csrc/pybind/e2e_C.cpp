@@ -38,6 +38,14 @@ class LanguageModel {
     for (const auto& s : labels) c.push_back(s.c_str());
     check(e2e_lm_load_arpa(path.c_str(), c.data(), (int)c.size(), case_sensitive ? 1 : 0, &lm_));
   }
+  // the model that scores nothing, from a word list (e2e_lm_load_words)
+  struct FromWords {};
+  LanguageModel(FromWords, const std::vector<std::string>& words, const std::vector<std::string>& labels, bool case_sensitive) {
+    std::vector<const char*> w, c;
+    for (const auto& s : words) w.push_back(s.c_str());
+    for (const auto& s : labels) c.push_back(s.c_str());
+    check(e2e_lm_load_words(w.data(), (int)w.size(), c.data(), (int)c.size(), case_sensitive ? 1 : 0, &lm_));
+  }
   ~LanguageModel() { e2e_lm_free(lm_); }
   LanguageModel(const LanguageModel&) = delete;
   LanguageModel& operator=(const LanguageModel&) = delete;
@@ -46,6 +54,9 @@ class LanguageModel {
   int order() const { return e2e_lm_order(lm_); }
   int device() const { return e2e_lm_device(lm_); }
   uint32_t word_index(const std::string& w) const { return e2e_lm_word_index(lm_, w.c_str()); }
+  void enable_lexicon() { check(e2e_lm_enable_lexicon(lm_)); }
+  bool has_lexicon() const { return e2e_lm_has_lexicon(lm_) != 0; }
+  int spelling_class(const std::string& s) const { return e2e_lm_spelling_class(lm_, s.c_str()); }
   double score(const std::vector<uint32_t>& ctx, uint32_t word) const {
     return e2e_lm_score(lm_, ctx.data(), (int)ctx.size(), word);
   }
@@ -207,18 +218,19 @@ PYBIND11_MODULE(_C, m) {
         [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
            int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, int nbest,
            uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts,
-           uintptr_t timesteps, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_ctc_beam_nbest(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
-                                   beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, nbest,
-                                   ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
-                                   ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(timesteps),
-                                   ptr<void>(workspace), workspace_bytes, ptr<void>(stream)));
+           uintptr_t timesteps, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon) {
+          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
+          check(e2e_ctc_beam_nbest_opt(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
+                                       beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, nbest,
+                                       ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
+                                       ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(timesteps),
+                                       ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
         },
         py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
         py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
         py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
         py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
-        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
+        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon") = false);
 
   m.def("ctc_align_workspace_bytes",
         [](int B, int T, int V, int Smax, bool is_ctc) { return e2e_ctc_align_workspace_bytes(B, T, V, Smax, is_ctc ? 1 : 0); });
@@ -240,7 +252,15 @@ PYBIND11_MODULE(_C, m) {
   py::class_<LanguageModel>(m, "LanguageModel")
       .def(py::init<const std::string&, const std::vector<std::string>&, bool>(), py::arg("path"), py::arg("labels"),
            py::arg("case_sensitive"))
+      .def_static("from_words",
+                  [](const std::vector<std::string>& words, const std::vector<std::string>& labels, bool case_sensitive) {
+                    return new LanguageModel(LanguageModel::FromWords{}, words, labels, case_sensitive);
+                  },
+                  py::arg("words"), py::arg("labels"), py::arg("case_sensitive"), py::return_value_policy::take_ownership)
       .def_property_readonly("handle", &LanguageModel::handle)
+      .def("enable_lexicon", &LanguageModel::enable_lexicon)
+      .def("has_lexicon", &LanguageModel::has_lexicon)
+      .def("spelling_class", &LanguageModel::spelling_class, py::arg("spelling"))
       .def("order", &LanguageModel::order)
       .def("device", &LanguageModel::device)
       .def("word_index", &LanguageModel::word_index, py::arg("word"))

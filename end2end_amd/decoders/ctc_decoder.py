@@ -24,6 +24,23 @@ NBestResults = namedtuple("NBestResults", ["decoded_targets", "decoded_targets_l
                                            "timesteps"])
 
 
+def read_lexicon(lexicon):
+    """The words of a lexicon, in order and once each: from an iterable of entries, or from the text file at a path with
+    one entry per line.  Of every entry the first white-space separated token counts; empty lines are skipped."""
+    if isinstance(lexicon, (str, bytes, os.PathLike)):
+        path = os.fsdecode(lexicon)
+        if not os.path.isfile(path):
+            raise CTCDecoderError("Can't find a lexicon: {}".format(path))
+        with open(path, encoding="utf-8") as f:
+            entries = f.read().splitlines()
+    else:
+        entries = [str(e) for e in lexicon]
+    words = list(dict.fromkeys(e.split()[0] for e in entries if e.split()))
+    if not words:
+        raise CTCDecoderError("the lexicon is empty")
+    return words
+
+
 class CTCDecoder:
     """
     :param beam_width: number of hypotheses kept; ``1`` means greedy (argmax) decoding
@@ -37,10 +54,16 @@ class CTCDecoder:
     :param oov_penalty: penalty per out-of-vocabulary word
     :param case_sensitive: look words up in the language model with their case
     :param keep_on_device: (extension) leave the decoded ids and lengths on the GPU
+    :param restrict_to_vocabulary: (extension) with ``lm_path``: the beam search only forms words of the language
+        model's vocabulary (the last word of a result may still be an unfinished prefix of one)
+    :param lexicon: (extension) restrict the beam search to these words without a language model: an iterable of words,
+        or the path of a text file with one entry per line whose first white-space separated token is the word (so a
+        pronunciation dictionary works).  ``lmwt`` and ``oov_penalty`` then count as 0; ``wip`` applies.
     """
 
     def __init__(self, beam_width=100, after_logsoftmax=False, blank_idx=0, time_major=False, labels=None,
-                 lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True, keep_on_device=False):
+                 lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True, keep_on_device=False,
+                 restrict_to_vocabulary=False, lexicon=None):
         self._beam_width = beam_width
         self._blank_idx = blank_idx
         self._after_logsoftmax = after_logsoftmax
@@ -51,10 +74,14 @@ class CTCDecoder:
         self._oov_penalty = oov_penalty
         self._time_major = time_major
         self._case_sensitive = case_sensitive
+        self._restrict = bool(restrict_to_vocabulary) or lexicon is not None
+        self._lexicon = lexicon
         self._check_params()
         self._decoder = CTCDecoderEngine(self._blank_idx, self._beam_width, self._labels, self._lm_path,
                                          self._lmwt, self._wip, self._oov_penalty, self._case_sensitive,
                                          keep_on_device=keep_on_device)
+        if self._restrict:
+            self._decoder.configure(restrict_to_vocabulary=True, lexicon=self._lexicon)
 
     def _check_params(self):
         if self._lm_path:
@@ -63,6 +90,16 @@ class CTCDecoder:
             # decode() then fails because the alphabet cannot spell words)
             if not os.path.isfile(self._lm_path):
                 raise CTCDecoderError("Can't find a model: {}".format(self._lm_path))
+        if self._restrict:
+            if self._lexicon is not None and self._lm_path:
+                raise CTCDecoderError("lexicon together with lm_path is not supported: restrict_to_vocabulary=True "
+                                      "uses the language model's own vocabulary")
+            if self._lexicon is None and not self._lm_path:
+                raise CTCDecoderError("restrict_to_vocabulary needs a vocabulary: lm_path or lexicon")
+            if self._beam_width == 1:
+                raise CTCDecoderError("a restricted search needs beam_width > 1: greedy decoding has no vocabulary")
+            if self._lexicon is not None:
+                self._lexicon = read_lexicon(self._lexicon)
 
     def _batch_major(self, logits, logits_lengths):
         if self._time_major:

@@ -330,17 +330,40 @@ class GramCTCLossEngine(_LatticeLossEngine):
 class LanguageModel:
     """n-gram model read from an ARPA file (plain or .gz); stands where KenLM stands upstream
     (ctc_decoder.cpp:60-71).  The device tables belong to one GPU: `on(device)` returns the copy for that device,
-    loading it on first use."""
+    loading it on first use.  With `words` (and no path) it is the model that scores nothing, built from a word list
+    (e2e_lm_load_words).  `lexicon=True`, or `enable_lexicon()` later, gives every copy the lexicon a search can be
+    restricted to; unrestricted decoders may go on sharing the model."""
 
-    def __init__(self, path, labels, case_sensitive):
+    def __init__(self, path, labels, case_sensitive, words=None, lexicon=False):
         self.path, self.labels, self.case_sensitive = path, list(labels), bool(case_sensitive)
+        self.words = None if words is None else list(words)
+        self._lexicon = bool(lexicon)
         self._per_device = {}
         self._first = self._load()
 
     def _load(self):
-        lm = _C.LanguageModel(self.path, self.labels, self.case_sensitive)
+        if self.words is not None:
+            lm = _C.LanguageModel.from_words(self.words, self.labels, self.case_sensitive)
+        else:
+            lm = _C.LanguageModel(self.path, self.labels, self.case_sensitive)
+        if self._lexicon:
+            lm.enable_lexicon()
         self._per_device[lm.device()] = lm
         return lm
+
+    def enable_lexicon(self):
+        """Build the lexicon on every copy loaded so far; copies loaded later carry it too.  Not while a decode that uses the
+        model is in flight (the tables are replaced)."""
+        for lm in self._per_device.values():
+            lm.enable_lexicon()
+        self._lexicon = True
+
+    def has_lexicon(self):
+        return self._first.has_lexicon()
+
+    def spelling_class(self, spelling):
+        """bit 0: a word of the lexicon; bit 1: a proper prefix of a longer word (0 without a lexicon)."""
+        return self._first.spelling_class(spelling)
 
     def on(self, device):
         lm = self._per_device.get(device.index)
@@ -363,14 +386,15 @@ class LanguageModel:
 
 class CTCDecoderEngine:
     """Same constructor arguments and defaults as the pybind class
-    (src/decoders/ctc_decoder_py.cpp:8-24); methods keep the reference's keyword names."""
+    (src/decoders/ctc_decoder_py.cpp:8-24); methods keep the reference's keyword names.  The constructor is the reference's;
+    what goes beyond it is set with `configure()` before the first decode."""
 
     def __init__(self, blank_idx, beam_width_=100, labels=None, lm_path="", lmwt_=1.0, wip_=0.0,
                  oov_penalty_=-1000.0, case_sensitive=False, keep_on_device=False):
         self.blank_idx = int(blank_idx)
         self.beam_width = int(beam_width_)
         self.labels = list(labels or [])
-        self.lmwt = float(lmwt_)
+        self.lmwt = self._lmwt_given = float(lmwt_)
         self.wip = float(wip_)
         self.oov_penalty = float(oov_penalty_)
         self.case_sensitive = bool(case_sensitive)
@@ -381,18 +405,54 @@ class CTCDecoderEngine:
         self._codes = (np.array([ord(c) for c in self.labels], dtype="<u4")
                        if self.labels and all(len(c) == 1 and not 0xD800 <= ord(c) <= 0xDFFF for c in self.labels) else None)
         self.lm = None
-        if self.labels and self.beam_width > 1:
-            # the beam lives in one workgroup's LDS: a width / alphabet it cannot hold is reported now, not at the first
-            # decode (upstream has no such limit, ctc_decoder.cpp:353-441; see include/e2e_ctc.h)
-            cap = _C.ctc_beam_max_width(len(self.labels), bool(lm_path))
-            if self.beam_width > cap:
-                raise ValueError("beam_width %d is not supported for an alphabet of %d labels%s: at most %d"
-                                 % (self.beam_width, len(self.labels), " with a language model" if lm_path else "", cap))
+        self.restrict = False
+        self._check_width(bool(lm_path))
         if lm_path:
             R.require_gpu()
             self.lm = LanguageModel(lm_path, self.labels, self.case_sensitive)
         else:
             self.lmwt = 0.0   # ctc_decoder.cpp:72-74
+
+    def _check_width(self, with_lm):
+        if self.labels and self.beam_width > 1:
+            # the beam lives in one workgroup's LDS: a width / alphabet it cannot hold is reported now, not at the first
+            # decode (upstream has no such limit, ctc_decoder.cpp:353-441; see include/e2e_ctc.h)
+            cap = _C.ctc_beam_max_width(len(self.labels), with_lm)
+            if self.beam_width > cap:
+                raise ValueError("beam_width %d is not supported for an alphabet of %d labels%s: at most %d"
+                                 % (self.beam_width, len(self.labels), " with a language model" if with_lm else "", cap))
+
+    def configure(self, restrict_to_vocabulary=False, lexicon=None, lm=None):
+        """Extensions, set once before decoding; returns self.
+        `restrict_to_vocabulary`: the beam search only forms words of the language model's vocabulary.
+        `lexicon`: an iterable of words; the search is restricted to them without a language model -- a model that scores
+        nothing is built from the list, `lmwt` and `oov_penalty` then count as 0 (as `lmwt` does upstream without a model),
+        `wip` applies, and the width limit is the one with a language model.
+        `lm`: a LanguageModel loaded already, for a decoder constructed without `lm_path`: decoders, restricted or not, may
+        share one instead of loading the file each."""
+        restrict = bool(restrict_to_vocabulary) or lexicon is not None
+        if sum(1 for m in (self.lm is not None, lexicon is not None, lm is not None) if m) > 1:
+            raise ValueError("lm_path, lexicon and lm exclude each other (a lexicon together with a language model is not supported)")
+        if restrict and self.lm is None and lexicon is None and lm is None:
+            raise ValueError("restrict_to_vocabulary needs a vocabulary: lm_path or lexicon")
+        if restrict and self.beam_width == 1:
+            raise ValueError("restrict_to_vocabulary needs beam_width > 1: greedy decoding has no vocabulary")
+        if lm is not None:
+            if lm.labels != self.labels or lm.case_sensitive != self.case_sensitive:
+                raise ValueError("the shared language model was loaded with other labels or another case_sensitive")
+            self._check_width(True)
+            self.lm = lm
+            self.lmwt = self._lmwt_given
+        elif lexicon is not None:
+            self._check_width(True)
+            R.require_gpu()
+            self.lm = LanguageModel(None, self.labels, self.case_sensitive, words=list(lexicon), lexicon=True)
+            self.lmwt = 0.0
+            self.oov_penalty = 0.0
+        if restrict and not self.lm.has_lexicon():
+            self.lm.enable_lexicon()
+        self.restrict = restrict
+        return self
 
     def _strings(self, rows, lens):
         # indices2str, ctc_decoder.cpp:203-220: "" when there are no labels.  The empty prefix wins as [-1] (quirk Q6);
@@ -453,6 +513,10 @@ class CTCDecoderEngine:
 
     def decode(self, logits_, logits_lengths_):
         """Prefix beam search on LOG-PROBABILITIES -> (indices (B,maxlen) int64, lengths (B), sentences)."""
+        if self.restrict:
+            # hypothesis 0 of the restricted n-best list (the restriction is an option of that call: e2e_ctc_beam_nbest_opt)
+            r = self.decode_nbest(logits_, logits_lengths_, nbest=1)
+            return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] for s in r[2]]
         x, xl, dev = self._prep(logits_, logits_lengths_)
         B, T, V = x.shape
         max_out = T + 1
@@ -508,7 +572,7 @@ class CTCDecoderEngine:
                                   self.lmwt, self.wip, self.oov_penalty, N,
                                   out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
                                   counts.data_ptr(), ts.data_ptr() if timesteps else 0,
-                                  ws.data_ptr(), ws.numel(), R.stream_handle(dev))
+                                  ws.data_ptr(), ws.numel(), R.stream_handle(dev), restrict_to_lexicon=self.restrict)
         nh = n_hyp.tolist()
         lens = out_len.tolist()
         # per-utterance and per-hypothesis status ride on the counts and lengths, as in decode()

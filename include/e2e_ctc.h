@@ -344,6 +344,54 @@ int e2e_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_
                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Beam search restricted to a vocabulary (additive, ABI 4: nothing above changes meaning).
+ *
+ * The lexicon L of a model is the set of its words -- the unigrams but <unk>, <s> and </s> -- spelled as the lookup of a
+ * beam's words spells them: the labels' UTF-8 bytes, A-Z folded unless the model is case sensitive.  Pref(L) is every
+ * non-empty byte prefix of a word of L, the words included.  A restricted search creates a prefix's child only if
+ *   - the character is no space and the child's last word is spelled in Pref(L), or
+ *   - the character is the space and the prefix is the root, ends in a space, or ends in a word of L.
+ * A child that is alive already is found as ever (quirk Q7 included); a pair without a child gives the child nothing and
+ * creates no candidate, while the prefix's own repeated-character share is taken as ever.  Scores, selection and tie order
+ * are the unrestricted search's.  The last word of a hypothesis may be a prefix that is no word: it counts as out of
+ * vocabulary, as it always did.
+ *
+ * e2e_lm_load_words      a model that scores nothing, from a word list (host strings without white space): order 1, every
+ *                        word and <unk> at log10 p = 0, <unk> = id 0, <s> and </s> present.  Unrestricted, with
+ *                        oov_penalty = 0, its search is the search without a model, bit for bit.  Uploads like
+ *                        e2e_lm_load_arpa.
+ * e2e_lm_enable_lexicon  builds the lexicon of a model and uploads it: the prefixes that are no words enter the vocabulary
+ *                        tables with id 0, so the probe that finds a word's id also answers "may this spelling go on?".
+ *                        Allocates and synchronises like the loader (no call may be in flight on the model); idempotent.
+ *                        Unrestricted calls compute what they computed before.  A model whose lexicon was never asked for
+ *                        keeps the tables it always had.  E2E_ERR_UNSUPPORTED if the labels can spell <unk>, <s> or </s>
+ *                        inside the lexicon (the tables hold those three, and could not tell them from words).
+ * e2e_lm_has_lexicon     1 once e2e_lm_enable_lexicon has succeeded.
+ * e2e_lm_spelling_class  host helper: bit 0 = the spelling is a word of L, bit 1 = it is a proper prefix of a longer word;
+ *                        0 for a model without a lexicon.
+ * e2e_ctc_beam_nbest_opt e2e_ctc_beam_nbest with options.  opts == NULL or restrict_to_lexicon == 0 is e2e_ctc_beam_nbest
+ *                        exactly.  restrict_to_lexicon != 0 with lm == NULL or a model without a lexicon is E2E_ERR_ARG, found
+ *                        before any launch.  Workspace, width limits and outputs are e2e_ctc_beam_nbest's.
+ */
+int e2e_lm_load_words(const char* const* words /* host */, int n_words, const char* const* labels /* host */, int V,
+                      int case_sensitive, e2e_lm** out);
+int e2e_lm_enable_lexicon(e2e_lm* lm);
+int e2e_lm_has_lexicon(const e2e_lm* lm);
+int e2e_lm_spelling_class(const e2e_lm* lm, const char* spelling /* host */);
+
+typedef struct e2e_ctc_beam_opts {
+  int restrict_to_lexicon;   /* 0: the plain search */
+} e2e_ctc_beam_opts;
+
+int e2e_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                           const int64_t* x_len, int B, int T, int V, int blank,
+                           int beam_width, int space_id, const e2e_lm* lm,
+                           double lmwt, double wip, double oov_penalty,
+                           int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                           double* scores, int32_t* counts, int64_t* timesteps,
+                           void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts);
+
+/* ------------------------------------------------------------------------
  * Viterbi forced alignment on the same lattice (max-plus instead of sum).
  * Replaces pytorch_end2end/utils/alignment.py:50-106 (_get_alignment_ctc_1d), :10-47
  * (_get_alignment_asg_1d, is_ctc = 0: no blanks) and the batch driver :109-138
