@@ -32,6 +32,10 @@
 // Two read-outs end the search: read_out() -- the best prefix's sentence, what upstream's sort + [0] keeps (e2e_ctc_beam) -- and
 // read_out_nbest() -- the first `nbest` of the ranked final beam with their scores, counts and, if asked for, the frame at which
 // each label's prefix was created (e2e_ctc_beam_nbest; no counterpart upstream).
+//
+// The search can stop after any frame and go on in a later launch (e2e_ctc_beam_stream): what a step hands to the next -- one
+// member set, the member count, the node pool and its counter -- is kept in a state row in HBM, everything else is rebuilt
+// at resume (StreamHeader, stream_open / stream_load_members / stream_suspend; the kernels' ST instances).
 #include <cstdio>
 #include <cstring>
 
@@ -83,7 +87,31 @@ struct BeamParams {
   int64_t* ts_out;                                    // (B,nbest,max_out) frames of the output ids, or null
   int* node_t;                                        // [B][NCAP] beside `nodes`: the frame at which a node was created.  Null unless
                                                       // timestamps were asked for: the step loop then stores nothing more
+  // The streaming call (e2e_ctc_beam_stream: the kernels' ST instances).  Every other call reads nothing below.  x_len is the
+  // chunk's lengths, T its width, NCAP the pool of st_max_frames frames; nodes / node_t above are not used (they live in the row).
+  unsigned char* st_rows; size_t st_row_bytes;        // (B, row_bytes): one self-contained state row per utterance (StreamHeader)
+  size_t st_nodes_off, st_ts_off;                     // the node pool and the nodes' frames inside a row (st_ts_off 0: not kept)
+  int st_max_frames;
+  int64_t* frames_done;                               // (B): frames consumed so far, or the in-band status
 };
+
+// ---- the state row of a stream: header (256 bytes), one member set, the node pool, the nodes' frames ----
+// The row holds indices only (node ids, positions in the beam, word ids), never an address: it may be moved or copied.
+// magic == 0 -- what a zeroed header has -- is a fresh utterance.  Of a member set everything that survives a step is kept
+// (probabilities, `full`, node, last character, guard, LM state; inc / kept in the state the rebuild leaves them in); what a
+// step rebuilds is not: the slot map, the child tables (from the guards) and the LM's answers, which are a function of a
+// member's LM state alone and are asked again at resume -- 8 * W * V bytes that would make the row depend on the alphabet
+// (6.4 MB at W = 100, V = 8000, against the 18 KB of the member set) for W * V look-ups per chunk, what a few steps ask anyway.
+// A status (node pool exhausted, too many frames, another configuration) stores nothing, so a stored row carries no error flag.
+constexpr unsigned kStreamMagic = 0x42533443u;
+constexpr int kStreamHeaderBytes = 256;
+struct StreamHeader {
+  unsigned magic;
+  int V, W, has_lm, max_frames, with_ts;              // the configuration the row was written under
+  int n, next_node, frames;                           // members, nodes allocated, frames consumed
+};
+static_assert(sizeof(StreamHeader) <= kStreamHeaderBytes, "stream header");
+constexpr int kStreamPoolExhausted = -1, kStreamTooManyFrames = -2, kStreamOtherConfig = -3;
 
 // inclusive prefix sum over the 64 lanes, all DPP (row_shr 1/2/4/8 with zero fill, row_bcast 15/31)
 __device__ __forceinline__ int wave_scan_i(int v) {
@@ -451,6 +479,55 @@ __device__ __forceinline__ void init_root(const BeamParams& p, BeamNode* nodes, 
   M0.lm[0] = l;
 }
 
+// ---- the phases of a streaming call (e2e_ctc_beam_stream), compiled into the kernels' ST instances only ----
+// What the row says before a chunk of T frames: the frames consumed so far (fresh row: 0, resume = false) or a status < 0.
+// The same for every thread of the workgroup (returned wave-uniform).
+__device__ __forceinline__ int stream_open(const BeamParams& p, const unsigned char* row, int T, bool& resume) {
+  const StreamHeader h = *reinterpret_cast<const StreamHeader*>(row);
+  int st = 0, res = 0;
+  if (h.magic != 0u) {
+    const bool same = h.magic == kStreamMagic && h.V == p.V && h.W == p.W && h.has_lm == p.has_lm &&
+                      h.max_frames == p.st_max_frames && h.with_ts == (p.st_ts_off ? 1 : 0) &&
+                      h.n >= 1 && h.n <= p.W && h.next_node >= 1 && h.next_node <= p.NCAP && h.frames >= 0 && h.frames <= p.st_max_frames;
+    if (same) { st = h.frames; res = 1; } else st = kStreamOtherConfig;
+  }
+  if (st >= 0 && st + T > p.st_max_frames) st = kStreamTooManyFrames;
+  resume = __builtin_amdgcn_readfirstlane(res) != 0;
+  return __builtin_amdgcn_readfirstlane(st);
+}
+// a status ends the utterance's workgroup before it touches anything: the row stays byte for byte what it was
+__device__ __forceinline__ void stream_refuse(const BeamParams& p, int status) {
+  if (threadIdx.x == 0) {
+    p.frames_done[blockIdx.x] = status;
+    if (p.nbest) p.n_hyp[blockIdx.x] = status;
+  }
+}
+// resume: the stored member set becomes set 0 (all threads; the caller's barrier follows)
+__device__ __forceinline__ void stream_load_members(unsigned char* set0, const unsigned char* row, size_t mbytes) {
+  const unsigned long long* src = reinterpret_cast<const unsigned long long*>(row + kStreamHeaderBytes);
+  unsigned long long* dst = reinterpret_cast<unsigned long long*>(set0);
+  for (size_t i = threadIdx.x; i < mbytes / 8; i += kThreads) dst[i] = src[i];
+}
+// suspend, behind the chunk's last step: the current member set, then the header (plain vector stores).  A chunk of no frames
+// stores nothing; neither does a chunk that ran out of nodes (err), whose status goes to frames_done.
+__device__ __forceinline__ void stream_suspend(const BeamParams& p, unsigned char* row, const unsigned char* set, size_t mbytes,
+                                               int n, int next_node, int t0, int T, int err) {
+  if (!err && T > 0) {
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(set);
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(row + kStreamHeaderBytes);
+    for (size_t i = threadIdx.x; i < mbytes / 8; i += kThreads) dst[i] = src[i];
+  }
+  if (threadIdx.x == 0) {
+    if (!err && T > 0) {
+      StreamHeader h;
+      h.magic = kStreamMagic; h.V = p.V; h.W = p.W; h.has_lm = p.has_lm; h.max_frames = p.st_max_frames; h.with_ts = p.st_ts_off ? 1 : 0;
+      h.n = n; h.next_node = next_node; h.frames = t0 + T;
+      *reinterpret_cast<StreamHeader*>(row) = h;
+    }
+    p.frames_done[blockIdx.x] = err ? kStreamPoolExhausted : t0 + T;
+  }
+}
+
 // what the score of a member's would-be children needs of its LM state (only these fields are ever loaded)
 template <bool LM>
 __device__ __forceinline__ LmFields score_fields(const LmFields& m) {
@@ -675,7 +752,10 @@ namespace e2e { namespace {
 #define BPROF(slot) do {} while (0)
 #endif
 
-template <typename IO, int LMK>
+// ST: the streaming call's instance.  The resume and suspend phases are compiled into it alone, so the kernels of the calls that
+// decode whole utterances are instruction for instruction what they are without them (as one kernel with a test on a null
+// pointer, the phases cost every instance ~30 more spilled SGPRs and the fast LM instance two VGPRs spilled to scratch).
+template <typename IO, int LMK, bool ST>
 __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   constexpr bool LM = LMK != 0, RS = lmk_restricted(LMK);
   extern __shared__ __align__(16) unsigned char smem[];
@@ -711,14 +791,25 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   __shared__ unsigned s_hi2[2], s_lo2[2];
   __shared__ unsigned long long s_prefix;
 
-  BeamNode* nodes = p.nodes + (size_t)b * p.NCAP;
-  int* const node_t = p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;     // (uniform: null in the plain call)
+  // (streaming: the utterance's state row holds the node pool and the nodes' frames; null, at compile time, in every other call)
+  unsigned char* const st_row = ST ? p.st_rows + (size_t)b * p.st_row_bytes : nullptr;
+  BeamNode* nodes = ST ? reinterpret_cast<BeamNode*>(st_row + p.st_nodes_off) : p.nodes + (size_t)b * p.NCAP;
+  int* const node_t = ST ? (p.st_ts_off ? reinterpret_cast<int*>(st_row + p.st_ts_off) : nullptr)
+                         : p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;         // (uniform: null in the plain call)
   const IO* lp = reinterpret_cast<const IO*>(p.lp) + (int64_t)b * p.sB;
   int64_t Tq = p.x_len[b];
   const int T = Tq < 0 ? 0 : (Tq > p.T ? p.T : (int)Tq);
+  // frames consumed before this call (node_t holds global frames; everything keyed on step parity uses the local step)
+  int t0 = 0, n0 = 1;
+  bool resume = false;
+  if (ST) {
+    t0 = stream_open(p, st_row, T, resume);
+    if (t0 < 0) { stream_refuse(p, t0); return; }
+    if (resume) n0 = __builtin_amdgcn_readfirstlane(reinterpret_cast<const StreamHeader*>(st_row)->n);
+  }
 
   // ---- pools, root prefix (get_initial_prefix, :222-230) ----
-  for (int c = tid; c < V; c += kThreads) ctab0[c] = -1;                             // set 0, member 0 = the root
+  for (int c = tid; c < n0 * V; c += kThreads) ctab0[c] = -1;                        // set 0: member 0 = the root, or the resumed members
   for (int h = tid; h < p.HS; h += kThreads) { sm0[h] = -1; sm0[2 * p.HS + h] = -1; }
   if (T > 0) for (int c = tid; c < V; c += kThreads) srow2[c] = (double)lp[(int64_t)c * p.sV];
   if (LM) {
@@ -742,13 +833,30 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   if (tid == 0) {
     s_next_node = 1; s_err = 0;                                                     // node 0 is taken
     s_hi2[0] = 0u; s_lo2[0] = 0xffffffffu; s_total_new2[0] = 0; s_nnew2[0] = 0;
-    init_root(p, nodes, M0);
+    if (!ST || !resume) init_root(p, nodes, M0);
+    else s_next_node = reinterpret_cast<const StreamHeader*>(st_row)->next_node;
+  }
+  if (ST && resume) stream_load_members(mem0, st_row, mbytes);
+  __syncthreads();
+  if (!ST || !resume) {
+    if (tid == 0) slot_map(0).insert(0, 0);
+    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
+  } else {
+    // what a step rebuilds: the slot map, the child tables (one entry per guard, as rebuild_guards writes them) and the
+    // members' LM answers (asked as a new member's are: the same function of the member's state)
+    const SlotMap map0 = slot_map(0);
+    for (int i = tid; i < n0; i += kThreads) {
+      map0.insert(M0.node[i], i);
+      const int go = M0.gown[i];
+      if (go >= 0) ctab0[go * V + M0.gchar[i]] = M0.gnode[i];
+    }
+    if (LM) for (int e = tid; e < n0 * V; e += kThreads) {
+      const int j2 = e / V, c = e - j2 * V;
+      if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[j2], M0.last[j2], c);
+    }
   }
   __syncthreads();
-  if (tid == 0) slot_map(0).insert(0, 0);
-  if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
-  __syncthreads();
-  int n = 1, cur = 0;
+  int n = n0, cur = 0;
   // the pair loop's thread layout depends on n alone, and n is W for all but an utterance's first steps: worked out when n
   // changes (three integer divisions, ~100 instructions per thread of a phase that is bound by the instructions it issues)
   int lay_n = -1, lay_P = 1, lay_mpp = kThreads, lay_ii0 = 0, lay_part = 0;
@@ -886,7 +994,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
           BeamNode nn;
           nn.parent = A.node[i]; nn.last_char = c;
           nodes[k] = nn;                                                          // (fire and forget)
-          if (node_t) node_t[k] = t;
+          if (node_t) node_t[k] = ST ? t0 + t : t;
           mapB.insert(k, j);
         }
         Bm.ppb[j] = ninf(); Bm.ppnb[j] = val; Bm.full[j] = lse2(val, ninf()); Bm.node[j] = k; Bm.last[j] = c;
@@ -1117,8 +1225,9 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   Members A;
   A.carve(mem0 + (size_t)cur * mbytes, W);
   // (the n-best read-out's scratch: the candidate keys and the selection's two histograms, dead after the last step)
+  if (ST) stream_suspend(p, st_row, mem0 + (size_t)cur * mbytes, mbytes, n, s_next_node, t0, T, s_err);
   if (p.nbest) read_out_nbest<LM>(p, A, n, reinterpret_cast<unsigned long long*>(key), hist, hist + kSelBins, nodes, node_t, s_err);
-  else read_out<LM>(p, A, n, key, nodes, s_err);
+  else if (!ST) read_out<LM>(p, A, n, key, nodes, s_err);               // (a stream fed with nbest = 0 reads nothing out)
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1160,7 +1269,7 @@ struct GenParams {
 
 __device__ __forceinline__ void gsync() { __threadfence_block(); __syncthreads(); }
 
-template <typename IO, int LMK>
+template <typename IO, int LMK, bool ST>
 __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p, GenParams g) {
   constexpr bool LM = LMK != 0, RS = lmk_restricted(LMK);
   extern __shared__ __align__(16) unsigned char smem[];
@@ -1190,26 +1299,52 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
   __shared__ unsigned long long s_prefix;
   LabelTab lt; lt.off = p.lm.label_off; lt.bytes = p.lm.label_bytes; lt.one = nullptr;
 
-  BeamNode* nodes = p.nodes + (size_t)b * p.NCAP;
-  int* const node_t = p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;     // (uniform: null in the plain call)
+  unsigned char* const st_row = ST ? p.st_rows + (size_t)b * p.st_row_bytes : nullptr;     // (streaming: see the fast kernel)
+  BeamNode* nodes = ST ? reinterpret_cast<BeamNode*>(st_row + p.st_nodes_off) : p.nodes + (size_t)b * p.NCAP;
+  int* const node_t = ST ? (p.st_ts_off ? reinterpret_cast<int*>(st_row + p.st_ts_off) : nullptr)
+                         : p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;         // (uniform: null in the plain call)
   const IO* lp = reinterpret_cast<const IO*>(p.lp) + (int64_t)b * p.sB;
   unsigned long long* const gkey = g.gkey + (size_t)b * ((size_t)W + (size_t)W * V);
   LmAnswer* const lmc0 = LM ? g.lmc + (size_t)b * 2 * (size_t)W * V : nullptr;
   int64_t Tq = p.x_len[b];
   const int T = Tq < 0 ? 0 : (Tq > p.T ? p.T : (int)Tq);
   Members M0; M0.carve(mem0, W);
+  int t0 = 0, n0 = 1;
+  bool resume = false;
+  if (ST) {
+    t0 = stream_open(p, st_row, T, resume);
+    if (t0 < 0) { stream_refuse(p, t0); return; }
+    if (resume) n0 = __builtin_amdgcn_readfirstlane(reinterpret_cast<const StreamHeader*>(st_row)->n);
+  }
 
   for (int h = tid; h < 2 * p.HS; h += kThreads) { sm0[h] = -1; sm0[2 * p.HS + h] = -1; }
   for (int h = tid; h < 2 * g.CH; h += kThreads) { cm0[h] = -1; cm0[2 * g.CH + h] = -1; }
   if (tid == 0) {
     s_next_node = 1; s_err = 0;                                                     // node 0 is taken
-    init_root(p, nodes, M0);
+    if (!ST || !resume) init_root(p, nodes, M0);
+    else s_next_node = reinterpret_cast<const StreamHeader*>(st_row)->next_node;
+  }
+  if (ST && resume) stream_load_members(mem0, st_row, mbytes);
+  gsync();
+  if (!ST || !resume) {
+    if (tid == 0) slot_map(0).insert(0, 0);
+    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
+  } else {
+    // what a step rebuilds: the slot map, the child map (one entry per guard) and the members' LM answer rows
+    const SlotMap map0 = slot_map(0);
+    const ChildMap cm = child_map(0);
+    for (int i = tid; i < n0; i += kThreads) {
+      map0.insert(M0.node[i], i);
+      const int go = M0.gown[i];
+      if (go >= 0) cm.insert(go * V + M0.gchar[i], M0.gnode[i]);
+    }
+    if (LM) for (size_t e = tid; e < (size_t)n0 * V; e += kThreads) {
+      const int j2 = (int)(e / V), c = (int)(e - (size_t)j2 * V);
+      if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[j2], M0.last[j2], c);
+    }
   }
   gsync();
-  if (tid == 0) slot_map(0).insert(0, 0);
-  if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
-  gsync();
-  int n = 1, cur = 0;
+  int n = n0, cur = 0;
   // q / n for the candidate numbers of a step (q < n * V, q * n < 2^32) by one multiplication: ceil(2^32 / n), worked out when
   // the beam's size changes (a division per candidate was a third of the pair loop's instructions at ~30 candidates per thread)
   // (exact while q * n < 2^32; a beam of 512 over an alphabet of 32 000 without the pre-selection is beyond that: plain division)
@@ -1374,7 +1509,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
           BeamNode nn;
           nn.parent = A.node[i]; nn.last_char = c;
           nodes[k] = nn;
-          if (node_t) node_t[k] = t;
+          if (node_t) node_t[k] = ST ? t0 + t : t;
           mapB.insert(k, j);
         }
         Bm.ppb[j] = ninf(); Bm.ppnb[j] = val; Bm.full[j] = lse2(val, ninf()); Bm.node[j] = k; Bm.last[j] = c;
@@ -1470,8 +1605,9 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
 
   Members A;
   A.carve(mem0 + (size_t)cur * mbytes, W);
+  if (ST) stream_suspend(p, st_row, mem0 + (size_t)cur * mbytes, mbytes, n, s_next_node, t0, T, s_err);
   if (p.nbest) read_out_nbest<LM>(p, A, n, reinterpret_cast<unsigned long long*>(fkey), sidx, hist, nodes, node_t, s_err);
-  else read_out<LM>(p, A, n, fkey, nodes, s_err);
+  else if (!ST) read_out<LM>(p, A, n, fkey, nodes, s_err);
 }
 
 struct GenLayout { size_t gkey, lmc, gmem, total, lds; int CH; bool members_in_ws; };
@@ -1570,16 +1706,42 @@ extern "C" size_t e2e_ctc_beam_nbest_workspace_bytes(int B, int T, int V, int be
 // what e2e_ctc_beam_nbest adds to the arguments of e2e_ctc_beam (null: the plain call)
 struct NBestOut { int nbest; int64_t* n_hyp; double* scores; int32_t* counts; int64_t* timesteps; };
 
+// ... and e2e_ctc_beam_stream (null: a call that decodes whole utterances)
+struct StreamIn { void* state; size_t row_bytes; int max_frames, with_timesteps; int64_t* frames_done; };
+// a state row: header | one member set | node pool of max_frames frames | the nodes' frames (with_timesteps), each 256-aligned
+struct StreamLayout { size_t nodes, frames, total; };
+static StreamLayout stream_layout(int max_frames, int V, int W, bool lm, bool ts) {
+  StreamLayout l;
+  const size_t ncap = (size_t)beam_layout(1, max_frames, V, W, lm).NCAP;
+  l.nodes = kStreamHeaderBytes + align_up(Members::bytes(W), 256);
+  l.frames = ts ? l.nodes + align_up(ncap * sizeof(BeamNode), 256) : 0;
+  l.total = ts ? l.frames + align_up(ncap * sizeof(int), 256) : l.nodes + align_up(ncap * sizeof(BeamNode), 256);
+  return l;
+}
+
+extern "C" size_t e2e_ctc_beam_stream_row_bytes(int max_frames, int V, int beam_width, int with_lm, int with_timesteps) {
+  if (max_frames < 1 || V < 1 || beam_width < 1 || (long long)beam_width * ((long long)max_frames + 3) + 8 > 0x7fffffffLL) return 0;
+  if (beam_width > e2e_ctc_beam_max_width(V, with_lm != 0)) return 0;
+  return stream_layout(max_frames, V, beam_width, with_lm != 0, with_timesteps != 0).total;
+}
+
+extern "C" size_t e2e_ctc_beam_stream_workspace_bytes(int B, int V, int beam_width, int with_lm) {
+  if (B < 0 || V < 1 || beam_width < 1) return 0;
+  if (!beam_takes_general(V, beam_width, with_lm != 0)) return 0;
+  const BeamLayout l = beam_layout(B, 1, V, beam_width, with_lm != 0);
+  return gen_layout(B, V, beam_width, l.WP2, l.HS, with_lm != 0).total + 256;
+}
+
 static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
                      const int64_t* x_len, int B, int T, int V, int blank,
                      int beam_width, int space_id, const e2e_lm* lm,
                      double lmwt, double wip, double oov_penalty,
                      int64_t* out, int64_t max_out, int64_t* out_len, const NBestOut* nb, bool restricted,
-                     void* workspace, size_t workspace_bytes, void* stream) {
+                     void* workspace, size_t workspace_bytes, void* stream, const StreamIn* st = nullptr) {
   if (dtype != E2E_F32 && dtype != E2E_F64 && !dtype_is_16bit(dtype)) { set_error("dtype must be E2E_F32, E2E_F64, E2E_F16 or E2E_BF16"); return E2E_ERR_ARG; }
   if (B < 0 || T < 1 || V < 1 || beam_width < 1 || max_out < 1) { set_error("bad sizes"); return E2E_ERR_ARG; }
   if (blank < 0 || blank >= V) { set_error("blank=%d outside [0,%d)", blank, V); return E2E_ERR_ARG; }
-  if (B > 0 && (!lp || !x_len || !out || !out_len)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  if (B > 0 && (!lp || !x_len || ((!out || !out_len) && !(st && nb->nbest == 0)))) { set_error("null pointer argument"); return E2E_ERR_ARG; }
   if (lm && !lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
   if (lm) {
     int cur = -1;
@@ -1596,7 +1758,8 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
       return E2E_ERR_ARG;
     }
   }
-  const BeamLayout l = beam_layout(B, T, V, beam_width, lm != nullptr);
+  // (a stream: the node pool is the row's, sized by max_frames; the workspace holds the general kernel's share alone)
+  const BeamLayout l = beam_layout(B, st ? st->max_frames : T, V, beam_width, lm != nullptr);
   const bool fast_ok = beam_fits(V, beam_width, lm != nullptr), gen_ok = gen_fits(V, beam_width, lm != nullptr);
   const bool general = beam_takes_general(V, beam_width, lm != nullptr);
   if (!fast_ok && !gen_ok) {
@@ -1607,9 +1770,10 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
   const GenLayout gl = gen_layout(B, V, beam_width, l.WP2, l.HS, lm != nullptr);
   uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
   const uintptr_t aligned = (base + 255) & ~(uintptr_t)255;
-  const size_t frames_at = l.total + (general ? gl.total : 0);
-  const size_t need = frames_at + (nb && nb->timesteps ? node_frames_bytes(B, l.NCAP) : 0);
-  if (!workspace || workspace_bytes < need + (aligned - base)) { set_error("workspace too small: need %zu", need + 256); return E2E_ERR_WORKSPACE; }
+  const size_t gen_at = st ? 0 : l.total;
+  const size_t frames_at = gen_at + (general ? gl.total : 0);
+  const size_t need = frames_at + (!st && nb && nb->timesteps ? node_frames_bytes(B, l.NCAP) : 0);
+  if (need && (!workspace || workspace_bytes < need + (aligned - base))) { set_error("workspace too small: need %zu", need + 256); return E2E_ERR_WORKSPACE; }
   if (B == 0) return E2E_OK;
   char* ws = reinterpret_cast<char*>(aligned);
   BeamParams p;
@@ -1625,31 +1789,42 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
   p.nbest = nb ? nb->nbest : 0;
   p.n_hyp = nb ? nb->n_hyp : nullptr; p.scores = nb ? nb->scores : nullptr; p.counts = nb ? nb->counts : nullptr;
   p.ts_out = nb ? nb->timesteps : nullptr;
-  p.node_t = nb && nb->timesteps ? reinterpret_cast<int*>(ws + frames_at) : nullptr;
+  p.node_t = !st && nb && nb->timesteps ? reinterpret_cast<int*>(ws + frames_at) : nullptr;
+  p.st_rows = nullptr; p.st_row_bytes = 0; p.st_nodes_off = 0; p.st_ts_off = 0; p.st_max_frames = 0; p.frames_done = nullptr;
+  if (st) {
+    const StreamLayout sl = stream_layout(st->max_frames, V, beam_width, lm != nullptr, st->with_timesteps != 0);
+    p.nodes = nullptr;
+    p.st_rows = static_cast<unsigned char*>(st->state); p.st_row_bytes = st->row_bytes;
+    p.st_nodes_off = sl.nodes; p.st_ts_off = sl.frames; p.st_max_frames = st->max_frames; p.frames_done = st->frames_done;
+  }
   hipStream_t s = (hipStream_t)stream;
   const bool fast_lm = lm && lm->d_ngs && lm->order - 1 <= kParCtx;
   const bool rs = lm && restricted;
   if (general) {
     GenParams g;
-    g.gkey = reinterpret_cast<unsigned long long*>(ws + l.total + gl.gkey);
-    g.lmc = lm ? reinterpret_cast<LmAnswer*>(ws + l.total + gl.lmc) : nullptr;
-    g.gmem = gl.members_in_ws ? reinterpret_cast<unsigned char*>(ws + l.total + gl.gmem) : nullptr;
+    g.gkey = reinterpret_cast<unsigned long long*>(ws + gen_at + gl.gkey);
+    g.lmc = lm ? reinterpret_cast<LmAnswer*>(ws + gen_at + gl.lmc) : nullptr;
+    g.gmem = gl.members_in_ws ? reinterpret_cast<unsigned char*>(ws + gen_at + gl.gmem) : nullptr;
     g.CH = gl.CH;
     // (16-bit log-probabilities are read as they are -- every one of them is an f32 number, so the search is the f32 one's, bit for bit)
-#define E2E_GEN_OF(IO) (!lm ? (const void*)&ctc_beam_general_kernel<IO, 0> : fast_lm ? (rs ? (const void*)&ctc_beam_general_kernel<IO, 4> : (const void*)&ctc_beam_general_kernel<IO, 2>) \
-                            : (rs ? (const void*)&ctc_beam_general_kernel<IO, 3> : (const void*)&ctc_beam_general_kernel<IO, 1>))
+#define E2E_GEN_LMK(IO, ST) (!lm ? (const void*)&ctc_beam_general_kernel<IO, 0, ST> : fast_lm ? (rs ? (const void*)&ctc_beam_general_kernel<IO, 4, ST> : (const void*)&ctc_beam_general_kernel<IO, 2, ST>) \
+                                 : (rs ? (const void*)&ctc_beam_general_kernel<IO, 3, ST> : (const void*)&ctc_beam_general_kernel<IO, 1, ST>))
+#define E2E_GEN_OF(IO) (st ? E2E_GEN_LMK(IO, true) : E2E_GEN_LMK(IO, false))
     const void* gfn = dtype == E2E_F32 ? E2E_GEN_OF(float) : dtype == E2E_F64 ? E2E_GEN_OF(double) : dtype == E2E_F16 ? E2E_GEN_OF(f16_t) : E2E_GEN_OF(bf16_t);
 #undef E2E_GEN_OF
+#undef E2E_GEN_LMK
     E2E_HIP_CHECK(allow_dynamic_lds(gfn, (int)gl.lds), "hipFuncSetAttribute");
     void* gargs[] = { &p, &g };
     E2E_HIP_CHECK(hipLaunchKernel(gfn, dim3(B), dim3(kThreads), gargs, gl.lds, s), "ctc_beam_general_kernel launch");
     E2E_HIP_CHECK(hipGetLastError(), "ctc_beam_general_kernel launch");
     return E2E_OK;
   }
-#define E2E_BEAM_OF(IO) (!lm ? (const void*)&ctc_beam_kernel<IO, 0> : fast_lm ? (rs ? (const void*)&ctc_beam_kernel<IO, 4> : (const void*)&ctc_beam_kernel<IO, 2>) \
-                             : (rs ? (const void*)&ctc_beam_kernel<IO, 3> : (const void*)&ctc_beam_kernel<IO, 1>))
+#define E2E_BEAM_LMK(IO, ST) (!lm ? (const void*)&ctc_beam_kernel<IO, 0, ST> : fast_lm ? (rs ? (const void*)&ctc_beam_kernel<IO, 4, ST> : (const void*)&ctc_beam_kernel<IO, 2, ST>) \
+                                  : (rs ? (const void*)&ctc_beam_kernel<IO, 3, ST> : (const void*)&ctc_beam_kernel<IO, 1, ST>))
+#define E2E_BEAM_OF(IO) (st ? E2E_BEAM_LMK(IO, true) : E2E_BEAM_LMK(IO, false))
   const void* fn = dtype == E2E_F32 ? E2E_BEAM_OF(float) : dtype == E2E_F64 ? E2E_BEAM_OF(double) : dtype == E2E_F16 ? E2E_BEAM_OF(f16_t) : E2E_BEAM_OF(bf16_t);
 #undef E2E_BEAM_OF
+#undef E2E_BEAM_LMK
   E2E_HIP_CHECK(allow_dynamic_lds(fn, (int)l.lds), "hipFuncSetAttribute");
   void* args[] = { &p };
   E2E_HIP_CHECK(hipLaunchKernel(fn, dim3(B), dim3(kThreads), args, l.lds, s), "ctc_beam_kernel launch");
@@ -1711,6 +1886,43 @@ extern "C" int e2e_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int
   }
   return nbest_call(lp, dtype, sB, sT, sV, x_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
                     nbest, out, max_out, out_len, n_hyp, scores, counts, timesteps, restricted, workspace, workspace_bytes, stream);
+}
+
+extern "C" int e2e_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                                   const int64_t* chunk_len, int B, int T, int V, int blank,
+                                   int beam_width, int space_id, const e2e_lm* lm,
+                                   double lmwt, double wip, double oov_penalty,
+                                   void* state, size_t row_bytes, int max_frames, int with_timesteps,
+                                   int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                                   double* scores, int32_t* counts, int64_t* timesteps, int64_t* frames_done,
+                                   void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts) {
+  // every argument error the host can see, before any launch
+  if (B < 0 || T < 1 || V < 1 || beam_width < 1 || max_frames < 1) { set_error("bad sizes"); return E2E_ERR_ARG; }
+  if (nbest < 0 || nbest > beam_width) { set_error("nbest=%d outside [0, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (B > 0 && (!state || !frames_done || !chunk_len)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  if (B > 0 && nbest > 0 && (!n_hyp || !scores || !counts || !out || !out_len)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  if (!with_timesteps && timesteps) { set_error("timesteps asked of a stream that was opened with_timesteps = 0"); return E2E_ERR_ARG; }
+  if (beam_width > e2e_ctc_beam_max_width(V, lm != nullptr)) {
+    set_error("beam_width = %d over an alphabet of %d%s: at most %d", beam_width, V, lm ? " with a language model" : "",
+              e2e_ctc_beam_max_width(V, lm != nullptr));
+    return E2E_ERR_ARG;
+  }
+  const size_t want = e2e_ctc_beam_stream_row_bytes(max_frames, V, beam_width, lm != nullptr, with_timesteps);
+  if (!want) { set_error("max_frames = %d: the node pool of a stream this long cannot be indexed", max_frames); return E2E_ERR_ARG; }
+  if (row_bytes < want || row_bytes % 8) {
+    set_error("row_bytes = %zu: a state row needs %zu bytes (e2e_ctc_beam_stream_row_bytes) and a multiple of 8", row_bytes, want);
+    return E2E_ERR_ARG;
+  }
+  if (B > 0 && reinterpret_cast<uintptr_t>(state) % 8) { set_error("the state must be 8-byte aligned"); return E2E_ERR_ARG; }
+  const bool restricted = opts && opts->restrict_to_lexicon != 0;
+  if (restricted && (!lm || !lm->has_lexicon)) {
+    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+    return E2E_ERR_ARG;
+  }
+  const NBestOut nb = { nbest, n_hyp, scores, counts, nbest > 0 ? timesteps : nullptr };
+  const StreamIn st = { state, row_bytes, max_frames, with_timesteps, frames_done };
+  return beam_call(lp, dtype, sB, sT, sV, chunk_len, B, T, V, blank, beam_width, space_id, lm, lmwt, wip, oov_penalty,
+                   out, nbest > 0 ? max_out : 1, out_len, &nb, restricted, workspace, workspace_bytes, stream, &st);
 }
 
 #ifdef E2E_BEAM_PROFILE

@@ -142,6 +142,17 @@ class CTCDecoder:
         return NBestResults(*self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest,
                                                         timesteps=timesteps))
 
+    def open_stream(self, batch_size, max_frames, device=None, timesteps=False):
+        """Streaming beam search (an extension): a ``CTCDecoderStream`` that is fed the logits in chunks and keeps the beams of
+        ``batch_size`` utterances of up to ``max_frames`` frames on the GPU in between.  After every chunk the result is that
+        of ``decode`` / ``decode_nbest`` on everything fed so far; the decoder's settings apply as they do there.
+
+        :param timesteps: keep the frames of the labels (``feed_nbest`` then returns them, counted from the stream's start)
+        """
+        if self._beam_width == 1:
+            raise CTCDecoderError("a stream needs beam_width > 1: greedy decoding has no beam to keep")
+        return CTCDecoderStream(self, self._decoder.open_stream(batch_size, max_frames, device=device, timesteps=timesteps))
+
     def _print_scores_for_sentence(self, words):
         self._decoder.print_scores_for_sentence(words)
 
@@ -152,3 +163,42 @@ class CTCDecoder:
         """
         logits, logits_lengths = self._batch_major(logits, logits_lengths)
         return DecoderResults(*self._decoder.decode_greedy(logits_=logits, logits_lengths_=logits_lengths))
+
+
+class CTCDecoderStream:
+    """What ``CTCDecoder.open_stream`` returns.  ``feed`` / ``feed_nbest`` take a chunk of logits shaped as ``decode`` takes them
+    (``logits_lengths``: the frames of this chunk per utterance, all by default, 0 allowed) and return ``DecoderResults`` /
+    ``NBestResults`` for everything fed so far; ``frames`` are the per-utterance totals, ``state`` the (batch, row_bytes)
+    uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts utterances anew."""
+
+    def __init__(self, decoder, stream):
+        self._owner, self._stream = decoder, stream
+
+    @property
+    def frames(self):
+        return self._stream.frames
+
+    @property
+    def state(self):
+        return self._stream.state
+
+    def reset(self, rows=None):
+        self._stream.reset(rows)
+
+    def _chunk(self, logits, logits_lengths):
+        d = self._owner
+        logits, logits_lengths = d._batch_major(logits, logits_lengths)
+        self._stream.check_chunk(tuple(logits.shape))             # (before any device work)
+        with torch.no_grad():
+            if not d._after_logsoftmax:
+                logits = torch.log_softmax(logits, -1)            # per frame: the same numbers whatever the chunking
+        return logits, logits_lengths
+
+    def feed(self, logits, logits_lengths=None):
+        logits, logits_lengths = self._chunk(logits, logits_lengths)
+        return DecoderResults(*self._stream.feed(logits, logits_lengths))
+
+    def feed_nbest(self, logits, logits_lengths=None, nbest=None):
+        logits, logits_lengths = self._chunk(logits, logits_lengths)
+        r = self._stream.feed_nbest(logits, logits_lengths, nbest=nbest)
+        return None if r is None else NBestResults(*r)

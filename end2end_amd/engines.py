@@ -573,6 +573,12 @@ class CTCDecoderEngine:
                                   out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
                                   counts.data_ptr(), ts.data_ptr() if timesteps else 0,
                                   ws.data_ptr(), ws.numel(), R.stream_handle(dev), restrict_to_lexicon=self.restrict)
+        return self._nbest_result(out, out_len, n_hyp, scores, counts, ts, max_out)
+
+    def _nbest_result(self, out, out_len, n_hyp, scores, counts, ts, max_out):
+        """What decode_nbest returns, from the buffers the n-best read-out has filled (ts: None without timestamps)."""
+        B, N = out_len.shape
+        timesteps = ts is not None
         nh = n_hyp.tolist()
         lens = out_len.tolist()
         # per-utterance and per-hypothesis status ride on the counts and lengths, as in decode()
@@ -591,6 +597,12 @@ class CTCDecoderEngine:
                 r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
                 r(counts[:, :, 1].contiguous()), r(n_hyp), r(ts[:, :, :width].contiguous()) if timesteps else None)
 
+    def open_stream(self, batch_size, max_frames, device=None, timesteps=False):
+        """Streaming beam search (e2e_ctc_beam_stream, include/e2e_ctc.h): a CTCBeamStream that is fed log-probabilities in
+        chunks and keeps the beams of `batch_size` utterances of up to `max_frames` frames on the GPU between the chunks.
+        After every chunk the result is, bit for bit, that of decode / decode_nbest on all the frames fed so far."""
+        return CTCBeamStream(self, batch_size, max_frames, device=device, timesteps=timesteps)
+
     def print_scores_for_sentence(self, words):
         """src/decoders/ctc_decoder.cpp:141-151: word, decoder index, vocabulary index, log10 score."""
         if self.lm is None:
@@ -602,3 +614,127 @@ class CTCDecoderEngine:
             idx = self.lm.word_index(key)
             print(w, idx, self.lm.word_index(w), self.lm.score(ctx, idx))
             ctx = ([idx] + ctx)[: max(order - 1, 0)]
+
+
+class CTCBeamStream:
+    """The beams of `batch_size` utterances, kept on the GPU between chunks (CTCDecoderEngine.open_stream).  Owns the
+    (batch_size, row_bytes) uint8 state tensor `state`: one self-contained row per utterance, allocated at the first chunk
+    (on `device`, else on the chunk's GPU, else on the current one).  Rows may be reordered or copied by the caller; a row
+    whose first 256 bytes are zero starts a new utterance."""
+
+    HEADER_BYTES = 256
+
+    def __init__(self, engine, batch_size, max_frames, device=None, timesteps=False):
+        if engine.beam_width < 2:
+            raise ValueError("a stream needs beam_width > 1: greedy decoding has no beam to keep")
+        if int(batch_size) < 1 or int(max_frames) < 1:
+            raise ValueError("batch_size and max_frames must be at least 1")
+        self.engine = engine
+        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
+        self.timesteps = bool(timesteps)
+        self.device = None if device is None else torch.device(device)
+        self.state = None
+        self.row_bytes = 0
+        self._frames = [0] * self.batch_size
+
+    @property
+    def frames(self):
+        """Frames consumed so far, per utterance."""
+        return list(self._frames)
+
+    def check_chunk(self, shape):
+        """The chunk's shape (batch, frames, alphabet) against the stream: a ValueError before any device work."""
+        if len(shape) != 3:
+            raise ValueError("logits must be (batch, time, alphabet)")
+        if shape[0] != self.batch_size:
+            raise ValueError("the chunk has %d utterances, the stream was opened for %d" % (shape[0], self.batch_size))
+        if not 1 <= shape[1] <= self.max_frames:
+            raise ValueError("a chunk of %d frames: the stream takes 1 .. max_frames = %d" % (shape[1], self.max_frames))
+
+    def reset(self, rows=None):
+        """Start the given utterances (all: None) anew: their headers are zeroed, nothing else is touched."""
+        idx = range(self.batch_size) if rows is None else [int(r) for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
+        for b in idx:
+            if not 0 <= b < self.batch_size:
+                raise ValueError("row %d outside the stream's %d utterances" % (b, self.batch_size))
+        if self.state is not None:
+            if rows is None:
+                self.state[:, : self.HEADER_BYTES].zero_()
+            else:
+                self.state[torch.as_tensor(list(idx), dtype=torch.long, device=self.state.device), : self.HEADER_BYTES] = 0
+        for b in idx:
+            self._frames[b] = 0
+
+    def _state_for(self, V, dev):
+        e = self.engine
+        if self.state is None:
+            self.row_bytes = _C.ctc_beam_stream_row_bytes(self.max_frames, V, e.beam_width, e.lm is not None, self.timesteps)
+            if not self.row_bytes:
+                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported" % (self.max_frames, e.beam_width))
+            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
+            self.state[:, : self.HEADER_BYTES].zero_()
+            self.device = dev
+        return self.state
+
+    def feed_nbest(self, logits_, logits_lengths_=None, nbest=None):
+        """Feed a chunk of LOG-PROBABILITIES (batch, frames, alphabet) -- logits_lengths_: the frames of this chunk per
+        utterance, 0 allowed, all of them by default -- and read the beams out: what decode_nbest returns for everything
+        fed so far (timestamps if the stream was opened with them).  nbest=0 feeds only and returns None."""
+        e = self.engine
+        N = e.beam_width if nbest is None else int(nbest)
+        if not 0 <= N <= e.beam_width:
+            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
+        self.check_chunk(tuple(logits_.shape))
+        B, Tc = logits_.shape[0], logits_.shape[1]
+        if logits_lengths_ is None:
+            logits_lengths_ = torch.full((B,), Tc, dtype=torch.long)
+        if self.device is not None and logits_.device != self.device:
+            logits_ = logits_.to(self.device)
+        x, xl, dev = e._prep(logits_, logits_lengths_)
+        V = x.shape[2]
+        state = self._state_for(V, dev)
+        if dev != state.device:
+            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
+        max_out = max(self._frames) + Tc + 1
+        frames_done = torch.empty(B, dtype=torch.long, device=dev)
+        out = out_len = n_hyp = scores = counts = ts = None
+        if N:
+            out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
+            out_len = torch.empty((B, N), dtype=torch.long, device=dev)
+            n_hyp = torch.empty(B, dtype=torch.long, device=dev)
+            scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
+            counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+            ts = torch.empty((B, N, max_out), dtype=torch.long, device=dev) if self.timesteps else None
+        with torch.cuda.device(dev):
+            lm = e.lm.on(dev).handle if e.lm is not None else 0
+            nbytes = _C.ctc_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
+            ws = R.workspace(dev, nbytes) if nbytes else None
+            sB, sT, sV = x.stride()
+            _C.ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V, e.blank_idx,
+                               e.beam_width, e.space_id, lm, e.lmwt, e.wip, e.oov_penalty,
+                               state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
+                               out.data_ptr() if N else 0, max_out, out_len.data_ptr() if N else 0,
+                               n_hyp.data_ptr() if N else 0, scores.data_ptr() if N else 0, counts.data_ptr() if N else 0,
+                               ts.data_ptr() if ts is not None else 0, frames_done.data_ptr(),
+                               ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, R.stream_handle(dev),
+                               restrict_to_lexicon=e.restrict)
+        done = frames_done.tolist()
+        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
+        bad = None
+        for b, f in enumerate(done):
+            if f >= 0:
+                self._frames[b] = f
+            elif bad is None:
+                bad = (b, f)
+        if bad is not None:
+            why = {-1: "ran out of prefix-tree nodes", -2: "would pass max_frames=%d with this chunk" % self.max_frames,
+                   -3: "has a state row that was written under another configuration"}
+            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
+        if not N:
+            return None
+        return e._nbest_result(out, out_len, n_hyp, scores, counts, ts, max_out)
+
+    def feed(self, logits_, logits_lengths_=None):
+        """Feed a chunk and return what decode returns for everything fed so far: (indices, lengths, sentences)."""
+        r = self.feed_nbest(logits_, logits_lengths_, nbest=1)
+        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] for s in r[2]]

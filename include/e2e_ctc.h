@@ -392,6 +392,62 @@ int e2e_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, in
                            void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * Streaming beam search: the same search fed in chunks, the beam kept on the device between the calls (additive, ABI 4:
+ * nothing above changes meaning).
+ *
+ * An utterance's search lives in one STATE ROW of device memory that the caller owns: a 256-byte header, the beam's members
+ * (probabilities, prefix, guard, language-model state), the prefix-tree node pool of max_frames frames and, with_timesteps,
+ * one int32 per node.  A call resumes every utterance from its row, consumes chunk_len[b] further frames, stores the row
+ * and reads the current beam out.  What a step rebuilds anyway is not stored: the node -> position map, the child tables
+ * (from the members' guards) and the language model's answers (asked again at resume: they are a function of a member's
+ * state, and the row stays independent of the alphabet).
+ *   - A row whose first 256 bytes are zero is a fresh utterance: hipMemsetAsync (or zeroing the header) opens or resets a
+ *     stream, no other call is needed.  The rest of a fresh row may hold anything.
+ *   - Rows are self-contained: indices, no addresses.  They may be moved, gathered or reordered between calls, and a batch
+ *     may mix fresh rows with rows of any age.
+ *   - The call is asynchronous on `stream`, allocates nothing, does not synchronise and is capturable.
+ *   - Every argument error the host can see is E2E_ERR_ARG before any launch: sizes, null pointers, row_bytes below the
+ *     query, nbest outside [0, beam_width], the width limit, the language model's device / alphabet, restrict_to_lexicon
+ *     without a lexicon, timesteps != NULL with with_timesteps == 0.
+ * CONTRACT.  After chunks whose lengths for utterance b sum to f_b, every output of the read-out -- out, out_len, n_hyp,
+ * scores, counts, timesteps -- equals, bit for bit, what e2e_ctc_beam_nbest_opt writes for the concatenated frames with
+ * x_len[b] = f_b and the same nbest, max_out and options.  Timestamps are frames of the whole stream, not of the chunk.
+ *   lp           (B,T,V) log-probabilities of this chunk, strides sB,sT,sV, any of the four dtypes (chunks may differ)
+ *   chunk_len    (B) int64, device: frames of this chunk per utterance, clamped to 0..T.  0 runs no step and stores
+ *                nothing: the read-out repeats the utterance's last result (a fresh row: the root's)
+ *   state        (B,row_bytes) device, 8-byte aligned; row_bytes >= e2e_ctc_beam_stream_row_bytes(...), a multiple of 8
+ *   max_frames   the longest stream a row can hold; V, beam_width, lm or not, max_frames and with_timesteps are the row's
+ *                configuration and are checked against the header at resume
+ *   nbest        0: feed only, no read-out, the outputs up to timesteps may be NULL and are not touched; else as in
+ *                e2e_ctc_beam_nbest (1 gives e2e_ctc_beam's result as hypothesis 0)
+ *   max_out      as in e2e_ctc_beam_nbest; f_b + 1 can never be exceeded
+ *   frames_done  (B) int64, device.  What only the device knows is reported here per utterance, and mirrored in n_hyp[b]
+ *                when nbest > 0:
+ *                  >= 0  frames consumed so far
+ *                  -1    the node pool ran out (cannot happen within max_frames)
+ *                  -2    this chunk would pass max_frames
+ *                  -3    the row was not written under this configuration
+ *                A status < 0 leaves the row's header and members as they were (-2 and -3: the whole row, byte for byte;
+ *                the utterance's other outputs are then not written), and the other utterances advance.
+ *   workspace    >= e2e_ctc_beam_stream_workspace_bytes(...): the general kernel's scratch only (0, and NULL allowed,
+ *                where the one-workgroup kernel takes the width; the choice does not depend on the frames)
+ *   opts         NULL, or e2e_ctc_beam_opts as in e2e_ctc_beam_nbest_opt; the same for every chunk of a stream
+ * Row size: 256 + 176 * beam_width + (beam_width * (max_frames + 3) + 8) * (8, or 12 with_timesteps), each part rounded up
+ * to 256: beam_width 100, max_frames 30 000: 24 MB (36 MB) per utterance, whatever the alphabet.
+ */
+size_t e2e_ctc_beam_stream_row_bytes(int max_frames, int V, int beam_width, int with_lm, int with_timesteps);
+size_t e2e_ctc_beam_stream_workspace_bytes(int B, int V, int beam_width, int with_lm);
+
+int e2e_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                        const int64_t* chunk_len, int B, int T, int V, int blank,
+                        int beam_width, int space_id, const e2e_lm* lm,
+                        double lmwt, double wip, double oov_penalty,
+                        void* state, size_t row_bytes, int max_frames, int with_timesteps,
+                        int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                        double* scores, int32_t* counts, int64_t* timesteps, int64_t* frames_done,
+                        void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts);
+
+/* ------------------------------------------------------------------------
  * Viterbi forced alignment on the same lattice (max-plus instead of sum).
  * Replaces pytorch_end2end/utils/alignment.py:50-106 (_get_alignment_ctc_1d), :10-47
  * (_get_alignment_asg_1d, is_ctc = 0: no blanks) and the batch driver :109-138
