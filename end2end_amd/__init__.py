@@ -7,10 +7,11 @@ is a drop-in for `from pytorch_end2end import CTCLoss, CTCDecoder, CTCEncoder`
 by hand-written HIP kernels (end2end_amd/csrc, C ABI in include/e2e_ctc.h).
 """
 from .decoders.ctc_decoder import CTCDecoder, CTCDecoderError, DecoderResults, NBestResults
+from .decoders.gram_ctc_decoder import GramCTCDecoder, GramGreedyResults, GramNBestResults
 from .encoders.text_encoders import CTCEncoder
 from .modules.alignment_loss import AlignedTargetsLoss
 from .modules.ctc_loss import CTCLoss, GramCTCLoss
 from .modules.ctc_without_blank import CTCWithoutBlankLoss
 
 __all__ = ["CTCLoss", "CTCDecoder", "CTCEncoder", "CTCDecoderError", "DecoderResults", "NBestResults", "CTCWithoutBlankLoss",
-           "AlignedTargetsLoss", "GramCTCLoss"]
+           "AlignedTargetsLoss", "GramCTCLoss", "GramCTCDecoder", "GramNBestResults", "GramGreedyResults"]

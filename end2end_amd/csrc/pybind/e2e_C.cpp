@@ -174,6 +174,40 @@ PYBIND11_MODULE(_C, m) {
         py::arg("max_order"), py::arg("losses"), py::arg("grads"), py::arg("workspace"), py::arg("workspace_bytes"),
         py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0, py::arg("reduction") = E2E_REDUCE_NONE);
 
+  m.def("gram_ctc_greedy",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
+           uintptr_t gram_ids, uintptr_t gram_len, int max_order, uintptr_t out, uintptr_t out_len, uintptr_t cols,
+           uintptr_t cols_len, uintptr_t stream) {
+          check(e2e_gram_ctc_greedy(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V,
+                                    ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
+                                    ptr<int64_t>(out), ptr<int64_t>(out_len), ptr<int64_t>(cols), ptr<int64_t>(cols_len),
+                                    ptr<void>(stream)));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"), py::arg("out"),
+        py::arg("out_len"), py::arg("cols"), py::arg("cols_len"), py::arg("stream"));
+
+  m.def("gram_beam_max_width", [](int V, int max_order) { return e2e_gram_beam_max_width(V, max_order); });
+  m.def("gram_beam_workspace_bytes", [](int B, int T, int V, int max_order, int beam_width) {
+    return e2e_gram_beam_workspace_bytes(B, T, V, max_order, beam_width);
+  });
+
+  m.def("gram_ctc_beam_nbest",
+        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
+           uintptr_t gram_ids, uintptr_t gram_len, int max_order, int beam_width, int nbest, uintptr_t out,
+           int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t workspace,
+           size_t workspace_bytes, uintptr_t stream) {
+          check(e2e_gram_ctc_beam_nbest(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V,
+                                        ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
+                                        beam_width, nbest, ptr<int64_t>(out), max_out, ptr<int64_t>(out_len),
+                                        ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<void>(workspace), workspace_bytes,
+                                        ptr<void>(stream)));
+        },
+        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"),
+        py::arg("beam_width"), py::arg("nbest"), py::arg("out"), py::arg("max_out"), py::arg("out_len"),
+        py::arg("n_hyp"), py::arg("scores"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
+
   m.def("ctc_scale_grads",
         [](uintptr_t grads, int dtype, uintptr_t scale, int B, int64_t row_elems, uintptr_t stream) {
           check(e2e_ctc_scale_grads(ptr<void>(grads), dtype, ptr<const void>(scale), B, row_elems, ptr<void>(stream)));

@@ -1,0 +1,92 @@
+"""GramCTCDecoder: greedy and prefix beam-search decoding for models trained with GramCTCLoss.  The constructor takes the
+loss's table (``num_base_labels, total_labels, label2ids``) and CTCDecoder's decoding arguments; the return conventions are
+CTCDecoder's.  Upstream has no such decoder (its Gram-CTC engine is empty); the definition is in include/e2e_ctc.h.
+
+Not provided for Gram-CTC: language model, lexicon, timestamps, streaming, a column segmentation per beam hypothesis
+(several segmentations spell one hypothesis), ``blank_idx != 0``.
+"""
+from collections import namedtuple
+
+import torch
+
+from ..engines import GramCTCDecoderEngine
+from .ctc_decoder import CTCDecoderError, DecoderResults
+
+# decode_nbest(): (B, N, ...) per utterance and hypothesis, ranked by `scores` (the log-probability of the labelling within
+# the beam); `decoded_sentences[b]` lists the num_hypotheses[b] sentences of utterance b
+GramNBestResults = namedtuple("GramNBestResults", ["decoded_targets", "decoded_targets_lengths", "decoded_sentences",
+                                                   "scores", "num_hypotheses"])
+
+# decode_greedy(return_columns=True): also the collapsed columns -- the gram segmentation the model chose
+GramGreedyResults = namedtuple("GramGreedyResults", ["decoded_targets", "decoded_targets_lengths", "decoded_sentences",
+                                                     "columns", "columns_lengths"])
+
+
+class GramCTCDecoder:
+    """
+    :param blank_idx: index of the blank column; only ``0`` is supported (as for ``GramCTCLoss``)
+    :param num_base_labels: R, the blank counted: base ids are ``1 .. R-1``
+    :param total_labels: V, the number of columns of the logits
+    :param label2ids: ``{column: [base ids]}`` for the gram columns ``R .. V-1`` (grams of 1 to 8 base ids)
+    :param beam_width: number of hypotheses kept; ``1`` makes ``decode`` greedy (argmax) decoding, as for ``CTCDecoder``
+    :param labels: the R base-label strings including the blank's, e.g. ``["_", "a", "b"]``
+    :param after_logsoftmax: inputs are log-probabilities (greedy ignores this)
+    :param time_major: inputs are ``(time, batch, alphabet)``
+    :param keep_on_device: leave the decoded ids and lengths on the GPU
+    """
+
+    def __init__(self, blank_idx=0, num_base_labels=None, total_labels=None, label2ids=None, beam_width=100, labels=None,
+                 after_logsoftmax=False, time_major=False, keep_on_device=False):
+        if num_base_labels is None or total_labels is None:
+            raise CTCDecoderError("GramCTCDecoder needs num_base_labels and total_labels (the arguments of GramCTCLoss)")
+        self._beam_width = beam_width
+        self._after_logsoftmax = after_logsoftmax
+        self._time_major = time_major
+        self._decoder = GramCTCDecoderEngine(blank_idx, num_base_labels, total_labels, label2ids or {}, beam_width,
+                                             labels, keep_on_device=keep_on_device)
+
+    def _batch_major(self, logits, logits_lengths):
+        if self._time_major:
+            logits = logits.transpose(1, 0)
+        logits = logits.detach()
+        if logits_lengths is None:
+            logits_lengths = torch.full((logits.size(0),), logits.size(1), dtype=torch.int32, device=logits.device)
+        return logits, logits_lengths
+
+    def _logprobs(self, logits):
+        with torch.no_grad():
+            if not self._after_logsoftmax:
+                logits = torch.log_softmax(logits, -1)
+        return logits
+
+    def decode_greedy(self, logits, logits_lengths=None, return_columns=False):
+        """Arg-max column per frame, runs collapsed, blanks dropped, grams expanded: raw logits or log-probabilities.
+
+        :return: ``DecoderResults(decoded_targets (batch, time * max_order) zero padded, decoded_targets_lengths,
+            decoded_sentences)``; with ``return_columns`` a ``GramGreedyResults`` that also has ``columns (batch, time)``
+            zero padded and ``columns_lengths``
+        """
+        logits, logits_lengths = self._batch_major(logits, logits_lengths)
+        r = self._decoder.decode_greedy(logits_=logits, logits_lengths_=logits_lengths, return_columns=return_columns)
+        return GramGreedyResults(*r) if return_columns else DecoderResults(*r)
+
+    def decode(self, logits, logits_lengths=None):
+        """Prefix beam search over base-label sequences; ``beam_width == 1`` routes to greedy decoding.
+
+        :return: ``DecoderResults(decoded_targets (batch, longest), decoded_targets_lengths, decoded_sentences)``
+        """
+        if self._beam_width == 1:
+            return self.decode_greedy(logits, logits_lengths)
+        logits, logits_lengths = self._batch_major(self._logprobs(logits), logits_lengths)
+        return DecoderResults(*self._decoder.decode(logits_=logits, logits_lengths_=logits_lengths))
+
+    def decode_nbest(self, logits, logits_lengths=None, nbest=None):
+        """The hypotheses the beam search ends with, best first.
+
+        :param nbest: how many to return per utterance, at most ``beam_width`` (the default)
+        :return: ``GramNBestResults(decoded_targets (batch, nbest, longest), decoded_targets_lengths (batch, nbest),
+            decoded_sentences (a list per utterance), scores (batch, nbest), num_hypotheses (batch))``; hypothesis 0 is
+            what ``decode`` returns, slots beyond ``num_hypotheses[b]`` are empty (length 0, score -inf)
+        """
+        logits, logits_lengths = self._batch_major(self._logprobs(logits), logits_lengths)
+        return GramNBestResults(*self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest))

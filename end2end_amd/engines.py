@@ -232,11 +232,11 @@ class CTCWithoutBlankLossEngine(_LatticeLossEngine):
 GRAM_MAX_ORDER = 8
 
 
-def gram_table(num_base_labels, total_labels, label2ids):
-    """Check upstream's (num_base_labels, total_labels, label2ids) and return the gram table of e2e_gram_ctc_fwd_bwd:
-    (keys int64 sorted ascending, their columns int32, max_order), host arrays.  Column 0 is the blank, columns
-    1 .. R-1 the unigrams, every column R .. V-1 a gram of label2ids (a sequence of 1..8 base ids in [1, R)); the key of
-    a gram is its sequence read as a number in radix R (upstream's get_hash, src/losses/gram_ctc_loss.cpp:22-28)."""
+def gram_columns(num_base_labels, total_labels, label2ids):
+    """Check upstream's (num_base_labels, total_labels, label2ids) and return ({column: base-id tuple} for the columns
+    1 .. V-1, max_order, {key: column}).  Column 0 is the blank, columns 1 .. R-1 the unigrams, every column R .. V-1 a
+    gram of label2ids (a sequence of 1..8 base ids in [1, R)); the key of a gram is its sequence read as a number in radix
+    R (upstream's get_hash, src/losses/gram_ctc_loss.cpp:22-28), and keys must be distinct."""
     R, V = int(num_base_labels), int(total_labels)
     if not 1 <= R <= V:
         raise ValueError("num_base_labels %d and total_labels %d: need 1 <= num_base_labels <= total_labels" % (R, V))
@@ -267,6 +267,13 @@ def gram_table(num_base_labels, total_labels, label2ids):
         if k in keys:
             raise ValueError("columns %d and %d spell the same gram %r" % (keys[k], c, list(grams[c])))
         keys[k] = c
+    return grams, order, keys
+
+
+def gram_table(num_base_labels, total_labels, label2ids):
+    """The gram table of e2e_gram_ctc_fwd_bwd from upstream's (num_base_labels, total_labels, label2ids), checked by
+    gram_columns: (keys int64 sorted ascending, their columns int32, max_order), host arrays."""
+    _, order, keys = gram_columns(num_base_labels, total_labels, label2ids)
     ks = sorted(keys)
     return np.array(ks, dtype=np.int64), np.array([keys[k] for k in ks], dtype=np.int32), order
 
@@ -325,6 +332,136 @@ class GramCTCLossEngine(_LatticeLossEngine):
         keys, cols = self._table(dev)
         _C.gram_ctc_fwd_bwd(*call, keys.data_ptr(), cols.data_ptr(), keys.numel(), self.num_base_labels, self.max_order,
                             *out, *opts)
+
+
+class GramCTCDecoderEngine:
+    """(blank_idx, num_base_labels, total_labels, label2ids, beam_width_=100, labels=None) -> decode_greedy /
+    decode_nbest for Gram-CTC (e2e_gram_ctc_greedy, e2e_gram_ctc_beam_nbest; the definition: include/e2e_ctc.h).  The table
+    check is GramCTCLossEngine's (gram_columns); the decoders take the table spelled out -- (V,8) base ids and (V) lengths
+    -- copied to a device on first use and kept per device.  `labels`: the R base-label strings (index 0 the blank's).
+    The width limit is checked here, not at the first decode.  Results are CPU tensors unless `keep_on_device`."""
+
+    def __init__(self, blank_idx, num_base_labels, total_labels, label2ids, beam_width_=100, labels=None,
+                 keep_on_device=False):
+        if int(blank_idx) != 0:
+            raise NotImplementedError("Gram-CTC supports blank_idx=0 only (as upstream)")
+        self.blank_idx = 0
+        self.num_base_labels = int(num_base_labels)
+        self.total_labels = int(total_labels)
+        grams, self.max_order, _ = gram_columns(num_base_labels, total_labels, label2ids)
+        self._ids = np.zeros((self.total_labels, GRAM_MAX_ORDER), dtype=np.int32)
+        self._len = np.zeros(self.total_labels, dtype=np.int32)
+        for c, seq in grams.items():
+            self._ids[c, :len(seq)] = seq
+            self._len[c] = len(seq)
+        self.beam_width = int(beam_width_)
+        self.labels = list(labels or [])
+        if self.labels and len(self.labels) != self.num_base_labels:
+            raise ValueError("the decoder has %d labels but num_base_labels=%d" % (len(self.labels), self.num_base_labels))
+        self.keep_on_device = bool(keep_on_device)
+        cap = _C.gram_beam_max_width(self.total_labels, self.max_order)
+        if self.beam_width < 1 or self.beam_width > cap:
+            raise ValueError("beam_width %d is not supported for a Gram-CTC table of %d columns (max_order %d): 1 to %d"
+                             % (self.beam_width, self.total_labels, self.max_order, cap))
+        self._per_device = {}
+
+    def _table(self, dev):
+        t = self._per_device.get(dev.index)
+        if t is None:
+            t = (torch.from_numpy(self._ids).to(dev), torch.from_numpy(self._len).to(dev))
+            self._per_device[dev.index] = t
+        return t
+
+    def _prep(self, logits_, logits_lengths_, dtypes):
+        if logits_.dim() != 3:
+            raise ValueError("logits must be (batch, time, alphabet)")
+        if logits_.shape[2] != self.total_labels:
+            raise ValueError("logits have %d columns; this Gram-CTC table has total_labels=%d"
+                             % (logits_.shape[2], self.total_labels))
+        dev = R.compute_device(logits_)
+        x = logits_.detach()
+        if x.dtype not in dtypes:
+            x = x.to(torch.float32)
+        x = x.to(dev)
+        xl = _as_long(logits_lengths_, dev)
+        if xl.numel() != x.shape[0]:
+            raise ValueError("logits_lengths_ must have one entry per utterance")
+        return x, xl, dev
+
+    def _result(self, t):
+        return t if self.keep_on_device else t.cpu()
+
+    def _strings(self, rows, lens):
+        if not self.labels:
+            return ["" for _ in lens]
+        return ["".join(self.labels[k] for k in row[:n]) for row, n in zip(rows.tolist(), lens)]
+
+    def decode_greedy(self, logits_, logits_lengths_, return_columns=False):
+        """argmax + collapse + gram expansion -> (base ids (B, T*max_order) int64 zero padded, lengths (B), sentences);
+        with return_columns also (columns (B,T) int64 zero padded, their lengths (B)): the grams the model chose."""
+        x, xl, dev = self._prep(logits_, logits_lengths_, _F32_F64 + _16BIT)
+        B, T, V = x.shape
+        out = torch.empty((B, T * self.max_order), dtype=torch.long, device=dev)
+        out_len = torch.empty(B, dtype=torch.long, device=dev)
+        cols = torch.empty((B, T), dtype=torch.long, device=dev)
+        cols_len = torch.empty(B, dtype=torch.long, device=dev)
+        if B and T:
+            with torch.cuda.device(dev):
+                ids, lens = self._table(dev)
+                sB, sT, sV = x.stride()
+                _C.gram_ctc_greedy(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
+                                   ids.data_ptr(), lens.data_ptr(), self.max_order, out.data_ptr(), out_len.data_ptr(),
+                                   cols.data_ptr(), cols_len.data_ptr(), R.stream_handle(dev))
+        else:
+            out_len.zero_()
+            cols_len.zero_()
+        out, out_len = self._result(out), self._result(out_len)
+        res = (out, out_len, self._strings(out.cpu(), out_len.tolist()))
+        return res + (self._result(cols), self._result(cols_len)) if return_columns else res
+
+    def decode_nbest(self, logits_, logits_lengths_, nbest=None):
+        """Prefix beam search on LOG-PROBABILITIES, read out as an n-best list -> (base ids (B,N,maxlen) int64, lengths
+        (B,N), sentences [B][n_hyp], scores (B,N) f64 = log probability of the labelling within the beam, num_hypotheses
+        (B)).  Ranked by score, ties by the prefix key; slots beyond num_hypotheses[b] are empty (length 0, -inf)."""
+        N = self.beam_width if nbest is None else int(nbest)
+        if not 1 <= N <= self.beam_width:
+            raise ValueError("nbest=%d outside [1, beam_width=%d]" % (N, self.beam_width))
+        x, xl, dev = self._prep(logits_, logits_lengths_, _F32_F64)
+        B, T, V = x.shape
+        max_out = max(T * self.max_order, 1)
+        out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
+        out_len = torch.empty((B, N), dtype=torch.long, device=dev)
+        n_hyp = torch.empty(B, dtype=torch.long, device=dev)
+        scores = torch.empty((B, N), dtype=torch.float64, device=dev)
+        if B:
+            with torch.cuda.device(dev):
+                ids, lens = self._table(dev)
+                nbytes = _C.gram_beam_workspace_bytes(B, T, V, self.max_order, self.beam_width)
+                if not nbytes:
+                    raise ValueError("Gram-CTC beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
+                ws = R.workspace(dev, nbytes)
+                sB, sT, sV = x.stride()
+                _C.gram_ctc_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
+                                       ids.data_ptr(), lens.data_ptr(), self.max_order, self.beam_width, N,
+                                       out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), R.stream_handle(dev))
+        nh = n_hyp.tolist()
+        lens_host = out_len.tolist()
+        for b in range(B):
+            if nh[b] < 0:
+                raise R.E2EError("Gram-CTC beam search: utterance %d ran out of candidate entries" % b)
+        width = max((max(row) for row in lens_host), default=0)
+        ids_out = out[:, :, :width].contiguous()       # packed to the longest hypothesis of the batch
+        ids_host = ids_out.cpu()
+        flat = self._strings(ids_host.reshape(B * N, width), [n for row in lens_host for n in row])
+        sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+        r = self._result
+        return (ids_out if self.keep_on_device else ids_host, r(out_len), sentences, r(scores), r(n_hyp))
+
+    def decode(self, logits_, logits_lengths_):
+        """Hypothesis 0 of decode_nbest -> (base ids (B,maxlen) int64, lengths (B), sentences)."""
+        r = self.decode_nbest(logits_, logits_lengths_, nbest=1)
+        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
 
 
 class LanguageModel:

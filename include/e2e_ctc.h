@@ -227,6 +227,79 @@ int e2e_gram_ctc_fwd_bwd(const void* x, int dtype, int input_is_logprobs, int64_
                          void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_loss_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * Gram-CTC decoding: greedy, and prefix beam search read out as an n-best list (additive, ABI 4: nothing above changes
+ * meaning).  Columns and labelling are e2e_gram_ctc_fwd_bwd's: column 0 the blank, 1 .. R-1 the unigrams, R .. V-1 grams of
+ * 1..8 base ids; a path is labelled by collapsing runs of one column, dropping blanks and concatenating the grams' base
+ * sequences.  The decoders take the table spelled out, not as keys:
+ *   gram_ids   (V,8) int32, device: the base ids of every column, zero padded (row 0, the blank's, is not read)
+ *   gram_len   (V) int32, device: how many of them count, 1 .. max_order (entry 0 is not read; a value outside the range
+ *              is clamped into it: the host cannot see the table)
+ *   max_order  the longest gram, 1..8 (E2E_ERR_ARG otherwise)
+ *
+ * GREEDY.  Arg-max column per frame (ties as e2e_ctc_greedy breaks them: first maximum, NaN counts as the maximum),
+ * collapse runs, drop the blank -- e2e_ctc_greedy with blank = 0 -- then every column expanded to its base ids.
+ *   x          (B,T,V) logits or log-probs, strides sB,sT,sV; the four dtypes of e2e_ctc_greedy
+ *   out        (B, T*max_order) int64 base ids, zero padded on the right; out_len (B) int64
+ *   cols       (B,T) int64: the collapsed columns, zero padded -- the gram segmentation the model chose; cols_len (B).
+ *              Both are required: the expansion reads them.
+ *
+ * BEAM SEARCH.  A hypothesis is a base-id prefix l with up to max_order + 1 SLOTS: slot 0 the mass of the paths that end in
+ * the blank, slot k >= 1 the mass of the paths whose last column is the order-k gram that spells the last k ids of l, and
+ * that column (gram keys are distinct: there is at most one).  Before frame 0 the beam is the empty prefix with mass 1 in
+ * slot 0.  At frame t, with y = exp(lp[t]) and tot(l) the sum of l's slots:
+ *   stay, blank           new[l].slot0 += tot(l) * y[0]
+ *   stay, run continues   for every filled slot k >= 1 with column c: new[l].slotk += p_k(l) * y[c]
+ *   extend                for every column c' >= 1 of order k': src = the sum of l's slots except a slot k' that holds c';
+ *                         if src > 0 (and src * y[c'] > 0): new[l + gram(c')].slot k' += src * y[c'], its column c'
+ * Candidates that spell the same base sequence are ONE hypothesis, whichever prefixes and columns they came from.  The new
+ * beam is the beam_width hypotheses of largest tot.  A prefix that left the beam and is formed again starts from its
+ * extension shares alone.
+ *   identity   a prefix is its 64-bit key: key(empty) = 0xcbf29ce484222325, key(l + [i]) = (key(l) XOR i) * 0x100000001b3
+ *              mod 2^64.  Two different prefixes with equal keys are merged: about 2^-64 per pair, i.e. correct with
+ *              overwhelming probability, not by construction (as for the language-model tables above).  A key of 0 is
+ *              kept as 1.
+ *   ranking    everywhere -- the per-frame cut and the n-best list -- by tot descending and, for exactly equal values, by
+ *              key ascending.  A (prefix, slot) receives at most two addends, its stay share and one extension share, and
+ *              tot is the sum of the slots in the order 0 .. max_order: no result depends on the order in which the
+ *              hardware meets the candidates, and two calls on the same input agree bit for bit.
+ *   arithmetic f64 in the probability domain.  After each frame's cut every kept mass is divided by 2^e, e the binary
+ *              exponent of the best hypothesis' tot (exact), and the e are summed into the score.  Mass that reaches
+ *              exactly 0 is "not a member": a search in which underflow to 0 decides membership (probabilities some 300
+ *              decades below the frame's best) is outside what is promised to equal the rules above.
+ *   lp         (B,T,V) LOG-PROBABILITIES, strides sB,sT,sV, f32 or f64 (16-bit: up-cast first; E2E_ERR_ARG)
+ *   x_len      (B) int64, clamped to 0..T; 0 yields the empty hypothesis alone, with score 0
+ *   nbest      1 <= nbest <= beam_width, else E2E_ERR_ARG
+ *   out        (B,nbest,max_out) int64 base ids, zero filled behind each hypothesis.  The empty hypothesis has length 0;
+ *              there is no -1 id.  max_out = T * max_order can never be exceeded.
+ *   out_len    (B,nbest) int64: 0 for slots >= n_hyp[b]; > max_out = truncated, that many ids were needed and the first
+ *              max_out were written (as in e2e_ctc_beam_nbest)
+ *   n_hyp      (B) int64: min(nbest, members of the final beam) -- below nbest when fewer sequences have non-zero
+ *              probability; -1 = the candidate table or node pool ran out (cannot happen with a workspace of
+ *              e2e_gram_beam_workspace_bytes(); nothing of the utterance may be used)
+ *   scores     (B,nbest) f64: log tot, natural log; -inf in empty slots
+ *   workspace  >= e2e_gram_beam_workspace_bytes(...): per utterance the frame's probabilities, an open-addressing table
+ *              of 2 * beam_width * V keys rounded up to a power of two (16 bytes each), 28 bytes per (member, column)
+ *              pair and 8 bytes per node of the pool of beam_width * (T + 1) + 1 (parent, column) nodes
+ *              (B=64, T=1000, V=379, beam_width=100: 254 MB)
+ * Limits: beam_width <= e2e_gram_beam_max_width(V, max_order) = min(128, 131072 / V) -- 128 up to V = 1024, 100 fits the
+ * loss's headline table V = 379, 16 at V = 8000 --, T <= 2^22; beyond them E2E_ERR_UNSUPPORTED, found on the host before
+ * any launch (e2e_gram_beam_workspace_bytes then returns 0).  The call is asynchronous on `stream`, allocates nothing,
+ * never synchronises and is capturable.  Not provided for Gram-CTC: language model, lexicon, timestamps, streaming, a
+ * column segmentation per beam hypothesis (several exist), blank_idx != 0.
+ */
+int e2e_gram_ctc_greedy(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                        int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                        int64_t* out, int64_t* out_len, int64_t* cols, int64_t* cols_len, void* stream);
+
+int e2e_gram_beam_max_width(int V, int max_order);
+size_t e2e_gram_beam_workspace_bytes(int B, int T, int V, int max_order, int beam_width);
+
+int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                            int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                            int beam_width, int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                            double* scores, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Greedy decode.  Replaces cpp_ctc_decoder.CTCDecoder.decode_greedy
  *   src/decoders/ctc_decoder.cpp:443-490 (argmax + blank/repeat collapse).
  *   x        (B,T,V) logits or log-probs, strides sB,sT,sV, f32/f64
