@@ -11,7 +11,9 @@ from .decoders.gram_ctc_decoder import GramCTCDecoder, GramGreedyResults, GramNB
 from .encoders.text_encoders import CTCEncoder
 from .modules.alignment_loss import AlignedTargetsLoss
 from .modules.ctc_loss import CTCLoss, GramCTCLoss
+from .modules.ctc_loss_segmented import CTCLossSegmented
 from .modules.ctc_without_blank import CTCWithoutBlankLoss
 
 __all__ = ["CTCLoss", "CTCDecoder", "CTCEncoder", "CTCDecoderError", "DecoderResults", "NBestResults", "CTCWithoutBlankLoss",
-           "AlignedTargetsLoss", "GramCTCLoss", "GramCTCDecoder", "GramNBestResults", "GramGreedyResults"]
+           "AlignedTargetsLoss", "GramCTCLoss", "GramCTCDecoder", "GramNBestResults", "GramGreedyResults",
+           "CTCLossSegmented"]

@@ -148,6 +148,19 @@ def load():
         L.e2e_ctc_align.restype = C.c_int
         L.e2e_ctc_align.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64, vp, C.c_size_t, vp]
+        L.e2e_ctc_wordseg_table_elems.restype = C.c_size_t
+        L.e2e_ctc_wordseg_table_elems.argtypes = [C.c_int] * 2
+        L.e2e_ctc_wordseg_workspace_bytes.restype = C.c_size_t
+        L.e2e_ctc_wordseg_workspace_bytes.argtypes = [C.c_int] * 2
+        L.e2e_ctc_wordseg_plan.restype = C.c_int
+        L.e2e_ctc_wordseg_plan.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64p, i64, i64p, i64p] + [C.c_int] * 7 + \
+                                          [vp, C.c_size_t, i64p, vp, C.c_size_t, vp]
+        L.e2e_ctc_wordseg_gather.restype = C.c_int
+        L.e2e_ctc_wordseg_gather.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p] + [C.c_int] * 4 + \
+                                            [vp, i64p, vp, C.c_int, C.c_int, C.c_int, vp, i64p, i64p, i64p, vp]
+        L.e2e_ctc_wordseg_finish.restype = C.c_int
+        L.e2e_ctc_wordseg_finish.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                             C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
         L.e2e_debug_gram_redo_flags.restype = C.c_int
         L.e2e_debug_gram_redo_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.e2e_debug_noblank_redo_flags.restype = C.c_int

@@ -312,6 +312,59 @@ PYBIND11_MODULE(_C, m) {
         py::arg("Smax"), py::arg("blank"), py::arg("is_ctc"), py::arg("out"), py::arg("pad_value"),
         py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
 
+  m.attr("WORDSEG_HEADER") = E2E_WORDSEG_HEADER;
+  m.attr("WORDSEG_WHOLE") = E2E_WORDSEG_WHOLE;
+  m.attr("WORDSEG_FRAME") = E2E_WORDSEG_FRAME;
+  m.attr("WORDSEG_CHUNK") = E2E_WORDSEG_CHUNK;
+  m.def("ctc_wordseg_table_elems", [](int B, int T) { return e2e_ctc_wordseg_table_elems(B, T); });
+  m.def("ctc_wordseg_workspace_bytes", [](int B, int T) { return e2e_ctc_wordseg_workspace_bytes(B, T); });
+
+  m.def("ctc_wordseg_plan",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t align, uintptr_t targets,
+           int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, int blank, int space,
+           int min_word_length, uintptr_t table, size_t table_elems, uintptr_t pool, uintptr_t workspace,
+           size_t workspace_bytes, uintptr_t stream) {
+          check(e2e_ctc_wordseg_plan(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(align),
+                                     ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
+                                     ptr<const int64_t>(t_len), B, T, V, Smax, blank, space, min_word_length,
+                                     ptr<int32_t>(table), table_elems, ptr<int64_t>(pool), ptr<void>(workspace),
+                                     workspace_bytes, ptr<void>(stream)));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("align"), py::arg("targets"),
+        py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"), py::arg("V"),
+        py::arg("Smax"), py::arg("blank"), py::arg("space"), py::arg("min_word_length"), py::arg("table"),
+        py::arg("table_elems"), py::arg("pool"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
+
+  m.def("ctc_wordseg_gather",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets, int64_t tgt_stride,
+           uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, uintptr_t table, uintptr_t pool,
+           uintptr_t idx, int n_idx, int L, int S, uintptr_t xg, uintptr_t tg, uintptr_t xlg, uintptr_t tlg,
+           uintptr_t stream) {
+          check(e2e_ctc_wordseg_gather(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(targets), tgt_stride,
+                                       ptr<const int64_t>(x_len), ptr<const int64_t>(t_len), B, T, V, Smax,
+                                       ptr<const int32_t>(table), ptr<const int64_t>(pool), ptr<const int32_t>(idx),
+                                       n_idx, L, S, ptr<void>(xg), ptr<int64_t>(tg), ptr<int64_t>(xlg),
+                                       ptr<int64_t>(tlg), ptr<void>(stream)));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("targets"),
+        py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"), py::arg("V"),
+        py::arg("Smax"), py::arg("table"), py::arg("pool"), py::arg("idx"), py::arg("n_idx"), py::arg("L"), py::arg("S"),
+        py::arg("xg"), py::arg("tg"), py::arg("xlg"), py::arg("tlg"), py::arg("stream"));
+
+  m.def("ctc_wordseg_finish",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t align, int B, int T, int V,
+           uintptr_t table, uintptr_t g_grads, uintptr_t g_losses, uintptr_t g_idx, int n_idx, int L, bool last,
+           uintptr_t losses, uintptr_t grads, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
+          check(e2e_ctc_wordseg_finish(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(align), B, T, V,
+                                       ptr<const int32_t>(table), ptr<const void>(g_grads), ptr<const void>(g_losses),
+                                       ptr<const int32_t>(g_idx), n_idx, L, last ? 1 : 0, ptr<void>(losses),
+                                       ptr<void>(grads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream)));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("align"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("table"), py::arg("g_grads"), py::arg("g_losses"), py::arg("g_idx"),
+        py::arg("n_idx"), py::arg("L"), py::arg("last"), py::arg("losses"), py::arg("grads"), py::arg("workspace"),
+        py::arg("workspace_bytes"), py::arg("stream"));
+
   py::class_<LanguageModel>(m, "LanguageModel")
       .def(py::init<const std::string&, const std::vector<std::string>&, bool>(), py::arg("path"), py::arg("labels"),
            py::arg("case_sensitive"))

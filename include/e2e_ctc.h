@@ -544,6 +544,95 @@ int e2e_ctc_align(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
                   int64_t* out, int64_t pad_value,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Word-segmented CTC: plan, gather, finish (additive, ABI 4: nothing above changes meaning).
+ * Replaces the host loops of pytorch_end2end/modules/ctc_loss_segmented.py:43-146 (CTCLossSegmented.forward): find the
+ * words the model already recognises frame for frame, cut every utterance at the spaces around them, train each piece with
+ * its own CTC loss.  The alignment comes from e2e_ctc_align and the pieces' losses from e2e_ctc_loss_fwd_bwd; these three
+ * calls are what lies between.  They are asynchronous on `stream`, allocate nothing, never synchronise and are capturable;
+ * every argument error the host can see is E2E_ERR_ARG before any launch.
+ *
+ * DEFINITION.  Per utterance, n = x_len[b]; a[t] = align[b,t] (e2e_ctc_align on log_softmax(x), is_ctc = 1); p[t] the
+ * arg-max column of x[b,t,:], first maximum, NaN counts as the maximum (as e2e_ctc_greedy).
+ *   boundaries  State bounds = [0], start_space = -1, clean = 1, wl = 0, last = -1, last_blank = 0.  For t = 0 .. n-1:
+ *                 a[t] != p[t]      clean = 0, nothing else changes;
+ *                 a[t] == space     if clean and wl >= min_word_length: append start_space if start_space != -1 and
+ *                                   bounds[-1] != start_space; append t if t > 0.  In every case start_space = t,
+ *                                   clean = 1, wl = 0, last = -1, last_blank = 0;
+ *                 a[t] == blank     last_blank = 1 (the space test comes first);
+ *                 else              wl += 1 if last_blank or a[t] != last; last = a[t], last_blank = 0.
+ *               After the loop n-1 is appended if bounds[-1] != n-1.
+ *   segments    len(bounds) <= 2, lengths outside 1 <= x_len <= T, 0 <= t_len <= Smax, or a target outside [0,V): ONE
+ *               WHOLE segment, frames 0 .. n-1 with the caller's targets and lengths (out of range: the loss gives it
+ *               its NaN slab).  Otherwise for k, start in enumerate(bounds[:-1]): if start != 0 a FRAME segment, the
+ *               single frame `start` with the target [a[start]], and start += 1; end = bounds[k+1], minus 1 unless k is
+ *               the last; if end >= start a CHUNK, frames start .. end, whose target is a[start..end] with runs collapsed
+ *               and blanks dropped afterwards (a a _ a gives a a).  The segments partition the frames 0 .. n-1.
+ *               (Upstream counts the segments before it builds them and raises where the two disagree -- a qualifying
+ *               space on the last frame, a first boundary at frame 1; here the built list is the definition.)
+ *
+ * PLAN.
+ *   x           (B,T,V) raw logits, strides sB,sT,sV (any), E2E_F32 or E2E_F64
+ *   align       (B,T) int64 contiguous
+ *   targets, tgt_stride, x_len, t_len, Smax   as for e2e_ctc_loss_fwd_bwd
+ *   blank, space  in [0,V); min_word_length any int (<= 0: every clean space qualifies)
+ *   table       int32, e2e_ctc_wordseg_table_elems(B,T) = 16 + (B+1) + 5*B*T elements, written:
+ *                 [0] N segments  [1] whole  [2] frame  [3] chunk segments  [4] the longest whole / chunk segment in
+ *                 frames  [5] its longest target  [6] utterances that were cut  [7..15] 0
+ *                 [16 .. 16+B]  first segment of every utterance, and N behind them
+ *                 then five arrays of B*T entries, the first N used, utterance-major and in the order above: length in
+ *                 frames, target length, kind (E2E_WORDSEG_*), utterance, start frame.
+ *               At most sum(x_len) <= B*T segments exist.  Counting is deterministic: per-utterance counts, then a scan.
+ *   pool        (B,T) int64: the target of a chunk or frame segment that starts at frame s of utterance b is
+ *               pool[b, s .. s + target length) -- a chunk has at most as many labels as frames
+ *   workspace   >= e2e_ctc_wordseg_workspace_bytes(B,T), 26 bytes per frame.  It carries the plan's per-frame state to
+ *               the gather and finish calls of the same batch: nothing else may write it in between.
+ *
+ * GATHER.  For the n_idx table indices in idx (device; whole segments and chunks -- frame segments are never gathered; an
+ * index outside [0,N) gives an empty row) writes the dense zero-padded batch e2e_ctc_loss_fwd_bwd takes:
+ *   xg (n_idx,L,V) contiguous, x's dtype;  tg (n_idx,S) int64;  xlg, tlg (n_idx) int64
+ *   L, S        >= the longest listed segment / target (1 <= L <= T, S >= 1); longer ones are cut, which the host avoids
+ * A whole segment hands on the caller's own lengths and targets.
+ *
+ * FINISH.  Called once per gathered batch and a last time with last = 1 (n_idx = 0 allowed):
+ *   g_grads (n_idx,L,V), g_losses (n_idx)   what the loss returned for the batch gathered with g_idx, L; x's dtype
+ *   grads       (B,T,V) contiguous: every listed segment's rows are copied to its own frames (plain stores; the frames
+ *               are disjoint)
+ *   last        != 0: also writes the frames no gathered segment owns -- a frame segment in closed form in f64, loss
+ *               logsumexp(x_t) - x_t[c], gradient softmax(x_t) - onehot(c); frames t >= x_len[b] 0 (the rest of the NaN
+ *               slab for an utterance that is one segment with a loss that is not finite) -- and
+ *   losses      (B) x's dtype: the f64 sum of the utterance's segment losses in table order, so that two calls on the
+ *               same input agree bit for bit; +inf and NaN propagate per utterance.
+ */
+#define E2E_WORDSEG_HEADER 16
+#define E2E_WORDSEG_WHOLE 0
+#define E2E_WORDSEG_FRAME 1
+#define E2E_WORDSEG_CHUNK 2
+
+size_t e2e_ctc_wordseg_table_elems(int B, int T);
+size_t e2e_ctc_wordseg_workspace_bytes(int B, int T);
+
+int e2e_ctc_wordseg_plan(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                         const int64_t* align, const int64_t* targets, int64_t tgt_stride,
+                         const int64_t* x_len, const int64_t* t_len,
+                         int B, int T, int V, int Smax, int blank, int space, int min_word_length,
+                         int32_t* table, size_t table_elems, int64_t* pool,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+int e2e_ctc_wordseg_gather(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                           const int64_t* targets, int64_t tgt_stride,
+                           const int64_t* x_len, const int64_t* t_len,
+                           int B, int T, int V, int Smax,
+                           const int32_t* table, const int64_t* pool,
+                           const int32_t* idx, int n_idx, int L, int S,
+                           void* xg, int64_t* tg, int64_t* xlg, int64_t* tlg, void* stream);
+
+int e2e_ctc_wordseg_finish(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                           const int64_t* align, int B, int T, int V, const int32_t* table,
+                           const void* g_grads, const void* g_losses, const int32_t* g_idx, int n_idx, int L,
+                           int last, void* losses, void* grads,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
