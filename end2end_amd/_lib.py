@@ -81,6 +81,21 @@ def load():
         L.e2e_gram_ctc_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
                                            C.c_int, C.c_int, C.c_int, C.c_int, i64p, vp, C.c_int, C.c_int, C.c_int,
                                            vp, vp, vp, C.c_size_t, vp, C.POINTER(LossOpts)]
+        L.e2e_asg_max_labels.restype = C.c_int
+        L.e2e_asg_max_labels.argtypes = []
+        L.e2e_asg_max_target_length.restype = C.c_int
+        L.e2e_asg_max_target_length.argtypes = []
+        L.e2e_asg_workspace_bytes.restype = C.c_size_t
+        L.e2e_asg_workspace_bytes.argtypes = [C.c_int] * 5
+        L.e2e_asg_fwd_bwd.restype = C.c_int
+        L.e2e_asg_fwd_bwd.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, i64, i64p, i64p,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t, vp,
+                                      C.POINTER(LossOpts)]
+        L.e2e_asg_viterbi_workspace_bytes.restype = C.c_size_t
+        L.e2e_asg_viterbi_workspace_bytes.argtypes = [C.c_int] * 3
+        L.e2e_asg_viterbi.restype = C.c_int
+        L.e2e_asg_viterbi.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, C.c_int, C.c_int, C.c_int,
+                                      i64p, i64, vp, i64p, i64p, vp, C.c_size_t, vp]
         L.e2e_gram_ctc_greedy.restype = C.c_int
         L.e2e_gram_ctc_greedy.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
                                           i64p, i64p, i64p, i64p, vp]

@@ -174,6 +174,45 @@ PYBIND11_MODULE(_C, m) {
         py::arg("max_order"), py::arg("losses"), py::arg("grads"), py::arg("workspace"), py::arg("workspace_bytes"),
         py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0, py::arg("reduction") = E2E_REDUCE_NONE);
 
+  m.def("asg_max_labels", [] { return e2e_asg_max_labels(); });
+  m.def("asg_max_target_length", [] { return e2e_asg_max_target_length(); });
+  m.def("asg_workspace_bytes", [](int B, int T, int V, int Smax, int dtype) {
+    return e2e_asg_workspace_bytes(B, T, V, Smax, dtype);
+  });
+
+  m.def("asg_fwd_bwd",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t targets,
+           int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, uintptr_t losses,
+           uintptr_t grads, uintptr_t tgrads, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
+           double grad_scale) {
+          if (dtype != E2E_F32 && dtype != E2E_F64) throw py::value_error("asg_fwd_bwd: dtype must be F32 or F64");
+          e2e_ctc_loss_opts o{grad_scale, nullptr, E2E_REDUCE_NONE, E2E_CHAINS_F64};
+          check(e2e_asg_fwd_bwd(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
+                                ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
+                                ptr<const int64_t>(t_len), B, T, V, Smax, ptr<void>(losses), ptr<void>(grads),
+                                ptr<void>(tgrads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
+        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
+        py::arg("V"), py::arg("Smax"), py::arg("losses"), py::arg("grads"), py::arg("tgrads"), py::arg("workspace"),
+        py::arg("workspace_bytes"), py::arg("stream"), py::arg("grad_scale") = 1.0);
+
+  m.def("asg_viterbi_workspace_bytes", [](int B, int T, int V) { return e2e_asg_viterbi_workspace_bytes(B, T, V); });
+
+  m.def("asg_viterbi",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t x_len, int B,
+           int T, int V, uintptr_t path, int64_t pad_value, uintptr_t scores, uintptr_t collapsed, uintptr_t lengths,
+           uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
+          check(e2e_asg_viterbi(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
+                                ptr<const int64_t>(x_len), B, T, V, ptr<int64_t>(path), pad_value, ptr<double>(scores),
+                                ptr<int64_t>(collapsed), ptr<int64_t>(lengths), ptr<void>(workspace), workspace_bytes,
+                                ptr<void>(stream)));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
+        py::arg("x_len"), py::arg("B"), py::arg("T"), py::arg("V"), py::arg("path"), py::arg("pad_value"),
+        py::arg("scores"), py::arg("collapsed"), py::arg("lengths"), py::arg("workspace"), py::arg("workspace_bytes"),
+        py::arg("stream"));
+
   m.def("gram_ctc_greedy",
         [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
            uintptr_t gram_ids, uintptr_t gram_len, int max_order, uintptr_t out, uintptr_t out_len, uintptr_t cols,

@@ -1,3 +1,3 @@
-from .text_encoders import CTCEncoder
+from .text_encoders import ASGEncoder, CTCEncoder
 
-__all__ = ["CTCEncoder"]
+__all__ = ["CTCEncoder", "ASGEncoder"]

@@ -18,6 +18,8 @@ to the C ABI (include/e2e_ctc.h) through the pybind11 layer `end2end_amd._C`.  C
 and the loss results moved back to the source device and dtype (forward_backward.cpp:55-56); decode results are CPU
 tensors as upstream (ctc_decoder.cpp:157,449) unless `keep_on_device` is set.
 """
+import threading
+
 import numpy as np
 import torch
 
@@ -227,6 +229,120 @@ class CTCWithoutBlankLossEngine(_LatticeLossEngine):
 
     def _launch(self, dev, call, out, opts):
         _C.ctc_noblank_fwd_bwd(*call, self.space_idx, *out, *opts)
+
+
+def _asg_check(V, Smax=0):
+    """The limits of the ASG kernels (e2e_asg_max_labels, e2e_asg_max_target_length), as a ValueError that states them."""
+    max_v, max_s = _C.asg_max_labels(), _C.asg_max_target_length()
+    if not 1 <= V <= max_v:
+        raise ValueError("ASG: an alphabet of %d columns is not supported: 1 to %d (exp(transitions) lives in one "
+                         "workgroup's LDS)" % (V, max_v))
+    if Smax > max_s:
+        raise ValueError("ASG: targets of %d labels are not supported: at most %d" % (Smax, max_s))
+
+
+def _asg_transitions(transitions, V, dev, dtype):
+    if transitions.dim() != 2 or transitions.shape[0] != V or transitions.shape[1] != V:
+        raise ValueError("transitions must be (%d, %d) for emissions of %d columns, not %s"
+                         % (V, V, V, tuple(transitions.shape)))
+    return transitions.detach().to(device=dev, dtype=dtype).contiguous()
+
+
+_asg_call = threading.local()           # the transitions of the compute() in flight on this thread, and its slab buffer
+
+
+class ASGLossEngine(_LatticeLossEngine):
+    """.compute(emissions, transitions, targets, logits_lengths, targets_lengths) -> (losses[B], grads[B,T,V],
+    tgrads[B,V,V]) for ASG with learned transitions, computed by e2e_asg_fwd_bwd (the definition: include/e2e_ctc.h).
+    `transitions[j, i]` scores label j after label i; `tgrads[b]` is the utterance's own transition gradient.  The device
+    and dtype contract is _ForwardBackwardEngine.compute's: any strides, CPU tensors in give CPU tensors out, losses and
+    grads come back in the emissions' dtype; 16-bit inputs are up-cast to f32, and `tgrads` then stays f32 (a sum over the
+    frames has no place in 16 bits).  The kernels keep every cell in f64 and have no
+    redo route, so there are no redo flags to read."""
+
+    def __init__(self, num_labels=None):
+        self.num_labels = None if num_labels is None else int(num_labels)
+        if self.num_labels is not None:
+            _asg_check(self.num_labels)
+
+    def _check(self, V):
+        if self.num_labels is not None and V != self.num_labels:
+            raise ValueError("emissions have %d columns; this ASG engine was made for %d" % (V, self.num_labels))
+        _asg_check(V)
+
+    def _workspace_bytes(self, B, T, V, Smax, code):
+        _asg_check(V, Smax)
+        return _C.asg_workspace_bytes(B, T, V, Smax, code)
+
+    def _launch(self, dev, call, out, opts):
+        x, code, _, sB, sT, sV, targets, tgt_stride, xl, tl, B, T, V, Smax = call
+        A = _asg_call.transitions
+        tgrads = _asg_call.tgrads = torch.empty((B, V, V), dtype=A.dtype, device=dev)
+        _C.asg_fwd_bwd(x, code, sB, sT, sV, A.data_ptr(), targets, tgt_stride, xl, tl, B, T, V, Smax,
+                       out[0], out[1], tgrads.data_ptr(), out[2], out[3], opts[0], opts[1])
+
+    def compute(self, emissions, transitions, targets, logits_lengths, targets_lengths, grad_scale=1.0):
+        """`emissions` is batch-major (B,T,V) unnormalised scores (any strides), `transitions` (V,V).  `grad_scale`
+        multiplies both gradients as the kernels write them."""
+        if emissions.dim() != 3:
+            raise ValueError("emissions must be (batch, time, alphabet)")
+        B, _, V = emissions.shape
+        self._check(V)
+        dev = R.compute_device(emissions)
+        dtype = emissions.dtype if emissions.dtype in _F32_F64 else torch.float32
+        _asg_call.transitions = _asg_transitions(transitions, V, dev, dtype)
+        _asg_call.tgrads = None
+        try:
+            losses, grads = super().compute(emissions, targets, logits_lengths, targets_lengths, True, grad_scale)
+            tgrads = _asg_call.tgrads
+        finally:
+            _asg_call.transitions = _asg_call.tgrads = None
+        if tgrads is None:                   # an empty batch: nothing was launched
+            tgrads = torch.zeros((B, V, V), dtype=dtype, device=dev)
+        if tgrads.device != emissions.device:
+            tgrads = tgrads.to(emissions.device)
+        return losses, grads, tgrads
+
+
+class ASGViterbiEngine:
+    """.compute(emissions, transitions, logits_lengths) -> (paths (B,T) int64 padded with `pad_value`, scores (B) f64,
+    collapsed (B,T) int64 zero padded, lengths (B) int64): the best path of e2e_asg_viterbi (include/e2e_ctc.h).
+    Results are CPU tensors, as the other decoders' are, unless `keep_on_device`."""
+
+    def __init__(self, pad_value=-100, keep_on_device=False):
+        self.pad_value = int(pad_value)
+        self.keep_on_device = bool(keep_on_device)
+
+    def compute(self, emissions, transitions, logits_lengths):
+        if emissions.dim() != 3:
+            raise ValueError("emissions must be (batch, time, alphabet)")
+        B, T, V = emissions.shape
+        _asg_check(V)
+        dev = R.compute_device(emissions)
+        x = emissions.detach().to(dev)
+        if x.dtype not in _F32_F64:
+            x = x.to(torch.float32)
+        A = _asg_transitions(transitions, V, dev, x.dtype)
+        xl = _as_long(logits_lengths, dev)
+        if xl.numel() != B:
+            raise ValueError("logits_lengths must have one entry per utterance")
+        path = torch.empty((B, T), dtype=torch.long, device=dev)
+        coll = torch.empty((B, T), dtype=torch.long, device=dev)
+        scores = torch.empty(B, dtype=torch.float64, device=dev)
+        lengths = torch.empty(B, dtype=torch.long, device=dev)
+        if B and T:
+            stream = R.stream_handle(dev)
+            with _on_device(dev):
+                ws = R.workspace(dev, _C.asg_viterbi_workspace_bytes(B, T, V), stream)
+                sB, sT, sV = x.stride()
+                _C.asg_viterbi(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr(), xl.data_ptr(), B, T, V,
+                               path.data_ptr(), self.pad_value, scores.data_ptr(), coll.data_ptr(), lengths.data_ptr(),
+                               ws.data_ptr(), ws.numel(), stream)
+        else:
+            lengths.zero_()
+            scores.fill_(float("nan"))
+        out = (path, scores, coll, lengths)
+        return out if self.keep_on_device else tuple(t.cpu() for t in out)
 
 
 GRAM_MAX_ORDER = 8

@@ -227,6 +227,68 @@ int e2e_gram_ctc_fwd_bwd(const void* x, int dtype, int input_is_logprobs, int64_
                          void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_loss_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * ASG, the Auto Segmentation Criterion with learned transitions (additive, ABI 4; Collobert et al. 2016, arXiv:1609.03193).
+ * Upstream names it (ASGEncoder raises NotImplementedError, pytorch_end2end/encoders/text_encoders.py) and has no loss.
+ * The definition, with n = x_len[b], s = t_len[b], y = targets[b, :s]:
+ *   path score   score(pi) = sum_{t<n} x[b,t,pi_t] + sum_{1<=t<n} A[pi_t, pi_{t-1}]; no start or end transition, and no
+ *                softmax anywhere: x holds unnormalised scores
+ *   FCC_b        log sum over all pi in {0..V-1}^n of exp(score(pi)): the fully connected graph
+ *   FAL_b        log sum over the alignments k of exp(score(y_k(0) .. y_k(n-1))), k(0) = 0, k(n-1) = s-1,
+ *                k(t) - k(t-1) in {0, 1}.  Alignments are counted by k, not by the labels they spell: with a repeated
+ *                label (a a) the entry A[a,a] carries mass both as "stay" and as "advance"
+ *   loss_b       FCC_b - FAL_b >= 0
+ * e2e_asg_fwd_bwd:
+ *   x            (B,T,V) emissions with element strides sB,sT,sV (any strides); E2E_F32 or E2E_F64 only -- the Python
+ *                engine up-casts 16-bit inputs to f32 before the call
+ *   transitions  (V,V) contiguous, x's dtype: A[j,i] (row = to, column = from: the wav2letter / flashlight layout) is
+ *                the score of label j at frame t after label i at frame t-1.  Finite numbers; -inf is not supported
+ *   targets      (B,*) int64, row stride tgt_stride, first t_len[b] entries used; what lies beyond them is never read
+ *   x_len,t_len  (B) int64 (1 <= x_len[b] <= T, 1 <= t_len[b] <= Smax: an empty target has no ASG lattice).  Lengths
+ *                outside these ranges or a target outside [0,V) give loss = NaN, a NaN gradient slab and a NaN tgrads
+ *                slab for that utterance only
+ *   losses       (B) x's dtype; +inf for an infeasible utterance (x_len[b] < t_len[b]), whose rows t < x_len[b] of grads
+ *                and whose tgrads slab are then NaN
+ *   grads        (B,T,V) contiguous, x's dtype: grad_scale * (P_fcc(pi_t = v) - P_fal(pi_t = v)) on rows t < x_len[b],
+ *                0 beyond
+ *   tgrads       (B,V,V) contiguous, x's dtype: per utterance grad_scale * sum_{1<=t<n} (P_fcc(pi_t = j, pi_{t-1} = i)
+ *                - P_fal(the same)); the parameter's gradient is the caller's sum_b w_b tgrads[b]
+ *   workspace    >= e2e_asg_workspace_bytes(...) bytes: log alpha of both recurrences and the pair sums in f64,
+ *                8 * (B*T*V + B*V*V + B + B*T*max(Smax,1)) bytes and alignment (B=256, T=1000, V=29, Smax=200: 471 MB;
+ *                B=64, T=256, V=128, Smax=60: 33 MB)
+ *   opts         NULL, or e2e_ctc_loss_opts: grad_scale multiplies both gradients; a reduction other than
+ *                E2E_REDUCE_NONE returns E2E_ERR_UNSUPPORTED (sum the B losses); `chains` is ignored
+ * All cells are f64 for both dtypes; the dense recurrence shifts every step by its row maximum, so there is no redo
+ * route and nothing to read back.  Results are bit-identical from call to call and stream to stream (no atomics).
+ * Limits (e2e_asg_max_labels, e2e_asg_max_target_length): 1 <= V <= 128 -- exp(A) lives in one workgroup's LDS, 132 KB of
+ * 160 at V = 128 -- and Smax <= 512; every T.  Beyond them the call returns E2E_ERR_UNSUPPORTED and the workspace
+ * queries return 0.
+ *
+ * e2e_asg_viterbi, the best path: delta_0[j] = x[0,j]; delta_t[j] = (max_i (delta_{t-1}[i] + A[j,i])) + x[t,j], evaluated
+ * in f64 in exactly this order (f32 inputs convert exactly).  Ties go to the lowest i; the end state is the lowest j of the
+ * largest delta_{n-1}.
+ *   x, transitions, x_len   as above (no targets)
+ *   path         (B,T) int64: the label of every frame t < x_len[b], pad_value beyond
+ *   scores       (B) f64: the path's score (for every dtype of x)
+ *   collapsed    (B,T) int64: the path with consecutive repeats merged, zero filled on the right; lengths (B) int64
+ *   workspace    >= e2e_asg_viterbi_workspace_bytes(...) bytes: one-byte back-pointers, B*T*V bytes
+ * An utterance with x_len[b] outside [1,T] gets a path of pad_value, score NaN and length 0.
+ */
+int e2e_asg_max_labels(void);
+int e2e_asg_max_target_length(void);
+size_t e2e_asg_workspace_bytes(int B, int T, int V, int Smax, int dtype);
+
+int e2e_asg_fwd_bwd(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                    const int64_t* targets, int64_t tgt_stride, const int64_t* x_len, const int64_t* t_len,
+                    int B, int T, int V, int Smax, void* losses, void* grads, void* tgrads, void* workspace,
+                    size_t workspace_bytes, void* stream, const e2e_ctc_loss_opts* opts);
+
+size_t e2e_asg_viterbi_workspace_bytes(int B, int T, int V);
+
+int e2e_asg_viterbi(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                    const int64_t* x_len, int B, int T, int V, int64_t* path, int64_t pad_value, double* scores,
+                    int64_t* collapsed, int64_t* lengths, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Gram-CTC decoding: greedy, and prefix beam search read out as an n-best list (additive, ABI 4: nothing above changes
  * meaning).  Columns and labelling are e2e_gram_ctc_fwd_bwd's: column 0 the blank, 1 .. R-1 the unigrams, R .. V-1 grams of
  * 1..8 base ids; a path is labelled by collapsing runs of one column, dropping blanks and concatenating the grams' base

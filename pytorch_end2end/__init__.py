@@ -8,7 +8,8 @@ tests import (`pytorch_end2end.modules.ctc_loss`, `.decoders.ctc_decoder`, `.enc
 `.modules.alignment_loss`, `.utils.alignment`).  The numba back-ends of CTC without blank and of the alignment run as HIP
 kernels here, and so does Gram-CTC (`.modules.ctc_loss.GramCTCLoss`, an empty stub upstream).
 Segmented CTC (`.modules.ctc_loss_segmented.CTCLossSegmented`, not importable upstream: a broken import) runs on the GPU
-too.
+too.  ASG, which upstream names and leaves unimplemented (`.encoders.ASGEncoder`), is served as
+`.encoders.ASGEncoder`, `.modules.asg_loss.ASGLoss` and `.decoders.ASGDecoder`.
 """
 from end2end_amd import CTCDecoder, CTCDecoderError, CTCEncoder, CTCLoss, DecoderResults
 

@@ -1,1 +1,1 @@
-from .text_encoders import CTCEncoder  # noqa: F401
+from .text_encoders import ASGEncoder, CTCEncoder  # noqa: F401

@@ -1,1 +1,1 @@
-from end2end_amd.encoders.text_encoders import CTCEncoder  # noqa: F401
+from end2end_amd.encoders.text_encoders import ASGEncoder, CTCEncoder  # noqa: F401
