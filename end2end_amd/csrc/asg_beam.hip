@@ -1,0 +1,526 @@
+// ASG prefix beam search with transitions and a word language model (the definition: include/e2e_ctc.h, beside the ASG loss).
+//
+// One workgroup per utterance, serial in t.  The beam's members (up to 128 label sequences: log mass, last label, 64-bit key,
+// read-out node and, with a model, the LM fields of ctc_beam.hip's prefixes) live in LDS, double buffered.
+//
+// What makes this search simpler than the Gram-CTC one (ctc_gram_decode.hip) is that a sequence has ONE parent: the candidate
+// y + (c) is reached by the pair (member y, label c) and by nothing else, so two pairs never meet.  A pair can only meet a
+// MEMBER -- the one that is y + (c) already and also stays.  So there is no table of candidates in memory: the members' keys sit in
+// a 512-slot open-addressing table in LDS, every pair looks its key up there, and a pair that finds a member leaves its share
+// in that member's `ext` cell (one writer: the parent is unique).  A candidate's mass is then log-sum(stay, ext) -- two terms,
+// symmetric in its arguments -- or the pair's share alone; no atomics on numbers, the same bits on every call.
+// The per-frame cut is ctc_gram_decode.hip's: an exact filter (a full beam's members are W candidates themselves: nothing below
+// the least of their new totals survives), a radix select on the order-preserving bits of the totals, ties cut by a second select
+// on the keys; the survivors are ranked (total descending, key ascending) and become the next members in that order.
+// The read-out walks the (parent node, label) pool backwards.
+//
+// The transitions are read from an f64 copy in the workspace, transposed to [from][to] by a small kernel of the same call: the
+// pairs of one member read one contiguous row (see DESIGN.md 4.10 for why not LDS).
+#include <cstring>
+#include <type_traits>
+
+#include "ctc_lm.h"
+
+namespace e2e {
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kMaxW = 128;                 // members of a beam (LDS)
+constexpr int kMaxV = 128;                 // e2e_asg_max_labels()
+constexpr int kMaxPairs = 16384;           // beam_width * V
+constexpr int kSlots = 512;                // the members' key table (<= 25 % full)
+constexpr uint64_t kKeyBasis = 0xcbf29ce484222325ull, kKeyPrime = 0x100000001b3ull;
+constexpr uint64_t kHashMul = 0x9e3779b97f4a7c15ull;
+constexpr unsigned long long kNoCand = 0ull;   // okey() of nothing: below every number's key (okey(-inf) = 0x000f...f)
+
+// order-preserving map double -> uint64 (larger double <=> larger key); -0.0 and +0.0 share one
+__device__ __forceinline__ unsigned long long okey(double d) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(d + 0.0);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double okey_inv(unsigned long long k) {
+  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
+}
+// log(exp(a) + exp(b)), symmetric in a and b (so no result depends on which share is called which); -inf is "no share"
+__device__ __forceinline__ double lse_sym(double a, double b) {
+  const double hi = a > b ? a : b, lo = a > b ? b : a;
+  if (lo == ninf()) return hi;
+  return hi + log1p(exp(lo - hi));
+}
+__device__ __forceinline__ unsigned long long child_key(unsigned long long key, int c) {
+  const unsigned long long k = (key ^ (unsigned long long)(unsigned)c) * kKeyPrime;
+  return k == 0ull ? 1ull : k;
+}
+
+struct Members {
+  double s[kMaxW];                       // log mass
+  unsigned long long key[kMaxW];
+  int last[kMaxW];                       // last label; -1: the root (frame 0 only)
+  int node[kMaxW], len[kMaxW], nw[kMaxW];
+};
+// the LM fields of a member (ctc_beam.hip's LmFields, as arrays)
+struct LmMembers {
+  unsigned long long hash[kMaxW];        // running FNV hash of the last word's expanded spelling
+  double lm[kMaxW], lmb[kMaxW];          // lm_score, lm_before
+  int oov[kMaxW], oovb[kMaxW];
+  unsigned st[kCtx][kMaxW], stb[kCtx][kMaxW];   // LM context after / before the last word, most recent first
+  int stn[kMaxW], stbn[kMaxW];
+};
+struct NoLm {};
+
+struct AsgBeamParams {
+  const void* x; int dtype; int64_t sB, sT, sV; const int64_t* x_len;
+  int B, T, V, R, W, space_id, nbest;
+  LmView lm; double lmwt, wip, oov;
+  int64_t* out; int64_t max_out; int64_t* out_len; int64_t* n_hyp; double* scores; int32_t* counts;
+  const double* At;                      // [from][to], f64
+  unsigned char* ws; size_t per_utt, off_sval, off_spos, off_nodes;
+};
+
+// may label c follow a sequence that ends in `a` (a == -1: nothing yet)?  c != a is the caller's.
+__device__ __forceinline__ bool spellable(const AsgBeamParams& p, int a, int c) {
+  const int nch = p.V - p.R;
+  return c < nch || (a >= 0 && a < nch && a != p.space_id);
+}
+
+// what the pair (member m, label c != space) asks of the model: the expanded word's hash, its id, its score in the context
+struct LmAnswer { unsigned long long h; uint32_t wi; float sc; };
+__device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned long long h, int c) {
+  for (int bi = lm.label_off[c]; bi < lm.label_off[c + 1]; bi++) {
+    unsigned char ch = lm.label_bytes[bi];
+    if (lm.fold_case && ch >= 'A' && ch <= 'Z') ch += 32;
+    h = fnv_step(h, ch);
+  }
+  return h;
+}
+__device__ __forceinline__ LmAnswer lm_query(const AsgBeamParams& p, const LmMembers& L, int m, int a, int c, bool new_word) {
+  LmAnswer ans;
+  unsigned long long h = new_word ? kFnvInit : L.hash[m];
+  const int nch = p.V - p.R;
+  if (c >= nch) { for (int r = c - nch; r >= 0; r--) h = spell(p.lm, h, a); }     // repeat label: `a` again, c - nch + 1 times
+  else h = spell(p.lm, h, c);
+  uint32_t ctx[kCtx];
+  const int cn = new_word ? L.stn[m] : L.stbn[m];
+#pragma unroll
+  for (int i = 0; i < kCtx; i++) ctx[i] = new_word ? L.st[i][m] : L.stb[i][m];
+  ans.h = h;
+  ans.wi = lm_word_lookup(p.lm, h);
+  ans.sc = lm_base_score(p.lm, ctx, cn, ans.wi, nullptr, nullptr);
+  return ans;
+}
+
+// total = ac + lmwt * lm_score - wip * num_words + oov_penalty * num_oov, in this order
+__device__ __forceinline__ double total_of(const AsgBeamParams& p, double ac, double lm, int nw, int noov) {
+  return ac + lm * p.lmwt - (double)nw * p.wip + (double)noov * p.oov;
+}
+
+template <bool LM>
+__global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
+  using LmSet = typename std::conditional<LM, LmMembers, NoLm>::type;
+  __shared__ Members mem[2];
+  __shared__ LmSet lms[2];
+  __shared__ double xs[kMaxV];
+  __shared__ double ext[kMaxW];
+  __shared__ unsigned long long tab_key[kSlots];
+  __shared__ int tab_mem[kSlots];
+  __shared__ unsigned hist[256];
+  __shared__ int sel_pos[kMaxW], sel_rank[kMaxW];
+  __shared__ double sel_tot[kMaxW];
+  __shared__ unsigned long long sel_key[kMaxW];
+  __shared__ int n_surv, n_sel, n_stay, sh_digit, sh_need, sh_count;
+  __shared__ int wave_part[4];
+  __shared__ unsigned long long sh_floor;
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int V = p.V, W = p.W;
+  const int64_t Tq = p.x_len[b];
+  if (Tq < 1 || Tq > p.T) { if (tid == 0) p.n_hyp[b] = 0; return; }
+  const int Tb = (int)Tq;
+  unsigned char* ws = p.ws + (size_t)b * p.per_utt;
+  unsigned long long* ctot = reinterpret_cast<unsigned long long*>(ws);           // okey(total) per pair id, kNoCand: none
+  unsigned long long* sval = reinterpret_cast<unsigned long long*>(ws + p.off_sval);
+  int* spos = reinterpret_cast<int*>(ws + p.off_spos);
+  int2* nodes = reinterpret_cast<int2*>(ws + p.off_nodes);
+
+  if (tid == 0) {
+    mem[0].s[0] = 0.0; mem[0].key[0] = kKeyBasis; mem[0].last[0] = -1; mem[0].node[0] = 0; mem[0].len[0] = 0; mem[0].nw[0] = 0;
+    if constexpr (LM) {
+      LmMembers& L = lms[0];
+      L.hash[0] = kFnvInit; L.lm[0] = 0.0; L.lmb[0] = 0.0; L.oov[0] = 0; L.oovb[0] = 0;
+      for (int i = 0; i < kCtx; i++) { L.st[i][0] = 0u; L.stb[i][0] = 0u; }
+      L.st[0][0] = p.lm.bos; L.stb[0][0] = p.lm.bos; L.stn[0] = 1; L.stbn[0] = 1;
+    }
+    nodes[0] = make_int2(-1, 0);
+  }
+  for (int i = tid; i < kSlots; i += kThreads) { tab_key[i] = 0ull; tab_mem[i] = -1; }
+  __syncthreads();
+
+  int cur = 0, n_mem = 1;
+  for (int t = 0; t < Tb && n_mem > 0; t++) {
+    const Members& M = mem[cur];
+    Members& N = mem[cur ^ 1];
+    // ---- the frame's emissions; no member has an extension share yet ----
+    {
+      const int64_t row = (int64_t)b * p.sB + (int64_t)t * p.sT;
+      for (int c = tid; c < V; c += kThreads) {
+        const int64_t at = row + (int64_t)c * p.sV;
+        xs[c] = p.dtype == E2E_F32 ? (double)reinterpret_cast<const float*>(p.x)[at] : reinterpret_cast<const double*>(p.x)[at];
+      }
+      if (tid < kMaxW) ext[tid] = ninf();
+      if (tid == 0) { n_surv = 0; n_sel = 0; n_stay = 0; sh_floor = ~0ull; }
+    }
+    __syncthreads();
+    // ---- every (member, label) pair: its share, and whom it goes to ----
+    const int n_now = n_mem * V;
+    for (int id = tid; id < n_now; id += kThreads) {
+      const int m = id / V, c = id - m * V;
+      const int a = M.last[m];
+      if (c == a) continue;                                       // the stay: below, once the extension shares are in
+      unsigned long long cand = kNoCand;
+      if (spellable(p, a, c)) {
+        const double v = a < 0 ? xs[c] : M.s[m] + p.At[a * V + c] + xs[c];
+        const unsigned long long key = child_key(M.key[m], c);
+        int hit = -1;
+        for (unsigned h = (unsigned)((key * kHashMul) >> 55), probe = 0; probe < (unsigned)kSlots; probe++, h = (h + 1u) & (kSlots - 1)) {
+          const unsigned long long k = tab_key[h];
+          if (k == key) { hit = tab_mem[h]; break; }
+          if (k == 0ull) break;
+        }
+        if (hit >= 0) ext[hit] = v;                               // (the only pair that spells member `hit`)
+        else if (v > ninf()) {                                    // (false for NaN as well)
+          const bool new_word = c != p.space_id && (a < 0 || a == p.space_id);
+          const int nw = M.nw[m] + (new_word ? 1 : 0);
+          double lm = 0.0; int noov = 0;
+          if constexpr (LM) {
+            const LmMembers& L = lms[cur];
+            if (c != p.space_id) {
+              const LmAnswer ans = lm_query(p, L, m, a, c, new_word);
+              lm = (new_word ? L.lm[m] : L.lmb[m]) + (double)ans.sc / 2.302585092994045684;     // quirk Q8: divides by ln 10
+              noov = (new_word ? L.oov[m] : L.oovb[m]) + (ans.wi == 0 ? 1 : 0);
+            } else { lm = L.lm[m]; noov = L.oov[m]; }
+          }
+          const double tot = total_of(p, v, lm, nw, noov);
+          if (tot > ninf()) cand = okey(tot);
+        }
+      }
+      ctot[id] = cand;
+    }
+    __syncthreads();
+    // ---- the members' own candidates: stay and extension share together ----
+    if (tid < n_mem) {
+      const int m = tid, a = M.last[m];
+      if (a >= 0) {
+        const double mass = lse_sym(M.s[m] + p.At[a * V + a] + xs[a], ext[m]);
+        double lm = 0.0; int noov = 0;
+        if constexpr (LM) { lm = lms[cur].lm[m]; noov = lms[cur].oov[m]; }
+        const double tot = total_of(p, mass, lm, M.nw[m], noov);
+        unsigned long long cand = kNoCand;
+        if (mass > ninf() && tot > ninf()) { cand = okey(tot); atomicMin(&sh_floor, cand); atomicAdd(&n_stay, 1); }
+        ctot[m * V + a] = cand;
+      }
+    }
+    __syncthreads();
+    // ---- an exact filter: a full beam's members are W candidates themselves, so nothing below the least of them can make
+    //      the cut; what is left (usually a few times W) is what the selection reads ----
+    const unsigned long long floor_bits = n_stay == W ? sh_floor : 1ull;
+    for (int id = tid; id < n_now; id += kThreads) {
+      const unsigned long long v = ctot[id];
+      if (v < floor_bits) continue;                               // (kNoCand = 0 is below both)
+      const int j = atomicAdd(&n_surv, 1);
+      sval[j] = v; spos[j] = id;
+    }
+    __syncthreads();
+    // ---- the cut: the W largest totals, exactly equal ones by ascending key ----
+    const int nsv = n_surv;
+    unsigned long long thr = 0ull, kthr = ~0ull;                 // selected: bits > thr, or bits == thr and key <= kthr
+    if (nsv > W) {
+      int need = W;
+      for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0u;
+        __syncthreads();
+        if (tid == 0) { sh_digit = 0; sh_need = need; sh_count = 0; }   // (behind the barrier: the last pass' digit has been read)
+        const unsigned long long mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
+        for (int i = tid; i < nsv; i += kThreads) {
+          const unsigned long long v = sval[i];
+          if ((v & mask) == thr) atomicAdd(&hist[(unsigned)(v >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        // the digit: the bin d with (count above d) < need <= (count above d) + hist[d]; a suffix sum over 256 threads
+        int h = 0, incl = 0;
+        if (tid < 256) {
+          h = (int)hist[tid]; incl = h;
+          for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_down(incl, o, 64); if ((tid & 63) + o < 64) incl += n; }
+          if ((tid & 63) == 0) wave_part[tid >> 6] = incl;
+        }
+        __syncthreads();
+        if (tid < 256) {
+          int above = incl - h;
+          for (int w = (tid >> 6) + 1; w < 4; w++) above += wave_part[w];
+          if (h > 0 && above < need && need <= above + h) { sh_digit = tid; sh_need = need - above; sh_count = h; }
+        }
+        __syncthreads();
+        thr |= (unsigned long long)sh_digit << shift;
+        need = sh_need;
+      }
+      if (sh_count > need) {                                     // more equal totals than places: the `need` smallest keys
+        unsigned long long kpre = 0ull;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+          __syncthreads();
+          if (tid < 256) hist[tid] = 0u;
+          if (tid == 0) { sh_digit = 255; sh_need = need; }
+          __syncthreads();
+          const unsigned long long mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
+          for (int i = tid; i < nsv; i += kThreads) {
+            if (sval[i] != thr) continue;
+            const int id = spos[i], m = id / V, c = id - m * V;
+            const unsigned long long kk = c == M.last[m] ? M.key[m] : child_key(M.key[m], c);
+            if ((kk & mask) == kpre) atomicAdd(&hist[(unsigned)(kk >> shift) & 255u], 1u);
+          }
+          __syncthreads();
+          int h = 0, incl = 0;
+          if (tid < 256) {
+            h = (int)hist[tid]; incl = h;
+            for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += n; }
+            if ((tid & 63) == 63) wave_part[tid >> 6] = incl;
+          }
+          __syncthreads();
+          if (tid < 256) {
+            int below = incl - h;
+            for (int w = 0; w < (tid >> 6); w++) below += wave_part[w];
+            if (h > 0 && below < need && need <= below + h) { sh_digit = tid; sh_need = need - below; }
+          }
+          __syncthreads();
+          kpre |= (unsigned long long)sh_digit << shift;
+          need = sh_need;
+        }
+        kthr = kpre;
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < nsv; i += kThreads) {
+      const unsigned long long v = sval[i];
+      if (v < thr) continue;
+      const int id = spos[i], m = id / V, c = id - m * V;
+      const unsigned long long kk = c == M.last[m] ? M.key[m] : child_key(M.key[m], c);
+      if (v == thr && kk > kthr) continue;
+      const int j = atomicAdd(&n_sel, 1);
+      if (j < W) { sel_pos[j] = id; sel_tot[j] = okey_inv(v); sel_key[j] = kk; }
+    }
+    // (the key table is the old members': every pair has looked its key up)
+    for (int i = tid; i < kSlots; i += kThreads) { tab_key[i] = 0ull; tab_mem[i] = -1; }
+    __syncthreads();
+    const int ns = min(n_sel, W);
+    if (ns == 0) { n_mem = 0; break; }                            // no candidate has a number for a total: no hypothesis is left
+    // ---- rank the survivors: they become the members in that order ----
+    if (tid < ns) {
+      const double mt = sel_tot[tid]; const unsigned long long mk = sel_key[tid];
+      int r = 0;
+      for (int i = 0; i < ns; i++) r += (sel_tot[i] > mt || (sel_tot[i] == mt && sel_key[i] < mk)) ? 1 : 0;
+      if (r >= ns) r = ns - 1;
+      sel_rank[tid] = r;
+    }
+    __syncthreads();
+    if (tid < ns) {
+      const int id = sel_pos[tid], r = sel_rank[tid];
+      const int m = id / V, c = id - m * V, a = M.last[m];
+      const unsigned long long key = sel_key[tid];
+      N.key[r] = key; N.last[r] = c;
+      if (c == a) {                                               // the member stays
+        N.s[r] = lse_sym(M.s[m] + p.At[a * V + a] + xs[a], ext[m]);
+        N.node[r] = M.node[m]; N.len[r] = M.len[m]; N.nw[r] = M.nw[m];
+        if constexpr (LM) {
+          const LmMembers& L = lms[cur]; LmMembers& O = lms[cur ^ 1];
+          O.hash[r] = L.hash[m]; O.lm[r] = L.lm[m]; O.lmb[r] = L.lmb[m]; O.oov[r] = L.oov[m]; O.oovb[r] = L.oovb[m];
+#pragma unroll
+          for (int i = 0; i < kCtx; i++) { O.st[i][r] = L.st[i][m]; O.stb[i][r] = L.stb[i][m]; }
+          O.stn[r] = L.stn[m]; O.stbn[r] = L.stbn[m];
+        }
+      } else {                                                    // a new sequence: member m's, and label c
+        N.s[r] = a < 0 ? xs[c] : M.s[m] + p.At[a * V + c] + xs[c];
+        const int node = 1 + t * W + r;
+        nodes[node] = make_int2(M.node[m], c);
+        N.node[r] = node; N.len[r] = M.len[m] + 1;
+        const bool new_word = c != p.space_id && (a < 0 || a == p.space_id);
+        N.nw[r] = M.nw[m] + (new_word ? 1 : 0);
+        if constexpr (LM) {                                        // get_next_prefix's LM part, as ctc_beam.hip's child_lm
+          const LmMembers& L = lms[cur]; LmMembers& O = lms[cur ^ 1];
+          if (c != p.space_id) {
+            const LmAnswer ans = lm_query(p, L, m, a, c, new_word);
+            int bn = new_word ? L.stn[m] : L.stbn[m];
+            O.stbn[r] = bn;
+#pragma unroll
+            for (int i = 0; i < kCtx; i++) O.stb[i][r] = new_word ? L.st[i][m] : L.stb[i][m];
+            O.lmb[r] = new_word ? L.lm[m] : L.lmb[m];
+            O.oovb[r] = new_word ? L.oov[m] : L.oovb[m];
+            if (bn > p.lm.order - 1) bn = p.lm.order - 1;
+            int sn = bn + 1; if (sn > p.lm.order - 1) sn = p.lm.order - 1;
+#pragma unroll
+            for (int i = kCtx - 1; i >= 1; i--) O.st[i][r] = i < sn ? O.stb[i - 1][r] : 0u;
+            O.st[0][r] = sn > 0 ? ans.wi : 0u;
+            O.stn[r] = sn;
+            O.hash[r] = ans.h;
+            O.lm[r] = O.lmb[r] + (double)ans.sc / 2.302585092994045684;
+            O.oov[r] = O.oovb[r] + (ans.wi == 0 ? 1 : 0);
+          } else {                                                // a space copies the fields
+            O.hash[r] = L.hash[m]; O.lm[r] = L.lm[m]; O.lmb[r] = L.lmb[m]; O.oov[r] = L.oov[m]; O.oovb[r] = L.oovb[m];
+#pragma unroll
+            for (int i = 0; i < kCtx; i++) { O.st[i][r] = L.st[i][m]; O.stb[i][r] = L.stb[i][m]; }
+            O.stn[r] = L.stn[m]; O.stbn[r] = L.stbn[m];
+          }
+        }
+      }
+      // the new member's key enters the table (two members with one key, 2^-64: the second is not entered and never extended into)
+      for (unsigned h = (unsigned)((key * kHashMul) >> 55), probe = 0; probe < (unsigned)kSlots; probe++, h = (h + 1u) & (kSlots - 1)) {
+        const unsigned long long old = atomicCAS(&tab_key[h], 0ull, key);
+        if (old == 0ull) { tab_mem[h] = r; break; }
+        if (old == key) break;
+      }
+    }
+    n_mem = ns; cur ^= 1;
+    __syncthreads();
+  }
+
+  // ---- read-out: the first nbest members, ranked already ----
+  const Members& F = mem[cur];
+  const int nbest = p.nbest;
+  const int64_t max_out = p.max_out;
+  int64_t* out = p.out + (int64_t)b * nbest * max_out;
+  __syncthreads();
+  if (tid < nbest) {
+    int64_t* row = out + (int64_t)tid * max_out;
+    int len = 0, nw = 0, noov = 0;
+    double ac = ninf(), lm = 0.0, tot = ninf();
+    if (tid < n_mem) {
+      len = F.len[tid]; ac = F.s[tid]; nw = F.nw[tid];
+      if constexpr (LM) { lm = lms[cur].lm[tid]; noov = lms[cur].oov[tid]; }
+      tot = total_of(p, ac, lm, nw, noov);
+      int at = len, node = F.node[tid];
+      for (int hops = 0; node > 0 && hops <= p.T; hops++) {
+        const int2 nd = nodes[node];
+        --at;
+        if (at >= 0 && at < max_out) row[at] = (int64_t)nd.y;
+        node = nd.x;
+      }
+    }
+    sel_pos[tid] = len;
+    const int64_t o = (int64_t)b * nbest + tid;
+    p.out_len[o] = len;
+    p.scores[o * 3 + 0] = tot; p.scores[o * 3 + 1] = ac; p.scores[o * 3 + 2] = lm;
+    p.counts[o * 2 + 0] = nw; p.counts[o * 2 + 1] = noov;
+  }
+  __syncthreads();
+  for (int j = 0; j < nbest; j++) {
+    int64_t* row = out + (int64_t)j * max_out;
+    for (int64_t i = sel_pos[j] + tid; i < max_out; i += kThreads) row[i] = 0;
+  }
+  if (tid == 0) p.n_hyp[b] = n_mem < nbest ? n_mem : nbest;
+}
+
+// the transitions as the search reads them: f64, [from][to]; all zero without a matrix
+__global__ void asg_beam_transpose_kernel(const void* A, int dtype, int V, double* At) {
+  const int n = V * V;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int from = i / V, to = i - from * V;
+    double v = 0.0;
+    if (A) v = dtype == E2E_F32 ? (double)reinterpret_cast<const float*>(A)[to * V + from] : reinterpret_cast<const double*>(A)[to * V + from];
+    At[i] = v;
+  }
+}
+
+struct Layout { size_t head, per_utt, off_sval, off_spos, off_nodes; };
+
+bool layout(int T, int V, int W, Layout& L) {
+  if (T < 1 || V < 1 || V > kMaxV || W < 1 || W > kMaxW || W * V > kMaxPairs || T > (1 << 22)) return false;
+  const size_t ids = (size_t)W * V;
+  L.head = align_up((size_t)V * V * 8, 256);
+  size_t at = align_up(ids * 8, 256);
+  L.off_sval = at; at += align_up(ids * 8, 256);
+  L.off_spos = at; at += align_up(ids * 4, 256);
+  L.off_nodes = at; at += align_up(((size_t)W * ((size_t)T + 1) + 1) * 8, 256);
+  L.per_utt = at;
+  return true;
+}
+
+}  // namespace
+}  // namespace e2e
+
+using namespace e2e;
+
+extern "C" {
+
+int e2e_asg_beam_max_width(int V) {
+  if (V < 1 || V > kMaxV) return 0;
+  const int w = kMaxPairs / V;
+  return w < kMaxW ? w : kMaxW;
+}
+
+size_t e2e_asg_beam_workspace_bytes(int B, int T, int V, int beam_width, int with_lm) {
+  (void)with_lm;                                                  // (the LM fields live in LDS: the workspace is the same)
+  Layout L;
+  if (B < 0 || !layout(T, V, beam_width, L)) return 0;
+  return L.head + (size_t)B * L.per_utt + 256;
+}
+
+int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                       const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                       const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                       int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
+  if (B < 0 || T < 1 || V < 1 || max_out < 0) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
+  if (V > e2e_asg_max_labels()) { set_error("V=%d exceeds e2e_asg_max_labels() = %d", V, e2e_asg_max_labels()); return E2E_ERR_UNSUPPORTED; }
+  if (num_replabels < 0 || num_replabels >= V) { set_error("num_replabels=%d outside [0, V=%d)", num_replabels, V); return E2E_ERR_ARG; }
+  if (space_id >= V - num_replabels) { set_error("space_id=%d is not one of the %d characters", space_id, V - num_replabels); return E2E_ERR_ARG; }
+  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
+  if (beam_width > e2e_asg_beam_max_width(V)) {
+    set_error("beam_width %d exceeds e2e_asg_beam_max_width(V=%d) = %d", beam_width, V, e2e_asg_beam_max_width(V));
+    return E2E_ERR_UNSUPPORTED;
+  }
+  if (nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  Layout L;
+  if (!layout(T, V, beam_width, L)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
+  if (lm) {
+    if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
+    if ((int)lm->label_off.size() - 1 != V) {
+      set_error("the language model was loaded with %d labels but the emissions have %d columns", (int)lm->label_off.size() - 1, V);
+      return E2E_ERR_ARG;
+    }
+  }
+  if (B > 0 && (!x || !x_len || !out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
+    set_error("null pointer argument"); return E2E_ERR_ARG;
+  }
+  if (B == 0) return E2E_OK;
+  if (lm) {
+    if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
+    int cur = -1;
+    E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
+    if (cur != lm->device) {
+      set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, cur);
+      return E2E_ERR_ARG;
+    }
+  }
+  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < L.head + (size_t)B * L.per_utt) {
+    set_error("workspace too small: %zu bytes, e2e_asg_beam_workspace_bytes() = %zu", workspace_bytes, L.head + (size_t)B * L.per_utt + 256);
+    return E2E_ERR_WORKSPACE;
+  }
+  AsgBeamParams p;
+  p.x = x; p.dtype = dtype; p.sB = sB; p.sT = sT; p.sV = sV; p.x_len = x_len;
+  p.B = B; p.T = T; p.V = V; p.R = num_replabels; p.W = beam_width; p.space_id = space_id < 0 ? -1 : space_id; p.nbest = nbest;
+  if (lm) p.lm = lm->dev_view(); else memset(&p.lm, 0, sizeof(p.lm));
+  p.lmwt = lm ? lmwt : 0.0; p.wip = wip; p.oov = oov_penalty;
+  p.out = out; p.max_out = max_out; p.out_len = out_len; p.n_hyp = n_hyp; p.scores = scores; p.counts = counts;
+  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
+  p.At = reinterpret_cast<const double*>(base);
+  p.ws = base + L.head; p.per_utt = L.per_utt; p.off_sval = L.off_sval; p.off_spos = L.off_spos; p.off_nodes = L.off_nodes;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(asg_beam_transpose_kernel, dim3((V * V + 255) / 256), dim3(256), 0, s, transitions, dtype, V,
+                     reinterpret_cast<double*>(base));
+  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_transpose_kernel launch");
+  if (lm) hipLaunchKernelGGL(asg_beam_kernel<true>, dim3(B), dim3(kThreads), 0, s, p);
+  else hipLaunchKernelGGL(asg_beam_kernel<false>, dim3(B), dim3(kThreads), 0, s, p);
+  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_kernel launch");
+  return E2E_OK;
+}
+
+}  // extern "C"

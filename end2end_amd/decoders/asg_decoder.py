@@ -1,15 +1,19 @@
-"""ASGDecoder: best-path decoding for models trained with ASGLoss -- the Viterbi path through emissions and learned
-transitions (e2e_asg_viterbi; the definition is in include/e2e_ctc.h), its repeats merged and its repeat labels expanded.
-Upstream has no ASG decoder; the return conventions are CTCDecoder's.
+"""ASGDecoder: decoding for models trained with ASGLoss or CTCWithoutBlankLoss.  As constructed: the Viterbi path
+through emissions and learned transitions (e2e_asg_viterbi), its repeats merged and its repeat labels expanded.
+After ``configure(beam_width > 1, ...)``: n-best prefix beam search with the transitions and, optionally, a word language model
+(e2e_asg_beam_nbest).  The definitions are in include/e2e_ctc.h; upstream has no ASG decoder; the return conventions
+are CTCDecoder's.
 
-Not provided for ASG: beam search, a language model, a lexicon.
+Not provided for ASG: a lexicon or vocabulary restriction, streaming, timestamps, widths or alphabets above 128,
+-inf transitions, custom transcriptions.
 """
+import os
 from collections import namedtuple
 
 import torch
 
-from ..engines import ASGViterbiEngine
-from .ctc_decoder import CTCDecoderError, DecoderResults
+from ..engines import ASGBeamEngine, ASGViterbiEngine
+from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults
 
 # decode_path(): the label of every frame, -100 past an utterance's length (as get_alignment_3d pads), and the paths' scores
 ASGPathResults = namedtuple("ASGPathResults", ["paths", "scores"])
@@ -25,6 +29,9 @@ class ASGDecoder:
         before, r more times" (``ASGEncoder``'s ids)
     :param time_major: emissions are ``(time, batch, alphabet)``
     :param keep_on_device: leave the decoded ids, lengths, paths and scores on the GPU
+
+    The constructor is the best-path decoder's; the beam search is set up with ``configure()``, as ``CTCDecoderEngine``
+    sets up what goes beyond upstream's constructor.
     """
 
     def __init__(self, labels=None, num_replabels=0, time_major=False, keep_on_device=False):
@@ -33,7 +40,41 @@ class ASGDecoder:
         self._labels = list(labels) if labels is not None else None
         self._num_replabels = int(num_replabels)
         self._time_major = time_major
+        self._keep_on_device = keep_on_device
         self._decoder = ASGViterbiEngine(PATH_PAD, keep_on_device=keep_on_device)
+        self._beam_width = 1
+        self._beam = None
+
+    def configure(self, beam_width=1, lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True):
+        """Set up the beam search, once, before decoding; returns self.  The names and defaults are ``CTCDecoder``'s.
+
+        :param beam_width: number of hypotheses kept; ``1`` (the default) means best-path (Viterbi) decoding, unchanged
+        :param lm_path: ARPA (optionally gzipped) language model, for ``beam_width > 1``; a word is looked up with its repeat
+            labels expanded
+        :param lmwt: language-model weight
+        :param wip: word insertion penalty
+        :param oov_penalty: penalty per out-of-vocabulary word
+        :param case_sensitive: look words up in the language model with their case
+
+        A width above the limit is refused here, an alphabet above it at the first call: both before any launch.
+        """
+        beam_width = int(beam_width)
+        lm_path = os.path.abspath(lm_path) if lm_path else ""
+        if beam_width < 1:
+            raise CTCDecoderError("beam_width must be >= 1")
+        if lm_path:
+            if beam_width == 1:
+                raise CTCDecoderError("lm_path needs beam_width > 1: best-path decoding has no language model")
+            if not os.path.isfile(lm_path):
+                raise CTCDecoderError("Can't find a model: {}".format(lm_path))
+            if self._labels is None:
+                raise CTCDecoderError("a language model needs labels: the alphabet spells its words")
+        self._beam = None
+        if beam_width > 1:
+            self._beam = ASGBeamEngine(self._labels, self._num_replabels, beam_width, lm_path, lmwt, wip, oov_penalty,
+                                       case_sensitive, keep_on_device=self._keep_on_device)
+        self._beam_width = beam_width
+        return self
 
     def _batch_major(self, emissions, logits_lengths):
         if self._time_major:
@@ -61,8 +102,11 @@ class ASGDecoder:
     def decode(self, emissions, transitions, logits_lengths=None):
         """:return: ``DecoderResults(decoded_targets (batch, time) -- the best path with consecutive repeats merged, zero
             padded as greedy decoding pads --, decoded_targets_lengths, decoded_sentences)``; the sentences have the
-            repeat labels expanded"""
+            repeat labels expanded.  ``beam_width > 1``: hypothesis 0 of ``decode_nbest``, the ids packed to the longest
+            result; ``transitions`` may then be ``None`` (all zero)"""
         emissions, logits_lengths = self._batch_major(emissions, logits_lengths)
+        if self._beam is not None:
+            return DecoderResults(*self._beam.decode(emissions, transitions, logits_lengths))
         V = emissions.size(2)
         num_chars = V - self._num_replabels
         if num_chars < 1:
@@ -76,3 +120,19 @@ class ASGDecoder:
         else:
             sentences = [self._sentence(row[:n], num_chars) for row, n in zip(ids.tolist(), lengths.tolist())]
         return DecoderResults(ids, lengths, sentences)
+
+    def decode_nbest(self, emissions, transitions, logits_lengths=None, nbest=None):
+        """The hypotheses the beam search ends with, best first (``beam_width > 1``).  ``transitions=None`` means zero
+        transitions: a ``CTCWithoutBlankLoss`` model is decoded by passing its log-softmax output, ``num_replabels=0``.
+
+        :param nbest: how many to return per utterance, at most ``beam_width`` (the default)
+        :return: ``CTCDecoder``'s ``NBestResults``: ``decoded_targets (batch, nbest, longest)`` -- the merged labels, repeat
+            labels as they are --, ``decoded_targets_lengths``, ``decoded_sentences`` (repeat labels expanded), ``scores``,
+            ``ctc_scores`` (the acoustic score: log of the summed path scores of the labelling, within the beam),
+            ``lm_scores``, ``num_words``, ``num_oov_words``, ``num_hypotheses``, ``timesteps=None``;
+            ``scores = ctc_scores + lmwt * lm_scores - wip * num_words + oov_penalty * num_oov_words``.
+        """
+        if self._beam is None:
+            raise CTCDecoderError("decode_nbest needs beam_width > 1: best-path decoding has no beam")
+        emissions, logits_lengths = self._batch_major(emissions, logits_lengths)
+        return NBestResults(*self._beam.decode_nbest(emissions, transitions, logits_lengths, nbest=nbest))

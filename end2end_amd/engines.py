@@ -345,6 +345,137 @@ class ASGViterbiEngine:
         return out if self.keep_on_device else tuple(t.cpu() for t in out)
 
 
+class ASGBeamEngine:
+    """(labels, num_replabels, beam_width_, lm_path, lmwt_, wip_, oov_penalty_, case_sensitive) -> decode_nbest / decode: the
+    ASG prefix beam search with transitions and a word language model (e2e_asg_beam_nbest; the definition:
+    include/e2e_ctc.h).  `labels`: the character strings of the columns 0 .. V - R - 1 (a list of all V columns is taken
+    too; None: no sentences, no space, no model).  The model is loaded once per device through LanguageModel, with the
+    labels of all V columns (the repeat columns' strings are never read), at the first call: only the emissions tell
+    whether `labels` lists the characters or all columns.  The width limit is checked here when the
+    alphabet is known, else at the first call -- before any launch either way.  Results are CPU tensors unless
+    `keep_on_device`."""
+
+    def __init__(self, labels=None, num_replabels=0, beam_width_=100, lm_path="", lmwt_=1.0, wip_=0.0,
+                 oov_penalty_=-1000.0, case_sensitive=False, keep_on_device=False):
+        self.num_replabels = int(num_replabels)
+        if self.num_replabels < 0:
+            raise ValueError("num_replabels must be >= 0")
+        self.beam_width = int(beam_width_)
+        self.labels = None if labels is None else list(labels)
+        self.lmwt = float(lmwt_) if lm_path else 0.0
+        self.wip = float(wip_)
+        self.oov_penalty = float(oov_penalty_)
+        self.case_sensitive = bool(case_sensitive)
+        self.keep_on_device = bool(keep_on_device)
+        self.num_labels = None                       # V, once it is known
+        self.lm = None
+        if self.beam_width < 1 or self.beam_width > _C.asg_beam_max_width(1):
+            raise ValueError("beam_width %d is not supported: 1 to %d" % (self.beam_width, _C.asg_beam_max_width(1)))
+        self._lm_path = lm_path or ""
+        if self._lm_path:
+            if self.labels is None:
+                raise ValueError("a language model needs the labels: the alphabet spells its words")
+            R.require_gpu()
+
+    def _chars(self):
+        return self.labels if self.num_labels is None else self.labels[: self.num_labels - self.num_replabels]
+
+    def _bind(self, V):
+        """The alphabet's size is known: the limits, the labels' count, the space."""
+        if self.num_labels == V:
+            return
+        if self.num_labels is not None:
+            raise ValueError("emissions have %d columns; this decoder was used with %d before" % (V, self.num_labels))
+        _asg_check(V)
+        num_chars = V - self.num_replabels
+        if num_chars < 1:
+            raise ValueError("%d columns leave no characters beside %d repeat labels" % (V, self.num_replabels))
+        if self.labels is not None and len(self.labels) not in (num_chars, V):
+            raise ValueError("the decoder has %d labels but the emissions have %d columns, %d of them repeat labels"
+                             % (len(self.labels), V, self.num_replabels))
+        cap = _C.asg_beam_max_width(V)
+        if self.beam_width > cap:
+            raise ValueError("beam_width %d is not supported for an ASG alphabet of %d columns: 1 to %d"
+                             % (self.beam_width, V, cap))
+        chars = self.labels[:num_chars] if self.labels is not None else []
+        self.space_id = chars.index(" ") if " " in chars else -1
+        if self._lm_path:                            # loaded once, now that the number of columns is known
+            self.lm = LanguageModel(self._lm_path, chars + ["<%d>" % (r + 1) for r in range(self.num_replabels)],
+                                    self.case_sensitive)
+        self.num_labels = V
+
+    def _strings(self, rows, lens):
+        if self.labels is None:
+            return ["" for _ in lens]
+        chars, out = self._chars(), []
+        for row, n in zip(rows.tolist(), lens):
+            s = []
+            for i in row[:n]:
+                if i < len(chars):
+                    s.append(chars[i])
+                elif s:
+                    s.extend([s[-1]] * (i - len(chars) + 1))
+            out.append("".join(s))
+        return out
+
+    def decode_nbest(self, emissions, transitions, logits_lengths, nbest=None):
+        """-> (ids (B,N,maxlen) int64 -- the merged labels, repeat labels as they are --, lengths (B,N), sentences [B][n_hyp]
+        with the repeat labels expanded, scores (B,N) f64, acoustic scores, lm_scores, num_words (B,N) int32, num_oov (B,N),
+        num_hypotheses (B), None): CTCDecoderEngine.decode_nbest's tuple.  `transitions` None: all zero."""
+        N = self.beam_width if nbest is None else int(nbest)
+        if not 1 <= N <= self.beam_width:
+            raise ValueError("nbest=%d outside [1, beam_width=%d]" % (N, self.beam_width))
+        if emissions.dim() != 3:
+            raise ValueError("emissions must be (batch, time, alphabet)")
+        B, T, V = emissions.shape
+        self._bind(V)
+        dev = R.compute_device(emissions)
+        x = emissions.detach().to(dev)
+        if x.dtype not in _F32_F64:
+            x = x.to(torch.float32)
+        A = None if transitions is None else _asg_transitions(transitions, V, dev, x.dtype)
+        xl = _as_long(logits_lengths, dev)
+        if xl.numel() != B:
+            raise ValueError("logits_lengths must have one entry per utterance")
+        max_out = max(T, 1)
+        # (an utterance whose length is outside [1, T] is not touched by the call: its slots are the empty ones from here)
+        out = torch.zeros((B, N, max_out), dtype=torch.long, device=dev)
+        out_len = torch.zeros((B, N), dtype=torch.long, device=dev)
+        n_hyp = torch.zeros(B, dtype=torch.long, device=dev)
+        scores = torch.full((B, N, 3), float("-inf"), dtype=torch.float64, device=dev)
+        scores[:, :, 2] = 0.0
+        counts = torch.zeros((B, N, 2), dtype=torch.int32, device=dev)
+        if B and T:
+            stream = R.stream_handle(dev)
+            with _on_device(dev):
+                lm = self.lm.on(dev).handle if self.lm is not None else 0
+                nbytes = _C.asg_beam_workspace_bytes(B, T, V, self.beam_width, self.lm is not None)
+                if not nbytes:
+                    raise ValueError("ASG beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
+                ws = R.workspace(dev, nbytes, stream)
+                sB, sT, sV = x.stride()
+                _C.asg_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
+                                  xl.data_ptr(), B, T, V, self.num_replabels, self.beam_width, self.space_id, lm,
+                                  self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
+                                  n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        nh = n_hyp.tolist()
+        lens = out_len.tolist()
+        width = max((max(row) for row in lens), default=0)
+        ids = out[:, :, :width].contiguous()       # packed to the longest hypothesis of the batch
+        ids_host = ids.cpu()
+        flat = self._strings(ids_host.reshape(B * N, width), [n for row in lens for n in row])
+        sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+        r = (lambda t: t) if self.keep_on_device else (lambda t: t.cpu())
+        return (ids if self.keep_on_device else ids_host, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
+                r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
+                r(counts[:, :, 1].contiguous()), r(n_hyp), None)
+
+    def decode(self, emissions, transitions, logits_lengths):
+        """Hypothesis 0 of decode_nbest -> (ids (B,maxlen) int64, lengths (B), sentences)."""
+        r = self.decode_nbest(emissions, transitions, logits_lengths, nbest=1)
+        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+
+
 GRAM_MAX_ORDER = 8
 
 

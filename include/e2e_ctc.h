@@ -362,6 +362,68 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
                             double* scores, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * ASG decoding: n-best prefix beam search with transitions and a word language model (additive, ABI 4: nothing above
+ * changes meaning).  Upstream has no ASG decoder; this is the definition.  Path score, x, transitions A[to, from], V, x_len
+ * and strides are e2e_asg_fwd_bwd's / e2e_asg_viterbi's: no softmax, no start or end transition.
+ *   labelling    a path is labelled by merging consecutive equal labels.  A hypothesis is such a label sequence y: non-empty,
+ *                no two equal neighbours.  ac(y) = log sum exp(score(pi)) over the paths pi of x_len[b] frames labelled y
+ *   repeat labels  the last R = num_replabels columns (ASGEncoder's ids).  A sequence is SPELLABLE if no repeat label is
+ *                its first label, directly follows the space label or directly follows another repeat label.  Unspellable
+ *                sequences are not hypotheses: their paths belong to nothing.  R = 0: every sequence is spellable
+ *   the search   the beam after frame t-1 holds at most beam_width members (y, a = last label, s = log mass).
+ *                frame 0: candidate (c) with mass x[0,c] for every label c that may start a sequence;
+ *                frame t >= 1, stay: every member puts (s + A[a,a]) + x[t,a] on its own sequence;
+ *                frame t >= 1, extension: for every c != a for which y + (c) is spellable, (s + A[c,a]) + x[t,c] on y + (c).
+ *                A candidate's mass is the log-sum of what it received -- at most its own stay and one extension from its
+ *                parent, if the parent is a member: hi + log1p(exp(lo - hi)), symmetric in the two.  A sequence that is not
+ *                a member has no mass; one that left the beam and is formed again starts from its extension share alone
+ *   arithmetic   every cell f64 in the log domain for both dtypes (f32 converts exactly); a candidate whose total is -inf
+ *                or NaN is no candidate.  -inf transitions are not supported
+ *   LM fields    lm_score, num_words, num_oov and the LM state are functions of the sequence alone, by e2e_ctc_beam's rules:
+ *                a word starts at a non-space label after the root or after a space; the model is asked at every label with
+ *                the partial word as if it were complete: lm_score = lm_before + base_score(state_before, idx(word)) / ln 10,
+ *                num_oov = oov_before + (idx == 0); a space copies the fields; without a model lmwt counts as 0 and wip
+ *                still applies.  A word is spelled with its repeat labels EXPANDED: repeat label r appends the bytes of the
+ *                character before it r more times (h e l <1> o looks up hello); case folding and byte comparison as in
+ *                e2e_ctc_beam.  The model must have been loaded with V labels; the repeat columns' strings are not read
+ *   identity     a sequence is its 64-bit key, e2e_gram_ctc_beam_nbest's: key(empty) = 0xcbf29ce484222325,
+ *                key(y + (c)) = (key(y) XOR c) * 0x100000001b3 mod 2^64, 0 kept as 1; equal keys are one sequence (2^-64)
+ *   cut, ranking total = ac + lmwt * lm_score - wip * num_words + oov_penalty * num_oov (evaluated left to right).  The
+ *                beam_width largest totals are kept, ties by key ascending; the n-best list is in the same order.  Two
+ *                calls on the same input agree bit for bit
+ *   x            (B,T,V) emissions, strides sB,sT,sV, E2E_F32 or E2E_F64 (16-bit: up-cast first; E2E_ERR_ARG)
+ *   transitions  (V,V) contiguous, x's dtype, or NULL: all zero (a CTC-without-blank model: pass its log-softmax, R = 0)
+ *   x_len        (B) int64; x_len[b] outside [1,T] gives n_hyp[b] = 0 and touches nothing else of the utterance
+ *   space_id     the space's column among the V - R characters, or negative: none (>= V - R: E2E_ERR_ARG)
+ *   lm           NULL or a model of e2e_lm_load_arpa on the current device; order <= 6
+ *   nbest        1 <= nbest <= beam_width, else E2E_ERR_ARG
+ *   out          (B,nbest,max_out) int64 labels (repeat labels as they are), zero filled behind each sequence; max_out = T
+ *                can never be exceeded
+ *   out_len      (B,nbest) int64: 0 for slots >= n_hyp[b]; > max_out = truncated, that many ids were needed and the first
+ *                max_out were written
+ *   n_hyp        (B) int64: min(nbest, members of the final beam)
+ *   scores       (B,nbest,3) f64: total, ac, lm_score (0 without a model); slots >= n_hyp[b]: -inf, -inf, 0
+ *   counts       (B,nbest,2) int32: num_words, num_oov (0 without a model)
+ *   workspace    >= e2e_asg_beam_workspace_bytes(...): 8 V^2 bytes for the transitions as f64, [from][to]; per utterance
+ *                20 bytes per (member, label) pair and 8 per node of the pool of beam_width * (T + 1) + 1 (parent, label)
+ *                nodes (B=64, T=1000, V=29, beam_width=100: 55 MB).  with_lm does not change it (the LM fields live in LDS)
+ * Limits: V <= e2e_asg_max_labels() = 128; beam_width <= e2e_asg_beam_max_width(V) = min(128, 16384 / V), 0 for an
+ * unsupported V -- the pair buffers are sized for 16384 pairs, which V <= 128 never exceeds at width 128, so the limit is
+ * 128 for every supported V; T <= 2^22.  Beyond them E2E_ERR_UNSUPPORTED (the workspace query returns 0).  Every argument
+ * error is found on the host before any launch.  Asynchronous on `stream`, allocates nothing, never synchronises,
+ * capturable.  Not provided: a lexicon or vocabulary restriction, streaming, timestamps, custom transcriptions.
+ */
+struct e2e_lm;   /* (e2e_lm_load_arpa, below) */
+int e2e_asg_beam_max_width(int V);
+size_t e2e_asg_beam_workspace_bytes(int B, int T, int V, int beam_width, int with_lm);
+
+int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                       const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                       const struct e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                       int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Greedy decode.  Replaces cpp_ctc_decoder.CTCDecoder.decode_greedy
  *   src/decoders/ctc_decoder.cpp:443-490 (argmax + blank/repeat collapse).
  *   x        (B,T,V) logits or log-probs, strides sB,sT,sV, f32/f64
