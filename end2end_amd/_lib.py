@@ -166,6 +166,18 @@ def load():
         L.e2e_lm_has_lexicon.argtypes = [vp]
         L.e2e_lm_spelling_class.restype = C.c_int
         L.e2e_lm_spelling_class.argtypes = [vp, C.c_char_p]
+        L.e2e_lm_load_transcriptions.restype = C.c_int
+        L.e2e_lm_load_transcriptions.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(vp)]
+        L.e2e_lm_is_transcribed.restype = C.c_int
+        L.e2e_lm_is_transcribed.argtypes = [vp]
+        L.e2e_lm_transcriptions_dropped.restype = C.c_int
+        L.e2e_lm_transcriptions_dropped.argtypes = [vp]
+        L.e2e_lm_transcribe.restype = C.c_int
+        L.e2e_lm_transcribe.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.POINTER(C.c_uint32), C.c_int,
+                                        C.POINTER(C.c_int)]
+        L.e2e_lm_word_string.restype = C.c_char_p
+        L.e2e_lm_word_string.argtypes = [vp, C.c_uint32]
         L.e2e_ctc_align_workspace_bytes.restype = C.c_size_t
         L.e2e_ctc_align_workspace_bytes.argtypes = [C.c_int] * 5
         L.e2e_ctc_align.restype = C.c_int

@@ -481,6 +481,10 @@ int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t
   Layout L;
   if (!layout(T, V, beam_width, L)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
   if (lm) {
+    if (lm->transcribed) {
+      set_error("the ASG search spells its words from the labels' strings: a model with custom transcriptions (e2e_lm_load_transcriptions) is not supported");
+      return E2E_ERR_UNSUPPORTED;
+    }
     if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
     if ((int)lm->label_off.size() - 1 != V) {
       set_error("the language model was loaded with %d labels but the emissions have %d columns", (int)lm->label_off.size() - 1, V);

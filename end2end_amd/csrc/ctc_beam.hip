@@ -262,12 +262,17 @@ __device__ __forceinline__ float lm_score_parallel(const LmView& lm, const LmCon
 // for an answer, and the pair loop creates no candidate for it.  The second follows from what a member holds already.
 constexpr uint32_t kNoChildWord = 0xFFFFFFFFu;
 // LMK, the kernels' template argument: 0 no language model, 1 the general LM walk, 2 the fast one (see lm_query); 3 and 4 are
-// 1 and 2 restricted to the lexicon (instances of their own: the unrestricted ones carry nothing of the rule)
-__host__ __device__ constexpr bool lmk_fast(int lmk) { return lmk == 2 || lmk == 4; }
-__host__ __device__ constexpr bool lmk_restricted(int lmk) { return lmk >= 3; }
+// 1 and 2 restricted to the lexicon (instances of their own: the unrestricted ones carry nothing of the rule); 5 to 8 are 1 to 4
+// for a model with homophones (custom transcriptions; instances of their own again: as a branch on the mark inside 1 to 4 the
+// second copy of the LM walk cost the fast instances their last free registers -- 12 to 20 bytes of scratch where there were none)
+__host__ __device__ constexpr int lmk_base(int lmk) { return lmk > 4 ? lmk - 4 : lmk; }
+__host__ __device__ constexpr bool lmk_fast(int lmk) { return lmk_base(lmk) == 2 || lmk_base(lmk) == 4; }
+__host__ __device__ constexpr bool lmk_restricted(int lmk) { return lmk_base(lmk) >= 3; }
+__host__ __device__ constexpr bool lmk_hom(int lmk) { return lmk > 4; }
 // FAST: the model has signature tables and at most kParCtx words of context (checked by the host): only the round-probed
 // walk is compiled in.  Otherwise: the general walk over the id tables (any order up to 6).
-template <bool FAST, bool RS>
+// HOM: the model has homophone sets (ctc_lm.h): a marked table value is resolved by scoring every word of its set.
+template <bool FAST, bool RS, bool HOM>
 __device__ __forceinline__ LmAnswer lm_query(const BeamParams& p, const LabelTab& lt, const LmFields& pr, int parent_last, int c) {
   const bool new_word = pr.num_words == 0 || parent_last == p.space_id;                           // :258-259 (c != space)
   LmAnswer a;
@@ -289,6 +294,19 @@ __device__ __forceinline__ LmAnswer lm_query(const BeamParams& p, const LabelTab
     if (RS && !in1 && !in2) { a.wi = kNoChildWord; a.sc = 0.f; return a; }
     a.wi = in1 ? e1.z : in2 ? e2.z : 0u;                             // NotFound() == <unk> == 0
     const float uni_prob = in1 ? __uint_as_float(e1.w) : in2 ? __uint_as_float(e2.w) : p.lm.unk_prob;
+    if (HOM && is_hom_ref(a.wi)) {
+      // homophones (a model with custom transcriptions): the word of this key is the one the model scores highest in this
+      // context, exact ties to the earliest listed.  The contexts are looked up already; one round of probes per candidate.
+      const uint32_t* set = p.lm.homs + (a.wi & ~kHomMark);
+      const uint32_t count = set[0];
+      a.sc = -INFINITY;
+      for (uint32_t i = 0; i < count; i++) {
+        const uint32_t w = set[1 + i];
+        const float sc = lm_score_parallel(p.lm, cx, cn, w, p.lm.uni[w].prob);
+        if (i == 0 || sc > a.sc) { a.sc = sc; a.wi = w; }
+      }
+      return a;
+    }
     a.sc = lm_score_parallel(p.lm, cx, cn, a.wi, uni_prob);
   } else {
     if (RS) {
@@ -296,6 +314,7 @@ __device__ __forceinline__ LmAnswer lm_query(const BeamParams& p, const LabelTab
     } else {
       a.wi = lm_word_lookup(p.lm, h);
     }
+    if (HOM && is_hom_ref(a.wi)) { a.wi = lm_homophone_choice(p.lm, a.wi, new_word ? pr.st : pr.stb, cn, &a.sc); return a; }
     a.sc = lm_base_score(p.lm, new_word ? pr.st : pr.stb, cn, a.wi, nullptr, nullptr);
   }
   return a;
@@ -840,7 +859,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
   __syncthreads();
   if (!ST || !resume) {
     if (tid == 0) slot_map(0).insert(0, 0);
-    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
+    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[0], -1, c);
   } else {
     // what a step rebuilds: the slot map, the child tables (one entry per guard, as rebuild_guards writes them) and the
     // members' LM answers (asked as a new member's are: the same function of the member's state)
@@ -852,7 +871,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
     }
     if (LM) for (int e = tid; e < n0 * V; e += kThreads) {
       const int j2 = e / V, c = e - j2 * V;
-      if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[j2], M0.last[j2], c);
+      if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[j2], M0.last[j2], c);
     }
   }
   __syncthreads();
@@ -1205,7 +1224,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_kernel(BeamParams p) {
       for (int t2 = tid; t2 < nnew * V; t2 += kThreads) {
         const int r = div_v(t2), c = t2 - r * V, j2 = newlist[r];
         if (c == blank || c == p.space_id) continue;
-        lmcB[j2 * V + c] = lm_query<lmk_fast(LMK), RS>(p, lt, Bm.lm[j2], Bm.last[j2], c);
+        lmcB[j2 * V + c] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, Bm.lm[j2], Bm.last[j2], c);
       }
       lds_barrier();
       BPROF(14);
@@ -1328,7 +1347,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
   gsync();
   if (!ST || !resume) {
     if (tid == 0) slot_map(0).insert(0, 0);
-    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[0], -1, c);
+    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[0], -1, c);
   } else {
     // what a step rebuilds: the slot map, the child map (one entry per guard) and the members' LM answer rows
     const SlotMap map0 = slot_map(0);
@@ -1340,7 +1359,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
     }
     if (LM) for (size_t e = tid; e < (size_t)n0 * V; e += kThreads) {
       const int j2 = (int)(e / V), c = (int)(e - (size_t)j2 * V);
-      if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS>(p, lt, M0.lm[j2], M0.last[j2], c);
+      if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[j2], M0.last[j2], c);
     }
   }
   gsync();
@@ -1595,7 +1614,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
         const int j2 = (int)(e / V), c = (int)(e - (size_t)j2 * V);
         const int f = Bm.from[j2];
         if (f >= 0) lmcB[e] = lmcA[(size_t)f * V + c];
-        else if (c != blank && c != p.space_id) lmcB[e] = lm_query<lmk_fast(LMK), RS>(p, lt, Bm.lm[j2], Bm.last[j2], c);
+        else if (c != blank && c != p.space_id) lmcB[e] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, Bm.lm[j2], Bm.last[j2], c);
       }
     }
     gsync();
@@ -1800,6 +1819,7 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
   hipStream_t s = (hipStream_t)stream;
   const bool fast_lm = lm && lm->d_ngs && lm->order - 1 <= kParCtx;
   const bool rs = lm && restricted;
+  const bool hom = lm && lm->homs.size() > 1;      // (a transcription model without a shared key takes the instances it always took)
   if (general) {
     GenParams g;
     g.gkey = reinterpret_cast<unsigned long long*>(ws + gen_at + gl.gkey);
@@ -1807,24 +1827,28 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
     g.gmem = gl.members_in_ws ? reinterpret_cast<unsigned char*>(ws + gen_at + gl.gmem) : nullptr;
     g.CH = gl.CH;
     // (16-bit log-probabilities are read as they are -- every one of them is an f32 number, so the search is the f32 one's, bit for bit)
-#define E2E_GEN_LMK(IO, ST) (!lm ? (const void*)&ctc_beam_general_kernel<IO, 0, ST> : fast_lm ? (rs ? (const void*)&ctc_beam_general_kernel<IO, 4, ST> : (const void*)&ctc_beam_general_kernel<IO, 2, ST>) \
-                                 : (rs ? (const void*)&ctc_beam_general_kernel<IO, 3, ST> : (const void*)&ctc_beam_general_kernel<IO, 1, ST>))
+#define E2E_GEN_LM(IO, ST, H) (fast_lm ? (rs ? (const void*)&ctc_beam_general_kernel<IO, 4 + H, ST> : (const void*)&ctc_beam_general_kernel<IO, 2 + H, ST>) \
+                                       : (rs ? (const void*)&ctc_beam_general_kernel<IO, 3 + H, ST> : (const void*)&ctc_beam_general_kernel<IO, 1 + H, ST>))
+#define E2E_GEN_LMK(IO, ST) (!lm ? (const void*)&ctc_beam_general_kernel<IO, 0, ST> : hom ? E2E_GEN_LM(IO, ST, 4) : E2E_GEN_LM(IO, ST, 0))
 #define E2E_GEN_OF(IO) (st ? E2E_GEN_LMK(IO, true) : E2E_GEN_LMK(IO, false))
     const void* gfn = dtype == E2E_F32 ? E2E_GEN_OF(float) : dtype == E2E_F64 ? E2E_GEN_OF(double) : dtype == E2E_F16 ? E2E_GEN_OF(f16_t) : E2E_GEN_OF(bf16_t);
 #undef E2E_GEN_OF
 #undef E2E_GEN_LMK
+#undef E2E_GEN_LM
     E2E_HIP_CHECK(allow_dynamic_lds(gfn, (int)gl.lds), "hipFuncSetAttribute");
     void* gargs[] = { &p, &g };
     E2E_HIP_CHECK(hipLaunchKernel(gfn, dim3(B), dim3(kThreads), gargs, gl.lds, s), "ctc_beam_general_kernel launch");
     E2E_HIP_CHECK(hipGetLastError(), "ctc_beam_general_kernel launch");
     return E2E_OK;
   }
-#define E2E_BEAM_LMK(IO, ST) (!lm ? (const void*)&ctc_beam_kernel<IO, 0, ST> : fast_lm ? (rs ? (const void*)&ctc_beam_kernel<IO, 4, ST> : (const void*)&ctc_beam_kernel<IO, 2, ST>) \
-                                  : (rs ? (const void*)&ctc_beam_kernel<IO, 3, ST> : (const void*)&ctc_beam_kernel<IO, 1, ST>))
+#define E2E_BEAM_LM(IO, ST, H) (fast_lm ? (rs ? (const void*)&ctc_beam_kernel<IO, 4 + H, ST> : (const void*)&ctc_beam_kernel<IO, 2 + H, ST>) \
+                                        : (rs ? (const void*)&ctc_beam_kernel<IO, 3 + H, ST> : (const void*)&ctc_beam_kernel<IO, 1 + H, ST>))
+#define E2E_BEAM_LMK(IO, ST) (!lm ? (const void*)&ctc_beam_kernel<IO, 0, ST> : hom ? E2E_BEAM_LM(IO, ST, 4) : E2E_BEAM_LM(IO, ST, 0))
 #define E2E_BEAM_OF(IO) (st ? E2E_BEAM_LMK(IO, true) : E2E_BEAM_LMK(IO, false))
   const void* fn = dtype == E2E_F32 ? E2E_BEAM_OF(float) : dtype == E2E_F64 ? E2E_BEAM_OF(double) : dtype == E2E_F16 ? E2E_BEAM_OF(f16_t) : E2E_BEAM_OF(bf16_t);
 #undef E2E_BEAM_OF
 #undef E2E_BEAM_LMK
+#undef E2E_BEAM_LM
   E2E_HIP_CHECK(allow_dynamic_lds(fn, (int)l.lds), "hipFuncSetAttribute");
   void* args[] = { &p };
   E2E_HIP_CHECK(hipLaunchKernel(fn, dim3(B), dim3(kThreads), args, l.lds, s), "ctc_beam_kernel launch");

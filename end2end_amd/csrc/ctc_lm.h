@@ -51,7 +51,19 @@ struct LmView {                    // what the kernel sees (device pointers) / w
   const NgSig* ngs; const VEntry* vt;                        // device only (null: n-gram hashes collide, use ng / vkeys)
   const UniEntry* uni; uint32_t nwords;                      // device only, with ngs
   float unk_prob;                                            // p(<unk>) (KenLM's -100 if the model has none)
+  const uint32_t* homs;                                      // transcription models: the homophone sets (count, ids ...); else null
 };
+
+// Custom transcriptions (e2e_lm_load_transcriptions): the vocabulary tables are keyed by a word's sequence of label ids
+// -- label c spells the two bytes of c + 1, so the kernel's spell() hashes ids, not characters -- and one key may belong
+// to several words (homophones).  A key with one word stores its id as always; a key with several stores kHomMark | offset
+// into LmView::homs, where the set lies as (count, id_1 .. id_count) in the order of the lexicon.  Only the language model
+// can choose between homophones: the word of such a key is the one with the greatest score in the asking prefix's context,
+// exact ties to the earliest listed (lm_query in ctc_beam.hip, e2e_lm_transcribe on the host).
+constexpr uint32_t kHomMark = 0x80000000u;
+constexpr int kMaxHomophones = 16;
+constexpr int kMaxTranscription = 255;
+__host__ __device__ inline bool is_hom_ref(uint32_t val) { return (val & kHomMark) != 0; }   // (a table value; never kNoChildWord)
 
 __host__ __device__ inline uint64_t fnv_step(uint64_t h, unsigned char b) { return (h ^ b) * 1099511628211ULL; }
 constexpr uint64_t kFnvInit = 1469598103934665603ULL;
@@ -127,6 +139,20 @@ __host__ __device__ inline float lm_base_score(const LmView& lm, const uint32_t*
   return result;
 }
 
+// the word of a homophone set in the context ctx: greatest lm_base_score, exact ties to the earliest listed
+__host__ __device__ inline uint32_t lm_homophone_choice(const LmView& lm, uint32_t ref, const uint32_t* ctx, int ctx_len, float* score) {
+  const uint32_t* set = lm.homs + (ref & ~kHomMark);
+  const uint32_t count = set[0];
+  uint32_t best = set[1];
+  float best_sc = lm_base_score(lm, ctx, ctx_len, best, nullptr, nullptr);
+  for (uint32_t i = 1; i < count; i++) {
+    const float sc = lm_base_score(lm, ctx, ctx_len, set[1 + i], nullptr, nullptr);
+    if (sc > best_sc) { best_sc = sc; best = set[1 + i]; }
+  }
+  *score = best_sc;
+  return best;
+}
+
 }  // namespace e2e
 
 // ------------------------------------------------------------------------------------------------------
@@ -151,12 +177,22 @@ struct e2e_lm {
   bool has_lexicon = false;
   std::unordered_map<std::string, unsigned char> lex_class;
   int device = -1;                                       // HIP device that holds the tables (-1: host only)
+  std::vector<std::string> words;                        // id -> word as the model lists it (e2e_lm_word_string)
+  // custom transcriptions (e2e_lm_load_transcriptions): fold_case still folds the WORDS; the label bytes are id codes and
+  // are never folded.  `folded`: folded word -> id, what the vocabulary table says of a model that spells its words.
+  bool transcribed = false;
+  int transcriptions_dropped = 0;
+  std::vector<uint32_t> homs; uint32_t* d_homs = nullptr;
+  std::unordered_map<std::string, uint32_t> folded;
+  std::vector<std::string> tr_keys;                      // the kept transcriptions, as id codes (the lexicon of such a model)
   e2e::LmView host_view() const {
     return {order, vkeys.data(), vvals.data(), (uint32_t)vkeys.size() - 1, ng.data(), (uint32_t)ng.size() - 1, bos,
-            label_bytes.data(), label_off.data(), fold_case, nullptr, nullptr, nullptr, nwords, unk_prob};
+            label_bytes.data(), label_off.data(), transcribed ? 0 : fold_case, nullptr, nullptr, nullptr, nwords, unk_prob,
+            homs.data()};
   }
   e2e::LmView dev_view() const {
     return {order, d_vkeys, d_vvals, (uint32_t)vkeys.size() - 1, d_ng, (uint32_t)ng.size() - 1, bos,
-            d_label_bytes, d_label_off, fold_case, d_ngs, d_ngs ? d_vt : nullptr, d_ngs ? d_uni : nullptr, nwords, unk_prob};
+            d_label_bytes, d_label_off, transcribed ? 0 : fold_case, d_ngs, d_ngs ? d_vt : nullptr, d_ngs ? d_uni : nullptr,
+            nwords, unk_prob, d_homs};
   }
 };

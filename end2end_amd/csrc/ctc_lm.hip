@@ -63,12 +63,14 @@ bool is_special(const std::string& w) { return w == "<unk>" || w == "<s>" || w =
 
 using namespace e2e;
 
-static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::vector<Entry>& entries,
-                        const char* const* labels, int V);
+// a transcription key: the id code of its labels (two bytes per label), its hash, and its words in the lexicon's order
+struct TrKey { std::string code; uint64_t h; std::vector<uint32_t> ids; };
 
-extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int V, int case_sensitive, e2e_lm** out) {
-  if (out) *out = nullptr;
-  if (!path || !out || V < 0 || (V > 0 && !labels)) { set_error("e2e_lm_load_arpa: bad argument"); return E2E_ERR_ARG; }
+static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::vector<Entry>& entries,
+                        const char* const* labels, int V, const std::vector<TrKey>* keys = nullptr);
+
+// reads an ARPA file into a fresh model: its words (lm->exact, id -> word) and n-grams; the tables are build_model's
+static int read_arpa(const char* path, int case_sensitive, e2e_lm** out, std::vector<std::string>& words, std::vector<Entry>& entries) {
   gzFile f = gzopen(path, "rb");
   if (!f) { set_error("cannot open language model %s", path); return E2E_ERR_IO; }
   {
@@ -86,7 +88,6 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
   }
   e2e_lm* lm = new e2e_lm();
   lm->fold_case = case_sensitive ? 0 : 1;
-  std::vector<std::string> words;                          // id -> word; id 0 is <unk>
   auto intern = [&](const std::string& w) -> uint32_t {
     auto it = lm->exact.find(w);
     if (it != lm->exact.end()) return it->second;
@@ -94,8 +95,7 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
     words.push_back(w); lm->exact.emplace(w, id);
     return id;
   };
-  intern("<unk>");
-  std::vector<Entry> entries;
+  intern("<unk>");                                         // id 0 is <unk>
   std::vector<char> buf(1 << 16);
   int section = 0; bool saw_data = false;
   while (gzgets(f, buf.data(), (int)buf.size())) {
@@ -125,15 +125,29 @@ extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int
   gzclose(f);
   if (!saw_data || lm->order == 0) { delete lm; set_error("%s: not an ARPA file (no \\data\\ / n-gram sections)", path); return E2E_ERR_IO; }
   if (lm->order > kLmMaxOrder) { delete lm; set_error("%s: order %d > %d", path, lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
+  *out = lm;
+  return E2E_OK;
+}
+
+extern "C" int e2e_lm_load_arpa(const char* path, const char* const* labels, int V, int case_sensitive, e2e_lm** out) {
+  if (out) *out = nullptr;
+  if (!path || !out || V < 0 || (V > 0 && !labels)) { set_error("e2e_lm_load_arpa: bad argument"); return E2E_ERR_ARG; }
+  std::vector<std::string> words;
+  std::vector<Entry> entries;
+  e2e_lm* lm = nullptr;
+  const int rc = read_arpa(path, case_sensitive, &lm, words, entries);
+  if (rc != E2E_OK) return rc;
   build_model(lm, words, entries, labels, V);
   *out = lm;
   return E2E_OK;
 }
 
 // The tables of a model whose words (id -> word, lm->exact filled) and n-grams have been read: the id-keyed host tables, the
-// kernel's forms of them, their self-check and their upload to the current device.
+// kernel's forms of them, their self-check and their upload to the current device.  With `keys` (custom transcriptions) the
+// vocabulary tables are keyed by those instead of the words' spellings, and label c spells the two bytes of c + 1.
 static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::vector<Entry>& entries,
-                        const char* const* labels, int V) {
+                        const char* const* labels, int V, const std::vector<TrKey>* keys) {
+  lm->words = words;
   {  // <unk> absent from the file: KenLM's default unknown_missing_logprob = -100
     bool has_unk = false;
     for (const auto& e : entries) if (e.n == 1 && e.ids[0] == 0) { has_unk = true; break; }
@@ -154,20 +168,32 @@ static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::
   }
   // vocabulary table keyed by the hash of the (optionally lower-cased) spelling; when two words fold to the same
   // string the reference keeps whichever its unordered_map iteration visits last (unspecified) -- here: lowest id
-  lm->vkeys.assign(pow2_at_least(words.size() * 4 + 16), 0);
+  lm->vkeys.assign(pow2_at_least((keys ? keys->size() : words.size()) * 4 + 16), 0);
   lm->vvals.assign(lm->vkeys.size(), 0);
   const uint32_t vmask = (uint32_t)lm->vkeys.size() - 1;
-  for (uint32_t id = 0; id < words.size(); id++) {
-    const uint64_t h = word_hash(lm->fold_case ? lower(words[id]) : words[id]);
+  auto vput = [&](uint64_t h, uint32_t val) {
     for (uint32_t i = (uint32_t)h & vmask;; i = (i + 1) & vmask) {
       if (lm->vkeys[i] == h) break;
-      if (lm->vkeys[i] == 0) { lm->vkeys[i] = h; lm->vvals[i] = id; break; }
+      if (lm->vkeys[i] == 0) { lm->vkeys[i] = h; lm->vvals[i] = val; break; }
     }
+  };
+  if (!keys) {
+    for (uint32_t id = 0; id < words.size(); id++) vput(word_hash(lm->fold_case ? lower(words[id]) : words[id]), id);
+  } else {
+    lm->transcribed = true;
+    for (const TrKey& k : *keys) {
+      if (k.ids.size() == 1) { vput(k.h, k.ids[0]); continue; }
+      vput(k.h, kHomMark | (uint32_t)lm->homs.size());
+      lm->homs.push_back((uint32_t)k.ids.size());
+      lm->homs.insert(lm->homs.end(), k.ids.begin(), k.ids.end());
+    }
+    if (lm->homs.empty()) lm->homs.push_back(0);
   }
   { auto it = lm->exact.find("<s>"); lm->bos = it != lm->exact.end() ? it->second : 0; }
   lm->label_off.assign(1, 0);
   for (int c = 0; c < V; c++) {
-    for (const char* s = labels[c]; *s; s++) lm->label_bytes.push_back((unsigned char)*s);
+    if (keys) { lm->label_bytes.push_back((unsigned char)((c + 1) & 255)); lm->label_bytes.push_back((unsigned char)((c + 1) >> 8)); }
+    else for (const char* s = labels[c]; *s; s++) lm->label_bytes.push_back((unsigned char)*s);
     lm->label_off.push_back((int)lm->label_bytes.size());
   }
   if (lm->label_bytes.empty()) lm->label_bytes.push_back(0);
@@ -215,7 +241,7 @@ static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::
   std::vector<VEntry> vt(lm->vkeys.size(), VEntry{0, 0u, 1.f});
   for (size_t i = 0; i < lm->vkeys.size() && sig_ok; i++) {      // (one entry per distinct folded spelling already)
     if (lm->vkeys[i] == 0) continue;
-    if (!cuckoo_insert(vt, VEntry{lm->vkeys[i], lm->vvals[i], uni[lm->vvals[i]].prob}))
+    if (!cuckoo_insert(vt, VEntry{lm->vkeys[i], lm->vvals[i], is_hom_ref(lm->vvals[i]) ? 1.f : uni[lm->vvals[i]].prob}))
       sig_ok = false;                                               // (never seen at load <= 1/4; the id-keyed walk takes over)
   }
   // Self-check of what the kernel will read, against the id tables it stands for: every spelling is found in one of its two
@@ -228,7 +254,7 @@ static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::
       uint32_t i1, i2;
       two_slots(lm->vkeys[i], vmask2, i1, i2);
       const VEntry* e = vt[i1].key == lm->vkeys[i] ? &vt[i1] : vt[i2].key == lm->vkeys[i] ? &vt[i2] : nullptr;
-      sig_ok = e && e->val == lm->vvals[i] && e->prob == uni[e->val].prob;
+      sig_ok = e && e->val == lm->vvals[i] && (is_hom_ref(e->val) || e->prob == uni[e->val].prob);
     }
     const LmView hv = lm->host_view();
     for (size_t i = 0; i < lm->ng.size() && sig_ok; i++) {
@@ -256,12 +282,14 @@ static void build_model(e2e_lm* lm, const std::vector<std::string>& words, std::
             up((void**)&lm->d_vvals, lm->vvals.data(), lm->vvals.size() * sizeof(uint32_t)) &&
             up((void**)&lm->d_ng, lm->ng.data(), lm->ng.size() * sizeof(NgSlot)) &&
             up((void**)&lm->d_label_bytes, lm->label_bytes.data(), lm->label_bytes.size()) &&
-            up((void**)&lm->d_label_off, lm->label_off.data(), lm->label_off.size() * sizeof(int));
+            up((void**)&lm->d_label_off, lm->label_off.data(), lm->label_off.size() * sizeof(int)) &&
+            (lm->homs.empty() || up((void**)&lm->d_homs, lm->homs.data(), lm->homs.size() * sizeof(uint32_t)));
   if (!ok) {
     // no usable GPU: keep the host tables (e2e_lm_word_index / e2e_lm_score still work); e2e_ctc_beam refuses it
     (void)hipGetLastError();
     (void)hipFree(lm->d_vkeys); (void)hipFree(lm->d_vvals); (void)hipFree(lm->d_ng);
     (void)hipFree(lm->d_label_bytes); (void)hipFree(lm->d_label_off); (void)hipFree(lm->d_ngs); (void)hipFree(lm->d_vt); (void)hipFree(lm->d_uni);
+    (void)hipFree(lm->d_homs); lm->d_homs = nullptr;
     lm->d_vkeys = nullptr; lm->d_vvals = nullptr; lm->d_ng = nullptr; lm->d_label_bytes = nullptr; lm->d_label_off = nullptr;
     lm->d_ngs = nullptr; lm->d_vt = nullptr; lm->d_uni = nullptr;
   } else if (hipGetDevice(&lm->device) != hipSuccess) {
@@ -273,6 +301,7 @@ extern "C" void e2e_lm_free(e2e_lm* lm) {
   if (!lm) return;
   (void)hipFree(lm->d_vkeys); (void)hipFree(lm->d_vvals); (void)hipFree(lm->d_ng);
   (void)hipFree(lm->d_label_bytes); (void)hipFree(lm->d_label_off); (void)hipFree(lm->d_ngs); (void)hipFree(lm->d_vt); (void)hipFree(lm->d_uni);
+  (void)hipFree(lm->d_homs);
   delete lm;
 }
 
@@ -283,6 +312,10 @@ extern "C" int e2e_lm_device(const e2e_lm* lm) { return lm ? lm->device : -1; }
 extern "C" uint32_t e2e_lm_word_index(const e2e_lm* lm, const char* word) {
   if (!lm || !word) return 0;
   const std::string w = lm->fold_case ? lower(word) : std::string(word);
+  if (lm->transcribed) {                                   // (the vocabulary table is keyed by transcriptions)
+    auto it = lm->folded.find(w);
+    return it == lm->folded.end() ? 0u : it->second;
+  }
   return lm_word_lookup(lm->host_view(), word_hash(w));
 }
 
@@ -323,7 +356,7 @@ extern "C" int e2e_lm_has_lexicon(const e2e_lm* lm) { return lm && lm->has_lexic
 
 // bit 0: the spelling is a word of the lexicon; bit 1: it is a proper prefix of a longer word.  0 without a lexicon.
 extern "C" int e2e_lm_spelling_class(const e2e_lm* lm, const char* spelling) {
-  if (!lm || !spelling || !lm->has_lexicon) return 0;
+  if (!lm || !spelling || !lm->has_lexicon || lm->transcribed) return 0;
   auto it = lm->lex_class.find(lm->fold_case ? lower(spelling) : std::string(spelling));
   return it == lm->lex_class.end() ? 0 : it->second;
 }
@@ -338,7 +371,10 @@ extern "C" int e2e_lm_enable_lexicon(e2e_lm* lm) {
   const LmView hv = lm->host_view();
   std::unordered_map<std::string, unsigned char> cls;
   std::vector<std::string> prefixes;                       // proper prefixes that are no words
-  for (const auto& kv : lm->exact) {
+  // (a transcription model: L is the kept transcriptions, as id codes, and a prefix ends on a label boundary)
+  const size_t unit = lm->transcribed ? 2 : 1;
+  if (lm->transcribed) for (const auto& k : lm->tr_keys) cls[k] |= 1;
+  else for (const auto& kv : lm->exact) {
     if (is_special(kv.first)) continue;
     cls[lm->fold_case ? lower(kv.first) : kv.first] |= 1;
   }
@@ -346,7 +382,7 @@ extern "C" int e2e_lm_enable_lexicon(e2e_lm* lm) {
     std::vector<std::string> ws;
     for (const auto& kv : cls) ws.push_back(kv.first);
     for (const auto& w : ws)
-      for (size_t n = 1; n < w.size(); n++) {
+      for (size_t n = unit; n < w.size(); n += unit) {
         unsigned char& c = cls[w.substr(0, n)];
         if (c == 0) prefixes.push_back(w.substr(0, n));
         c |= 2;
@@ -360,8 +396,10 @@ extern "C" int e2e_lm_enable_lexicon(e2e_lm* lm) {
     std::string s((const char*)lm->label_bytes.data() + lm->label_off[c], (size_t)(lm->label_off[c + 1] - lm->label_off[c]));
     return lm->fold_case ? lower(s) : s;
   };
+  // (A transcription model cannot spell them at all: they have no transcription.)
   for (const char* sp : {"<unk>", "<s>", "</s>"}) {
     const std::string s = sp;
+    if (lm->transcribed) break;
     if (!lm->exact.count(s) && !(lm->fold_case && lm_word_lookup(hv, word_hash(s)))) continue;
     std::vector<char> reach(s.size() + 1, 0);
     reach[0] = 1;
@@ -438,5 +476,136 @@ extern "C" int e2e_lm_enable_lexicon(e2e_lm* lm) {
   lm->vkeys.swap(vkeys); lm->vvals.swap(vvals);
   lm->lex_class.swap(cls);
   lm->has_lexicon = true;
+  return E2E_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// custom transcriptions (a pronunciation lexicon), homophones included: the definition is in DESIGN.md 4.4
+// ------------------------------------------------------------------------------------------------------
+extern "C" int e2e_lm_is_transcribed(const e2e_lm* lm) { return lm && lm->transcribed ? 1 : 0; }
+extern "C" int e2e_lm_transcriptions_dropped(const e2e_lm* lm) { return lm ? lm->transcriptions_dropped : 0; }
+extern "C" const char* e2e_lm_word_string(const e2e_lm* lm, uint32_t id) {
+  return lm && id < lm->words.size() ? lm->words[id].c_str() : nullptr;
+}
+
+extern "C" int e2e_lm_load_transcriptions(const char* path, const char* const* entry_words, const int32_t* entry_label_ids,
+                                          const int32_t* entry_off, int n_entries, const char* const* labels, int V,
+                                          int case_sensitive, e2e_lm** out) {
+  if (out) *out = nullptr;
+  if (!out || n_entries < 0 || V < 1 || !labels || (n_entries > 0 && (!entry_words || !entry_off || !entry_label_ids))) {
+    set_error("e2e_lm_load_transcriptions: bad argument");
+    return E2E_ERR_ARG;
+  }
+  if (n_entries == 0) { set_error("e2e_lm_load_transcriptions: the lexicon is empty"); return E2E_ERR_ARG; }
+  if (V > 65535) { set_error("e2e_lm_load_transcriptions: %d labels: a label's code has two bytes, at most 65535", V); return E2E_ERR_UNSUPPORTED; }
+  // every entry's form, before anything is loaded
+  for (int i = 0; i < n_entries; i++) {
+    const char* w = entry_words[i];
+    if (!w || !*w || strpbrk(w, " \t\r\n")) { set_error("e2e_lm_load_transcriptions: entry %d: the word is empty or holds white space", i); return E2E_ERR_ARG; }
+    if (is_special(w)) { set_error("e2e_lm_load_transcriptions: entry %d: %s has no transcription", i, w); return E2E_ERR_ARG; }
+    const int64_t k = (int64_t)entry_off[i + 1] - entry_off[i];
+    if (entry_off[i] < 0 || k < 1) { set_error("e2e_lm_load_transcriptions: entry %d (%s) has no labels", i, w); return E2E_ERR_ARG; }
+    if (k > kMaxTranscription) {
+      set_error("e2e_lm_load_transcriptions: entry %d (%s) has %lld labels: at most %d", i, w, (long long)k, kMaxTranscription);
+      return E2E_ERR_UNSUPPORTED;
+    }
+    for (int j = entry_off[i]; j < entry_off[i + 1]; j++) {
+      const int c = entry_label_ids[j];
+      if (c < 0 || c >= V) { set_error("e2e_lm_load_transcriptions: entry %d (%s): %d is no label id (V = %d)", i, w, c, V); return E2E_ERR_ARG; }
+      if (strcmp(labels[c], " ") == 0) { set_error("e2e_lm_load_transcriptions: entry %d (%s): the space is the word boundary and no token", i, w); return E2E_ERR_ARG; }
+    }
+  }
+  std::vector<std::string> words;
+  std::vector<Entry> entries;
+  e2e_lm* lm = nullptr;
+  if (path) {
+    const int rc = read_arpa(path, case_sensitive, &lm, words, entries);
+    if (rc != E2E_OK) return rc;
+  } else {                                                 // the model that scores nothing (e2e_lm_load_words) over the entries' words
+    lm = new e2e_lm();
+    lm->fold_case = case_sensitive ? 0 : 1;
+    lm->order = 1;
+    auto add = [&](const std::string& w) {
+      if (!lm->exact.emplace(w, (uint32_t)words.size()).second) return;
+      Entry e; e.n = 1; e.ids[0] = (uint32_t)words.size(); e.prob = 0.f; e.bo = 0.f;
+      words.push_back(w); entries.push_back(e);
+    };
+    add("<unk>"); add("<s>"); add("</s>");
+    for (int i = 0; i < n_entries; i++) add(entry_words[i]);
+  }
+  for (uint32_t id = 0; id < words.size(); id++)           // (two words that fold to one string: the lowest id, as build_model)
+    lm->folded.emplace(lm->fold_case ? lower(words[id]) : words[id], id);
+  std::vector<TrKey> keys;
+  std::unordered_map<std::string, size_t> at;              // code -> index in keys
+  std::unordered_map<uint64_t, size_t> by_hash;
+  for (int i = 0; i < n_entries; i++) {
+    const std::string w = lm->fold_case ? lower(entry_words[i]) : std::string(entry_words[i]);
+    auto it = lm->folded.find(w);
+    if (it == lm->folded.end() || is_special(words[it->second])) { lm->transcriptions_dropped++; continue; }
+    std::string code;
+    for (int j = entry_off[i]; j < entry_off[i + 1]; j++) {
+      const int c = entry_label_ids[j] + 1;
+      code.push_back((char)(c & 255)); code.push_back((char)(c >> 8));
+    }
+    auto ins = at.emplace(code, keys.size());
+    if (ins.second) {
+      const uint64_t h = word_hash(code);
+      if (!by_hash.emplace(h, keys.size()).second) {
+        delete lm;
+        set_error("e2e_lm_load_transcriptions: entry %d (%s): its transcription shares a 64-bit hash with another", i, entry_words[i]);
+        return E2E_ERR_UNSUPPORTED;
+      }
+      keys.push_back(TrKey{code, h, {}});
+    }
+    std::vector<uint32_t>& ids = keys[ins.first->second].ids;
+    if (std::find(ids.begin(), ids.end(), it->second) != ids.end()) continue;        // (listed twice: once)
+    if ((int)ids.size() == kMaxHomophones) {
+      delete lm;
+      set_error("e2e_lm_load_transcriptions: entry %d (%s): more than %d words share its transcription", i, entry_words[i], kMaxHomophones);
+      return E2E_ERR_UNSUPPORTED;
+    }
+    ids.push_back(it->second);
+  }
+  for (const TrKey& k : keys) lm->tr_keys.push_back(k.code);
+  build_model(lm, words, entries, labels, V, &keys);
+  *out = lm;
+  return E2E_OK;
+}
+
+// The words of a label sequence, as a search over this model reads them: split at the space (empty pieces skipped), each
+// piece looked up as the kernel spells it, a homophone set resolved in the running context (lm_homophone_choice).  A piece
+// that is no key is <unk> (0).  Writes at most max_words ids; *n_words is the number of pieces.
+extern "C" int e2e_lm_transcribe(const e2e_lm* lm, const int64_t* ids, int64_t n, int space_id, uint32_t* word_ids_out,
+                                 int max_words, int* n_words) {
+  if (n_words) *n_words = 0;
+  if (!lm || n < 0 || (n > 0 && !ids) || max_words < 0 || (max_words > 0 && !word_ids_out) || !n_words) {
+    set_error("e2e_lm_transcribe: bad argument");
+    return E2E_ERR_ARG;
+  }
+  const int V = (int)lm->label_off.size() - 1;
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] < 0 || ids[i] >= V) { set_error("e2e_lm_transcribe: id %lld at %lld is no label (V = %d)", (long long)ids[i], (long long)i, V); return E2E_ERR_ARG; }
+  const LmView hv = lm->host_view();
+  uint32_t ctx[kLmMaxOrder] = {lm->bos}; int ctx_len = 1;
+  int count = 0;
+  for (int64_t i = 0; i < n;) {
+    if (ids[i] == space_id) { i++; continue; }
+    uint64_t h = kFnvInit;
+    for (; i < n && ids[i] != space_id; i++)
+      for (int b = lm->label_off[ids[i]]; b < lm->label_off[ids[i] + 1]; b++) {
+        unsigned char ch = lm->label_bytes[b];
+        if (hv.fold_case && ch >= 'A' && ch <= 'Z') ch += 32;
+        h = fnv_step(h, ch);
+      }
+    uint32_t w = lm_word_lookup(hv, h);
+    if (is_hom_ref(w)) { float sc; w = lm_homophone_choice(hv, w, ctx, ctx_len, &sc); }
+    uint32_t next[kLmMaxOrder]; int next_len = 0;
+    (void)lm_base_score(hv, ctx, ctx_len, w, next, &next_len);
+    for (int k = 0; k < next_len; k++) ctx[k] = next[k];
+    ctx_len = next_len;
+    if (count < max_words) word_ids_out[count] = w;
+    count++;
+  }
+  *n_words = count;
   return E2E_OK;
 }

@@ -46,6 +46,19 @@ class LanguageModel {
     for (const auto& s : labels) c.push_back(s.c_str());
     check(e2e_lm_load_words(w.data(), (int)w.size(), c.data(), (int)c.size(), case_sensitive ? 1 : 0, &lm_));
   }
+  // a model keyed by custom transcriptions (e2e_lm_load_transcriptions); path "": the model that scores nothing
+  struct FromTranscriptions {};
+  LanguageModel(FromTranscriptions, const std::string& path, const std::vector<std::string>& words,
+                const std::vector<int32_t>& label_ids, const std::vector<int32_t>& offsets,
+                const std::vector<std::string>& labels, bool case_sensitive) {
+    if (offsets.size() != words.size() + 1 || (int64_t)label_ids.size() != (offsets.empty() ? 0 : offsets.back()))
+      throw E2EError("libe2e_ctc: transcriptions: offsets must have one entry per word and one more, the last the number of label ids");
+    std::vector<const char*> w, c;
+    for (const auto& s : words) w.push_back(s.c_str());
+    for (const auto& s : labels) c.push_back(s.c_str());
+    check(e2e_lm_load_transcriptions(path.empty() ? nullptr : path.c_str(), w.data(), label_ids.data(), offsets.data(),
+                                     (int)w.size(), c.data(), (int)c.size(), case_sensitive ? 1 : 0, &lm_));
+  }
   ~LanguageModel() { e2e_lm_free(lm_); }
   LanguageModel(const LanguageModel&) = delete;
   LanguageModel& operator=(const LanguageModel&) = delete;
@@ -59,6 +72,19 @@ class LanguageModel {
   int spelling_class(const std::string& s) const { return e2e_lm_spelling_class(lm_, s.c_str()); }
   double score(const std::vector<uint32_t>& ctx, uint32_t word) const {
     return e2e_lm_score(lm_, ctx.data(), (int)ctx.size(), word);
+  }
+  bool is_transcribed() const { return e2e_lm_is_transcribed(lm_) != 0; }
+  int transcriptions_dropped() const { return e2e_lm_transcriptions_dropped(lm_); }
+  std::vector<uint32_t> transcribe(const std::vector<int64_t>& ids, int space_id) const {
+    std::vector<uint32_t> out(ids.size() + 1);
+    int n = 0;
+    check(e2e_lm_transcribe(lm_, ids.data(), (int64_t)ids.size(), space_id, out.data(), (int)out.size(), &n));
+    out.resize((size_t)n);
+    return out;
+  }
+  py::object word_string(uint32_t id) const {
+    const char* s = e2e_lm_word_string(lm_, id);
+    return s ? py::object(py::str(s)) : py::object(py::none());
   }
 
  private:
@@ -434,6 +460,18 @@ PYBIND11_MODULE(_C, m) {
                     return new LanguageModel(LanguageModel::FromWords{}, words, labels, case_sensitive);
                   },
                   py::arg("words"), py::arg("labels"), py::arg("case_sensitive"), py::return_value_policy::take_ownership)
+      .def_static("from_transcriptions",
+                  [](const std::string& path, const std::vector<std::string>& words, const std::vector<int32_t>& label_ids,
+                     const std::vector<int32_t>& offsets, const std::vector<std::string>& labels, bool case_sensitive) {
+                    return new LanguageModel(LanguageModel::FromTranscriptions{}, path, words, label_ids, offsets, labels,
+                                             case_sensitive);
+                  },
+                  py::arg("path"), py::arg("words"), py::arg("label_ids"), py::arg("offsets"), py::arg("labels"),
+                  py::arg("case_sensitive"), py::return_value_policy::take_ownership)
+      .def("is_transcribed", &LanguageModel::is_transcribed)
+      .def("transcriptions_dropped", &LanguageModel::transcriptions_dropped)
+      .def("transcribe", &LanguageModel::transcribe, py::arg("ids"), py::arg("space_id"))
+      .def("word_string", &LanguageModel::word_string, py::arg("id"))
       .def_property_readonly("handle", &LanguageModel::handle)
       .def("enable_lexicon", &LanguageModel::enable_lexicon)
       .def("has_lexicon", &LanguageModel::has_lexicon)

@@ -59,11 +59,19 @@ class CTCDecoder:
     :param lexicon: (extension) restrict the beam search to these words without a language model: an iterable of words,
         or the path of a text file with one entry per line whose first white-space separated token is the word (so a
         pronunciation dictionary works).  ``lmwt`` and ``oov_penalty`` then count as 0; ``wip`` applies.
+    :param transcriptions: (extension) custom transcriptions for models whose labels do not spell the words letter by
+        letter (phonemes, word pieces, multi-character labels): the path of a text file with one entry ``word tok tok ...``
+        per line, a mapping ``word -> tokens`` (or ``-> [tokens, tokens, ...]`` for variants), or an iterable of
+        ``(word, tokens)``; every token is one of ``labels``, neither the blank nor the space.  A word is then found by its
+        sequence of labels; of several words with one transcription (homophones) the language model picks the likeliest in
+        its context.  Goes with ``lm_path`` (entries whose word the model does not list are dropped, with a warning) or
+        alone (nothing is scored, the first listed homophone wins), and with ``restrict_to_vocabulary=True``.
+        ``decoded_sentences`` are the chosen words joined by single spaces, ``<unk>`` for a piece that is no word.
     """
 
     def __init__(self, beam_width=100, after_logsoftmax=False, blank_idx=0, time_major=False, labels=None,
                  lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True, keep_on_device=False,
-                 restrict_to_vocabulary=False, lexicon=None):
+                 restrict_to_vocabulary=False, lexicon=None, transcriptions=None):
         self._beam_width = beam_width
         self._blank_idx = blank_idx
         self._after_logsoftmax = after_logsoftmax
@@ -76,11 +84,20 @@ class CTCDecoder:
         self._case_sensitive = case_sensitive
         self._restrict = bool(restrict_to_vocabulary) or lexicon is not None
         self._lexicon = lexicon
+        self._transcriptions = transcriptions
         self._check_params()
-        self._decoder = CTCDecoderEngine(self._blank_idx, self._beam_width, self._labels, self._lm_path,
+        # (a transcription model is loaded once, by configure: the engine's constructor would key it by spellings)
+        self._decoder = CTCDecoderEngine(self._blank_idx, self._beam_width, self._labels,
+                                         "" if transcriptions is not None else self._lm_path,
                                          self._lmwt, self._wip, self._oov_penalty, self._case_sensitive,
                                          keep_on_device=keep_on_device)
-        if self._restrict:
+        if transcriptions is not None:
+            try:
+                self._decoder.configure(restrict_to_vocabulary=self._restrict, transcriptions=transcriptions,
+                                        lm_path=self._lm_path or None)
+            except ValueError as e:
+                raise CTCDecoderError(str(e)) from e
+        elif self._restrict:
             self._decoder.configure(restrict_to_vocabulary=True, lexicon=self._lexicon)
 
     def _check_params(self):
@@ -90,6 +107,13 @@ class CTCDecoder:
             # decode() then fails because the alphabet cannot spell words)
             if not os.path.isfile(self._lm_path):
                 raise CTCDecoderError("Can't find a model: {}".format(self._lm_path))
+        if self._transcriptions is not None:
+            if self._lexicon is not None:
+                raise CTCDecoderError("lexicon together with transcriptions is not supported: restrict_to_vocabulary=True "
+                                      "restricts the search to the transcriptions")
+            if self._beam_width == 1:
+                raise CTCDecoderError("transcriptions need beam_width > 1: greedy decoding forms no words")
+            return
         if self._restrict:
             if self._lexicon is not None and self._lm_path:
                 raise CTCDecoderError("lexicon together with lm_path is not supported: restrict_to_vocabulary=True "
@@ -152,6 +176,15 @@ class CTCDecoder:
         if self._beam_width == 1:
             raise CTCDecoderError("a stream needs beam_width > 1: greedy decoding has no beam to keep")
         return CTCDecoderStream(self, self._decoder.open_stream(batch_size, max_frames, device=device, timesteps=timesteps))
+
+    def transcribe(self, ids):
+        """The words of a sequence of label ids as the search reads them: split at the space, every piece looked up by its
+        labels, homophones chosen by the language model in the running context; ``<unk>`` for a piece that is no word.
+        Needs ``transcriptions``."""
+        lm = self._decoder.lm
+        if lm is None or not lm.is_transcribed():
+            raise CTCDecoderError("transcribe needs a decoder with transcriptions")
+        return lm.transcribe([int(k) for k in ids if int(k) >= 0], self._decoder.space_id)
 
     def _print_scores_for_sentence(self, words):
         self._decoder.print_scores_for_sentence(words)

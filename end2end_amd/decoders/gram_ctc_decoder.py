@@ -36,7 +36,9 @@ class GramCTCDecoder:
     """
 
     def __init__(self, blank_idx=0, num_base_labels=None, total_labels=None, label2ids=None, beam_width=100, labels=None,
-                 after_logsoftmax=False, time_major=False, keep_on_device=False):
+                 after_logsoftmax=False, time_major=False, keep_on_device=False, transcriptions=None):
+        if transcriptions is not None:
+            raise CTCDecoderError("GramCTCDecoder does not support custom transcriptions: its search carries no word model")
         if num_base_labels is None or total_labels is None:
             raise CTCDecoderError("GramCTCDecoder needs num_base_labels and total_labels (the arguments of GramCTCLoss)")
         self._beam_width = beam_width

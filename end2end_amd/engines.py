@@ -18,7 +18,9 @@ to the C ABI (include/e2e_ctc.h) through the pybind11 layer `end2end_amd._C`.  C
 and the loss results moved back to the source device and dtype (forward_backward.cpp:55-56); decode results are CPU
 tensors as upstream (ctc_decoder.cpp:157,449) unless `keep_on_device` is set.
 """
+import os
 import threading
+import warnings
 
 import numpy as np
 import torch
@@ -711,22 +713,80 @@ class GramCTCDecoderEngine:
         return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
 
 
+def read_transcriptions(transcriptions, labels, blank_idx=None):
+    """The entries of a transcription lexicon as [(word, [label ids])], in order: from the text file at a path (wav2letter's
+    format: one entry per line, `word tok tok ...`, split at white space), from a mapping word -> tokens or -> a list of
+    token sequences (variants), or from an iterable of (word, tokens).  Tokens are label strings, matched exactly; an
+    unknown token, the blank or the space as a token is a ValueError that names the entry."""
+    if isinstance(transcriptions, (str, bytes, os.PathLike)):
+        path = os.fsdecode(transcriptions)
+        if not os.path.isfile(path):
+            raise ValueError("Can't find a transcription lexicon: {}".format(path))
+        with open(path, encoding="utf-8") as f:
+            entries = [(ln.split()[0], ln.split()[1:]) for ln in f.read().splitlines() if ln.split()]
+    elif hasattr(transcriptions, "items"):
+        entries = []
+        for w, t in transcriptions.items():
+            variants = [t] if (isinstance(t, str) or not t or isinstance(t[0], str)) else t
+            entries += [(w, v) for v in variants]
+    else:
+        entries = [(w, t) for w, t in transcriptions]
+    index = {}
+    for i, s in enumerate(labels):
+        index.setdefault(s, i)
+    out = []
+    for n, (w, toks) in enumerate(entries):
+        toks = toks.split() if isinstance(toks, str) else list(toks)
+        name = "entry %d (%s)" % (n, w)
+        if not toks:
+            raise ValueError("transcriptions: %s has no tokens" % name)
+        ids = []
+        for t in toks:
+            if t not in index:
+                raise ValueError("transcriptions: %s: the token %r is none of the labels" % (name, t))
+            if t == " ":
+                raise ValueError("transcriptions: %s: the space is the word boundary and no token" % name)
+            if blank_idx is not None and index[t] == blank_idx:
+                raise ValueError("transcriptions: %s: the blank %r is no token" % (name, t))
+            ids.append(index[t])
+        out.append((str(w), ids))
+    if not out:
+        raise ValueError("transcriptions: the lexicon is empty")
+    return out
+
+
 class LanguageModel:
     """n-gram model read from an ARPA file (plain or .gz); stands where KenLM stands upstream
     (ctc_decoder.cpp:60-71).  The device tables belong to one GPU: `on(device)` returns the copy for that device,
     loading it on first use.  With `words` (and no path) it is the model that scores nothing, built from a word list
     (e2e_lm_load_words).  `lexicon=True`, or `enable_lexicon()` later, gives every copy the lexicon a search can be
-    restricted to; unrestricted decoders may go on sharing the model."""
+    restricted to; unrestricted decoders may go on sharing the model.  With `transcriptions` (see read_transcriptions;
+    together with a path, or with None for the model that scores nothing) a word is found by its sequence of labels instead
+    of their spelling, homophones included (e2e_lm_load_transcriptions); entries whose word the ARPA file does not list
+    are dropped, with one warning that counts them."""
 
-    def __init__(self, path, labels, case_sensitive, words=None, lexicon=False):
+    def __init__(self, path, labels, case_sensitive, words=None, lexicon=False, transcriptions=None, blank_idx=None):
         self.path, self.labels, self.case_sensitive = path, list(labels), bool(case_sensitive)
         self.words = None if words is None else list(words)
+        if transcriptions is not None and words is not None:
+            raise ValueError("words and transcriptions exclude each other")
+        self.transcriptions = None if transcriptions is None else read_transcriptions(transcriptions, self.labels, blank_idx)
         self._lexicon = bool(lexicon)
         self._per_device = {}
         self._first = self._load()
+        if self.transcriptions is not None and self._first.transcriptions_dropped():
+            warnings.warn("transcriptions: %d of %d entries dropped: the language model does not list their words"
+                          % (self._first.transcriptions_dropped(), len(self.transcriptions)))
 
     def _load(self):
-        if self.words is not None:
+        if self.transcriptions is not None:
+            flat, off = [], [0]
+            for _, ids in self.transcriptions:
+                flat += ids
+                off.append(len(flat))
+            lm = _C.LanguageModel.from_transcriptions(self.path or "", [w for w, _ in self.transcriptions], flat, off,
+                                                      self.labels, self.case_sensitive)
+        elif self.words is not None:
             lm = _C.LanguageModel.from_words(self.words, self.labels, self.case_sensitive)
         else:
             lm = _C.LanguageModel(self.path, self.labels, self.case_sensitive)
@@ -767,6 +827,18 @@ class LanguageModel:
     def score(self, ctx, word):
         return self._first.score(list(ctx), word)
 
+    def is_transcribed(self):
+        return self._first.is_transcribed()
+
+    def transcriptions_dropped(self):
+        return self._first.transcriptions_dropped()
+
+    def transcribe(self, ids, space_id):
+        """The words of a label sequence as a search over this model reads them (e2e_lm_transcribe): split at the space,
+        homophones chosen by the model in the running context; a piece that is no word is '<unk>'."""
+        f = self._first
+        return [f.word_string(w) if w else "<unk>" for w in f.transcribe([int(k) for k in ids], int(space_id))]
+
 
 class CTCDecoderEngine:
     """Same constructor arguments and defaults as the pybind class
@@ -806,14 +878,27 @@ class CTCDecoderEngine:
                 raise ValueError("beam_width %d is not supported for an alphabet of %d labels%s: at most %d"
                                  % (self.beam_width, len(self.labels), " with a language model" if with_lm else "", cap))
 
-    def configure(self, restrict_to_vocabulary=False, lexicon=None, lm=None):
+    def configure(self, restrict_to_vocabulary=False, lexicon=None, lm=None, transcriptions=None, lm_path=None):
         """Extensions, set once before decoding; returns self.
         `restrict_to_vocabulary`: the beam search only forms words of the language model's vocabulary.
         `lexicon`: an iterable of words; the search is restricted to them without a language model -- a model that scores
         nothing is built from the list, `lmwt` and `oov_penalty` then count as 0 (as `lmwt` does upstream without a model),
         `wip` applies, and the width limit is the one with a language model.
         `lm`: a LanguageModel loaded already, for a decoder constructed without `lm_path`: decoders, restricted or not, may
-        share one instead of loading the file each."""
+        share one instead of loading the file each.
+        `transcriptions`: a transcription lexicon (read_transcriptions): words are found by their label sequences, homophones
+        chosen by the language model; `sentences` are then the words.  With the constructor's `lm_path` or the `lm_path` given
+        here the model scores them; alone it is the model that scores nothing (every listed word at log10 p = 0)."""
+        if lm_path is not None and transcriptions is None:
+            raise ValueError("lm_path is the constructor's; configure takes it only together with transcriptions")
+        if transcriptions is not None:
+            if lexicon is not None or lm is not None:
+                raise ValueError("transcriptions exclude lexicon and lm (restrict_to_vocabulary=True restricts to the transcriptions)")
+            if self.beam_width == 1:
+                raise ValueError("transcriptions need beam_width > 1: greedy decoding forms no words")
+            path = lm_path or (self.lm.path if self.lm is not None else None)
+            self.lm = None
+            lm = LanguageModel(path, self.labels, self.case_sensitive, transcriptions=transcriptions, blank_idx=self.blank_idx)
         restrict = bool(restrict_to_vocabulary) or lexicon is not None
         if sum(1 for m in (self.lm is not None, lexicon is not None, lm is not None) if m) > 1:
             raise ValueError("lm_path, lexicon and lm exclude each other (a lexicon together with a language model is not supported)")
@@ -843,6 +928,11 @@ class CTCDecoderEngine:
         # the reference then reads labels[-1] out of bounds (undefined behaviour) -- here that id spells nothing.
         if not self.labels:
             return ["" for _ in lens]
+        if self.lm is not None and self.lm.is_transcribed():
+            # a transcription model: the words the search chose, not the labels' strings
+            if isinstance(rows, torch.Tensor):
+                rows = rows.tolist()
+            return [" ".join(self.lm.transcribe([k for k in row[:n] if k >= 0], self.space_id)) for row, n in zip(rows, lens)]
         if self._codes is not None and len(lens) and isinstance(rows, torch.Tensor):
             # one-character labels (the usual alphabet): one table lookup and one decode for the whole batch instead of a
             # Python-level join per id (4 ms of a 17 ms beam-search call at B=64, T=1500)

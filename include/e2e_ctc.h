@@ -589,6 +589,53 @@ int e2e_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, in
                            void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * Custom transcriptions: a pronunciation lexicon, homophones included (additive, ABI 4: nothing above changes meaning).
+ *
+ * A transcription lexicon is a list of entries (word, t_1 .. t_k), k >= 1, every t_i a label of the decoder that is neither
+ * the blank nor the space.  A word may have several entries (variants); a transcription may belong to several words
+ * (homophones).  A model loaded with one finds a prefix's last word by its sequence of label IDS between two spaces, not by
+ * the labels' strings: with labels A, AH, HK, K the transcriptions "A HK" and "AH K" are different keys.  Everything else
+ * of the search -- e2e_ctc_beam, _nbest, _nbest_opt, _stream -- is what it was.
+ *   - Wd(s) is the set of the model's words with transcription s, in the order of their first entry.  The word of a child
+ *     whose last word is transcribed s is the w in Wd(s) with the greatest log10 p(w | the LM state before the word), the f32
+ *     value the search's own LM walk computes; exact ties go to the earliest of Wd(s).  Its LM score, LM state and
+ *     out-of-vocabulary count are that word's.  The choice is made again at every label, from the state before the word.
+ *   - A transcription that is no key, or only a proper prefix of one, is <unk> (id 0, out of vocabulary).
+ *   - Restricted to the lexicon (e2e_lm_enable_lexicon, restrict_to_lexicon): L is the set of kept transcriptions, Pref(L)
+ *     their non-empty prefixes on label boundaries; the rule above holds on these.
+ * Limits: a transcription has at most 255 labels; at most 16 words share one (E2E_ERR_UNSUPPORTED beyond either); the word
+ * boundary is the label " "; at most 65535 labels; LM order <= 6.  <unk>, <s> and </s> have no transcription (E2E_ERR_ARG as an entry's word).
+ * e2e_asg_beam refuses such a model (E2E_ERR_UNSUPPORTED).
+ *
+ * e2e_lm_load_transcriptions     path: an ARPA file (as e2e_lm_load_arpa), or NULL for the model that scores nothing over the
+ *                                entries' words (as e2e_lm_load_words: homophones always tie, the first listed wins).
+ *                                entry_words[i] is entry i's word; its label ids are entry_label_ids[entry_off[i] ..
+ *                                entry_off[i+1]) (all host).  Words are matched to the model's as e2e_lm_word_index matches
+ *                                them (lower-cased on both sides unless case_sensitive).  With an ARPA file an entry whose
+ *                                word the model does not list is dropped.  E2E_ERR_ARG, naming the entry, for an empty
+ *                                lexicon, an entry without labels, an id outside [0, V) or the space as a token.  (The blank
+ *                                is not known here: the caller keeps it out of the entries.)  Uploads like e2e_lm_load_arpa
+ *                                and also works with no GPU (e2e_lm_device == -1).
+ * e2e_lm_is_transcribed          1 for a model of e2e_lm_load_transcriptions.  On such a model e2e_lm_word_index still takes a
+ *                                word's string; e2e_lm_spelling_class, which takes a spelling, answers 0.
+ * e2e_lm_transcriptions_dropped  the number of entries dropped at load.
+ * e2e_lm_transcribe              host helper: the words of a label sequence as the search reads them.  ids (host, n of them) is
+ *                                split at space_id, empty pieces skipped; every piece is looked up and a homophone set is
+ *                                resolved in the running context with the host scorer, starting behind <s>.  Writes at most
+ *                                max_words word ids (0 = <unk>: no key) and the number of pieces to *n_words.  Works on every
+ *                                model: one without transcriptions spells the pieces from the labels' strings.
+ * e2e_lm_word_string             the word of an id as the model lists it (owned by the model), NULL for an id it has not.
+ */
+int e2e_lm_load_transcriptions(const char* path /* host or NULL */, const char* const* entry_words /* host */,
+                               const int32_t* entry_label_ids /* host */, const int32_t* entry_off /* host, n_entries + 1 */,
+                               int n_entries, const char* const* labels /* host */, int V, int case_sensitive, e2e_lm** out);
+int e2e_lm_is_transcribed(const e2e_lm* lm);
+int e2e_lm_transcriptions_dropped(const e2e_lm* lm);
+int e2e_lm_transcribe(const e2e_lm* lm, const int64_t* ids /* host */, int64_t n, int space_id,
+                      uint32_t* word_ids_out /* host */, int max_words, int* n_words /* host */);
+const char* e2e_lm_word_string(const e2e_lm* lm, uint32_t id);
+
+/* ------------------------------------------------------------------------
  * Streaming beam search: the same search fed in chunks, the beam kept on the device between the calls (additive, ABI 4:
  * nothing above changes meaning).
  *
