@@ -69,7 +69,9 @@ class Search:
         self.chars, self.lm, self.case_sensitive = chars, lm, case_sensitive
         self.lmwt = lmwt if lm is not None else 0.0
         self.wip, self.oov = wip, oov
-        self.min_gap = math.inf      # smallest positive gap between the W-th and (W+1)-th total over all cuts
+        # the smallest gap between the W-th and the (W+1)-th total over all cuts (0: an exact tie, cut by key) and between
+        # neighbours of a final ranking whose totals differ
+        self.min_gap = math.inf
 
     def child_fields(self, p, last, c):
         n = LmFields()
@@ -100,13 +102,21 @@ class Search:
         return ac + f.lm * self.lmwt - f.words * self.wip + f.oov * self.oov
 
     def ranked(self, cands, cut):
-        """cands: {seq: (ac, fields)} -> [(seq, ac, fields, total)] by total descending, key ascending."""
+        """cands: {seq: (ac, fields)} -> [(seq, ac, fields, total)] by total descending, key ascending.  A candidate whose
+        total is -inf or NaN is no candidate: it is dropped before the sort and before the cut."""
         rows = [(seq, ac, f, self.total(ac, f)) for seq, (ac, f) in cands.items()]
-        rows.sort(key=lambda r: (-r[3], key_of(r[0])))
+        rows = [r for r in rows if r[3] > NEG_INF]
+        rows.sort(key=lambda r: -r[3])
+        i = 0
+        while i < len(rows):                                              # (a key costs its sequence's length: only ties ask)
+            j = i + 1
+            while j < len(rows) and rows[j][3] == rows[i][3]:
+                j += 1
+            if j - i > 1:
+                rows[i:j] = sorted(rows[i:j], key=lambda r: key_of(r[0]))
+            i = j
         if cut and self.W is not None and len(rows) > self.W:
-            gap = rows[self.W - 1][3] - rows[self.W][3]
-            if gap > 0:
-                self.min_gap = min(self.min_gap, gap)
+            self.min_gap = min(self.min_gap, rows[self.W - 1][3] - rows[self.W][3])
             rows = rows[: self.W]
         return rows
 
@@ -121,6 +131,8 @@ class Search:
                 cands[(c,)] = (float(x[0][c]), self.child_fields(root, None, c))
         beam = self.ranked(cands, cut=True)
         for t in range(1, n):
+            if not beam:                                                  # nothing has a number for a total: no hypotheses
+                return []
             members = {seq: (ac, f) for seq, ac, f, _ in beam}
             stay, extn, fields = {}, {}, {}
             for seq, (s, f) in members.items():
@@ -138,12 +150,15 @@ class Search:
                         fields[child] = self.child_fields(f, a, c)
             cands = {seq: (lse(stay.get(seq, NEG_INF), extn.get(seq, NEG_INF)), fields[seq]) for seq in set(stay) | set(extn)}
             beam = self.ranked(cands, cut=True)
+        for hi, lo in zip(beam, beam[1:]):                                # (the final order is compared exactly)
+            if hi[3] != lo[3]:
+                self.min_gap = min(self.min_gap, hi[3] - lo[3])
         return [dict(ids=seq, total=tot, ac=ac, lm=f.lm, words=f.words, oov=f.oov) for seq, ac, f, tot in beam]
 
 
 def beam(x, A, x_len, V, R=0, space_id=-1, W=None, chars=None, lm=None, case_sensitive=True, lmwt=1.0, wip=0.0,
          oov_penalty=0.0):
-    """The whole final ranking of every utterance of x (B,T,V) and the smallest positive cut gap met:
+    """The whole final ranking of every utterance of x (B,T,V) and the smallest margin met (Search.min_gap):
     ([ranking per utterance], gap).  W None: unbounded.  An utterance with x_len outside [1,T] has an empty ranking."""
     s = Search(V, R, space_id, W, chars, lm, case_sensitive, lmwt, wip, oov_penalty)
     out = [s.run(x[b], A, int(x_len[b])) if 1 <= int(x_len[b]) <= len(x[b]) else [] for b in range(len(x))]
@@ -151,7 +166,8 @@ def beam(x, A, x_len, V, R=0, space_id=-1, W=None, chars=None, lm=None, case_sen
 
 
 def enumerate_paths(x, A, n, V, R=0, space_id=-1):
-    """{labelling: ac} over all V**n paths of the first n frames of x (T,V), unspellable labellings dropped."""
+    """{labelling: ac} over all V**n paths of the first n frames of x (T,V), unspellable labellings dropped.  A path whose
+    score is -inf contributes nothing, and a labelling without any other path is absent."""
     groups = {}
     for path in itertools.product(range(V), repeat=n):
         sc = float(x[0][path[0]])
@@ -161,7 +177,8 @@ def enumerate_paths(x, A, n, V, R=0, space_id=-1):
         groups.setdefault(seq, []).append(sc)
     out = {}
     for seq, scores in groups.items():
-        if spellable(seq, V, R, space_id):
+        scores = [s for s in scores if s > NEG_INF]
+        if scores and spellable(seq, V, R, space_id):
             m = max(scores)
             out[seq] = m + math.log(math.fsum(math.exp(s - m) for s in scores))
     return out
