@@ -9,9 +9,9 @@
 // a 512-slot open-addressing table in LDS, every pair looks its key up there, and a pair that finds a member leaves its share
 // in that member's `ext` cell (one writer: the parent is unique).  A candidate's mass is then log-sum(stay, ext) -- two terms,
 // symmetric in its arguments -- or the pair's share alone; no atomics on numbers, the same bits on every call.
-// The per-frame cut is ctc_gram_decode.hip's: an exact filter (a full beam's members are W candidates themselves: nothing below
-// the least of their new totals survives), a radix select on the order-preserving bits of the totals, ties cut by a second select
-// on the keys; the survivors are ranked (total descending, key ascending) and become the next members in that order.
+// The per-frame cut first drops what cannot matter (a full beam's members are W candidates themselves: nothing below the
+// least of their new totals survives); the select and the ranking are beam_cut.h's, the select on the order-preserving
+// bits of the totals, and the survivors become the next members in the order of their ranks.
 // The read-out walks the (parent node, label) pool backwards.
 //
 // The transitions are read from an f64 copy in the workspace, transposed to [from][to] by a small kernel of the same call: the
@@ -19,18 +19,16 @@
 #include <cstring>
 #include <type_traits>
 
+#include "beam_cut.h"
 #include "ctc_lm.h"
 
 namespace e2e {
 namespace {
 
 constexpr int kThreads = 1024;
-constexpr int kMaxW = 128;                 // members of a beam (LDS)
 constexpr int kMaxV = 128;                 // e2e_asg_max_labels()
 constexpr int kMaxPairs = 16384;           // beam_width * V
 constexpr int kSlots = 512;                // the members' key table (<= 25 % full)
-constexpr uint64_t kKeyBasis = 0xcbf29ce484222325ull, kKeyPrime = 0x100000001b3ull;
-constexpr uint64_t kHashMul = 0x9e3779b97f4a7c15ull;
 constexpr unsigned long long kNoCand = 0ull;   // okey() of nothing: below every number's key (okey(-inf) = 0x000f...f)
 
 // order-preserving map double -> uint64 (larger double <=> larger key); -0.0 and +0.0 share one
@@ -114,6 +112,36 @@ __device__ __forceinline__ LmAnswer lm_query(const AsgBeamParams& p, const LmMem
 __device__ __forceinline__ double total_of(const AsgBeamParams& p, double ac, double lm, int nw, int noov) {
   return ac + lm * p.lmwt - (double)nw * p.wip + (double)noov * p.oov;
 }
+// the mass of member m's sequence (last label a) extended by label c != a: the share of the pair (m, c)
+__device__ __forceinline__ double ext_mass(const AsgBeamParams& p, const Members& M, const double* xs, int m, int a, int c) {
+  return a < 0 ? xs[c] : M.s[m] + p.At[a * p.V + c] + xs[c];
+}
+// the mass of member m (last label a >= 0) once it has stayed on a and taken its extension share
+__device__ __forceinline__ double stay_mass(const AsgBeamParams& p, const Members& M, const double* xs, const double* ext, int m, int a) {
+  return lse_sym(M.s[m] + p.At[a * p.V + a] + xs[a], ext[m]);
+}
+// does label c, after a sequence that ends in `a`, begin a word?
+__device__ __forceinline__ bool new_word(const AsgBeamParams& p, int a, int c) {
+  return c != p.space_id && (a < 0 || a == p.space_id);
+}
+// O[r] = L[m]
+__device__ __forceinline__ void copy_lm(LmMembers& O, int r, const LmMembers& L, int m) {
+  O.hash[r] = L.hash[m]; O.lm[r] = L.lm[m]; O.lmb[r] = L.lmb[m]; O.oov[r] = L.oov[m]; O.oovb[r] = L.oovb[m];
+#pragma unroll
+  for (int i = 0; i < kCtx; i++) { O.st[i][r] = L.st[i][m]; O.stb[i][r] = L.stb[i][m]; }
+  O.stn[r] = L.stn[m]; O.stbn[r] = L.stbn[m];
+}
+// the LM score and the OOV count of member m's child by a label that is no space: before its last word (m's own where the
+// child begins a word) and with it
+struct ChildLm { double lmb, lm; int oovb, oov; };
+__device__ __forceinline__ ChildLm child_lm(const LmMembers& L, int m, bool nw, const LmAnswer& ans) {
+  ChildLm s;
+  s.lmb = nw ? L.lm[m] : L.lmb[m];
+  s.oovb = nw ? L.oov[m] : L.oovb[m];
+  s.lm = s.lmb + (double)ans.sc / 2.302585092994045684;         // quirk Q8: divides by ln 10
+  s.oov = s.oovb + (ans.wi == 0 ? 1 : 0);
+  return s;
+}
 
 template <bool LM>
 __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
@@ -124,12 +152,8 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   __shared__ double ext[kMaxW];
   __shared__ unsigned long long tab_key[kSlots];
   __shared__ int tab_mem[kSlots];
-  __shared__ unsigned hist[256];
-  __shared__ int sel_pos[kMaxW], sel_rank[kMaxW];
-  __shared__ double sel_tot[kMaxW];
-  __shared__ unsigned long long sel_key[kMaxW];
-  __shared__ int n_surv, n_sel, n_stay, sh_digit, sh_need, sh_count;
-  __shared__ int wave_part[4];
+  __shared__ BeamCut cut;
+  __shared__ int n_surv, n_stay;
   __shared__ unsigned long long sh_floor;
 
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -168,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
         xs[c] = p.dtype == E2E_F32 ? (double)reinterpret_cast<const float*>(p.x)[at] : reinterpret_cast<const double*>(p.x)[at];
       }
       if (tid < kMaxW) ext[tid] = ninf();
-      if (tid == 0) { n_surv = 0; n_sel = 0; n_stay = 0; sh_floor = ~0ull; }
+      if (tid == 0) { n_surv = 0; cut.n_sel = 0; n_stay = 0; sh_floor = ~0ull; }
     }
     __syncthreads();
     // ---- every (member, label) pair: its share, and whom it goes to ----
@@ -179,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
       if (c == a) continue;                                       // the stay: below, once the extension shares are in
       unsigned long long cand = kNoCand;
       if (spellable(p, a, c)) {
-        const double v = a < 0 ? xs[c] : M.s[m] + p.At[a * V + c] + xs[c];
+        const double v = ext_mass(p, M, xs, m, a, c);
         const unsigned long long key = child_key(M.key[m], c);
         int hit = -1;
         for (unsigned h = (unsigned)((key * kHashMul) >> 55), probe = 0; probe < (unsigned)kSlots; probe++, h = (h + 1u) & (kSlots - 1)) {
@@ -189,15 +213,14 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
         }
         if (hit >= 0) ext[hit] = v;                               // (the only pair that spells member `hit`)
         else if (v > ninf()) {                                    // (false for NaN as well)
-          const bool new_word = c != p.space_id && (a < 0 || a == p.space_id);
-          const int nw = M.nw[m] + (new_word ? 1 : 0);
+          const bool nwd = new_word(p, a, c);
+          const int nw = M.nw[m] + (nwd ? 1 : 0);
           double lm = 0.0; int noov = 0;
           if constexpr (LM) {
             const LmMembers& L = lms[cur];
             if (c != p.space_id) {
-              const LmAnswer ans = lm_query(p, L, m, a, c, new_word);
-              lm = (new_word ? L.lm[m] : L.lmb[m]) + (double)ans.sc / 2.302585092994045684;     // quirk Q8: divides by ln 10
-              noov = (new_word ? L.oov[m] : L.oovb[m]) + (ans.wi == 0 ? 1 : 0);
+              const ChildLm s = child_lm(L, m, nwd, lm_query(p, L, m, a, c, nwd));
+              lm = s.lm; noov = s.oov;
             } else { lm = L.lm[m]; noov = L.oov[m]; }
           }
           const double tot = total_of(p, v, lm, nw, noov);
@@ -211,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
     if (tid < n_mem) {
       const int m = tid, a = M.last[m];
       if (a >= 0) {
-        const double mass = lse_sym(M.s[m] + p.At[a * V + a] + xs[a], ext[m]);
+        const double mass = stay_mass(p, M, xs, ext, m, a);
         double lm = 0.0; int noov = 0;
         if constexpr (LM) { lm = lms[cur].lm[m]; noov = lms[cur].oov[m]; }
         const double tot = total_of(p, mass, lm, M.nw[m], noov);
@@ -232,127 +255,43 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
     }
     __syncthreads();
     // ---- the cut: the W largest totals, exactly equal ones by ascending key ----
-    const int nsv = n_surv;
-    unsigned long long thr = 0ull, kthr = ~0ull;                 // selected: bits > thr, or bits == thr and key <= kthr
-    if (nsv > W) {
-      int need = W;
-      for (int shift = 56; shift >= 0; shift -= 8) {
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        if (tid == 0) { sh_digit = 0; sh_need = need; sh_count = 0; }   // (behind the barrier: the last pass' digit has been read)
-        const unsigned long long mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-        for (int i = tid; i < nsv; i += kThreads) {
-          const unsigned long long v = sval[i];
-          if ((v & mask) == thr) atomicAdd(&hist[(unsigned)(v >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        // the digit: the bin d with (count above d) < need <= (count above d) + hist[d]; a suffix sum over 256 threads
-        int h = 0, incl = 0;
-        if (tid < 256) {
-          h = (int)hist[tid]; incl = h;
-          for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_down(incl, o, 64); if ((tid & 63) + o < 64) incl += n; }
-          if ((tid & 63) == 0) wave_part[tid >> 6] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-          int above = incl - h;
-          for (int w = (tid >> 6) + 1; w < 4; w++) above += wave_part[w];
-          if (h > 0 && above < need && need <= above + h) { sh_digit = tid; sh_need = need - above; sh_count = h; }
-        }
-        __syncthreads();
-        thr |= (unsigned long long)sh_digit << shift;
-        need = sh_need;
-      }
-      if (sh_count > need) {                                     // more equal totals than places: the `need` smallest keys
-        unsigned long long kpre = 0ull;
-        for (int shift = 56; shift >= 0; shift -= 8) {
-          __syncthreads();
-          if (tid < 256) hist[tid] = 0u;
-          if (tid == 0) { sh_digit = 255; sh_need = need; }
-          __syncthreads();
-          const unsigned long long mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-          for (int i = tid; i < nsv; i += kThreads) {
-            if (sval[i] != thr) continue;
-            const int id = spos[i], m = id / V, c = id - m * V;
-            const unsigned long long kk = c == M.last[m] ? M.key[m] : child_key(M.key[m], c);
-            if ((kk & mask) == kpre) atomicAdd(&hist[(unsigned)(kk >> shift) & 255u], 1u);
-          }
-          __syncthreads();
-          int h = 0, incl = 0;
-          if (tid < 256) {
-            h = (int)hist[tid]; incl = h;
-            for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += n; }
-            if ((tid & 63) == 63) wave_part[tid >> 6] = incl;
-          }
-          __syncthreads();
-          if (tid < 256) {
-            int below = incl - h;
-            for (int w = 0; w < (tid >> 6); w++) below += wave_part[w];
-            if (h > 0 && below < need && need <= below + h) { sh_digit = tid; sh_need = need - below; }
-          }
-          __syncthreads();
-          kpre |= (unsigned long long)sh_digit << shift;
-          need = sh_need;
-        }
-        kthr = kpre;
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < nsv; i += kThreads) {
-      const unsigned long long v = sval[i];
-      if (v < thr) continue;
-      const int id = spos[i], m = id / V, c = id - m * V;
-      const unsigned long long kk = c == M.last[m] ? M.key[m] : child_key(M.key[m], c);
-      if (v == thr && kk > kthr) continue;
-      const int j = atomicAdd(&n_sel, 1);
-      if (j < W) { sel_pos[j] = id; sel_tot[j] = okey_inv(v); sel_key[j] = kk; }
-    }
+    beam_cut<kThreads>(cut, sval, spos, n_surv, W,
+        [&](int id) { const int m = id / V, c = id - m * V; return c == M.last[m] ? M.key[m] : child_key(M.key[m], c); },
+        okey_inv);
     // (the key table is the old members': every pair has looked its key up)
     for (int i = tid; i < kSlots; i += kThreads) { tab_key[i] = 0ull; tab_mem[i] = -1; }
     __syncthreads();
-    const int ns = min(n_sel, W);
+    const int ns = beam_cut_count(cut, W);
     if (ns == 0) { n_mem = 0; break; }                            // no candidate has a number for a total: no hypothesis is left
     // ---- rank the survivors: they become the members in that order ----
-    if (tid < ns) {
-      const double mt = sel_tot[tid]; const unsigned long long mk = sel_key[tid];
-      int r = 0;
-      for (int i = 0; i < ns; i++) r += (sel_tot[i] > mt || (sel_tot[i] == mt && sel_key[i] < mk)) ? 1 : 0;
-      if (r >= ns) r = ns - 1;
-      sel_rank[tid] = r;
-    }
+    beam_cut_rank(cut, ns);
     __syncthreads();
     if (tid < ns) {
-      const int id = sel_pos[tid], r = sel_rank[tid];
+      const int id = cut.sel_pos[tid], r = cut.sel_rank[tid];
       const int m = id / V, c = id - m * V, a = M.last[m];
-      const unsigned long long key = sel_key[tid];
+      const unsigned long long key = cut.sel_key[tid];
       N.key[r] = key; N.last[r] = c;
       if (c == a) {                                               // the member stays
-        N.s[r] = lse_sym(M.s[m] + p.At[a * V + a] + xs[a], ext[m]);
+        N.s[r] = stay_mass(p, M, xs, ext, m, a);
         N.node[r] = M.node[m]; N.len[r] = M.len[m]; N.nw[r] = M.nw[m];
-        if constexpr (LM) {
-          const LmMembers& L = lms[cur]; LmMembers& O = lms[cur ^ 1];
-          O.hash[r] = L.hash[m]; O.lm[r] = L.lm[m]; O.lmb[r] = L.lmb[m]; O.oov[r] = L.oov[m]; O.oovb[r] = L.oovb[m];
-#pragma unroll
-          for (int i = 0; i < kCtx; i++) { O.st[i][r] = L.st[i][m]; O.stb[i][r] = L.stb[i][m]; }
-          O.stn[r] = L.stn[m]; O.stbn[r] = L.stbn[m];
-        }
+        if constexpr (LM) copy_lm(lms[cur ^ 1], r, lms[cur], m);
       } else {                                                    // a new sequence: member m's, and label c
-        N.s[r] = a < 0 ? xs[c] : M.s[m] + p.At[a * V + c] + xs[c];
+        N.s[r] = ext_mass(p, M, xs, m, a, c);
         const int node = 1 + t * W + r;
         nodes[node] = make_int2(M.node[m], c);
         N.node[r] = node; N.len[r] = M.len[m] + 1;
-        const bool new_word = c != p.space_id && (a < 0 || a == p.space_id);
-        N.nw[r] = M.nw[m] + (new_word ? 1 : 0);
+        const bool nwd = new_word(p, a, c);
+        N.nw[r] = M.nw[m] + (nwd ? 1 : 0);
         if constexpr (LM) {                                        // get_next_prefix's LM part, as ctc_beam.hip's child_lm
           const LmMembers& L = lms[cur]; LmMembers& O = lms[cur ^ 1];
           if (c != p.space_id) {
-            const LmAnswer ans = lm_query(p, L, m, a, c, new_word);
-            int bn = new_word ? L.stn[m] : L.stbn[m];
+            const LmAnswer ans = lm_query(p, L, m, a, c, nwd);
+            const ChildLm s = child_lm(L, m, nwd, ans);
+            int bn = nwd ? L.stn[m] : L.stbn[m];
             O.stbn[r] = bn;
 #pragma unroll
-            for (int i = 0; i < kCtx; i++) O.stb[i][r] = new_word ? L.st[i][m] : L.stb[i][m];
-            O.lmb[r] = new_word ? L.lm[m] : L.lmb[m];
-            O.oovb[r] = new_word ? L.oov[m] : L.oovb[m];
+            for (int i = 0; i < kCtx; i++) O.stb[i][r] = nwd ? L.st[i][m] : L.stb[i][m];
+            O.lmb[r] = s.lmb; O.oovb[r] = s.oovb;
             if (bn > p.lm.order - 1) bn = p.lm.order - 1;
             int sn = bn + 1; if (sn > p.lm.order - 1) sn = p.lm.order - 1;
 #pragma unroll
@@ -360,14 +299,8 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
             O.st[0][r] = sn > 0 ? ans.wi : 0u;
             O.stn[r] = sn;
             O.hash[r] = ans.h;
-            O.lm[r] = O.lmb[r] + (double)ans.sc / 2.302585092994045684;
-            O.oov[r] = O.oovb[r] + (ans.wi == 0 ? 1 : 0);
-          } else {                                                // a space copies the fields
-            O.hash[r] = L.hash[m]; O.lm[r] = L.lm[m]; O.lmb[r] = L.lmb[m]; O.oov[r] = L.oov[m]; O.oovb[r] = L.oovb[m];
-#pragma unroll
-            for (int i = 0; i < kCtx; i++) { O.st[i][r] = L.st[i][m]; O.stb[i][r] = L.stb[i][m]; }
-            O.stn[r] = L.stn[m]; O.stbn[r] = L.stbn[m];
-          }
+            O.lm[r] = s.lm; O.oov[r] = s.oov;
+          } else copy_lm(O, r, L, m);                             // a space copies the fields
         }
       }
       // the new member's key enters the table (two members with one key, 2^-64: the second is not entered and never extended into)
@@ -403,7 +336,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
         node = nd.x;
       }
     }
-    sel_pos[tid] = len;
+    cut.sel_pos[tid] = len;
     const int64_t o = (int64_t)b * nbest + tid;
     p.out_len[o] = len;
     p.scores[o * 3 + 0] = tot; p.scores[o * 3 + 1] = ac; p.scores[o * 3 + 2] = lm;
@@ -412,7 +345,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   __syncthreads();
   for (int j = 0; j < nbest; j++) {
     int64_t* row = out + (int64_t)j * max_out;
-    for (int64_t i = sel_pos[j] + tid; i < max_out; i += kThreads) row[i] = 0;
+    for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kThreads) row[i] = 0;
   }
   if (tid == 0) p.n_hyp[b] = n_mem < nbest ? n_mem : nbest;
 }

@@ -10,11 +10,11 @@
 // function of the pair (src * y[c]) and is recomputed by whoever walks the list.  A (prefix, slot) receives at most its
 // stay share and one extension share, so a slot is the sum of two numbers and a total the sum of the slots in the order
 // 0 .. max_order -- the same bits whatever order the pairs arrived in.  The per-frame cut first drops what cannot matter
-// (a full beam's members are W candidates themselves: nothing below the least of their new totals survives), then is a
-// radix select on the bits of the totals (positive doubles order as integers), ties cut by a second select on the keys;
-// the survivors are ranked (total descending, key ascending) and become the next members in that order.  The table is cleared entry by entry
-// from the frame's candidate list.  The read-out walks the (parent node, column) pool backwards and expands the grams.
-#include "common.h"
+// (a full beam's members are W candidates themselves: nothing below the least of their new totals survives); the select
+// and the ranking are beam_cut.h's, the select on the bits of the totals (positive doubles order as integers), and the
+// survivors become the next members in the order of their ranks.  The table is cleared entry by entry from the frame's
+// candidate list.  The read-out walks the (parent node, column) pool backwards and expands the grams.
+#include "beam_cut.h"
 
 namespace e2e {
 
@@ -25,11 +25,8 @@ namespace {
 
 constexpr int kExpandThreads = 256;
 constexpr int kBeamThreads = 1024;
-constexpr int kMaxW = 128;                 // members of a beam (LDS)
 constexpr int kMaxK = 8;                   // longest gram
 constexpr int kMaxPairs = 131072;          // beam_width * V
-constexpr uint64_t kKeyBasis = 0xcbf29ce484222325ull, kKeyPrime = 0x100000001b3ull;
-constexpr uint64_t kHashMul = 0x9e3779b97f4a7c15ull;
 
 __device__ __forceinline__ int order_of(const int32_t* gram_len, int c, int K) {
   const int k = gram_len[c];
@@ -148,12 +145,8 @@ __device__ __forceinline__ double eval_total(const Eval& E, int K) {
 
 __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams p) {
   __shared__ Members mem[2];
-  __shared__ unsigned hist[256];
-  __shared__ int sel_pos[kMaxW], sel_rank[kMaxW];
-  __shared__ double sel_tot[kMaxW];
-  __shared__ unsigned long long sel_key[kMaxW];
-  __shared__ int n_cand, n_surv, n_sel, sh_digit, sh_need, sh_count, overflow;
-  __shared__ int wave_part[4];
+  __shared__ BeamCut cut;
+  __shared__ int n_cand, n_surv, overflow;
   __shared__ unsigned long long sh_floor;
   __shared__ double sh_best;
 
@@ -197,7 +190,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
         y[c] = exp(v);
       }
     }
-    if (tid == 0) { n_cand = 0; n_surv = 0; n_sel = 0; sh_floor = ~0ull; }
+    if (tid == 0) { n_cand = 0; n_surv = 0; cut.n_sel = 0; sh_floor = ~0ull; }
     __syncthreads();
     // ---- members and (member, column) pairs meet at their prefix's key ----
     const unsigned n_now = (unsigned)n_mem * (unsigned)V;
@@ -248,82 +241,11 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
     }
     __syncthreads();
     // ---- the cut: the W largest totals, exactly equal ones by ascending key ----
-    const int nsv = n_surv;
-    unsigned long long thr = 0ull, kthr = ~0ull;                 // selected: bits > thr, or bits == thr and key <= kthr
-    if (nsv > W) {
-      int need = W;
-      for (int shift = 56; shift >= 0; shift -= 8) {
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        if (tid == 0) { sh_digit = 0; sh_need = need; sh_count = 0; }   // (behind the barrier: the last pass' digit has been read)
-        const unsigned long long mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-        for (int i = tid; i < nsv; i += kBeamThreads) {
-          const unsigned long long v = sval[i];
-          if ((v & mask) == thr) atomicAdd(&hist[(unsigned)(v >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        // the digit: the bin d with (count above d) < need <= (count above d) + hist[d]; a suffix sum over 256 threads
-        int h = 0, incl = 0;
-        if (tid < 256) {
-          h = (int)hist[tid]; incl = h;
-          for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_down(incl, o, 64); if ((tid & 63) + o < 64) incl += n; }
-          if ((tid & 63) == 0) wave_part[tid >> 6] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-          int above = incl - h;
-          for (int w = (tid >> 6) + 1; w < 4; w++) above += wave_part[w];
-          if (h > 0 && above < need && need <= above + h) { sh_digit = tid; sh_need = need - above; sh_count = h; }
-        }
-        __syncthreads();
-        thr |= (unsigned long long)sh_digit << shift;
-        need = sh_need;
-      }
-      if (sh_count > need) {                                     // more equal totals than places: the `need` smallest keys
-        unsigned long long kpre = 0ull;
-        for (int shift = 56; shift >= 0; shift -= 8) {
-          __syncthreads();
-          if (tid < 256) hist[tid] = 0u;
-          if (tid == 0) { sh_digit = 255; sh_need = need; }
-          __syncthreads();
-          const unsigned long long mask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-          for (int i = tid; i < nsv; i += kBeamThreads) {
-            if (sval[i] != thr) continue;
-            const unsigned long long kk = __hip_atomic_load(&table[list[spos[i]]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((kk & mask) == kpre) atomicAdd(&hist[(unsigned)(kk >> shift) & 255u], 1u);
-          }
-          __syncthreads();
-          int h = 0, incl = 0;
-          if (tid < 256) {
-            h = (int)hist[tid]; incl = h;
-            for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += n; }
-            if ((tid & 63) == 63) wave_part[tid >> 6] = incl;
-          }
-          __syncthreads();
-          if (tid < 256) {
-            int below = incl - h;
-            for (int w = 0; w < (tid >> 6); w++) below += wave_part[w];
-            if (h > 0 && below < need && need <= below + h) { sh_digit = tid; sh_need = need - below; }
-          }
-          __syncthreads();
-          kpre |= (unsigned long long)sh_digit << shift;
-          need = sh_need;
-        }
-        kthr = kpre;
-      }
-    }
+    beam_cut<kBeamThreads>(cut, sval, spos, n_surv, W,
+        [&](int pos) { return __hip_atomic_load(&table[list[pos]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
+        [](unsigned long long v) { return __longlong_as_double((long long)v); });
     __syncthreads();
-    for (int i = tid; i < nsv; i += kBeamThreads) {
-      const unsigned long long v = sval[i];
-      if (v < thr) continue;
-      const int pos = spos[i];
-      const unsigned long long kk = __hip_atomic_load(&table[list[pos]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (v == thr && kk > kthr) continue;
-      const int j = atomicAdd(&n_sel, 1);
-      if (j < W) { sel_pos[j] = pos; sel_tot[j] = __longlong_as_double((long long)v); sel_key[j] = kk; }
-    }
-    __syncthreads();
-    const int ns = min(n_sel, W);
+    const int ns = beam_cut_count(cut, W);
     if (ns == 0) {                                               // every path has probability 0: no hypothesis is left
       for (int pos = tid; pos < nc; pos += kBeamThreads) { Entry& en = table[list[pos]]; en.key = 0ull; en.head = -1; }
       n_mem = 0;
@@ -331,19 +253,13 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
       break;
     }
     // ---- rank the survivors: they become the members in that order ----
-    if (tid < ns) {
-      const double mt = sel_tot[tid]; const unsigned long long mk = sel_key[tid];
-      int r = 0;
-      for (int i = 0; i < ns; i++) r += (sel_tot[i] > mt || (sel_tot[i] == mt && sel_key[i] < mk)) ? 1 : 0;
-      if (r >= ns) r = ns - 1;
-      sel_rank[tid] = r;
-      if (r == 0) sh_best = mt;
-    }
+    beam_cut_rank(cut, ns);
+    if (tid < ns && cut.sel_rank[tid] == 0) sh_best = cut.sel_tot[tid];
     __syncthreads();
     int ex = 0;
     (void)frexp(sh_best, &ex);                                   // best = f * 2^ex, f in [0.5, 1)
     if (tid < ns) {
-      const int pos = sel_pos[tid], r = sel_rank[tid];
+      const int pos = cut.sel_pos[tid], r = cut.sel_rank[tid];
       const int head = __hip_atomic_load(&table[list[pos]].head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       Eval E;
       eval_list(E, M, head, next, y, p.gram_len, (unsigned)V, K, n_ids);
@@ -354,7 +270,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
         N.p[k][r] = pk; N.col[k][r] = (k >= 1 && pk > 0.0) ? E.c[k] : 0;
         if (k <= K) tot += pk;
       }
-      N.tot[r] = tot; N.key[r] = sel_key[tid];
+      N.tot[r] = tot; N.key[r] = cut.sel_key[tid];
       if (E.stay >= 0) { N.node[r] = M.node[E.stay]; N.len[r] = M.len[E.stay]; }
       else {
         const unsigned pid = (unsigned)E.pair < n_ids ? (unsigned)E.pair : 0u;
@@ -390,14 +306,14 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
         node = nd.x;
       }
     }
-    sel_pos[tid] = len;
+    cut.sel_pos[tid] = len;
     p.out_len[(int64_t)b * nbest + tid] = len;
     p.scores[(int64_t)b * nbest + tid] = score;
   }
   __syncthreads();
   for (int j = 0; j < nbest; j++) {
     int64_t* row = out + (int64_t)j * max_out;
-    for (int64_t i = sel_pos[j] + tid; i < max_out; i += kBeamThreads) row[i] = 0;
+    for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kBeamThreads) row[i] = 0;
   }
   if (tid == 0) p.n_hyp[b] = overflow ? -1 : (n_mem < nbest ? n_mem : nbest);
 }

@@ -51,6 +51,19 @@ def _on_device(dev):
     return torch.cuda.device(dev)
 
 
+def _pack_nbest(out, lens, nh, strings, keep_on_device):
+    """The tail of an n-best read-out: out (B,N,max_out) on the device, lens [B][N] and nh [B] on the host, strings(rows, lens)
+    the engine's spelling -> (ids (B,N,width) packed to the longest hypothesis of the batch, on the device or the host as
+    keep_on_device says; sentences [B][nh[b]]; width)."""
+    B, N = out.shape[:2]
+    width = max((max(row) for row in lens), default=0)
+    ids = out[:, :, :width].contiguous()
+    ids_host = ids.cpu()
+    flat = strings(ids_host.reshape(B * N, width), [n for row in lens for n in row])   # one lookup per batch
+    sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+    return ids if keep_on_device else ids_host, sentences, width
+
+
 class _NullCtx:
     def __enter__(self):
         return None
@@ -460,15 +473,9 @@ class ASGBeamEngine:
                                   xl.data_ptr(), B, T, V, self.num_replabels, self.beam_width, self.space_id, lm,
                                   self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
                                   n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        nh = n_hyp.tolist()
-        lens = out_len.tolist()
-        width = max((max(row) for row in lens), default=0)
-        ids = out[:, :, :width].contiguous()       # packed to the longest hypothesis of the batch
-        ids_host = ids.cpu()
-        flat = self._strings(ids_host.reshape(B * N, width), [n for row in lens for n in row])
-        sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+        ids, sentences, _ = _pack_nbest(out, out_len.tolist(), n_hyp.tolist(), self._strings, self.keep_on_device)
         r = (lambda t: t) if self.keep_on_device else (lambda t: t.cpu())
-        return (ids if self.keep_on_device else ids_host, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
+        return (ids, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
                 r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
                 r(counts[:, :, 1].contiguous()), r(n_hyp), None)
 
@@ -699,13 +706,9 @@ class GramCTCDecoderEngine:
         for b in range(B):
             if nh[b] < 0:
                 raise R.E2EError("Gram-CTC beam search: utterance %d ran out of candidate entries" % b)
-        width = max((max(row) for row in lens_host), default=0)
-        ids_out = out[:, :, :width].contiguous()       # packed to the longest hypothesis of the batch
-        ids_host = ids_out.cpu()
-        flat = self._strings(ids_host.reshape(B * N, width), [n for row in lens_host for n in row])
-        sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+        ids_out, sentences, _ = _pack_nbest(out, lens_host, nh, self._strings, self.keep_on_device)
         r = self._result
-        return (ids_out if self.keep_on_device else ids_host, r(out_len), sentences, r(scores), r(n_hyp))
+        return (ids_out, r(out_len), sentences, r(scores), r(n_hyp))
 
     def decode(self, logits_, logits_lengths_):
         """Hypothesis 0 of decode_nbest -> (base ids (B,maxlen) int64, lengths (B), sentences)."""
@@ -1061,13 +1064,9 @@ class CTCDecoderEngine:
                 raise R.E2EError("beam search: utterance %d ran out of prefix-tree nodes" % b)
             if max(lens[b]) > max_out:
                 raise R.E2EError("beam search: utterance %d needs %d output ids, %d provided" % (b, max(lens[b]), max_out))
-        width = max((max(row) for row in lens), default=0)
-        ids = out[:, :, :width].contiguous()       # packed to the longest hypothesis of the batch
-        ids_host = ids.cpu()
-        flat = self._strings(ids_host.reshape(B * N, width), [n for row in lens for n in row])   # one lookup per batch
-        sentences = [flat[b * N: b * N + nh[b]] for b in range(B)]
+        ids, sentences, width = _pack_nbest(out, lens, nh, self._strings, self.keep_on_device)
         r = self._result
-        return (ids if self.keep_on_device else ids_host, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
+        return (ids, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
                 r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
                 r(counts[:, :, 1].contiguous()), r(n_hyp), r(ts[:, :, :width].contiguous()) if timesteps else None)
 

@@ -163,6 +163,20 @@ def test_all_equal_logits_decode_the_same_bits_twice():
     assert int(a.num_hypotheses[0]) == 16
 
 
+@pytest.mark.parametrize("T", [2, 3])
+def test_multi_frame_ties_equal_the_restatement(T):
+    """All-equal log-probabilities at width 16: the cut of every frame is decided by keys.  Frame 0 cuts the equal
+    single-share candidates of a beam that is not full (the key select with the floor filter off), the later frames cut
+    those of a full beam (with it on); at T = 2 the restatement keeps 8 hypotheses at -4.990432586779 and 8 at
+    -5.395897694887."""
+    R, V, l2i, _ = DR.pruned_cases()
+    lp = torch.log_softmax(torch.zeros(1, T, V, dtype=torch.float64), -1)
+    want = DR.beam_search(lp[0].numpy(), GR.grams_of(R, V, l2i), 16)
+    assert len(want[0]) == 16
+    res = decoder(R, V, l2i, 16).decode_nbest(lp.to(DEV))
+    check_against_restatement(res, [want])
+
+
 # ---- 5. edges -----------------------------------------------------------------------------------------------------
 def _edge_inputs(B, T, seed):
     R, V, l2i, _ = DR.pruned_cases()
