@@ -19,12 +19,15 @@
 //     beta backwards through the segment, forms the posteriors alpha*beta/sum, accumulates them
 //     per label in LDS and writes the gradient rows (prob - posterior), coalesced.
 //     Every row checks sum_j alpha*beta against the chains' partition sum (finish_rows).
+//     Targets of 128..255 labels: the banded form (segment_wave_band) -- two pairs per lane over the 128 pairs of the lattice
+//     that carry the segment's posterior mass, found from the checkpoint rows' group exponents.
 //  exact kernel (ctc_loss_exact.hip) re-does the utterances F1/F2 flag: infeasible alignments,
 //     rows that fail the self-check or leave f32's range (segments redone in f64 from the
 //     checkpoints first), alpha/beta log Z mismatch, targets that contain the blank id.
 //
 // Reference semantics restated: src/losses/ctc_loss.cpp:33-117 (recurrences, loss, gradient).
 #include "fast_common.h"
+#include <atomic>
 
 namespace e2e {
 using namespace fastk;
@@ -1095,9 +1098,10 @@ struct SegIn {
   int eA7, eA15, eB0, eB8;          // rescale exponents inside the segment
   int EA0, EB16;                    // what the chains had removed in total: alpha before step t0, beta down to step t0+16
   float zfrac; int zint;            // the chains' log2 of the tilted partition sum (zt2), split: zint + zfrac
-  __device__ void load(const FastParams& p, int b, int seg, int S, int lane) {
+  // the rescale exponents and the chains' partition sum: what does not depend on the lane's cells (the banded form,
+  // segment_wave_band, loads in two rounds: this in the first ...)
+  __device__ void load_frame(const FastParams& p, int b, int seg) {
     const int t0 = seg * kSeg;
-    const bool in_lattice = lane * 2 * PPL <= 2 * S;      // (the chains store no cells past the lattice's 2S+1)
     const int* cA = p.cumA + (size_t)b * p.NB + (t0 >> 3);
     const int* cB = p.cumB + (size_t)b * p.NB + (t0 >> 3);
     const int* tA = p.trkA + (size_t)b * p.NB + (t0 >> 3);
@@ -1108,6 +1112,21 @@ struct SegIn {
     EA0 = a0; EB16 = b2;
     { const double z = p.zt2[b]; const double zi = floor(z); zfrac = (float)(z - zi);
       zint = (int)fmax(fmin(zi, 1e9), -1e9); if (!(z == z)) zfrac = z; }      // (infeasible: -inf; never passes the check)
+  }
+  // ... and the checkpoint cells of pairs base + 2 lane, base + 2 lane + 1 (PPL == 2; `stored`: the chains wrote the lane's
+  // four-pair group; the caller sets ownA / ownB from the group exponents it already holds)
+  __device__ void load_band(const FastParams& p, int b, int seg, bool stored, int base, int lane) {
+    static_assert(PPL == 2, "a lane's four cells are one 16-byte load");
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    f4 va = {0.f, 0.f, 0.f, 0.f}, vq = va;
+    if (seg > 0 && stored) va = *reinterpret_cast<const f4*>(p.ckA + ((size_t)b * p.NS + seg) * p.CELLS + 2 * base + 4 * lane);
+    if (seg + 1 < p.NS && stored) vq = *reinterpret_cast<const f4*>(p.ckQ + ((size_t)b * p.NS + seg + 1) * p.CELLS + 2 * base + 4 * lane);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { a[k] = va[k]; q[k] = vq[k]; }
+  }
+  __device__ void load(const FastParams& p, int b, int seg, int S, int lane) {
+    const bool in_lattice = lane * 2 * PPL <= 2 * S;      // (the chains store no cells past the lattice's 2S+1)
+    load_frame(p, b, seg);
     ownA = 0;
 #pragma unroll
     for (int k = 0; k < 2 * PPL; k++) a[k] = 0.f;
@@ -1152,7 +1171,11 @@ template <int PPL, bool FULL, typename P, typename GL>
 __device__ __forceinline__ void segment_body(const P& p, int b, int seg, int T, int S, int n,
                                              const LaneCells<PPL>& lc, const int (&rank)[PPL],
                                              const SegIn<PPL>& in,
-                                             const F2Lds<PPL>& lds, const GL& gl, int lane, float& smin, float& smax) {
+                                             const F2Lds<PPL>& lds, const GL& gl, int lane, float& smin, float& smax,
+                                             int base = 0) {
+  // base: the lane's pairs are base + PPL * lane + r (the banded form, segment_wave_band; 0 everywhere else).  Only the lattice's
+  // two ends are tied to absolute cell numbers: the first row's cell 0 (segment 0, whose window starts at pair 0) and the last
+  // row's cells L-1 and L-2.  The edge lanes' hand-over factors are 0, which IS the window's cut.
   constexpr int NC = 2 * PPL;
   constexpr int kSlope = 3 * NC;    // exponent drop allowed per lane (see the alpha load below)
   constexpr int PROW = F2Lds<PPL>::PROW;
@@ -1280,7 +1303,7 @@ __device__ __forceinline__ void segment_body(const P& p, int b, int seg, int T, 
   } else {
 #pragma unroll
     for (int k = 0; k < NC; k++) q[k] = 0.f;
-    const int eA_ref = __shfl(eA, (L - 1) / NC, 64);          // lane holding cell L-1
+    const int eA_ref = __shfl(eA, (L - 1 - 2 * base) / NC, 64);          // lane holding cell L-1
     end_unit = ldexpf(1.f, max(min(eA - eA_ref, 126), -126));
     unit_exp = eA_ref;
   }
@@ -1306,7 +1329,7 @@ __device__ __forceinline__ void segment_body(const P& p, int b, int seg, int T, 
         if (!FULL && t == T - 1) {
 #pragma unroll
           for (int r = 0; r < PPL; r++) {
-            const int i = PPL * lane + r;
+            const int i = base + PPL * lane + r;
             bs[2 * r] = (2 * i == L - 1 && cond) ? end_unit : 0.f;
             bs[2 * r + 1] = (2 * i + 1 == L - 2) ? rr * end_unit : 0.f;
           }
@@ -1537,6 +1560,57 @@ __device__ __forceinline__ void segment_body_pk(const P& p, int b, int seg, int 
   }
 }
 
+// ---- pieces the two segment waves (segment_wave, segment_wave_band) share ----
+// frames past the utterance's end: exp(lp) in log-prob mode (quirk Q1), zero for fused logits
+template <typename P>
+__device__ __forceinline__ void seg_dead_frames(const P& p, int b, int t0, int T, int lane) {
+  const int V = p.V, Tmax = p.T;
+  const size_t g0 = (size_t)b * Tmax * V;
+  const int64_t xo = (int64_t)b * p.sB;
+  const int tend = min(t0 + kSeg, Tmax);
+  for (int t = max(t0, T); t < tend; t++)
+    for (int v = lane; v < V; v += 64)
+      store_elem(p.grads, g0 + (size_t)t * V + v,
+                 p.logprobs ? expf(load_elem(p.x, xo + (int64_t)t * p.sT + (int64_t)v * p.sV, p.xdt)) * p.gscale : 0.f, p.xdt);
+}
+// the segment's probability tile of an alphabet of up to kMaxSmallV columns: [label][16 steps] in the table as in LDS;
+// N = ceil(4 kMaxSmallV / 64) loads per lane
+typedef float seg_f4 __attribute__((ext_vector_type(4)));
+template <int N>
+__device__ __forceinline__ void seg_load_tile(seg_f4 (&tile)[N], const float* tab, int V, int lane) {
+  const seg_f4* src = reinterpret_cast<const seg_f4*>(tab);
+#pragma unroll
+  for (int j = 0; j < N; j++)
+    if (64 * j < 4 * V) tile[j] = src[min(64 * j + lane, 4 * V - 1)];     // (uniform test; the last load's surplus lanes re-read the end)
+}
+template <int N>
+__device__ __forceinline__ void seg_stage_tile(const seg_f4 (&tile)[N], float* ys, int V, int n, int lane) {
+  // one 16-byte LDS write per load: label (lane >> 2) + 16 j, steps 4 (lane & 3) .. + 3
+  float* dst = ys + (lane >> 2) * kYs + 4 * (lane & 3);
+  const int q4 = 4 * (lane & 3);
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    if (64 * j < 4 * V) {
+      seg_f4 v = tile[j];
+      if (n < kSeg) {                                                    // (uniform) dead steps of a short last segment: zeros
+#pragma unroll
+        for (int c = 0; c < 4; c++) v[c] = q4 + c < n ? v[c] : 0.f;
+      }
+      if (64 * j + lane < 4 * V) *reinterpret_cast<seg_f4*>(dst + 16 * j * kYs) = v;
+    }
+  }
+}
+// the range check at a segment wave's end and the segment's bit in the mask (see segment_wave)
+template <typename P>
+__device__ __forceinline__ void seg_close(const P& p, int b, int seg, int lane, float smin, float smax) {
+  const bool finite_ok = smax < __builtin_huge_valf();
+  if (!(smin > 0.f) || !finite_ok) {
+    if (lane == 0) { atomicOr(&p.flags[b], finite_ok ? 8 : 16); atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31)); }
+  } else if (smin < __builtin_huge_valf()) {
+    if (lane == 0) atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31));
+  }
+}
+
 template <int PPL, typename P>
 __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
   const int b = blockIdx.y, seg = blockIdx.x, lane = threadIdx.x & 63;
@@ -1586,10 +1660,7 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
   };
   if (BIG) load_cols(0);
   else {
-    const f4* src = reinterpret_cast<const f4*>(p.ytab + ((size_t)b * p.NS + seg) * V * kSeg);
-#pragma unroll
-    for (int j = 0; j < kTileLoads; j++)
-      if (64 * j < 4 * V) tile[j] = src[min(64 * j + lane, 4 * V - 1)];     // (uniform test; the last load's surplus lanes re-read the end)
+    seg_load_tile(tile, p.ytab + ((size_t)b * p.NS + seg) * V * kSeg, V, lane);
   }
   // (c) alpha checkpoint and the rescale exponents
   SegIn<PPL> in;
@@ -1597,16 +1668,7 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
 
   if (Tq < 1 || Tq > Tmax || Sq < 0 || Sq > p.Smax) return;    // flagged by F1, the exact kernel poisons it
   const int T = (int)Tq, S = (int)Sq;
-  {
-    // frames past the utterance's end: exp(lp) in log-prob mode (quirk Q1), zero for fused logits
-    const size_t g0 = (size_t)b * Tmax * V;
-    const int64_t xo = (int64_t)b * p.sB;
-    const int tend = min(t0 + kSeg, Tmax);
-    for (int t = max(t0, T); t < tend; t++)
-      for (int v = lane; v < V; v += 64)
-        store_elem(p.grads, g0 + (size_t)t * V + v,
-                   p.logprobs ? expf(load_elem(p.x, xo + (int64_t)t * p.sT + (int64_t)v * p.sV, p.xdt)) * p.gscale : 0.f, p.xdt);
-  }
+  seg_dead_frames(p, b, t0, T, lane);
   if (t0 >= T) return;
   const int n = min(t0 + kSeg, T) - t0;
 
@@ -1619,20 +1681,7 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
   else { lds.starts[lane] = s0; lds.starts[64 + lane] = s1; if (lane < 2) lds.starts[128 + lane] = s2; }
   if (lane < kYs) lds.ys[V * kYs + lane] = 0.f;                           // the zero row V
   if (!BIG) {
-    // one 16-byte LDS write per load: label (lane >> 2) + 16 j, steps 4 (lane & 3) .. + 3
-    float* dst = lds.ys + (lane >> 2) * kYs + 4 * (lane & 3);
-    const int q4 = 4 * (lane & 3);
-#pragma unroll
-    for (int j = 0; j < kTileLoads; j++) {
-      if (64 * j < 4 * V) {
-        f4 v = tile[j];
-        if (n < kSeg) {                                                    // (uniform) dead steps of a short last segment: zeros
-#pragma unroll
-          for (int c = 0; c < 4; c++) v[c] = q4 + c < n ? v[c] : 0.f;
-        }
-        if (64 * j + lane < 4 * V) *reinterpret_cast<f4*>(dst + 16 * j * kYs) = v;
-      }
-    }
+    seg_stage_tile(tile, lds.ys, V, n, lane);
   } else {
     // the lane's columns into the transposed tile: four 16-byte writes per column
     auto put_cols = [&](int c0) {
@@ -1669,7 +1718,6 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
 #endif
   F2_FLUSH
   // range check: everything that carries posterior mass was representable (see the header comment)
-  const bool finite_ok = smax < __builtin_huge_valf();
   // (smin: a row sum that can still be inverted and whose terms of relative weight 2^-6 are normal f32.  What decides
   // whether the rows kept everything that mattered is the self-check in finish_rows, which also zeroes smin: with a
   // margin alone -- 2^-90 -- two utterances in three with emissions that contradict their targets were sent to the f64
@@ -1678,15 +1726,231 @@ __device__ __forceinline__ void segment_wave(const P& p, unsigned char* smem) {
   // at t%8 == 0, so every row in between carries nine steps of decay.)
   // (the segment's bit in the mask: what the f64 redo of a range-flagged utterance takes -- the segments that failed and the
   //  borderline ones; the rows of every other segment passed their self-check with room to spare and stay as written)
-  if (!(smin > 0.f) || !finite_ok) {
-    if (lane == 0) { atomicOr(&p.flags[b], finite_ok ? 8 : 16); atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31)); }
-  } else if (smin < __builtin_huge_valf()) {
-    if (lane == 0) atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31));
-  }
+  seg_close(p, b, seg, lane, smin, smax);
   if (seg == 0 && lane == 0) {
     const double za = p.logz[2 * b], zb = p.logz[2 * b + 1];
     if (!(fabs(za - zb) <= 1e-6 * fabs(za) + 1e-4)) atomicOr(&p.flags[b], 32);
   }
+}
+
+// ---- the banded form: two pairs per lane over the 128 pairs of the lattice that carry the segment's posterior mass ----
+// Targets of 128..255 labels have a lattice of up to 256 pairs, but the rows of ONE segment have posterior mass on far fewer of
+// them (tools/diag/band_width.py: at most 94 pairs down to 2^-60 of Z for uninformative emissions, a dozen for trained ones).
+// Lane l holds pairs base + 2l, base + 2l + 1; base = 4 lo is wave-uniform, a multiple of the chains' four-pair exponent group.
+//
+// The window, from the group exponents of the four checkpoint rows around the segment (64 groups g of four pairs, lane g):
+//   lo = the first group with  EA[seg][g] + max(EB[seg][g], EB[seg][g+1]) + cumA(t0) + cumB(t0) - floor(zt2) > kBandCut
+//   hi = the last  group with  EB[seg+1][g] + max(EA[seg+1][g], EA[seg+1][g-1]) + cumA(t0+16) + cumB(t0+16) - floor(zt2) > kBandCut
+// (segment 0: lo = 0; the utterance's last segment: hi = the group of cell L-1).
+// Bound.  Alignments are monotone, so zeroing the alpha checkpoint below cell 8 lo drops exactly the paths that are below it at
+// t0 - 1, and zeroing the beta checkpoint above group hi exactly the paths above it at t0 + 16: every alpha*beta product inside
+// the window, and every row sum, loses the mass of those paths and nothing else.  The paths through cell j at t0 - 1 weigh
+// alpha[j] * (q[j] + r q[j+1] + r^2 skip q[j+2]) with q the beta checkpoint of t0 (which carries t0's emission: the transition is
+// applied, nothing is divided out), those through cell j at t0 + 16 weigh (alpha[j] + r alpha[j-1] + r^2 skip alpha[j-2]) * q[j]
+// with the checkpoints of t0 + 15 and t0 + 16.  A group's cells are below 2^(E+1), it has 8 of them, 1 + r + r^2 <= 73 < 2^7 (the
+// tilt is at most 8, fast_tilt), and floor(zt2) is at most one below log2 Z: a group left out holds less than
+// 2^(3 + 2 + 7 + 1 + kBandCut) = 2^-37 of Z, all (at most 63) groups left out on a side less than 2^-31, both sides less than 2^-30
+// -- three orders of magnitude under the gradient's tolerance.  Group exponents only overestimate.  No margin for drift is
+// needed: what moves out of the window's top before t0 + 16 is on a path that is above it at t0 + 16.
+// The self-check stays: a window that lost mass lowers the row sums and is caught like any other loss (finish_rows).
+// A window of more than 128 pairs: the wave writes nothing, marks its segment and sets flag 8 -- the flagged launch redoes the
+// segment in f64 from the checkpoints (E2E_ALGO_FAST: the utterance is poisoned, as for every flag); ctl[7] counts them.
+// Second stage.  Group maxima overestimate most where the rows are steep -- a blank that dominates the emissions (an untrained
+// model) costs every label step a factor of a few hundred, and the maxima of alpha and beta sit at opposite ends of the 16 cells
+// the first rule pairs: its window then exceeds 128 pairs where the mass itself does not (tools/diag/band_width.py).  So a wave
+// whose first window does not fit reads the four checkpoint rows themselves, lane g the cells of group g, and forms the
+// group's weight as written above, cell by cell in f32 in the unit 2^(E + E'): a group is left out if that weight, by its
+// exponent, is below 2^kBandCutCells = 2^-39 of 2^floor(zt2).  Products below f32's normal range are lost to that sum: less
+// than 8 cells x 2^(1 + 7 - 126) of the unit, i.e. 2^(m - 115) of Z with m the first stage's figure without its 12 bits of
+// allowance; the second stage is believed only where m <= 72 (else the first stage's answer stands), so a group left out holds
+// less than 2^-39 + 2^-43 < 2^-38 of Z, a side less than 2^-32, both less than 2^-31.  Skips are taken as allowed everywhere.
+constexpr int kBandCut = -50;
+constexpr int kBandCutCells = -39;
+constexpr int kBandPairs = 128;
+
+// SIDE 0: the rows of t0 - 1 (alpha) and t0 (beta), weight alpha[j] (q[j] + r q[j+1] + r^2 q[j+2]); SIDE 1: the rows of t0 + 15 and
+// t0 + 16, weight (alpha[j] + r alpha[j-1] + r^2 alpha[j-2]) q[j].  row: the checkpoint row; eA / eQ: the lane's group exponents
+// (-30000: nothing stored); frame: cumA + cumB - floor(zt2) of the rows.  Returns whether group `lane` has to be inside the window.
+template <int SIDE>
+__device__ __forceinline__ bool band_group_matters(const FastParams& p, int b, int row, int lane, int eA, int eQ, int frame, float r) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  float a[10], q[10];                       // SIDE 0: q[8], q[9] from the group above; SIDE 1: a[0], a[1] from the group below
+  constexpr int oa = SIDE == 0 ? 0 : 2, oq = 0;
+  {
+    const size_t at = ((size_t)b * p.NS + row) * p.CELLS + 8 * lane;
+    f4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, q0 = a0, q1 = a0;
+    if (eA > -30000) { a0 = *reinterpret_cast<const f4*>(p.ckA + at); a1 = *reinterpret_cast<const f4*>(p.ckA + at + 4); }
+    if (eQ > -30000) { q0 = *reinterpret_cast<const f4*>(p.ckQ + at); q1 = *reinterpret_cast<const f4*>(p.ckQ + at + 4); }
+#pragma unroll
+    for (int k = 0; k < 4; k++) { a[oa + k] = a0[k]; a[oa + 4 + k] = a1[k]; q[oq + k] = q0[k]; q[oq + 4 + k] = q1[k]; }
+  }
+  const float r2 = r * r;
+  float mass = 0.f;
+  int m;
+  if (SIDE == 0) {
+    const int en = __shfl_down(eQ, 1, 64);
+    const float n0 = __shfl_down(q[0], 1, 64), n1 = __shfl_down(q[1], 1, 64);
+    const int eQn = lane < 63 ? en : -30000;
+    const int eref = max(eQ, eQn);
+    const int so = max(eQ - eref, -200), sn = max(eQn - eref, -200);
+#pragma unroll
+    for (int k = 0; k < 8; k++) q[k] = ldexpf(q[k], so);
+    q[8] = lane < 63 ? ldexpf(n0, sn) : 0.f; q[9] = lane < 63 ? ldexpf(n1, sn) : 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) mass += a[k] * (q[k] + r * q[k + 1] + r2 * q[k + 2]);
+    m = eA + eref + frame;
+  } else {
+    const int ep = __shfl_up(eA, 1, 64);
+    const float p0 = __shfl_up(a[8], 1, 64), p1 = __shfl_up(a[9], 1, 64);
+    const int eAp = lane > 0 ? ep : -30000;
+    const int eref = max(eA, eAp);
+    const int so = max(eA - eref, -200), sp = max(eAp - eref, -200);
+#pragma unroll
+    for (int k = 2; k < 10; k++) a[k] = ldexpf(a[k], so);
+    a[0] = lane > 0 ? ldexpf(p0, sp) : 0.f; a[1] = lane > 0 ? ldexpf(p1, sp) : 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) mass += (a[k + 2] + r * a[k + 1] + r2 * a[k]) * q[k];
+    m = eQ + eref + frame;
+  }
+  if (!(m > kBandCut)) return false;                       // the first stage's rule: the group's bound is already small enough
+  if (m > 72) return true;                                 // (what f32 may have lost is not bounded well enough: the first stage stands)
+  return mass > 0.f && __builtin_amdgcn_frexp_expf(mass) + m > kBandCutCells;      // (mass < 2^frexp_exp in the unit that is 2^m of Z)
+}
+
+template <typename P>
+__device__ __forceinline__ void segment_wave_band(const P& p, unsigned char* smem) {
+  constexpr int PPL = 2;
+  const int b = blockIdx.y, seg = blockIdx.x, lane = threadIdx.x & 63;
+  const int V = p.V, Tmax = p.T, t0 = seg * kSeg;
+  const F2Lds<PPL> lds(smem, V);
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  F2_STAMP(-1)
+
+  // First round trip: everything whose address does not depend on the window.
+  const int64_t Tq = p.x_len[b], Sq = p.t_len[b];
+  const int segn = min(seg + 1, p.NS - 1);                 // (row seg + 1 of the last segment does not exist and is not used)
+  const short* ce0 = p.ckE + ((size_t)b * p.NS + seg) * 2 * 64 + lane;
+  const short* ce1 = p.ckE + ((size_t)b * p.NS + segn) * 2 * 64 + lane;
+  int xAs = ce0[0], xBs = ce0[64], xAe = ce1[0], xBe = ce1[64];
+  SegIn<PPL> in;
+  in.load_frame(p, b, seg);
+  const int cA2 = p.cumA[(size_t)b * p.NB + (t0 >> 3) + 2], cB0 = p.cumB[(size_t)b * p.NB + (t0 >> 3)];
+  const int* ls = p.lstart + (size_t)b * p.LS;
+  int s0 = ls[lane], s1 = ls[64 + lane], s2 = ls[128 + (lane & 1)];
+  constexpr int kTileLoads = (4 * kMaxSmallV + 63) / 64;
+  f4 tile[kTileLoads];
+  {
+    seg_load_tile(tile, p.ytab + ((size_t)b * p.NS + seg) * V * kSeg, V, lane);
+  }
+
+  if (Tq < 1 || Tq > Tmax || Sq < 0 || Sq > p.Smax) return;    // flagged by F1, the exact kernel poisons it
+  const int T = (int)Tq, S = (int)Sq;
+  seg_dead_frames(p, b, t0, T, lane);
+  if (seg == 0 && lane == 0) {
+    const double za = p.logz[2 * b], zb = p.logz[2 * b + 1];
+    if (!(fabs(za - zb) <= 1e-6 * fabs(za) + 1e-4)) atomicOr(&p.flags[b], 32);
+  }
+  if (t0 >= T) return;
+  const int n = min(t0 + kSeg, T) - t0;
+  const bool last_seg = t0 + n == T;
+
+  // ---- the window (see above); lane g speaks for group g ----
+  const bool gvalid = 4 * lane <= S;                        // (the chains store nothing for groups past the lattice)
+  xAs = gvalid ? xAs : -30000; xBs = gvalid ? xBs : -30000; xAe = gvalid ? xAe : -30000; xBe = gvalid ? xBe : -30000;
+  int lo = 0, hi = S >> 2;
+  if (seg > 0) {
+    const int up = __shfl_down(xBs, 1, 64);
+    const int m = xAs + max(xBs, lane < 63 ? up : -30000) + in.EA0 + cB0 - in.zint;
+    const unsigned long long any = __ballot(gvalid && m > kBandCut);
+    lo = any ? __builtin_ctzll(any) : 0;
+  }
+  if (!last_seg) {
+    const int dn = __shfl_up(xAe, 1, 64);
+    const int m = xBe + max(xAe, lane > 0 ? dn : -30000) + cA2 + in.EB16 - in.zint;
+    const unsigned long long any = __ballot(gvalid && m > kBandCut);
+    hi = any ? 63 - __builtin_clzll(any) : lo;
+  }
+  lo = __builtin_amdgcn_readfirstlane(lo); hi = __builtin_amdgcn_readfirstlane(hi);
+  if (4 * hi + 3 > min(4 * lo, 256 - kBandPairs) + kBandPairs - 1) {
+    // the second stage (see above): a round trip more, for the waves whose first window does not fit
+    const float r = fast_tilt(S, T);
+    if (seg > 0) {
+      const unsigned long long any = __ballot(band_group_matters<0>(p, b, seg, lane, xAs, xBs, in.EA0 + cB0 - in.zint, r));
+      lo = any ? __builtin_ctzll(any) : 0;
+    }
+    if (!last_seg) {
+      const unsigned long long any = __ballot(band_group_matters<1>(p, b, seg + 1, lane, xAe, xBe, cA2 + in.EB16 - in.zint, r));
+      hi = any ? 63 - __builtin_clzll(any) : lo;
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo); hi = __builtin_amdgcn_readfirstlane(hi);
+  }
+  const int base = min(4 * lo, 256 - kBandPairs);                  // (the description holds 256 pairs: the last window starts at 128)
+  if (4 * hi + 3 > base + kBandPairs - 1) {
+    if (lane == 0) {
+      atomicOr(&p.flags[b], 8); atomicOr(&p.segmask[(size_t)b * p.MW + (seg >> 5)], 1u << (seg & 31));
+      atomicAdd(&p.ctl[7], 1);
+    }
+    return;
+  }
+
+  // Second round trip: the lattice description and the checkpoint cells of the window.
+  unsigned w[PPL];
+  {
+    const unsigned* ci = p.cinfo + (size_t)b * (p.CELLS / 2) + base + PPL * lane;
+#pragma unroll
+    for (int r = 0; r < PPL; r++) w[r] = ci[r];
+  }
+  const int grp = (base >> 2) + (lane >> 1);               // this lane's exponent group: two lanes share one
+  in.load_band(p, b, seg, 4 * grp <= S, base, lane);
+  in.ownA = seg > 0 ? __shfl(xAs, grp, 64) : 0;
+  in.ownB = seg + 1 < p.NS ? __shfl(xBe, grp, 64) : 0;
+
+  LaneCells<PPL> lc;
+  int rank[PPL];
+  lc.unpack(w, S, T, rank);
+  // Label sums inside the window.  The description's label-sorted slots run over the whole utterance (0..255), a row here holds
+  // the window's 128: mark the window's slots, count the marks below every slot (one wave scan over 4 marks per lane), and a
+  // pair's local slot is the count below its slot, a label's local start the count below its start.  (The marks lie where the
+  // rows of products go later.)
+  {
+    int* mk = reinterpret_cast<int*>(smem);
+    typedef int i4 __attribute__((ext_vector_type(4)));
+    *reinterpret_cast<i4*>(mk + 4 * lane) = i4{0, 0, 0, 0};
+    F2_LDS_ORDER
+#pragma unroll
+    for (int r = 0; r < PPL; r++) mk[min(rank[r], 255)] = 1;
+    F2_LDS_ORDER
+    const i4 m4 = *reinterpret_cast<i4*>(mk + 4 * lane);
+    const int c = m4.x + m4.y + m4.z + m4.w;
+    const int incl = (int)wave_scan((float)c);              // (counts of at most 128: exact)
+    const int ex = incl - c;
+    *reinterpret_cast<i4*>(mk + 4 * lane) = i4{ex, ex + m4.x, ex + m4.x + m4.y, ex + m4.x + m4.y + m4.z};
+    if (lane == 63) mk[256] = incl;
+    F2_LDS_ORDER
+#pragma unroll
+    for (int r = 0; r < PPL; r++) rank[r] = mk[min(rank[r], 255)];
+    s0 = mk[min(max(s0, 0), 256)]; s1 = mk[min(max(s1, 0), 256)]; s2 = mk[min(max(s2, 0), 256)];
+    F2_LDS_ORDER
+  }
+#pragma unroll
+  for (int r = 0; r < PPL; r++) rank[r] = ps_slot_address(lds.Ps, rank[r]);      // kept as LDS byte addresses: see ps_put
+  lds.starts[lane] = s0; lds.starts[64 + lane] = s1; if (lane < 2) lds.starts[128 + lane] = s2;
+  if (lane < kYs) lds.ys[V * kYs + lane] = 0.f;                           // the zero row V
+  {
+    seg_stage_tile(tile, lds.ys, V, n, lane);
+  }
+  if (lane < kHalf) lds.Ps[lane * F2Lds<PPL>::PROW - 1] = 0.f;           // the rows' zero guards
+  F2_LDS_ORDER   // staged rows visible to this (single) wave
+  GradLanes gl;
+  gl.init(lds, V, p.blank, lane);
+  F2_STAMP(0)
+  float smin = __builtin_huge_valf(), smax = 0.f;
+  const bool full = __builtin_amdgcn_readfirstlane((seg > 0 && n == kSeg && t0 + n < T) ? 1 : 0) != 0;
+  if (full) segment_body<PPL, true>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax, base);
+  else segment_body<PPL, false>(p, b, seg, T, S, n, lc, rank, in, lds, gl, lane, smin, smax, base);
+  F2_FLUSH
+  // (the range check and the segment's bit in the mask: as in segment_wave)
+  seg_close(p, b, seg, lane, smin, smax);
 }
 
 // (Folding the flagged-utterance scan and the loss reduction into this kernel's tail -- every wave takes a ticket, the
@@ -1707,6 +1971,26 @@ __global__ E2E_KERNEL_ALIGN __launch_bounds__(64, PPL == 8 ? 1 : PPL == 2 ? kSeg
   static_cast<FastParams&>(q) = p;
   segment_wave<PPL>(q, smem);
 }
+
+template <bool O16>
+__global__ E2E_KERNEL_ALIGN __launch_bounds__(64, kSegMinWaves2) void ctc_fast_segment_band_kernel(FastParams p) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  SegParams<O16> q;
+  static_cast<FastParams&>(q) = p;
+  segment_wave_band(q, smem);
+}
+
+// The banded form behind the chains of a call with targets of 128..255 labels and at most kMaxSmallV columns.
+int launch_segments_band(const FastParams& p, hipStream_t stream) {
+  const dim3 grid(p.NS, p.B), block(64);
+  const size_t lds = F2Lds<2>::bytes(p.V);
+  if (dtype_is_16bit(p.xdt)) hipLaunchKernelGGL((ctc_fast_segment_band_kernel<true>), grid, block, lds, stream, p);
+  else hipLaunchKernelGGL((ctc_fast_segment_band_kernel<false>), grid, block, lds, stream, p);
+  E2E_HIP_CHECK(hipGetLastError(), "ctc_fast_segment_band_kernel launch");
+  return E2E_OK;
+}
+// Diagnostics (e2e_debug_segment_band): 0 puts the four-pair instance back where the banded form runs, for A/B timing
+std::atomic<int> g_segment_band{1};
 
 // the segment kernel behind a chain kernel: the instance of the gradient's element width
 template <int PPL, bool BIG = false>
@@ -1774,6 +2058,8 @@ bool long_wide_rows(int V) { return V > kMaxSmallV || HfLds::of<ChainF64L>(V).to
 //   6. the single-wave chains, whose frame the segment kernel takes from cumA / cumB; their ring is four blocks deep instead
 //      of eight where B > 256 and eight blocks need more than 80 KB of LDS and four do not (eight would keep a second
 //      workgroup off a CU that the batch has work for).
+// Behind rules 3..7 with PPL 4 the segment kernel is the banded form (launch_segments_band) unless e2e_debug_segment_band(0) has
+// put the four-pair instance back (A/B timing); the wide-row and eight-pair forms have no banded instance.
 // E2E_F1_F32 / _SINGLE / _HALO are for the tests: they force kernels onto shapes that the rule gives to others.
 // The number of the rule above that picks a call's chains (rule 6 with the ring of four blocks: 7); `force`: bit 0 E2E_F1_F32,
 // 1 _SINGLE, 2 _HALO.  launch_fast_ppl follows it, and e2e_debug_loss_route reports it.
@@ -1823,6 +2109,9 @@ int launch_fast_ppl(const FastParams& p, hipStream_t stream) {
   if (rc != E2E_OK) return rc;
   if constexpr (PPL >= 4) {
     if (wide) return launch_segments<PPL, true>(q, F2Lds<PPL>::bytes(p.V), stream);
+  }
+  if constexpr (PPL == 4) {
+    if (g_segment_band.load(std::memory_order_relaxed)) return launch_segments_band(q, stream);
   }
   return launch_segments<PPL>(q, F2Lds<PPL>::bytes(p.V), stream);
 }
@@ -2013,6 +2302,21 @@ extern "C" int e2e_debug_flagged_counters(const void* workspace, int B, int T, i
   if (hipMemcpy(ctl, ws + l.ctl, sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
   *timeouts_host = ctl[4]; *failed_redos_host = ctl[5];
   return E2E_OK;
+}
+// Diagnostics: segments of the last call whose window did not fit the banded segment kernel (redone in f64).  Synchronises.
+extern "C" int e2e_debug_band_misses(const void* workspace, int B, int T, int V, int Smax, int* count_host) {
+  const char* ws; e2e::FastLayout l;
+  if (debug_workspace(workspace, B, T, V, Smax, ws, l) != E2E_OK) return E2E_ERR_HIP;
+  int ctl[8];
+  if (hipMemcpy(ctl, ws + l.ctl, sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return E2E_ERR_HIP;
+  *count_host = ctl[7];
+  return E2E_OK;
+}
+// Diagnostics: which segment kernel the calls that follow give targets of 128..255 labels (1, the default: the banded form; 0: the
+// four-pair instance over the whole lattice).  Returns the previous setting.
+extern "C" int e2e_debug_segment_band(int on) {
+  if (on == 0 || on == 1) return e2e::g_segment_band.exchange(on, std::memory_order_relaxed);
+  return e2e::g_segment_band.load(std::memory_order_relaxed);
 }
 // Diagnostics: the fast path's per-utterance flag words and both log Z values.  Synchronises.
 extern "C" int e2e_debug_fast_state(const void* workspace, int B, int T, int V, int Smax, int* flags_host, double* logz_host) {

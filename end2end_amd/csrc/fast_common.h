@@ -59,6 +59,7 @@ struct FastParams {
   int LS;
   int* ctl;        // [4]  0: fallback workgroups that have finished (F1 clears it; the last one reduces the losses);
                    //      1: flagged utterances the f64 redo of the segments could not settle (diagnostics)
+                   //      7: segments whose window did not fit the banded segment kernel (diagnostics, e2e_debug_band_misses)
   float gscale;    // every gradient element is multiplied by this as it is written (e2e_ctc_loss_opts.grad_scale)
   float ztol;      // |log2| tolerance of the segment kernel's self-check (kZTol with f64 chains, kZTolF32 with f32 chains)
   int chains;      // host side: E2E_CHAINS_* of the call

@@ -80,6 +80,16 @@ int e2e_debug_flagged_phases(const void* workspace, int B, int T, int V, int Sma
  * exact kernel) and f64 redos of single segments that failed (handed to the extended-range redo).  Synchronises. */
 int e2e_debug_flagged_counters(const void* workspace, int B, int T, int V, int Smax, int* timeouts_host, int* failed_redos_host);
 
+/* Segments of that call whose window of posterior mass did not fit the banded segment kernel's 128 label pairs (targets tensors
+ * of 128..255 columns): they set flag 8 and were redone in f64 by the flagged launch.  Synchronises. */
+int e2e_debug_band_misses(const void* workspace, int B, int T, int V, int Smax, int* count_host);
+
+/* Which segment kernel the calls that follow run behind the chains of targets tensors of 128..255 columns (alphabets of up to 96
+ * columns): 1 (the default) the banded form, two label pairs per lane over the 128 pairs that carry the segment's posterior
+ * mass; 0 the four-pair instance over the whole lattice.  Any other value changes nothing.  Returns the previous setting.
+ * A process-wide switch for A/B timing (tools/diag); not synchronised with calls in flight on other threads. */
+int e2e_debug_segment_band(int on);
+
 #ifdef E2E_FAST_PROFILE   /* only in builds made by tools/diag/build_profile_lib.sh */
 int e2e_debug_fast_zdev(float* host, int reset);
 int e2e_debug_fast_profile(unsigned long long* host, int n);
