@@ -31,11 +31,7 @@ constexpr int kMaxPairs = 16384;           // beam_width * V
 constexpr int kSlots = 512;                // the members' key table (<= 25 % full)
 constexpr unsigned long long kNoCand = 0ull;   // okey() of nothing: below every number's key (okey(-inf) = 0x000f...f)
 
-// order-preserving map double -> uint64 (larger double <=> larger key); -0.0 and +0.0 share one
-__device__ __forceinline__ unsigned long long okey(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d + 0.0);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
+// (okey: beam_cut.h) ... and back
 __device__ __forceinline__ double okey_inv(unsigned long long k) {
   const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
   return __longlong_as_double((long long)u);

@@ -19,6 +19,14 @@ constexpr uint64_t kHashMul = 0x9e3779b97f4a7c15ull;
 
 constexpr int kMaxW = 128;                 // members of a beam (LDS)
 
+// The encoding of a total that the beam searches hand to a select (here, and the radix select of ctc_beam_common.h): an
+// order-preserving map double -> uint64, larger double <=> larger key.  -0.0 and +0.0 compare equal as doubles -- the oracle's
+// order -- so the key is taken of d + 0.0, which is +0.0 for both.
+__device__ __forceinline__ unsigned long long okey(double d) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(d + 0.0);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
 // the cut's LDS state: a kernel declares one __shared__ and zeroes n_sel (behind a barrier) before every beam_cut
 struct BeamCut {
   double sel_tot[kMaxW];                                // the survivors: total,
