@@ -36,6 +36,11 @@ class BeamOpts(C.Structure):
     _fields_ = [("restrict_to_lexicon", C.c_int)]
 
 
+class AsgBeamOpts(C.Structure):
+    """e2e_asg_beam_opts (include/e2e_ctc.h)."""
+    _fields_ = [("restrict_to_lexicon", C.c_int), ("timesteps", C.c_void_p)]
+
+
 class E2EError(RuntimeError):
     """An error reported by the native library (message from e2e_last_error())."""
 
@@ -114,6 +119,8 @@ def load():
         L.e2e_asg_beam_nbest.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int, i64p, i64, i64p, i64p,
                                          vp, vp, vp, C.c_size_t, vp]
+        L.e2e_asg_beam_nbest_opt.restype = C.c_int
+        L.e2e_asg_beam_nbest_opt.argtypes = L.e2e_asg_beam_nbest.argtypes + [C.POINTER(AsgBeamOpts)]
         L.e2e_ctc_scale_grads.restype = C.c_int
         L.e2e_ctc_scale_grads.argtypes = [vp, C.c_int, vp, C.c_int, i64, vp]
         L.e2e_ctc_greedy.restype = C.c_int

@@ -12,7 +12,10 @@
 // The per-frame cut first drops what cannot matter (a full beam's members are W candidates themselves: nothing below the
 // least of their new totals survives); the select and the ranking are beam_cut.h's, the select on the order-preserving
 // bits of the totals, and the survivors become the next members in the order of their ranks.
-// The read-out walks the (parent node, label) pool backwards.
+// The read-out walks the (parent node, label) pool backwards; a node's index, 1 + t * W + rank, also says at which frame its
+// sequence was created (the optional timesteps).
+// Restricted to the model's lexicon (e2e_asg_beam_nbest_opt, the LEX instances): a pair whose sequence is not admissible is
+// no candidate -- one probe of the vocabulary table for a label, the member's own OOV counts for the space.
 //
 // The transitions are read from an f64 copy in the workspace, transposed to [from][to] by a small kernel of the same call: the
 // pairs of one member read one contiguous row (see DESIGN.md 4.10 for why not LDS).
@@ -70,6 +73,7 @@ struct AsgBeamParams {
   int64_t* out; int64_t max_out; int64_t* out_len; int64_t* n_hyp; double* scores; int32_t* counts;
   const double* At;                      // [from][to], f64
   unsigned char* ws; size_t per_utt, off_sval, off_spos, off_nodes;
+  int64_t* timesteps;                    // (B,nbest,max_out): the frame each label's node was created at; the TS instances only
 };
 
 // may label c follow a sequence that ends in `a` (a == -1: nothing yet)?  c != a is the caller's.
@@ -79,7 +83,8 @@ __device__ __forceinline__ bool spellable(const AsgBeamParams& p, int a, int c) 
 }
 
 // what the pair (member m, label c != space) asks of the model: the expanded word's hash, its id, its score in the context
-struct LmAnswer { unsigned long long h; uint32_t wi; float sc; };
+// (`listed`, the restricted search's: the spelling is in the table at all -- a word, or with id 0 a prefix of one)
+struct LmAnswer { unsigned long long h; uint32_t wi; float sc; bool listed; };
 __device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned long long h, int c) {
   for (int bi = lm.label_off[c]; bi < lm.label_off[c + 1]; bi++) {
     unsigned char ch = lm.label_bytes[bi];
@@ -88,6 +93,7 @@ __device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned l
   }
   return h;
 }
+template <bool LEX = false>
 __device__ __forceinline__ LmAnswer lm_query(const AsgBeamParams& p, const LmMembers& L, int m, int a, int c, bool new_word) {
   LmAnswer ans;
   unsigned long long h = new_word ? kFnvInit : L.hash[m];
@@ -99,7 +105,9 @@ __device__ __forceinline__ LmAnswer lm_query(const AsgBeamParams& p, const LmMem
 #pragma unroll
   for (int i = 0; i < kCtx; i++) ctx[i] = new_word ? L.st[i][m] : L.stb[i][m];
   ans.h = h;
-  ans.wi = lm_word_lookup(p.lm, h);
+  if constexpr (LEX) ans.listed = lm_word_find(p.lm, h, ans.wi);
+  else { ans.wi = lm_word_lookup(p.lm, h); ans.listed = true; }
+  if (LEX && !ans.listed) { ans.sc = 0.f; return ans; }           // no candidate: nothing to score
   ans.sc = lm_base_score(p.lm, ctx, cn, ans.wi, nullptr, nullptr);
   return ans;
 }
@@ -139,8 +147,12 @@ __device__ __forceinline__ ChildLm child_lm(const LmMembers& L, int m, bool nw, 
   return s;
 }
 
-template <bool LM>
+// LEX (with LM): the search restricted to the model's lexicon.  TS: the read-out also writes the timesteps -- an instance of
+// its own, because the plain read-out's walk (T dependent hops) must not pay for the division, nor the frames for a pointer
+// more in scalar registers: without TS the code is the kernel's before there were timesteps, instruction for instruction
+template <bool LM, bool LEX, bool TS>
 __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
+  static_assert(LM || !LEX, "a restricted search has a model");
   using LmSet = typename std::conditional<LM, LmMembers, NoLm>::type;
   __shared__ Members mem[2];
   __shared__ LmSet lms[2];
@@ -212,15 +224,22 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
           const bool nwd = new_word(p, a, c);
           const int nw = M.nw[m] + (nwd ? 1 : 0);
           double lm = 0.0; int noov = 0;
+          bool admissible = true;
           if constexpr (LM) {
             const LmMembers& L = lms[cur];
             if (c != p.space_id) {
-              const ChildLm s = child_lm(L, m, nwd, lm_query(p, L, m, a, c, nwd));
+              const LmAnswer ans = lm_query<LEX>(p, L, m, a, c, nwd);
+              const ChildLm s = child_lm(L, m, nwd, ans);
               lm = s.lm; noov = s.oov;
-            } else { lm = L.lm[m]; noov = L.oov[m]; }
+              if constexpr (LEX) admissible = ans.listed;          // the last word, expanded, is spelled in Pref(L)
+            } else {
+              lm = L.lm[m]; noov = L.oov[m];
+              // the space ends a word of L: the member's last lookup found an id, so it counted no OOV (a prefix has id 0)
+              if constexpr (LEX) admissible = a < 0 || L.oov[m] == L.oovb[m];
+            }
           }
           const double tot = total_of(p, v, lm, nw, noov);
-          if (tot > ninf()) cand = okey(tot);
+          if (admissible && tot > ninf()) cand = okey(tot);
         }
       }
       ctot[id] = cand;
@@ -315,9 +334,13 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   const int nbest = p.nbest;
   const int64_t max_out = p.max_out;
   int64_t* out = p.out + (int64_t)b * nbest * max_out;
+  int64_t* ts = nullptr;
+  if constexpr (TS) ts = p.timesteps + (int64_t)b * nbest * max_out;
   __syncthreads();
   if (tid < nbest) {
     int64_t* row = out + (int64_t)tid * max_out;
+    int64_t* trow = nullptr;
+    if constexpr (TS) trow = ts + (int64_t)tid * max_out;
     int len = 0, nw = 0, noov = 0;
     double ac = ninf(), lm = 0.0, tot = ninf();
     if (tid < n_mem) {
@@ -328,7 +351,10 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
       for (int hops = 0; node > 0 && hops <= p.T; hops++) {
         const int2 nd = nodes[node];
         --at;
-        if (at >= 0 && at < max_out) row[at] = (int64_t)nd.y;
+        if (at >= 0 && at < max_out) {
+          row[at] = (int64_t)nd.y;
+          if constexpr (TS) trow[at] = (int64_t)((node - 1) / W);   // node = 1 + t * W + rank
+        }
         node = nd.x;
       }
     }
@@ -342,6 +368,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   for (int j = 0; j < nbest; j++) {
     int64_t* row = out + (int64_t)j * max_out;
     for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kThreads) row[i] = 0;
+    if constexpr (TS) for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kThreads) ts[(int64_t)j * max_out + i] = -1;
   }
   if (tid == 0) p.n_hyp[b] = n_mem < nbest ? n_mem : nbest;
 }
@@ -391,11 +418,14 @@ size_t e2e_asg_beam_workspace_bytes(int B, int T, int V, int beam_width, int wit
   return L.head + (size_t)B * L.per_utt + 256;
 }
 
-int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
-                       const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
-                       const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
-                       int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
-                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+int e2e_asg_beam_nbest_opt(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                           const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                           const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                           int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                           const e2e_asg_beam_opts* opts) {
+  const bool restricted = opts && opts->restrict_to_lexicon != 0;
+  int64_t* timesteps = opts ? opts->timesteps : nullptr;
   if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
   if (B < 0 || T < 1 || V < 1 || max_out < 0) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
   if (V > e2e_asg_max_labels()) { set_error("V=%d exceeds e2e_asg_max_labels() = %d", V, e2e_asg_max_labels()); return E2E_ERR_UNSUPPORTED; }
@@ -420,6 +450,10 @@ int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t
       return E2E_ERR_ARG;
     }
   }
+  if (restricted && (!lm || !lm->has_lexicon)) {
+    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+    return E2E_ERR_ARG;
+  }
   if (B > 0 && (!x || !x_len || !out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
     set_error("null pointer argument"); return E2E_ERR_ARG;
   }
@@ -443,6 +477,7 @@ int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t
   if (lm) p.lm = lm->dev_view(); else memset(&p.lm, 0, sizeof(p.lm));
   p.lmwt = lm ? lmwt : 0.0; p.wip = wip; p.oov = oov_penalty;
   p.out = out; p.max_out = max_out; p.out_len = out_len; p.n_hyp = n_hyp; p.scores = scores; p.counts = counts;
+  p.timesteps = timesteps;
   unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
   p.At = reinterpret_cast<const double*>(base);
   p.ws = base + L.head; p.per_utt = L.per_utt; p.off_sval = L.off_sval; p.off_spos = L.off_spos; p.off_nodes = L.off_nodes;
@@ -450,10 +485,23 @@ int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t
   hipLaunchKernelGGL(asg_beam_transpose_kernel, dim3((V * V + 255) / 256), dim3(256), 0, s, transitions, dtype, V,
                      reinterpret_cast<double*>(base));
   E2E_HIP_CHECK(hipGetLastError(), "asg_beam_transpose_kernel launch");
-  if (lm) hipLaunchKernelGGL(asg_beam_kernel<true>, dim3(B), dim3(kThreads), 0, s, p);
-  else hipLaunchKernelGGL(asg_beam_kernel<false>, dim3(B), dim3(kThreads), 0, s, p);
+  auto kernel = asg_beam_kernel<false, false, false>;
+  if (timesteps) kernel = restricted ? asg_beam_kernel<true, true, true> : lm ? asg_beam_kernel<true, false, true> : asg_beam_kernel<false, false, true>;
+  else if (restricted) kernel = asg_beam_kernel<true, true, false>;
+  else if (lm) kernel = asg_beam_kernel<true, false, false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(kThreads), 0, s, p);
   E2E_HIP_CHECK(hipGetLastError(), "asg_beam_kernel launch");
   return E2E_OK;
+}
+
+int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                       const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                       const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                       int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  return e2e_asg_beam_nbest_opt(x, dtype, sB, sT, sV, transitions, x_len, B, T, V, num_replabels, beam_width, space_id, lm, lmwt,
+                                wip, oov_penalty, nbest, out, max_out, out_len, n_hyp, scores, counts, workspace,
+                                workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"

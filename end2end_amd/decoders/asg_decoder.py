@@ -1,11 +1,15 @@
 """ASGDecoder: decoding for models trained with ASGLoss or CTCWithoutBlankLoss.  As constructed: the Viterbi path
 through emissions and learned transitions (e2e_asg_viterbi), its repeats merged and its repeat labels expanded.
 After ``configure(beam_width > 1, ...)``: n-best prefix beam search with the transitions and, optionally, a word language model
-(e2e_asg_beam_nbest).  The definitions are in include/e2e_ctc.h; upstream has no ASG decoder; the return conventions
-are CTCDecoder's.
+(e2e_asg_beam_nbest).  ``restrict_to_vocabulary()`` restricts that search to the language model's words or to a word list,
+``decode_nbest(..., timesteps=True)`` says at which frame each label entered the beam (e2e_asg_beam_nbest_opt).  The
+definitions are in include/e2e_ctc.h; upstream has no ASG decoder; the return conventions are CTCDecoder's.
 
-Not provided for ASG: a lexicon or vocabulary restriction, streaming, timestamps, widths or alphabets above 128,
--inf transitions, custom transcriptions.
+With ``num_replabels=0`` (a ``CTCWithoutBlankLoss`` model) a word with a doubled letter cannot be spelled -- equal neighbours
+merge --, so a restricted search never produces it.
+
+Not provided for ASG: streaming, custom transcriptions, a lexicon together with a language model, widths or alphabets
+above 128, -inf transitions.
 """
 import os
 from collections import namedtuple
@@ -13,7 +17,7 @@ from collections import namedtuple
 import torch
 
 from ..engines import ASGBeamEngine, ASGViterbiEngine
-from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults
+from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults, read_lexicon
 
 # decode_path(): the label of every frame, -100 past an utterance's length (as get_alignment_3d pads), and the paths' scores
 ASGPathResults = namedtuple("ASGPathResults", ["paths", "scores"])
@@ -76,6 +80,29 @@ class ASGDecoder:
         self._beam_width = beam_width
         return self
 
+    def restrict_to_vocabulary(self, lexicon=None):
+        """Restrict the beam search to a vocabulary, after ``configure(beam_width > 1, ...)``; returns self.  The search then
+        only forms words of the vocabulary: a label is taken only if the last word, repeat labels expanded, is still the
+        beginning of a word, and a space only after a whole word (the last word of a result may still be an unfinished
+        prefix of one, counted as out of vocabulary).
+
+        :param lexicon: ``None``: the words of the configured language model (``lm_path``).  Otherwise an iterable of words, or
+            the path of a text file with one entry per line whose first white-space separated token is the word: the search
+            is restricted to them without a language model; ``lmwt`` and ``oov_penalty`` then count as 0, ``wip`` applies.
+            Not together with ``lm_path``.
+
+        A later ``configure()`` builds a new search and drops the restriction.
+        """
+        if self._labels is None:
+            raise CTCDecoderError("restrict_to_vocabulary needs labels: the alphabet spells the vocabulary's words")
+        if self._beam is None:
+            raise CTCDecoderError("restrict_to_vocabulary needs beam_width > 1: best-path decoding has no vocabulary")
+        try:
+            self._beam.restrict(None if lexicon is None else read_lexicon(lexicon))
+        except ValueError as e:
+            raise CTCDecoderError(str(e))
+        return self
+
     def _batch_major(self, emissions, logits_lengths):
         if self._time_major:
             emissions = emissions.transpose(1, 0)
@@ -121,18 +148,21 @@ class ASGDecoder:
             sentences = [self._sentence(row[:n], num_chars) for row, n in zip(ids.tolist(), lengths.tolist())]
         return DecoderResults(ids, lengths, sentences)
 
-    def decode_nbest(self, emissions, transitions, logits_lengths=None, nbest=None):
+    def decode_nbest(self, emissions, transitions, logits_lengths=None, nbest=None, timesteps=False):
         """The hypotheses the beam search ends with, best first (``beam_width > 1``).  ``transitions=None`` means zero
         transitions: a ``CTCWithoutBlankLoss`` model is decoded by passing its log-softmax output, ``num_replabels=0``.
 
         :param nbest: how many to return per utterance, at most ``beam_width`` (the default)
+        :param timesteps: also return ``timesteps (batch, nbest, longest)`` int64: for every label the frame at which the
+            sequence ending in it last entered the beam, ``-1`` behind a sequence.  In a wide beam a sequence can enter the beam
+            before its last label becomes likely
         :return: ``CTCDecoder``'s ``NBestResults``: ``decoded_targets (batch, nbest, longest)`` -- the merged labels, repeat
             labels as they are --, ``decoded_targets_lengths``, ``decoded_sentences`` (repeat labels expanded), ``scores``,
             ``ctc_scores`` (the acoustic score: log of the summed path scores of the labelling, within the beam),
-            ``lm_scores``, ``num_words``, ``num_oov_words``, ``num_hypotheses``, ``timesteps=None``;
+            ``lm_scores``, ``num_words``, ``num_oov_words``, ``num_hypotheses``, ``timesteps`` (``None`` unless asked for);
             ``scores = ctc_scores + lmwt * lm_scores - wip * num_words + oov_penalty * num_oov_words``.
         """
         if self._beam is None:
             raise CTCDecoderError("decode_nbest needs beam_width > 1: best-path decoding has no beam")
         emissions, logits_lengths = self._batch_major(emissions, logits_lengths)
-        return NBestResults(*self._beam.decode_nbest(emissions, transitions, logits_lengths, nbest=nbest))
+        return NBestResults(*self._beam.decode_nbest(emissions, transitions, logits_lengths, nbest=nbest, timesteps=timesteps))

@@ -367,8 +367,8 @@ class ASGBeamEngine:
     too; None: no sentences, no space, no model).  The model is loaded once per device through LanguageModel, with the
     labels of all V columns (the repeat columns' strings are never read), at the first call: only the emissions tell
     whether `labels` lists the characters or all columns.  The width limit is checked here when the
-    alphabet is known, else at the first call -- before any launch either way.  Results are CPU tensors unless
-    `keep_on_device`."""
+    alphabet is known, else at the first call -- before any launch either way.  `restrict()` restricts the search to a
+    vocabulary (e2e_asg_beam_nbest_opt).  Results are CPU tensors unless `keep_on_device`."""
 
     def __init__(self, labels=None, num_replabels=0, beam_width_=100, lm_path="", lmwt_=1.0, wip_=0.0,
                  oov_penalty_=-1000.0, case_sensitive=False, keep_on_device=False):
@@ -384,6 +384,8 @@ class ASGBeamEngine:
         self.keep_on_device = bool(keep_on_device)
         self.num_labels = None                       # V, once it is known
         self.lm = None
+        self.restricted = False
+        self._words = None                           # restrict(lexicon=...): the word list of the model that scores nothing
         if self.beam_width < 1 or self.beam_width > _C.asg_beam_max_width(1):
             raise ValueError("beam_width %d is not supported: 1 to %d" % (self.beam_width, _C.asg_beam_max_width(1)))
         self._lm_path = lm_path or ""
@@ -391,6 +393,42 @@ class ASGBeamEngine:
             if self.labels is None:
                 raise ValueError("a language model needs the labels: the alphabet spells its words")
             R.require_gpu()
+
+    def restrict(self, lexicon=None):
+        """Restrict the search to a vocabulary (the definition: e2e_asg_beam_nbest_opt); returns self.  `lexicon` None: the
+        words of the language model of `lm_path`.  `lexicon` an iterable of words: the model that scores nothing is built
+        from them (e2e_lm_load_words) -- `lmwt` and `oov_penalty` then count as 0, `wip` applies; not together with `lm_path`.
+        The model is loaded, and its lexicon built, when the number of columns is known."""
+        if self.labels is None:
+            raise ValueError("restrict needs the labels: the alphabet spells the vocabulary's words")
+        if lexicon is not None and self._lm_path:
+            raise ValueError("lm_path and lexicon exclude each other (a lexicon together with a language model is not supported)")
+        if lexicon is None and not self._lm_path and self._words is None:
+            raise ValueError("restrict needs a vocabulary: lm_path or lexicon")
+        if lexicon is not None:
+            words = [str(w) for w in lexicon]
+            if not words:
+                raise ValueError("the lexicon is empty")
+            R.require_gpu()
+            self._words = words
+            self.lmwt = 0.0
+            self.oov_penalty = 0.0
+            self.lm = None
+        self.restricted = True
+        if self.num_labels is not None:
+            self._load_model(self.num_labels)
+        return self
+
+    def _load_model(self, V):
+        """The model over all V columns (the repeat columns' strings are never spelled), with its lexicon if restricted."""
+        labels = self.labels[: V - self.num_replabels] + ["<%d>" % (r + 1) for r in range(self.num_replabels)]
+        if self.lm is None:
+            if self._words is not None:
+                self.lm = LanguageModel(None, labels, self.case_sensitive, words=self._words, lexicon=True)
+            elif self._lm_path:
+                self.lm = LanguageModel(self._lm_path, labels, self.case_sensitive)
+        if self.restricted and not self.lm.has_lexicon():
+            self.lm.enable_lexicon()
 
     def _chars(self):
         return self.labels if self.num_labels is None else self.labels[: self.num_labels - self.num_replabels]
@@ -414,9 +452,8 @@ class ASGBeamEngine:
                              % (self.beam_width, V, cap))
         chars = self.labels[:num_chars] if self.labels is not None else []
         self.space_id = chars.index(" ") if " " in chars else -1
-        if self._lm_path:                            # loaded once, now that the number of columns is known
-            self.lm = LanguageModel(self._lm_path, chars + ["<%d>" % (r + 1) for r in range(self.num_replabels)],
-                                    self.case_sensitive)
+        if self._lm_path or self._words is not None:  # loaded once, now that the number of columns is known
+            self._load_model(V)
         self.num_labels = V
 
     def _strings(self, rows, lens):
@@ -433,10 +470,12 @@ class ASGBeamEngine:
             out.append("".join(s))
         return out
 
-    def decode_nbest(self, emissions, transitions, logits_lengths, nbest=None):
+    def decode_nbest(self, emissions, transitions, logits_lengths, nbest=None, timesteps=False):
         """-> (ids (B,N,maxlen) int64 -- the merged labels, repeat labels as they are --, lengths (B,N), sentences [B][n_hyp]
         with the repeat labels expanded, scores (B,N) f64, acoustic scores, lm_scores, num_words (B,N) int32, num_oov (B,N),
-        num_hypotheses (B), None): CTCDecoderEngine.decode_nbest's tuple.  `transitions` None: all zero."""
+        num_hypotheses (B), timesteps): CTCDecoderEngine.decode_nbest's tuple.  `transitions` None: all zero.  `timesteps`:
+        (B,N,maxlen) int64, the frame at which each label's sequence last entered the beam, -1 behind a sequence, cut to the
+        longest result as `ids` is; None unless asked for."""
         N = self.beam_width if nbest is None else int(nbest)
         if not 1 <= N <= self.beam_width:
             raise ValueError("nbest=%d outside [1, beam_width=%d]" % (N, self.beam_width))
@@ -460,6 +499,7 @@ class ASGBeamEngine:
         scores = torch.full((B, N, 3), float("-inf"), dtype=torch.float64, device=dev)
         scores[:, :, 2] = 0.0
         counts = torch.zeros((B, N, 2), dtype=torch.int32, device=dev)
+        ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if timesteps else None
         if B and T:
             stream = R.stream_handle(dev)
             with _on_device(dev):
@@ -472,12 +512,15 @@ class ASGBeamEngine:
                 _C.asg_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
                                   xl.data_ptr(), B, T, V, self.num_replabels, self.beam_width, self.space_id, lm,
                                   self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
-                                  n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        ids, sentences, _ = _pack_nbest(out, out_len.tolist(), n_hyp.tolist(), self._strings, self.keep_on_device)
+                                  n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream,
+                                  self.restricted, ts.data_ptr() if ts is not None else 0)
+        ids, sentences, width = _pack_nbest(out, out_len.tolist(), n_hyp.tolist(), self._strings, self.keep_on_device)
         r = (lambda t: t) if self.keep_on_device else (lambda t: t.cpu())
+        if ts is not None:
+            ts = r(ts[:, :, :width].contiguous())
         return (ids, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
                 r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
-                r(counts[:, :, 1].contiguous()), r(n_hyp), None)
+                r(counts[:, :, 1].contiguous()), r(n_hyp), ts)
 
     def decode(self, emissions, transitions, logits_lengths):
         """Hypothesis 0 of decode_nbest -> (ids (B,maxlen) int64, lengths (B), sentences)."""

@@ -411,7 +411,9 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
  * unsupported V -- the pair buffers are sized for 16384 pairs, which V <= 128 never exceeds at width 128, so the limit is
  * 128 for every supported V; T <= 2^22.  Beyond them E2E_ERR_UNSUPPORTED (the workspace query returns 0).  Every argument
  * error is found on the host before any launch.  Asynchronous on `stream`, allocates nothing, never synchronises,
- * capturable.  Not provided: a lexicon or vocabulary restriction, streaming, timestamps, custom transcriptions.
+ * capturable.  A restriction to the model's vocabulary and label timestamps: e2e_asg_beam_nbest_opt, below the lexicon
+ * functions.  Not provided: streaming, custom transcriptions, a lexicon together with a language model, widths or alphabets
+ * above 128.
  */
 struct e2e_lm;   /* (e2e_lm_load_arpa, below) */
 int e2e_asg_beam_max_width(int V);
@@ -587,6 +589,48 @@ int e2e_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, in
                            int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
                            double* scores, int32_t* counts, int64_t* timesteps,
                            void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts);
+
+/* ------------------------------------------------------------------------
+ * ASG beam search restricted to a vocabulary, and label timestamps (additive, ABI 4: nothing above changes meaning).
+ *
+ * e2e_asg_beam_nbest_opt is e2e_asg_beam_nbest with options; opts == NULL, or both fields zero, is e2e_asg_beam_nbest bit
+ * for bit.  Workspace (e2e_asg_beam_workspace_bytes), width and alphabet limits, outputs, ranking and tie order do not change.
+ *
+ * restrict_to_lexicon   L and Pref(L) are those of e2e_ctc_beam_nbest_opt: the model's words, folded as the lookup folds them,
+ *                       and every non-empty byte prefix of a word.  The LAST WORD of a sequence is the run of labels after its
+ *                       last space, spelled with repeat labels expanded, exactly as the LM lookup of e2e_asg_beam_nbest spells
+ *                       it.  A sequence is ADMISSIBLE if it is spellable and every one of its prefixes y + (c) obeys:
+ *                         - c is not the space: the last word of y + (c) is spelled in Pref(L);
+ *                         - c is the space: y is empty, or the last word of y is a word of L.
+ *                       A restricted search forms only admissible sequences: an inadmissible y + (c) is no candidate at frame 0
+ *                       and no extension later, like an unspellable one.  Admissibility is a function of the sequence alone, so
+ *                       the cut and the re-formation rule are untouched; masses, LM fields, totals, cut and ranking are the
+ *                       unrestricted search's.  The last word of a hypothesis may be a proper prefix that is no word: it counts
+ *                       as out of vocabulary, as it always did.  Spellings are not canonicalised: a <2> and a <1> a remain two
+ *                       sequences.  With num_replabels = 0 a word with a doubled letter cannot be spelled (equal neighbours
+ *                       merge), so a restricted search never produces it.
+ *                       != 0 with lm == NULL or a model without a lexicon (e2e_lm_enable_lexicon): E2E_ERR_ARG, before any
+ *                       launch.  A transcription model stays refused (E2E_ERR_UNSUPPORTED).
+ * timesteps             NULL, or (B,nbest,max_out) int64: for every id written to `out`, the frame at which the pool node that
+ *                       carries it was created -- the frame at which the sequence ending in that label last entered the beam on
+ *                       this path, (node - 1) / beam_width, read during the read-out's backward walk: no workspace, no per-frame
+ *                       work.  Along a sequence the values increase strictly; the first is 0 (a one-label sequence is only
+ *                       formed at frame 0); entry k is >= k and < x_len[b]; behind the sequence and in slots >= n_hyp[b]: -1.
+ *                       x_len[b] outside [1,T] leaves the utterance's timesteps untouched, like everything else of it.
+ *                       The caveat of e2e_ctc_beam_nbest's timesteps holds here too: in a wide beam a sequence can enter the
+ *                       beam before its last label becomes likely, so a value can precede the frame where the label is heard.
+ */
+typedef struct e2e_asg_beam_opts {
+  int restrict_to_lexicon;   /* 0: the plain search */
+  int64_t* timesteps;        /* NULL, or (B,nbest,max_out) int64 */
+} e2e_asg_beam_opts;
+
+int e2e_asg_beam_nbest_opt(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                           const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                           const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                           int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                           const e2e_asg_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
  * Custom transcriptions: a pronunciation lexicon, homophones included (additive, ABI 4: nothing above changes meaning).
