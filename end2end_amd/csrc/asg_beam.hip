@@ -17,6 +17,11 @@
 // Restricted to the model's lexicon (e2e_asg_beam_nbest_opt, the LEX instances): a pair whose sequence is not admissible is
 // no candidate -- one probe of the vocabulary table for a label, the member's own OOV counts for the space.
 //
+// The search can stop after any frame and go on in a later launch (e2e_asg_beam_stream, the ST instances): what a frame hands
+// to the next is one member set (with a model: its LM fields too), the member count and the node pool.  They live in a state
+// row of the caller's (AsgStreamHeader | Members | LmMembers | nodes); the key table is rebuilt from the members' keys at
+// resume, ctot / sval / spos are a frame's scratch.  A node's index counts the frames of the STREAM, so the timesteps need nothing.
+//
 // The transitions are read from an f64 copy in the workspace, transposed to [from][to] by a small kernel of the same call: the
 // pairs of one member read one contiguous row (see DESIGN.md 4.10 for why not LDS).
 #include <cstring>
@@ -75,6 +80,32 @@ struct AsgBeamParams {
   unsigned char* ws; size_t per_utt, off_sval, off_spos, off_nodes;
   int64_t* timesteps;                    // (B,nbest,max_out): the frame each label's node was created at; the TS instances only
 };
+
+// ---- the state row of a stream (e2e_asg_beam_stream): header (256 bytes) | Members | LmMembers (with a model) | node pool ----
+// Indices only, never an address: a row may be moved or copied.  magic == 0 -- what a zeroed header has -- is a fresh utterance.
+// A status (too many frames, another configuration) stores nothing, so a stored row carries no error flag.
+constexpr unsigned kAsgStreamMagic = 0x53475341u;
+constexpr int kAsgStreamHeaderBytes = 256;
+struct AsgStreamHeader {
+  unsigned magic;
+  int V, R, W, has_lm, max_frames;       // the configuration the row was written under
+  int n, frames, dead;                   // members, frames consumed, 1: no hypothesis is left (then n == 0)
+};
+static_assert(sizeof(AsgStreamHeader) <= kAsgStreamHeaderBytes, "stream header");
+constexpr int kAsgStreamTooManyFrames = -2, kAsgStreamOtherConfig = -3;
+// what the streaming call adds to AsgBeamParams (whose x_len is then the chunk's lengths, T its width; ws holds no nodes)
+struct AsgStream {
+  unsigned char* rows; size_t row_bytes, off_lm, off_nodes;   // (B,row_bytes); the LM fields and the node pool inside a row
+  int max_frames;
+  int64_t* frames_done;                  // (B): frames consumed so far, or the in-band status
+};
+struct AsgStreamParams { AsgBeamParams b; AsgStream s; };
+// the kernel's parameter block: the ST instances take the stream's, the others the one they always took
+template <bool ST> using AsgKernelParams = typename std::conditional<ST, AsgStreamParams, AsgBeamParams>::type;
+__device__ __forceinline__ const AsgBeamParams& beam_of(const AsgBeamParams& q) { return q; }
+__device__ __forceinline__ const AsgBeamParams& beam_of(const AsgStreamParams& q) { return q.b; }
+__device__ __forceinline__ AsgStream stream_of(const AsgBeamParams&) { return AsgStream{}; }
+__device__ __forceinline__ const AsgStream& stream_of(const AsgStreamParams& q) { return q.s; }
 
 // may label c follow a sequence that ends in `a` (a == -1: nothing yet)?  c != a is the caller's.
 __device__ __forceinline__ bool spellable(const AsgBeamParams& p, int a, int c) {
@@ -147,12 +178,54 @@ __device__ __forceinline__ ChildLm child_lm(const LmMembers& L, int m, bool nw, 
   return s;
 }
 
+// the key of new member r enters the table (two members with one key, 2^-64: the second is not entered and never extended into)
+__device__ __forceinline__ void table_insert(unsigned long long* tab_key, int* tab_mem, unsigned long long key, int r) {
+  for (unsigned h = (unsigned)((key * kHashMul) >> 55), probe = 0; probe < (unsigned)kSlots; probe++, h = (h + 1u) & (kSlots - 1)) {
+    const unsigned long long old = atomicCAS(&tab_key[h], 0ull, key);
+    if (old == 0ull) { tab_mem[h] = r; break; }
+    if (old == key) break;
+  }
+}
+
+// ---- the phases of a streaming call, compiled into the ST instances only ----
+// What the row says before a chunk of Tc frames: the frames consumed so far (a fresh row: 0, resume = false) or a status < 0;
+// n: the members to resume with.  The same for every thread of the workgroup (returned wave-uniform).
+template <bool LM>
+__device__ __forceinline__ int asg_stream_open(const AsgBeamParams& p, const AsgStream& sp, const unsigned char* row, int Tc,
+                                               bool& resume, int& n) {
+  const AsgStreamHeader h = *reinterpret_cast<const AsgStreamHeader*>(row);
+  int st = 0, res = 0, nn = 1;
+  if (h.magic != 0u) {
+    const bool same = h.magic == kAsgStreamMagic && h.V == p.V && h.R == p.R && h.W == p.W && h.has_lm == (LM ? 1 : 0) &&
+                      h.max_frames == sp.max_frames && h.n >= 0 && h.n <= p.W && h.dead == (h.n == 0 ? 1 : 0) &&
+                      h.frames >= 1 && h.frames <= sp.max_frames;
+    if (same) { st = h.frames; res = 1; nn = h.n; } else st = kAsgStreamOtherConfig;
+  }
+  if (st >= 0 && st + Tc > sp.max_frames) st = kAsgStreamTooManyFrames;
+  resume = __builtin_amdgcn_readfirstlane(res) != 0;
+  n = __builtin_amdgcn_readfirstlane(nn);
+  return __builtin_amdgcn_readfirstlane(st);
+}
+// a member set between LDS and the row, as it stands (all threads; plain vector loads and stores)
+__device__ __forceinline__ void asg_stream_copy(void* dst, const void* src, size_t bytes) {
+  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(dst);
+  for (size_t i = threadIdx.x; i < bytes / 8; i += kThreads) d[i] = s[i];
+}
+
+// The search of one utterance, whole (ST = false: the parameter block is AsgBeamParams and sp is not read) or streamed: one
+// piece of source, and without ST the code the kernel had before it could stream, instruction for instruction
+// (tools/diag/isa_compare.py).
 // LEX (with LM): the search restricted to the model's lexicon.  TS: the read-out also writes the timesteps -- an instance of
 // its own, because the plain read-out's walk (T dependent hops) must not pay for the division, nor the frames for a pointer
-// more in scalar registers: without TS the code is the kernel's before there were timesteps, instruction for instruction
-template <bool LM, bool LEX, bool TS>
-__global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
+// more in scalar registers: without TS the code is the kernel's before there were timesteps, instruction for instruction.
+// ST: resume from the state row, run the chunk's frames as frames f0 .. of the stream, suspend; the timesteps are then a
+// run-time test on p.timesteps (TS is not read).
+template <bool LM, bool LEX, bool TS, bool ST = false>
+__global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgKernelParams<ST> q) {
   static_assert(LM || !LEX, "a restricted search has a model");
+  const AsgBeamParams& p = beam_of(q);
+  const AsgStream& sp = stream_of(q);
   using LmSet = typename std::conditional<LM, LmMembers, NoLm>::type;
   __shared__ Members mem[2];
   __shared__ LmSet lms[2];
@@ -167,15 +240,32 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int V = p.V, W = p.W;
   const int64_t Tq = p.x_len[b];
-  if (Tq < 1 || Tq > p.T) { if (tid == 0) p.n_hyp[b] = 0; return; }
-  const int Tb = (int)Tq;
+  int Tb, f0 = 0, n_mem = 1;                                      // the frames to run, the stream's frames before them, the members
+  bool resume = false;
+  unsigned char* row = nullptr;
+  if constexpr (ST) {
+    row = sp.rows + (size_t)b * sp.row_bytes;
+    Tb = Tq < 0 ? 0 : Tq > p.T ? p.T : (int)Tq;
+    f0 = asg_stream_open<LM>(p, sp, row, Tb, resume, n_mem);
+    // a status, or a fresh row fed nothing (the whole call on no frames): nothing of the row or the utterance is touched
+    if (f0 < 0 || f0 + Tb == 0) {
+      if (tid == 0) { sp.frames_done[b] = f0; if (p.nbest) p.n_hyp[b] = f0; }
+      return;
+    }
+  } else {
+    if (Tq < 1 || Tq > p.T) { if (tid == 0) p.n_hyp[b] = 0; return; }
+    Tb = (int)Tq;
+  }
   unsigned char* ws = p.ws + (size_t)b * p.per_utt;
   unsigned long long* ctot = reinterpret_cast<unsigned long long*>(ws);           // okey(total) per pair id, kNoCand: none
   unsigned long long* sval = reinterpret_cast<unsigned long long*>(ws + p.off_sval);
   int* spos = reinterpret_cast<int*>(ws + p.off_spos);
-  int2* nodes = reinterpret_cast<int2*>(ws + p.off_nodes);
+  int2* nodes = reinterpret_cast<int2*>(ST ? row + sp.off_nodes : ws + p.off_nodes);
 
-  if (tid == 0) {
+  if (ST && resume) {                                             // the row's members become set 0
+    asg_stream_copy(&mem[0], row + kAsgStreamHeaderBytes, sizeof(Members));
+    if constexpr (LM) asg_stream_copy(&lms[0], row + sp.off_lm, sizeof(LmMembers));
+  } else if (tid == 0) {
     mem[0].s[0] = 0.0; mem[0].key[0] = kKeyBasis; mem[0].last[0] = -1; mem[0].node[0] = 0; mem[0].len[0] = 0; mem[0].nw[0] = 0;
     if constexpr (LM) {
       LmMembers& L = lms[0];
@@ -187,8 +277,12 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   }
   for (int i = tid; i < kSlots; i += kThreads) { tab_key[i] = 0ull; tab_mem[i] = -1; }
   __syncthreads();
+  if constexpr (ST) {                                             // the table of the resumed members, as the step's last phase fills it
+    if (resume && tid < n_mem) table_insert(tab_key, tab_mem, mem[0].key[tid], tid);
+    __syncthreads();
+  }
 
-  int cur = 0, n_mem = 1;
+  int cur = 0;
   for (int t = 0; t < Tb && n_mem > 0; t++) {
     const Members& M = mem[cur];
     Members& N = mem[cur ^ 1];
@@ -292,7 +386,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
         if constexpr (LM) copy_lm(lms[cur ^ 1], r, lms[cur], m);
       } else {                                                    // a new sequence: member m's, and label c
         N.s[r] = ext_mass(p, M, xs, m, a, c);
-        const int node = 1 + t * W + r;
+        const int node = 1 + (ST ? f0 + t : t) * W + r;           // (the frame of the stream, not of the chunk)
         nodes[node] = make_int2(M.node[m], c);
         N.node[r] = node; N.len[r] = M.len[m] + 1;
         const bool nwd = new_word(p, a, c);
@@ -318,29 +412,44 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
           } else copy_lm(O, r, L, m);                             // a space copies the fields
         }
       }
-      // the new member's key enters the table (two members with one key, 2^-64: the second is not entered and never extended into)
-      for (unsigned h = (unsigned)((key * kHashMul) >> 55), probe = 0; probe < (unsigned)kSlots; probe++, h = (h + 1u) & (kSlots - 1)) {
-        const unsigned long long old = atomicCAS(&tab_key[h], 0ull, key);
-        if (old == 0ull) { tab_mem[h] = r; break; }
-        if (old == key) break;
-      }
+      table_insert(tab_key, tab_mem, key, r);
     }
     n_mem = ns; cur ^= 1;
     __syncthreads();
+  }
+
+  // ---- suspend, behind the chunk's last frame: the current set, then the header.  A chunk of no frames stores nothing ----
+  if constexpr (ST) {
+    if (Tb > 0) {
+      asg_stream_copy(row + kAsgStreamHeaderBytes, &mem[cur], sizeof(Members));
+      if constexpr (LM) asg_stream_copy(row + sp.off_lm, &lms[cur], sizeof(LmMembers));
+    }
+    if (tid == 0) {
+      if (Tb > 0) {
+        AsgStreamHeader h;
+        h.magic = kAsgStreamMagic; h.V = V; h.R = p.R; h.W = W; h.has_lm = LM ? 1 : 0; h.max_frames = sp.max_frames;
+        h.n = n_mem; h.frames = f0 + Tb; h.dead = n_mem == 0 ? 1 : 0;
+        *reinterpret_cast<AsgStreamHeader*>(row) = h;
+      }
+      sp.frames_done[b] = f0 + Tb;
+    }
+    if (p.nbest == 0) return;                                     // feed only
   }
 
   // ---- read-out: the first nbest members, ranked already ----
   const Members& F = mem[cur];
   const int nbest = p.nbest;
   const int64_t max_out = p.max_out;
+  const bool want_ts = ST ? p.timesteps != nullptr : TS;
+  const int max_hops = ST ? f0 + Tb : p.T;                        // a sequence has at most one node per frame consumed
   int64_t* out = p.out + (int64_t)b * nbest * max_out;
   int64_t* ts = nullptr;
-  if constexpr (TS) ts = p.timesteps + (int64_t)b * nbest * max_out;
+  if (want_ts) ts = p.timesteps + (int64_t)b * nbest * max_out;
   __syncthreads();
   if (tid < nbest) {
     int64_t* row = out + (int64_t)tid * max_out;
     int64_t* trow = nullptr;
-    if constexpr (TS) trow = ts + (int64_t)tid * max_out;
+    if (want_ts) trow = ts + (int64_t)tid * max_out;
     int len = 0, nw = 0, noov = 0;
     double ac = ninf(), lm = 0.0, tot = ninf();
     if (tid < n_mem) {
@@ -348,12 +457,13 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
       if constexpr (LM) { lm = lms[cur].lm[tid]; noov = lms[cur].oov[tid]; }
       tot = total_of(p, ac, lm, nw, noov);
       int at = len, node = F.node[tid];
-      for (int hops = 0; node > 0 && hops <= p.T; hops++) {
+      for (int hops = 0; node > 0 && hops <= max_hops; hops++) {
+        if constexpr (ST) { if (node > W * sp.max_frames) break; }  // (no node of this row's pool: the row is not this call's)
         const int2 nd = nodes[node];
         --at;
         if (at >= 0 && at < max_out) {
           row[at] = (int64_t)nd.y;
-          if constexpr (TS) trow[at] = (int64_t)((node - 1) / W);   // node = 1 + t * W + rank
+          if (want_ts) trow[at] = (int64_t)((node - 1) / W);        // node = 1 + t * W + rank
         }
         node = nd.x;
       }
@@ -368,7 +478,7 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgBeamParams p) {
   for (int j = 0; j < nbest; j++) {
     int64_t* row = out + (int64_t)j * max_out;
     for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kThreads) row[i] = 0;
-    if constexpr (TS) for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kThreads) ts[(int64_t)j * max_out + i] = -1;
+    if (want_ts) for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kThreads) ts[(int64_t)j * max_out + i] = -1;
   }
   if (tid == 0) p.n_hyp[b] = n_mem < nbest ? n_mem : nbest;
 }
@@ -396,6 +506,49 @@ bool layout(int T, int V, int W, Layout& L) {
   L.off_nodes = at; at += align_up(((size_t)W * ((size_t)T + 1) + 1) * 8, 256);
   L.per_utt = at;
   return true;
+}
+
+// a state row of a stream: header | Members | LmMembers (with a model) | node pool of max_frames frames, each 256-aligned
+struct StreamLayout { size_t off_lm, off_nodes, total; };
+bool stream_layout(int max_frames, int V, int W, bool lm, StreamLayout& S) {
+  Layout L;
+  if (max_frames < 1 || !layout(max_frames, V, W, L)) return false;
+  S.off_lm = kAsgStreamHeaderBytes + align_up(sizeof(Members), 256);
+  S.off_nodes = S.off_lm + (lm ? align_up(sizeof(LmMembers), 256) : 0);
+  S.total = S.off_nodes + align_up(((size_t)W * ((size_t)max_frames + 1) + 1) * 8, 256);
+  return true;
+}
+
+// the model's argument errors, the whole call's and the stream's: what the host sees without a HIP call ...
+int check_model(const e2e_lm* lm, int V, bool restricted) {
+  if (lm) {
+    if (lm->transcribed) {
+      set_error("the ASG search spells its words from the labels' strings: a model with custom transcriptions (e2e_lm_load_transcriptions) is not supported");
+      return E2E_ERR_UNSUPPORTED;
+    }
+    if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
+    if ((int)lm->label_off.size() - 1 != V) {
+      set_error("the language model was loaded with %d labels but the emissions have %d columns", (int)lm->label_off.size() - 1, V);
+      return E2E_ERR_ARG;
+    }
+  }
+  if (restricted && (!lm || !lm->has_lexicon)) {
+    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+    return E2E_ERR_ARG;
+  }
+  return E2E_OK;
+}
+// ... and the device its tables are on
+int check_model_device(const e2e_lm* lm) {
+  if (!lm) return E2E_OK;
+  if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
+  int cur = -1;
+  E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
+  if (cur != lm->device) {
+    set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, cur);
+    return E2E_ERR_ARG;
+  }
+  return E2E_OK;
 }
 
 }  // namespace
@@ -439,34 +592,12 @@ int e2e_asg_beam_nbest_opt(const void* x, int dtype, int64_t sB, int64_t sT, int
   if (nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
   Layout L;
   if (!layout(T, V, beam_width, L)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
-  if (lm) {
-    if (lm->transcribed) {
-      set_error("the ASG search spells its words from the labels' strings: a model with custom transcriptions (e2e_lm_load_transcriptions) is not supported");
-      return E2E_ERR_UNSUPPORTED;
-    }
-    if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_UNSUPPORTED; }
-    if ((int)lm->label_off.size() - 1 != V) {
-      set_error("the language model was loaded with %d labels but the emissions have %d columns", (int)lm->label_off.size() - 1, V);
-      return E2E_ERR_ARG;
-    }
-  }
-  if (restricted && (!lm || !lm->has_lexicon)) {
-    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
-    return E2E_ERR_ARG;
-  }
+  if (const int rc = check_model(lm, V, restricted)) return rc;
   if (B > 0 && (!x || !x_len || !out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
     set_error("null pointer argument"); return E2E_ERR_ARG;
   }
   if (B == 0) return E2E_OK;
-  if (lm) {
-    if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
-    int cur = -1;
-    E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
-    if (cur != lm->device) {
-      set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, cur);
-      return E2E_ERR_ARG;
-    }
-  }
+  if (const int rc = check_model_device(lm)) return rc;
   if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < L.head + (size_t)B * L.per_utt) {
     set_error("workspace too small: %zu bytes, e2e_asg_beam_workspace_bytes() = %zu", workspace_bytes, L.head + (size_t)B * L.per_utt + 256);
     return E2E_ERR_WORKSPACE;
@@ -502,6 +633,86 @@ int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t
   return e2e_asg_beam_nbest_opt(x, dtype, sB, sT, sV, transitions, x_len, B, T, V, num_replabels, beam_width, space_id, lm, lmwt,
                                 wip, oov_penalty, nbest, out, max_out, out_len, n_hyp, scores, counts, workspace,
                                 workspace_bytes, stream, nullptr);
+}
+
+size_t e2e_asg_beam_stream_row_bytes(int max_frames, int V, int beam_width, int with_lm) {
+  StreamLayout S;
+  return stream_layout(max_frames, V, beam_width, with_lm != 0, S) ? S.total : 0;
+}
+
+size_t e2e_asg_beam_stream_workspace_bytes(int B, int V, int beam_width, int with_lm) {
+  (void)with_lm;
+  Layout L;
+  if (B < 0 || !layout(1, V, beam_width, L)) return 0;
+  return L.head + (size_t)B * L.off_nodes + 256;                  // (the node pool lives in the row)
+}
+
+int e2e_asg_beam_stream(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                        const int64_t* chunk_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                        const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                        void* state, size_t row_bytes, int max_frames,
+                        int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                        int32_t* counts, int64_t* frames_done,
+                        void* workspace, size_t workspace_bytes, void* stream, const e2e_asg_beam_opts* opts) {
+  const bool restricted = opts && opts->restrict_to_lexicon != 0;
+  // every argument error the host can see, before any launch
+  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
+  if (B < 0 || T < 1 || V < 1 || (nbest > 0 && max_out < 0)) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
+  if (V > e2e_asg_max_labels()) { set_error("V=%d exceeds e2e_asg_max_labels() = %d", V, e2e_asg_max_labels()); return E2E_ERR_UNSUPPORTED; }
+  if (num_replabels < 0 || num_replabels >= V) { set_error("num_replabels=%d outside [0, V=%d)", num_replabels, V); return E2E_ERR_ARG; }
+  if (space_id >= V - num_replabels) { set_error("space_id=%d is not one of the %d characters", space_id, V - num_replabels); return E2E_ERR_ARG; }
+  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
+  if (beam_width > e2e_asg_beam_max_width(V)) {
+    set_error("beam_width %d exceeds e2e_asg_beam_max_width(V=%d) = %d", beam_width, V, e2e_asg_beam_max_width(V));
+    return E2E_ERR_UNSUPPORTED;
+  }
+  if (nbest < 0 || nbest > beam_width) { set_error("nbest=%d outside [0, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (max_frames < 1 || max_frames > (1 << 22)) { set_error("max_frames=%d outside [1, %d]", max_frames, 1 << 22); return E2E_ERR_ARG; }
+  StreamLayout S;
+  Layout L;
+  if (!stream_layout(max_frames, V, beam_width, lm != nullptr, S) || !layout(1, V, beam_width, L)) {
+    set_error("max_frames=%d frames are more than the search takes", max_frames); return E2E_ERR_UNSUPPORTED;
+  }
+  if (row_bytes < S.total || row_bytes % 8) {
+    set_error("row_bytes = %zu: a state row needs %zu bytes (e2e_asg_beam_stream_row_bytes) and a multiple of 8", row_bytes, S.total);
+    return E2E_ERR_ARG;
+  }
+  if (const int rc = check_model(lm, V, restricted)) return rc;
+  if (B > 0 && (!x || !chunk_len || !state || !frames_done)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  if (B > 0 && nbest > 0 && (!out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
+    set_error("null pointer argument"); return E2E_ERR_ARG;
+  }
+  if (B > 0 && reinterpret_cast<uintptr_t>(state) % 8) { set_error("the state must be 8-byte aligned"); return E2E_ERR_ARG; }
+  if (B == 0) return E2E_OK;
+  const size_t per_utt = L.off_nodes;
+  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < L.head + (size_t)B * per_utt) {
+    set_error("workspace too small: %zu bytes, e2e_asg_beam_stream_workspace_bytes() = %zu", workspace_bytes, L.head + (size_t)B * per_utt + 256);
+    return E2E_ERR_WORKSPACE;
+  }
+  if (const int rc = check_model_device(lm)) return rc;
+  AsgStreamParams sp;
+  AsgBeamParams& p = sp.b;
+  p.x = x; p.dtype = dtype; p.sB = sB; p.sT = sT; p.sV = sV; p.x_len = chunk_len;
+  p.B = B; p.T = T; p.V = V; p.R = num_replabels; p.W = beam_width; p.space_id = space_id < 0 ? -1 : space_id; p.nbest = nbest;
+  if (lm) p.lm = lm->dev_view(); else memset(&p.lm, 0, sizeof(p.lm));
+  p.lmwt = lm ? lmwt : 0.0; p.wip = wip; p.oov = oov_penalty;
+  p.out = out; p.max_out = nbest > 0 ? max_out : 0; p.out_len = out_len; p.n_hyp = n_hyp; p.scores = scores; p.counts = counts;
+  p.timesteps = nbest > 0 && opts ? opts->timesteps : nullptr;
+  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
+  p.At = reinterpret_cast<const double*>(base);
+  p.ws = base + L.head; p.per_utt = per_utt; p.off_sval = L.off_sval; p.off_spos = L.off_spos; p.off_nodes = 0;
+  sp.s.rows = reinterpret_cast<unsigned char*>(state); sp.s.row_bytes = row_bytes; sp.s.off_lm = S.off_lm; sp.s.off_nodes = S.off_nodes;
+  sp.s.max_frames = max_frames; sp.s.frames_done = frames_done;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(asg_beam_transpose_kernel, dim3((V * V + 255) / 256), dim3(256), 0, s, transitions, dtype, V,
+                     reinterpret_cast<double*>(base));
+  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_transpose_kernel launch");
+  auto kernel = asg_beam_kernel<false, false, false, true>;
+  if (restricted) kernel = asg_beam_kernel<true, true, false, true>;
+  else if (lm) kernel = asg_beam_kernel<true, false, false, true>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(kThreads), 0, s, sp);
+  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_kernel (stream) launch");
+  return E2E_OK;
 }
 
 }  // extern "C"

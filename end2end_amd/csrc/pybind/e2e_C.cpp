@@ -298,6 +298,35 @@ PYBIND11_MODULE(_C, m) {
         py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon") = false,
         py::arg("timesteps") = (uintptr_t)0);
 
+  m.def("asg_beam_stream_row_bytes", [](int max_frames, int V, int beam_width, bool with_lm) {
+    return e2e_asg_beam_stream_row_bytes(max_frames, V, beam_width, with_lm ? 1 : 0);
+  });
+  m.def("asg_beam_stream_workspace_bytes", [](int B, int V, int beam_width, bool with_lm) {
+    return e2e_asg_beam_stream_workspace_bytes(B, V, beam_width, with_lm ? 1 : 0);
+  });
+
+  m.def("asg_beam_stream",
+        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t chunk_len, int B,
+           int T, int V, int num_replabels, int beam_width, int space_id, uintptr_t lm, double lmwt, double wip,
+           double oov_penalty, uintptr_t state, size_t row_bytes, int max_frames, int nbest, uintptr_t out,
+           int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t frames_done,
+           uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon, uintptr_t timesteps) {
+          e2e_asg_beam_opts o{restrict_to_lexicon ? 1 : 0, ptr<int64_t>(timesteps)};
+          check(e2e_asg_beam_stream(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
+                                    ptr<const int64_t>(chunk_len), B, T, V, num_replabels, beam_width, space_id,
+                                    ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, ptr<void>(state), row_bytes, max_frames,
+                                    nbest, ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
+                                    ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(frames_done),
+                                    ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+        },
+        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
+        py::arg("chunk_len"), py::arg("B"), py::arg("T"), py::arg("V"), py::arg("num_replabels"), py::arg("beam_width"),
+        py::arg("space_id"), py::arg("lm"), py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"),
+        py::arg("row_bytes"), py::arg("max_frames"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
+        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("frames_done"),
+        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon") = false,
+        py::arg("timesteps") = (uintptr_t)0);
+
   m.def("ctc_scale_grads",
         [](uintptr_t grads, int dtype, uintptr_t scale, int B, int64_t row_elems, uintptr_t stream) {
           check(e2e_ctc_scale_grads(ptr<void>(grads), dtype, ptr<const void>(scale), B, row_elems, ptr<void>(stream)));

@@ -2,13 +2,15 @@
 through emissions and learned transitions (e2e_asg_viterbi), its repeats merged and its repeat labels expanded.
 After ``configure(beam_width > 1, ...)``: n-best prefix beam search with the transitions and, optionally, a word language model
 (e2e_asg_beam_nbest).  ``restrict_to_vocabulary()`` restricts that search to the language model's words or to a word list,
-``decode_nbest(..., timesteps=True)`` says at which frame each label entered the beam (e2e_asg_beam_nbest_opt).  The
+``decode_nbest(..., timesteps=True)`` says at which frame each label entered the beam (e2e_asg_beam_nbest_opt).
+``open_stream(transitions, batch_size, max_frames)`` is the same search fed in chunks, the beams kept on the GPU in between
+(e2e_asg_beam_stream): after every chunk the result of ``decode`` / ``decode_nbest`` on everything fed so far.  The
 definitions are in include/e2e_ctc.h; upstream has no ASG decoder; the return conventions are CTCDecoder's.
 
 With ``num_replabels=0`` (a ``CTCWithoutBlankLoss`` model) a word with a doubled letter cannot be spelled -- equal neighbours
 merge --, so a restricted search never produces it.
 
-Not provided for ASG: streaming, custom transcriptions, a lexicon together with a language model, widths or alphabets
+Not provided for ASG: custom transcriptions, a lexicon together with a language model, widths or alphabets
 above 128, -inf transitions.
 """
 import os
@@ -166,3 +168,59 @@ class ASGDecoder:
             raise CTCDecoderError("decode_nbest needs beam_width > 1: best-path decoding has no beam")
         emissions, logits_lengths = self._batch_major(emissions, logits_lengths)
         return NBestResults(*self._beam.decode_nbest(emissions, transitions, logits_lengths, nbest=nbest, timesteps=timesteps))
+
+    def open_stream(self, transitions, batch_size, max_frames, timesteps=False):
+        """Streaming beam search, after ``configure(beam_width > 1, ...)``: an ``ASGDecoderStream`` that is fed the emissions in
+        chunks and keeps the beams of ``batch_size`` utterances of up to ``max_frames`` frames on the GPU in between.  After
+        every chunk the result is that of ``decode`` / ``decode_nbest`` on everything fed so far; the decoder's settings,
+        a restriction set with ``restrict_to_vocabulary()`` included, apply as they do there.
+
+        :param transitions: the ``(V, V)`` transitions of every chunk, given once; ``None``: all zero
+        :param timesteps: ``feed_nbest`` also returns the frames of the labels, counted from the stream's start
+        """
+        if self._beam is None:
+            raise CTCDecoderError("a stream needs configure(beam_width > 1): best-path decoding has no beam to keep")
+        try:
+            return ASGDecoderStream(self, self._beam.open_stream(transitions, batch_size, max_frames, timesteps=timesteps))
+        except ValueError as e:
+            raise CTCDecoderError(str(e))
+
+
+class ASGDecoderStream:
+    """What ``ASGDecoder.open_stream`` returns: ``CTCDecoderStream``'s surface.  ``feed`` / ``feed_nbest`` take a chunk of
+    emissions shaped as ``decode`` takes them (``logits_lengths``: the frames of this chunk per utterance, all by default, 0
+    allowed) and return ``DecoderResults`` / ``NBestResults`` for everything fed so far; ``frames`` are the per-utterance
+    totals, ``state`` the (batch, row_bytes) uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts
+    utterances anew."""
+
+    def __init__(self, decoder, stream):
+        self._owner, self._stream = decoder, stream
+
+    @property
+    def frames(self):
+        return self._stream.frames
+
+    @property
+    def state(self):
+        return self._stream.state
+
+    @property
+    def row_bytes(self):
+        return self._stream.row_bytes
+
+    def reset(self, rows=None):
+        self._stream.reset(rows)
+
+    def _chunk(self, emissions, logits_lengths):
+        emissions, logits_lengths = self._owner._batch_major(emissions, logits_lengths)
+        self._stream.check_chunk(tuple(emissions.shape))          # (before any device work)
+        return emissions, logits_lengths
+
+    def feed(self, emissions, logits_lengths=None):
+        emissions, logits_lengths = self._chunk(emissions, logits_lengths)
+        return DecoderResults(*self._stream.feed(emissions, logits_lengths))
+
+    def feed_nbest(self, emissions, logits_lengths=None, nbest=None):
+        emissions, logits_lengths = self._chunk(emissions, logits_lengths)
+        r = self._stream.feed_nbest(emissions, logits_lengths, nbest=nbest)
+        return None if r is None else NBestResults(*r)

@@ -514,6 +514,10 @@ class ASGBeamEngine:
                                   self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
                                   n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream,
                                   self.restricted, ts.data_ptr() if ts is not None else 0)
+        return self._nbest_result(out, out_len, n_hyp, scores, counts, ts)
+
+    def _nbest_result(self, out, out_len, n_hyp, scores, counts, ts):
+        """What decode_nbest returns, from the buffers the read-out has filled (ts: None without timesteps)."""
         ids, sentences, width = _pack_nbest(out, out_len.tolist(), n_hyp.tolist(), self._strings, self.keep_on_device)
         r = (lambda t: t) if self.keep_on_device else (lambda t: t.cpu())
         if ts is not None:
@@ -525,6 +529,154 @@ class ASGBeamEngine:
     def decode(self, emissions, transitions, logits_lengths):
         """Hypothesis 0 of decode_nbest -> (ids (B,maxlen) int64, lengths (B), sentences)."""
         r = self.decode_nbest(emissions, transitions, logits_lengths, nbest=1)
+        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+
+    def open_stream(self, transitions, batch_size, max_frames, device=None, timesteps=False):
+        """Streaming beam search (e2e_asg_beam_stream, include/e2e_ctc.h): an ASGBeamStream that is fed emissions in chunks
+        and keeps the beams of `batch_size` utterances of up to `max_frames` frames on the GPU between the chunks.
+        `transitions` (None: all zero) are given once, here.  After every chunk the result is, bit for bit, that of
+        decode / decode_nbest on all the frames fed so far."""
+        return ASGBeamStream(self, transitions, batch_size, max_frames, device=device, timesteps=timesteps)
+
+
+class ASGBeamStream:
+    """The beams of `batch_size` utterances, kept on the GPU between chunks (ASGBeamEngine.open_stream): CTCBeamStream's
+    surface.  Owns the (batch_size, row_bytes) uint8 state tensor `state`: one self-contained row per utterance, allocated
+    at the first chunk (on `device`, else on the chunk's GPU, else on the current one).  Rows may be reordered or copied by
+    the caller; a row whose first 256 bytes are zero starts a new utterance.  The transitions are the stream's: converted to
+    a chunk's dtype on first use and kept."""
+
+    HEADER_BYTES = 256
+
+    def __init__(self, engine, transitions, batch_size, max_frames, device=None, timesteps=False):
+        if int(batch_size) < 1 or int(max_frames) < 1:
+            raise ValueError("batch_size and max_frames must be at least 1")
+        self.engine = engine
+        self.transitions = None if transitions is None else transitions.detach()
+        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
+        self.timesteps = bool(timesteps)
+        self.device = None if device is None else torch.device(device)
+        self.state = None
+        self.row_bytes = 0
+        self._frames = [0] * self.batch_size
+        self._A = {}                              # dtype -> the transitions on the stream's device
+
+    @property
+    def frames(self):
+        """Frames consumed so far, per utterance."""
+        return list(self._frames)
+
+    def check_chunk(self, shape):
+        """The chunk's shape (batch, frames, alphabet) against the stream: a ValueError before any device work."""
+        if len(shape) != 3:
+            raise ValueError("emissions must be (batch, time, alphabet)")
+        if shape[0] != self.batch_size:
+            raise ValueError("the chunk has %d utterances, the stream was opened for %d" % (shape[0], self.batch_size))
+        if not 1 <= shape[1] <= self.max_frames:
+            raise ValueError("a chunk of %d frames: the stream takes 1 .. max_frames = %d" % (shape[1], self.max_frames))
+
+    def reset(self, rows=None):
+        """Start the given utterances (all: None) anew: their headers are zeroed, nothing else is touched."""
+        idx = range(self.batch_size) if rows is None else [int(r) for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
+        for b in idx:
+            if not 0 <= b < self.batch_size:
+                raise ValueError("row %d outside the stream's %d utterances" % (b, self.batch_size))
+        if self.state is not None:
+            if rows is None:
+                self.state[:, : self.HEADER_BYTES].zero_()
+            else:
+                self.state[torch.as_tensor(list(idx), dtype=torch.long, device=self.state.device), : self.HEADER_BYTES] = 0
+        for b in idx:
+            self._frames[b] = 0
+
+    def _state_for(self, V, dev):
+        e = self.engine
+        if self.state is None:
+            self.row_bytes = _C.asg_beam_stream_row_bytes(self.max_frames, V, e.beam_width, e.lm is not None)
+            if not self.row_bytes:
+                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported" % (self.max_frames, e.beam_width))
+            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
+            self.state[:, : self.HEADER_BYTES].zero_()
+            self.device = dev
+        return self.state
+
+    def _transitions_for(self, V, dev, dtype):
+        if self.transitions is None:
+            return None
+        A = self._A.get(dtype)
+        if A is None:
+            A = self._A[dtype] = _asg_transitions(self.transitions, V, dev, dtype)
+        return A
+
+    def feed_nbest(self, emissions, lengths=None, nbest=None):
+        """Feed a chunk of emissions (batch, frames, alphabet) -- lengths: the frames of this chunk per utterance, 0 allowed,
+        all of them by default -- and read the beams out: what decode_nbest returns for everything fed so far (timesteps if
+        the stream was opened with them).  nbest=0 feeds only and returns None."""
+        e = self.engine
+        N = e.beam_width if nbest is None else int(nbest)
+        if not 0 <= N <= e.beam_width:
+            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
+        self.check_chunk(tuple(emissions.shape))
+        B, Tc, V = emissions.shape
+        e._bind(V)
+        if lengths is None:
+            lengths = torch.full((B,), Tc, dtype=torch.long)
+        if self.device is not None and emissions.device != self.device:
+            emissions = emissions.to(self.device)
+        dev = R.compute_device(emissions)
+        x = emissions.detach().to(dev)
+        if x.dtype not in _F32_F64:
+            x = x.to(torch.float32)
+        xl = _as_long(lengths, dev)
+        if xl.numel() != B:
+            raise ValueError("lengths must have one entry per utterance")
+        state = self._state_for(V, dev)
+        if dev != state.device:
+            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
+        A = self._transitions_for(V, dev, x.dtype)
+        max_out = max(self._frames) + Tc
+        frames_done = torch.empty(B, dtype=torch.long, device=dev)
+        out = out_len = n_hyp = scores = counts = ts = None
+        if N:
+            # (an utterance that has been fed no frame is not touched by the call: its slots are the empty ones from here)
+            out = torch.zeros((B, N, max_out), dtype=torch.long, device=dev)
+            out_len = torch.zeros((B, N), dtype=torch.long, device=dev)
+            n_hyp = torch.zeros(B, dtype=torch.long, device=dev)
+            scores = torch.full((B, N, 3), float("-inf"), dtype=torch.float64, device=dev)
+            scores[:, :, 2] = 0.0
+            counts = torch.zeros((B, N, 2), dtype=torch.int32, device=dev)
+            ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if self.timesteps else None
+        stream = R.stream_handle(dev)
+        with _on_device(dev):
+            lm = e.lm.on(dev).handle if e.lm is not None else 0
+            ws = R.workspace(dev, _C.asg_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None), stream)
+            sB, sT, sV = x.stride()
+            _C.asg_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
+                               xl.data_ptr(), B, Tc, V, e.num_replabels, e.beam_width, e.space_id, lm,
+                               e.lmwt, e.wip, e.oov_penalty, state.data_ptr(), self.row_bytes, self.max_frames, N,
+                               out.data_ptr() if N else 0, max_out, out_len.data_ptr() if N else 0,
+                               n_hyp.data_ptr() if N else 0, scores.data_ptr() if N else 0, counts.data_ptr() if N else 0,
+                               frames_done.data_ptr(), ws.data_ptr(), ws.numel(), stream,
+                               e.restricted, ts.data_ptr() if ts is not None else 0)
+        done = frames_done.tolist()
+        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
+        bad = None
+        for b, f in enumerate(done):
+            if f >= 0:
+                self._frames[b] = f
+            elif bad is None:
+                bad = (b, f)
+        if bad is not None:
+            why = {-2: "would pass max_frames=%d with this chunk" % self.max_frames,
+                   -3: "has a state row that was written under another configuration"}
+            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
+        if not N:
+            return None
+        return e._nbest_result(out, out_len, n_hyp, scores, counts, ts)
+
+    def feed(self, emissions, lengths=None):
+        """Feed a chunk and return what decode returns for everything fed so far: (ids, lengths, sentences)."""
+        r = self.feed_nbest(emissions, lengths, nbest=1)
         return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
 
 

@@ -412,7 +412,7 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
  * 128 for every supported V; T <= 2^22.  Beyond them E2E_ERR_UNSUPPORTED (the workspace query returns 0).  Every argument
  * error is found on the host before any launch.  Asynchronous on `stream`, allocates nothing, never synchronises,
  * capturable.  A restriction to the model's vocabulary and label timestamps: e2e_asg_beam_nbest_opt, below the lexicon
- * functions.  Not provided: streaming, custom transcriptions, a lexicon together with a language model, widths or alphabets
+ * functions; the same search fed in chunks: e2e_asg_beam_stream, below that.  Not provided: custom transcriptions, a lexicon together with a language model, widths or alphabets
  * above 128.
  */
 struct e2e_lm;   /* (e2e_lm_load_arpa, below) */
@@ -631,6 +631,72 @@ int e2e_asg_beam_nbest_opt(const void* x, int dtype, int64_t sB, int64_t sT, int
                            int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
                            int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
                            const e2e_asg_beam_opts* opts);
+
+/* ------------------------------------------------------------------------
+ * Streaming ASG beam search: e2e_asg_beam_nbest_opt fed in chunks, the beam kept on the device between the calls (additive,
+ * ABI 4: nothing above changes meaning).  The conventions are e2e_ctc_beam_stream's.
+ *
+ * An utterance's search lives in one STATE ROW of device memory that the caller owns.  Its parts, each rounded up to 256
+ * bytes: a 256-byte header (a magic value; the configuration V, num_replabels, beam_width, model or not, max_frames; the
+ * member count, the frames consumed, whether the beam is dead), the beam's current members (log mass, key, last label, node,
+ * length, word count: 4096 bytes), with a model their language-model fields (10240 bytes), and the pool of
+ * beam_width * (max_frames + 1) + 1 (parent, label) nodes of 8 bytes.  A call resumes every utterance from its row, runs
+ * chunk_len[b] further frames, stores the row and reads the current beam out.  What a frame rebuilds anyway is not stored:
+ * the members' key table is refilled from their keys at resume, the pair buffers are a frame's scratch.  A node's index,
+ * 1 + frame * beam_width + rank, counts the frames of the STREAM, so the timesteps need no storage.  The transitions are not
+ * part of the row: the caller passes them with every chunk.
+ *   - A row whose first 256 bytes are zero is a fresh utterance: hipMemsetAsync (or zeroing the header) opens or resets a
+ *     stream, no other call is needed.  The rest of a fresh row may hold anything.
+ *   - Rows are self-contained: indices, no addresses.  They may be moved, permuted, gathered or reordered between calls,
+ *     and a batch may mix fresh rows with rows of any age.
+ *   - The call is asynchronous on `stream`, allocates nothing, does not synchronise and is capturable.
+ *   - Every argument error the host can see is found before any launch, with e2e_asg_beam_nbest_opt's codes: the dtype,
+ *     sizes, the alphabet and width limits (E2E_ERR_UNSUPPORTED), num_replabels, space_id, nbest outside [0, beam_width],
+ *     max_frames outside [1, 2^22], row_bytes below the query or no multiple of 8, the language model's alphabet, order
+ *     and device (a model with transcriptions stays refused, E2E_ERR_UNSUPPORTED), restrict_to_lexicon without a lexicon,
+ *     null pointers, the workspace's size (E2E_ERR_WORKSPACE).
+ * CONTRACT.  After chunks whose lengths for utterance b sum to f_b >= 1 -- fed with the same transitions, beam_width, model,
+ * lmwt / wip / oov_penalty and options throughout -- every output of the read-out (out, out_len, n_hyp, scores, counts,
+ * opts->timesteps) equals, bit for bit, what e2e_asg_beam_nbest_opt writes for the concatenated frames with x_len[b] = f_b
+ * and the same nbest, max_out and options.  Timesteps are frames of the stream, not of the chunk.  A beam that died (no
+ * candidate with a number for a total: n_hyp = 0, lengths 0, totals -inf) stays dead over later chunks and reads out as the
+ * whole call does.  f_b = 0 (a fresh row fed no frames): n_hyp[b] = 0, frames_done[b] = 0 and nothing else of the
+ * utterance is written, as the whole call leaves an utterance alone whose length is outside [1,T].
+ *   x            (B,T,V) emissions of this chunk, strides sB,sT,sV, E2E_F32 or E2E_F64 (chunks may differ in dtype; the
+ *                transitions have the chunk's)
+ *   transitions  (V,V) contiguous, x's dtype, or NULL: all zero; the same values with every chunk
+ *   chunk_len    (B) int64, device: frames of this chunk per utterance, clamped to 0..T.  0 runs no frame and stores
+ *                nothing: the read-out repeats the utterance's last result
+ *   state        (B,row_bytes) device, 8-byte aligned; row_bytes >= e2e_asg_beam_stream_row_bytes(...), a multiple of 8
+ *   max_frames   the longest stream a row can hold, 1 .. 2^22; part of the row's configuration, checked at resume
+ *   nbest        0: feed only, no read-out: the outputs up to counts (and opts->timesteps) may be NULL and are not touched;
+ *                else 1 .. beam_width as in e2e_asg_beam_nbest
+ *   frames_done  (B) int64, device.  What only the device knows is reported here per utterance, and mirrored in n_hyp[b]
+ *                when nbest > 0:
+ *                  >= 0  frames consumed so far
+ *                  -2    this chunk would pass max_frames
+ *                  -3    the row was not written under this configuration
+ *                Both statuses are found before anything of the row is touched: they leave the whole row byte for byte and
+ *                write none of the utterance's other outputs, and the other utterances advance.  There is no -1: the pool
+ *                is sized exactly.
+ *   workspace    >= e2e_asg_beam_stream_workspace_bytes(...): 8 V^2 bytes for the transitions as f64, [from][to], and per
+ *                utterance 20 bytes per (member, label) pair.  It does not depend on the frames: the node pool is the row's
+ *   opts         NULL or e2e_asg_beam_opts as in e2e_asg_beam_nbest_opt; restrict_to_lexicon the same for every chunk,
+ *                timesteps NULL or (B,nbest,max_out) per call
+ * Row size: 256 + 4096 + (10240 with_lm) + 8 * (beam_width * (max_frames + 1) + 1) rounded up to 256; 0 for a width,
+ * alphabet or max_frames that is not supported.  beam_width 100, max_frames 30 000: 24 005 376 bytes (24 015 616 with a
+ * model) per utterance, whatever the alphabet: 24 MB, the node pool being all but 4 KB (14 KB) of it.
+ */
+size_t e2e_asg_beam_stream_row_bytes(int max_frames, int V, int beam_width, int with_lm);
+size_t e2e_asg_beam_stream_workspace_bytes(int B, int V, int beam_width, int with_lm);
+
+int e2e_asg_beam_stream(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                        const int64_t* chunk_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                        const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                        void* state, size_t row_bytes, int max_frames,
+                        int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                        int32_t* counts, int64_t* frames_done,
+                        void* workspace, size_t workspace_bytes, void* stream, const e2e_asg_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
  * Custom transcriptions: a pronunciation lexicon, homophones included (additive, ABI 4: nothing above changes meaning).

@@ -10,6 +10,9 @@ another namespace or another source).  Of each kernel two things are compared, l
     (.LBB<function>_<block>: the number is the function's place in its file) and every mangled symbol an instruction names
     replaced by its demangled, namespace-free form;
   * the .amdhsa_* descriptor block (registers, scratch, LDS, next_free_*), as it stands.
+  tools/diag/isa_compare.py A B 'REGEX=REPLACEMENT'   the same after renaming on both sides: for a kernel whose name changed
+      but whose code should not have (a template argument more, with a default: asg_beam.hip's ST,
+      'asg_beam_kernel<(\w+, \w+, \w+), false>\(.*?\)=asg_beam_kernel<\1>(AsgBeamParams)')
 One line per kernel, then the counts; the exit status is 0 only if every kernel is on both sides and identical.
 It compares two dumps with each other and nothing more."""
 import os
@@ -66,8 +69,22 @@ def kernels(path):
     return res
 
 
-def main(a, b):
-    A, B = kernels(a), kernels(b)
+def renamed(K, rule):
+    """K with the rule REGEX=REPLACEMENT applied to the kernels' names and to the names inside their instructions (the symbols
+    of a kernel's LDS variables carry its name)."""
+    if not rule:
+        return K
+    pat, repl = rule.split("=", 1)
+    res = {}
+    for k, (code, desc) in K.items():
+        name = re.sub(pat, repl, k)
+        assert name not in res, "the rule names two kernels %s" % name
+        res[name] = ([re.sub(pat, repl, ln) for ln in code], desc)
+    return res
+
+
+def main(a, b, rule=None):
+    A, B = renamed(kernels(a), rule), renamed(kernels(b), rule)
     same = 0
     for k in sorted(set(A) | set(B)):
         if k not in A or k not in B:
@@ -82,6 +99,6 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    if len(sys.argv) not in (3, 4):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(*sys.argv[1:]))
