@@ -111,6 +111,12 @@ def load():
         L.e2e_gram_ctc_beam_nbest.restype = C.c_int
         L.e2e_gram_ctc_beam_nbest.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
                                               C.c_int, C.c_int, i64p, i64, i64p, i64p, vp, vp, C.c_size_t, vp]
+        L.e2e_gram_beam_workspace_bytes_lm.restype = C.c_size_t
+        L.e2e_gram_beam_workspace_bytes_lm.argtypes = [C.c_int] * 6
+        L.e2e_gram_ctc_beam_nbest_lm.restype = C.c_int
+        L.e2e_gram_ctc_beam_nbest_lm.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
+                                                 C.c_int, i64p, i64, i64p, i64p, vp, vp, vp, C.c_size_t, vp]
         L.e2e_asg_beam_max_width.restype = C.c_int
         L.e2e_asg_beam_max_width.argtypes = [C.c_int]
         L.e2e_asg_beam_workspace_bytes.restype = C.c_size_t

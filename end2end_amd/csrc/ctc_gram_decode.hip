@@ -14,7 +14,20 @@
 // and the ranking are beam_cut.h's, the select on the bits of the totals (positive doubles order as integers), and the
 // survivors become the next members in the order of their ranks.  The table is cleared entry by entry from the frame's
 // candidate list.  The read-out walks the (parent node, column) pool backwards and expands the grams.
+//
+// With a word language model (e2e_gram_ctc_beam_nbest_lm, the LM instance): a member also carries the LM fields of
+// asg_beam.hip's members, in LDS beside the slots.  They are functions of the base-id sequence alone, so a candidate may take
+// them from any pair that spells it: walk_gram applies get_next_prefix's rule to the gram's ids one at a time and asks the
+// model only where the answer can matter (a word's last id inside the gram, the gram's last id).  The model is not asked
+// per pair and frame: when a prefix becomes a member the answers of its V children (lm_score, num_words, num_oov) are
+// computed once and kept in a row of the workspace for as long as the prefix stays in the beam (2 W rows, a member keeps its
+// row's index).  The cut then runs on okey(log tot + lmwt lm - wip words + oov_penalty oovs) as the ASG
+// kernel's does.  The no-LM instance is the kernel as it was, instruction for instruction (tools/diag/isa_compare.py).
+#include <cstring>
+#include <type_traits>
+
 #include "beam_cut.h"
+#include "ctc_lm.h"
 
 namespace e2e {
 
@@ -143,12 +156,135 @@ __device__ __forceinline__ double eval_total(const Eval& E, int K) {
   return t;
 }
 
-__global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams p) {
+// ---- the language model's part (the LM instance only) ---------------------------------------------------------------
+constexpr unsigned long long kNoCand = 0ull;   // okey() of nothing: below every number's key (okey(-inf) = 0x000f...f)
+__device__ __forceinline__ double okey_inv(unsigned long long k) {
+  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
+}
+
+// the LM fields of a member: asg_beam.hip's LmMembers, and with them the number of words, the last base id (-1: the empty
+// prefix) and the row of the answer cache that holds the member's children
+struct LmMembers {
+  unsigned long long hash[kMaxW];        // running FNV hash of the last word's spelling
+  double lm[kMaxW], lmb[kMaxW];          // lm_score, lm_before
+  int oov[kMaxW], oovb[kMaxW];
+  unsigned st[kCtx][kMaxW], stb[kCtx][kMaxW];   // LM context after / before the last word, most recent first
+  int stn[kMaxW], stbn[kMaxW];
+  int nw[kMaxW], last[kMaxW], row[kMaxW];
+};
+// the LM instance's LDS: both member sets' fields and the frame's row bookkeeping (rows < 2 * kMaxW = 256, ranks < kMaxW)
+struct LmState {
+  LmMembers lms[2];
+  unsigned char used[2 * kMaxW];         // the row belongs to a member that stays
+  unsigned char free_list[2 * kMaxW];
+  unsigned char new_list[kMaxW];         // the ranks of the frame's new members
+  int n_stay, n_new, n_free;
+};
+struct Answer { double lm; int nw, oov; };                       // what the cut needs of a child: 16 bytes per (row, column)
+
+struct GramLmParams {
+  GramBeamParams b;
+  LmView lm; int has_lm, space_id, R; double lmwt, wip, oov;    // R: the base labels, the model's label strings
+  int32_t* counts; size_t off_cache;
+};
+template <bool LM> using GramKernelParams = typename std::conditional<LM, GramLmParams, GramBeamParams>::type;
+__device__ __forceinline__ const GramBeamParams& beam_of(const GramBeamParams& q) { return q; }
+__device__ __forceinline__ const GramBeamParams& beam_of(const GramLmParams& q) { return q.b; }
+
+// the fields of one sequence, in registers
+struct LmWalk {
+  unsigned long long hash; double lm, lmb; int oov, oovb, nw, last, stn, stbn;
+  unsigned st[kCtx], stb[kCtx];
+};
+__device__ __forceinline__ LmWalk load_walk(const LmMembers& L, int m) {
+  LmWalk w;
+  w.hash = L.hash[m]; w.lm = L.lm[m]; w.lmb = L.lmb[m]; w.oov = L.oov[m]; w.oovb = L.oovb[m];
+  w.nw = L.nw[m]; w.last = L.last[m]; w.stn = L.stn[m]; w.stbn = L.stbn[m];
+#pragma unroll
+  for (int i = 0; i < kCtx; i++) { w.st[i] = L.st[i][m]; w.stb[i] = L.stb[i][m]; }
+  return w;
+}
+__device__ __forceinline__ void store_walk(LmMembers& O, int r, const LmWalk& w) {
+  O.hash[r] = w.hash; O.lm[r] = w.lm; O.lmb[r] = w.lmb; O.oov[r] = w.oov; O.oovb[r] = w.oovb;
+  O.nw[r] = w.nw; O.last[r] = w.last; O.stn[r] = w.stn; O.stbn[r] = w.stbn;
+#pragma unroll
+  for (int i = 0; i < kCtx; i++) { O.st[i][r] = w.st[i]; O.stb[i][r] = w.stb[i]; }
+}
+__device__ __forceinline__ LmWalk root_walk(const GramLmParams& q) {
+  LmWalk w;
+  w.hash = kFnvInit; w.lm = 0.0; w.lmb = 0.0; w.oov = 0; w.oovb = 0; w.nw = 0; w.last = -1;
+#pragma unroll
+  for (int i = 0; i < kCtx; i++) { w.st[i] = 0u; w.stb[i] = 0u; }
+  w.st[0] = q.has_lm ? q.lm.bos : 0u; w.stb[0] = w.st[0]; w.stn = 1; w.stbn = 1;
+  return w;
+}
+__device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned long long h, int c) {
+  for (int bi = lm.label_off[c]; bi < lm.label_off[c + 1]; bi++) {
+    unsigned char ch = lm.label_bytes[bi];
+    if (lm.fold_case && ch >= 'A' && ch <= 'Z') ch += 32;
+    h = fnv_step(h, ch);
+  }
+  return h;
+}
+// w: the fields of a sequence -> those of the sequence extended by column c's k base ids: get_next_prefix's LM part
+// (asg_beam.hip's child_lm and what follows it there) applied id by id.  The model is asked where a word ends inside the
+// gram and at the gram's last id; the answers in between would be overwritten (each is lm_before + one score, state_before
+// + one word), so leaving them out changes no bit.  Without a model only the words are counted.
+__device__ __forceinline__ void walk_gram(const GramLmParams& q, LmWalk& w, int c, int k) {
+  const int32_t* ids = q.b.gram_ids + c * kMaxK;
+  int id = ids[0];
+  for (int j = 0; j < k; j++) {
+    const int nxt = j + 1 < k ? ids[j + 1] : -1;
+    if (id != q.space_id) {                                       // (a space copies the fields)
+      if (w.last < 0 || w.last == q.space_id) {                   // the id begins a word
+        w.nw++;
+        w.lmb = w.lm; w.oovb = w.oov; w.stbn = w.stn; w.hash = kFnvInit;
+#pragma unroll
+        for (int i = 0; i < kCtx; i++) w.stb[i] = w.st[i];
+      }
+      if (q.has_lm) {
+        if ((unsigned)id < (unsigned)q.R) w.hash = spell(q.lm, w.hash, id);   // (the host cannot see the table: no id spells outside the strings)
+        if (j + 1 == k || nxt == q.space_id) {
+          const uint32_t wi = lm_word_lookup(q.lm, w.hash);
+          const float sc = lm_base_score(q.lm, w.stb, w.stbn, wi, nullptr, nullptr);
+          w.lm = w.lmb + (double)sc / 2.302585092994045684;       // quirk Q8: divides by ln 10
+          w.oov = w.oovb + (wi == 0 ? 1 : 0);
+          int bn = w.stbn; if (bn > q.lm.order - 1) bn = q.lm.order - 1;
+          int sn = bn + 1; if (sn > q.lm.order - 1) sn = q.lm.order - 1;
+#pragma unroll
+          for (int i = kCtx - 1; i >= 1; i--) w.st[i] = i < sn ? w.stb[i - 1] : 0u;
+          w.st[0] = sn > 0 ? wi : 0u;
+          w.stn = sn;
+        }
+      }
+    }
+    w.last = id;
+    id = nxt;
+  }
+}
+// total = log tot + lmwt * lm_score - wip * num_words + oov_penalty * num_oov, in this order
+__device__ __forceinline__ double total_of(const GramLmParams& q, double ac, double lm, int nw, int noov) {
+  return ac + lm * q.lmwt - (double)nw * q.wip + (double)noov * q.oov;
+}
+
+// LM = false: the search on the masses alone (e2e_gram_ctc_beam_nbest), the parameter block GramBeamParams.  LM = true: the
+// cut and the ranking on the totals with the language model's fields (e2e_gram_ctc_beam_nbest_lm).
+template <bool LM>
+__global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParams<LM> q) {
+  const GramBeamParams& p = beam_of(q);
   __shared__ Members mem[2];
   __shared__ BeamCut cut;
   __shared__ int n_cand, n_surv, overflow;
   __shared__ unsigned long long sh_floor;
   __shared__ double sh_best;
+  LmState* S = nullptr;
+  Answer* cache = nullptr;                                       // [row][column], rows < 2 W
+  if constexpr (LM) {
+    __shared__ LmState lm_state;
+    S = &lm_state;
+    cache = reinterpret_cast<Answer*>(p.ws + (size_t)blockIdx.x * p.per_utt + q.off_cache);
+  }
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int V = p.V, K = p.K, W = p.W;
@@ -167,13 +303,23 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
   const int Tb = Tq < 0 ? 0 : (Tq > p.T ? p.T : (int)Tq);
 
   for (unsigned i = tid; i < H; i += kBeamThreads) { table[i].key = 0ull; table[i].head = -1; }
+  if constexpr (LM) { if (tid < kMaxW) { S->lms[0].row[tid] = 0; S->lms[1].row[tid] = 0; } }   // (never a row outside the cache)
   if (tid == 0) {
     for (int k = 0; k <= kMaxK; k++) { mem[0].p[k][0] = k == 0 ? 1.0 : 0.0; mem[0].col[k][0] = 0; }
     mem[0].key[0] = kKeyBasis; mem[0].tot[0] = 1.0; mem[0].node[0] = 0; mem[0].len[0] = 0;
     nodes[0] = make_int2(-1, 0);
     overflow = 0;
+    if constexpr (LM) { store_walk(S->lms[0], 0, root_walk(q)); S->lms[0].row[0] = 0; }
   }
   __syncthreads();
+  if constexpr (LM) {                                            // the root's children, into row 0
+    if (q.has_lm && Tb > 0)
+      for (int c = 1 + tid; c < V; c += kBeamThreads) {
+        LmWalk w = load_walk(S->lms[0], 0);
+        walk_gram(q, w, c, order_of(p.gram_len, c, K));
+        cache[c] = Answer{w.lm, w.nw, w.oov};
+      }
+  }
 
   int cur = 0, n_mem = 1;
   long long esum = 0;                                           // exponents taken out of the frames so far
@@ -191,6 +337,10 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
       }
     }
     if (tid == 0) { n_cand = 0; n_surv = 0; cut.n_sel = 0; sh_floor = ~0ull; }
+    if constexpr (LM) {
+      if (tid < 2 * kMaxW) S->used[tid] = 0;
+      if (tid == 0) { S->n_stay = 0; S->n_new = 0; S->n_free = 0; }
+    }
     __syncthreads();
     // ---- members and (member, column) pairs meet at their prefix's key ----
     const unsigned n_now = (unsigned)n_mem * (unsigned)V;
@@ -225,25 +375,63 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
       Eval E;
       eval_list(E, M, head, next, y, p.gram_len, (unsigned)V, K, n_ids);
       const double tot = eval_total(E, K);
-      ctot[pos] = tot;
-      if (E.stay >= 0) atomicMin(&sh_floor, tot > 0.0 ? (unsigned long long)__double_as_longlong(tot) : 0ull);
+      if constexpr (LM) {
+        // the order key of the total; the fields are the member's own where the prefix stays, else its smallest pair's
+        // (a model's answers from the parent's row, the words alone counted on the spot)
+        const LmMembers& L = S->lms[cur];
+        unsigned long long cand = kNoCand;
+        if (tot > 0.0) {
+          Answer a;
+          if (E.stay >= 0) a = Answer{L.lm[E.stay], L.nw[E.stay], L.oov[E.stay]};
+          else {
+            const unsigned pid = (unsigned)E.pair < n_ids ? (unsigned)E.pair : 0u;
+            const unsigned pm = pid / (unsigned)V, pc = pid - pm * (unsigned)V;
+            if (q.has_lm) a = cache[(size_t)L.row[pm] * V + pc];
+            else {
+              LmWalk w = load_walk(L, (int)pm);
+              walk_gram(q, w, (int)pc, order_of(p.gram_len, (int)pc, K));
+              a = Answer{0.0, w.nw, 0};
+            }
+          }
+          const double total = total_of(q, log(tot), a.lm, a.nw, a.oov);
+          if (total > ninf()) {                                   // (false for NaN as well)
+            cand = okey(total);
+            if (E.stay >= 0) { atomicMin(&sh_floor, cand); atomicAdd(&S->n_stay, 1); }
+          }
+        }
+        reinterpret_cast<unsigned long long*>(ctot)[pos] = cand;
+      } else {
+        ctot[pos] = tot;
+        if (E.stay >= 0) atomicMin(&sh_floor, tot > 0.0 ? (unsigned long long)__double_as_longlong(tot) : 0ull);
+      }
     }
     __syncthreads();
     // ---- an exact filter: a full beam's members are W candidates themselves, so nothing below the least of them can
     //      make the cut; what is left (usually a few times W) is what the selection reads ----
-    const unsigned long long floor_bits = n_mem == W ? sh_floor : 0ull;
-    for (int pos = tid; pos < nc; pos += kBeamThreads) {
-      const double tot = ctot[pos];
-      const unsigned long long v = (unsigned long long)__double_as_longlong(tot);
-      if (!(tot > 0.0) || v < floor_bits) continue;              // (NaN totals, from NaN inputs, are no members either)
-      const int j = atomicAdd(&n_surv, 1);
-      sval[j] = v; spos[j] = pos;
+    if constexpr (LM) {                                          // (on the totals' order keys: the members that ARE candidates)
+      const unsigned long long floor_bits = S->n_stay == W ? sh_floor : 1ull;
+      for (int pos = tid; pos < nc; pos += kBeamThreads) {
+        const unsigned long long v = reinterpret_cast<const unsigned long long*>(ctot)[pos];
+        if (v < floor_bits) continue;                            // (kNoCand = 0 is below both)
+        const int j = atomicAdd(&n_surv, 1);
+        sval[j] = v; spos[j] = pos;
+      }
+    } else {
+      const unsigned long long floor_bits = n_mem == W ? sh_floor : 0ull;
+      for (int pos = tid; pos < nc; pos += kBeamThreads) {
+        const double tot = ctot[pos];
+        const unsigned long long v = (unsigned long long)__double_as_longlong(tot);
+        if (!(tot > 0.0) || v < floor_bits) continue;            // (NaN totals, from NaN inputs, are no members either)
+        const int j = atomicAdd(&n_surv, 1);
+        sval[j] = v; spos[j] = pos;
+      }
     }
     __syncthreads();
     // ---- the cut: the W largest totals, exactly equal ones by ascending key ----
-    beam_cut<kBeamThreads>(cut, sval, spos, n_surv, W,
-        [&](int pos) { return __hip_atomic_load(&table[list[pos]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        [](unsigned long long v) { return __longlong_as_double((long long)v); });
+    const auto key_at = [&](int pos) { return __hip_atomic_load(&table[list[pos]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    if constexpr (LM) beam_cut<kBeamThreads>(cut, sval, spos, n_surv, W, key_at, okey_inv);
+    else beam_cut<kBeamThreads>(cut, sval, spos, n_surv, W, key_at,
+                                [](unsigned long long v) { return __longlong_as_double((long long)v); });
     __syncthreads();
     const int ns = beam_cut_count(cut, W);
     if (ns == 0) {                                               // every path has probability 0: no hypothesis is left
@@ -254,7 +442,16 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
     }
     // ---- rank the survivors: they become the members in that order ----
     beam_cut_rank(cut, ns);
-    if (tid < ns && cut.sel_rank[tid] == 0) sh_best = cut.sel_tot[tid];
+    if constexpr (LM) {                                          // (sel_tot is the total: the rescale wants the best's mass)
+      if (tid < ns && cut.sel_rank[tid] == 0) {
+        const int head = __hip_atomic_load(&table[list[cut.sel_pos[tid]]].head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        Eval E;
+        eval_list(E, M, head, next, y, p.gram_len, (unsigned)V, K, n_ids);
+        sh_best = eval_total(E, K);
+      }
+    } else {
+      if (tid < ns && cut.sel_rank[tid] == 0) sh_best = cut.sel_tot[tid];
+    }
     __syncthreads();
     int ex = 0;
     (void)frexp(sh_best, &ex);                                   // best = f * 2^ex, f in [0.5, 1)
@@ -271,18 +468,51 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
         if (k <= K) tot += pk;
       }
       N.tot[r] = tot; N.key[r] = cut.sel_key[tid];
-      if (E.stay >= 0) { N.node[r] = M.node[E.stay]; N.len[r] = M.len[E.stay]; }
-      else {
+      if (E.stay >= 0) {
+        N.node[r] = M.node[E.stay]; N.len[r] = M.len[E.stay];
+        if constexpr (LM) {                                      // the fields and the row of answers stay the member's
+          const LmMembers& L = S->lms[cur];
+          store_walk(S->lms[cur ^ 1], r, load_walk(L, E.stay));
+          S->lms[cur ^ 1].row[r] = L.row[E.stay];
+          S->used[L.row[E.stay]] = 1;
+        }
+      } else {
         const unsigned pid = (unsigned)E.pair < n_ids ? (unsigned)E.pair : 0u;
         const unsigned pm = pid / (unsigned)V, pc = pid - pm * (unsigned)V;
         const int node = 1 + t * W + r;
         nodes[node] = make_int2(M.node[pm], (int)pc);
         N.node[r] = node; N.len[r] = M.len[pm] + order_of(p.gram_len, (int)pc, K);
+        if constexpr (LM) {                                      // a new prefix: its parent's fields walked through the gram
+          LmWalk w = load_walk(S->lms[cur], (int)pm);
+          walk_gram(q, w, (int)pc, order_of(p.gram_len, (int)pc, K));
+          store_walk(S->lms[cur ^ 1], r, w);
+          S->new_list[atomicAdd(&S->n_new, 1)] = (unsigned char)r;
+        }
       }
     }
     __syncthreads();                                             // (the lists above are read to the end before they go)
     // ---- free the frame's entries ----
     for (int pos = tid; pos < nc; pos += kBeamThreads) { Entry& en = table[list[pos]]; en.key = 0ull; en.head = -1; }
+    if constexpr (LM) {
+      // ---- the new members take the rows that no staying member holds (at least W of the 2 W), and the answers of their
+      //      children are computed once: lm_score, num_words, num_oov of (member, column), read by the cuts to come ----
+      LmMembers& O = S->lms[cur ^ 1];
+      if (q.has_lm) {
+        if (tid < 2 * W && !S->used[tid]) S->free_list[atomicAdd(&S->n_free, 1)] = (unsigned char)tid;
+        __syncthreads();
+        const int n_new = S->n_new;
+        if (tid < n_new) O.row[S->new_list[tid]] = S->free_list[tid];
+        __syncthreads();
+        for (int i = tid; i < n_new * V; i += kBeamThreads) {
+          const int j = i / V, c = i - j * V;
+          if (c == 0) continue;
+          const int r = S->new_list[j];
+          LmWalk w = load_walk(O, r);
+          walk_gram(q, w, c, order_of(p.gram_len, c, K));
+          cache[(size_t)O.row[r] * V + c] = Answer{w.lm, w.nw, w.oov};
+        }
+      }
+    }
     esum += ex; n_mem = ns; cur ^= 1;
     __syncthreads();
   }
@@ -308,7 +538,19 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
     }
     cut.sel_pos[tid] = len;
     p.out_len[(int64_t)b * nbest + tid] = len;
-    p.scores[(int64_t)b * nbest + tid] = score;
+    if constexpr (LM) {                                          // scores: total, ac, lm_score; counts: words, OOVs
+      const int64_t o = (int64_t)b * nbest + tid;
+      double lm = 0.0, tot = score; int nw = 0, noov = 0;
+      if (tid < n_mem) {
+        const LmMembers& L = S->lms[cur];
+        lm = L.lm[tid]; nw = L.nw[tid]; noov = L.oov[tid];
+        tot = total_of(q, score, lm, nw, noov);
+      }
+      p.scores[o * 3 + 0] = tot; p.scores[o * 3 + 1] = score; p.scores[o * 3 + 2] = lm;
+      q.counts[o * 2 + 0] = nw; q.counts[o * 2 + 1] = noov;
+    } else {
+      p.scores[(int64_t)b * nbest + tid] = score;
+    }
   }
   __syncthreads();
   for (int j = 0; j < nbest; j++) {
@@ -318,9 +560,10 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramBeamParams 
   if (tid == 0) p.n_hyp[b] = overflow ? -1 : (n_mem < nbest ? n_mem : nbest);
 }
 
-struct BeamLayout { size_t per_utt, off_table, off_next, off_list, off_tot, off_sval, off_spos, off_nodes; int logH; };
+struct BeamLayout { size_t per_utt, off_table, off_next, off_list, off_tot, off_sval, off_spos, off_nodes, off_cache; int logH; };
 
-bool beam_layout(int T, int V, int K, int W, BeamLayout& L) {
+// with_lm: behind the nodes the children's answers of 2 W prefixes, 16 bytes per (row, column)
+bool beam_layout(int T, int V, int K, int W, BeamLayout& L, bool with_lm = false) {
   if (T < 1 || V < 1 || K < 1 || K > kMaxK || W < 1 || W > kMaxW || (int64_t)W * V > kMaxPairs || T > (1 << 22)) return false;
   const size_t ids = (size_t)W * V;
   int logH = 6;
@@ -333,8 +576,24 @@ bool beam_layout(int T, int V, int K, int W, BeamLayout& L) {
   L.off_sval = at; at += align_up(ids * 8, 256);
   L.off_spos = at; at += align_up(ids * 4, 256);
   L.off_nodes = at; at += align_up(((size_t)W * ((size_t)T + 1) + 1) * 8, 256);
+  L.off_cache = at; if (with_lm) at += align_up(2 * ids * sizeof(Answer), 256);
   L.per_utt = at; L.logH = logH;
   return true;
+}
+
+// every argument error of the two n-best calls that the host can see, before any launch
+int check_beam_args(int dtype, int B, int T, int V, int max_order, int beam_width, int nbest, int64_t max_out) {
+  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
+  if (B < 0 || T < 1 || V < 1 || max_out < 0) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
+  if (max_order < 1 || max_order > kMaxK) { set_error("max_order %d is not in [1, %d]", max_order, kMaxK); return E2E_ERR_ARG; }
+  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
+  if (beam_width > e2e_gram_beam_max_width(V, max_order)) {
+    set_error("beam_width %d exceeds e2e_gram_beam_max_width(V=%d, max_order=%d) = %d", beam_width, V, max_order,
+              e2e_gram_beam_max_width(V, max_order));
+    return E2E_ERR_UNSUPPORTED;
+  }
+  if (nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  return E2E_OK;
 }
 
 }  // namespace
@@ -377,16 +636,7 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
                             int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
                             int beam_width, int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
                             double* scores, void* workspace, size_t workspace_bytes, void* stream) {
-  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
-  if (B < 0 || T < 1 || V < 1 || max_out < 0) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
-  if (max_order < 1 || max_order > kMaxK) { set_error("max_order %d is not in [1, %d]", max_order, kMaxK); return E2E_ERR_ARG; }
-  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
-  if (beam_width > e2e_gram_beam_max_width(V, max_order)) {
-    set_error("beam_width %d exceeds e2e_gram_beam_max_width(V=%d, max_order=%d) = %d", beam_width, V, max_order,
-              e2e_gram_beam_max_width(V, max_order));
-    return E2E_ERR_UNSUPPORTED;
-  }
-  if (nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (const int rc = check_beam_args(dtype, B, T, V, max_order, beam_width, nbest, max_out)) return rc;
   BeamLayout L;
   if (!beam_layout(T, V, max_order, beam_width, L)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
   if (B > 0 && (!lp || !x_len || !gram_ids || !gram_len || !out_len || !n_hyp || !scores || (max_out > 0 && !out))) {
@@ -400,8 +650,68 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
   GramBeamParams p{lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
                    out, max_out, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
                    L.per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, L.off_nodes, L.logH};
-  hipLaunchKernelGGL(gram_beam_kernel, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(gram_beam_kernel<false>, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, p);
   E2E_HIP_CHECK(hipGetLastError(), "gram_beam_kernel launch");
+  return E2E_OK;
+}
+
+size_t e2e_gram_beam_workspace_bytes_lm(int B, int T, int V, int max_order, int beam_width, int with_lm) {
+  BeamLayout L;
+  if (B < 0 || !beam_layout(T, V, max_order, beam_width, L, with_lm != 0)) return 0;
+  return (size_t)B * L.per_utt + 256;
+}
+
+int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                               int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                               int num_base_labels, int beam_width, int space_id, const e2e_lm* lm, double lmwt,
+                               double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
+                               int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  if (const int rc = check_beam_args(dtype, B, T, V, max_order, beam_width, nbest, max_out)) return rc;
+  if (num_base_labels < 1 || num_base_labels > V) { set_error("num_base_labels=%d outside [1, V=%d]", num_base_labels, V); return E2E_ERR_ARG; }
+  if (space_id >= num_base_labels) { set_error("space_id=%d is not one of the %d base labels", space_id, num_base_labels); return E2E_ERR_ARG; }
+  if (lm) {
+    if (lm->transcribed || lm->words_only) {
+      set_error("the Gram-CTC search spells its words from the base labels' strings and has no restricted search: a model with "
+                "custom transcriptions (e2e_lm_load_transcriptions) or a word list (e2e_lm_load_words) is not supported");
+      return E2E_ERR_ARG;
+    }
+    if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_ARG; }
+    if ((int)lm->label_off.size() - 1 != num_base_labels) {
+      set_error("the language model was loaded with %d labels but the table has num_base_labels=%d",
+                (int)lm->label_off.size() - 1, num_base_labels);
+      return E2E_ERR_ARG;
+    }
+  }
+  BeamLayout L;
+  if (!beam_layout(T, V, max_order, beam_width, L, lm != nullptr)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
+  if (B > 0 && (!lp || !x_len || !gram_ids || !gram_len || !out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
+    set_error("null pointer argument"); return E2E_ERR_ARG;
+  }
+  if (B == 0) return E2E_OK;
+  if (lm) {
+    if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
+    int dev = -1;
+    E2E_HIP_CHECK(hipGetDevice(&dev), "hipGetDevice");
+    if (dev != lm->device) {
+      set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, dev);
+      return E2E_ERR_ARG;
+    }
+  }
+  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < (size_t)B * L.per_utt) {
+    set_error("workspace too small: %zu bytes, e2e_gram_beam_workspace_bytes_lm() = %zu", workspace_bytes, (size_t)B * L.per_utt + 256);
+    return E2E_ERR_WORKSPACE;
+  }
+  GramLmParams q;
+  q.b = GramBeamParams{lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
+                       out, max_out, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
+                       L.per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, L.off_nodes, L.logH};
+  if (lm) q.lm = lm->dev_view(); else memset(&q.lm, 0, sizeof(q.lm));
+  q.has_lm = lm ? 1 : 0; q.space_id = space_id < 0 ? -1 : space_id; q.R = num_base_labels;
+  q.lmwt = lm ? lmwt : 0.0; q.wip = wip; q.oov = oov_penalty;
+  q.counts = counts; q.off_cache = L.off_cache;
+  hipLaunchKernelGGL(gram_beam_kernel<true>, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, q);
+  E2E_HIP_CHECK(hipGetLastError(), "gram_beam_kernel (LM) launch");
   return E2E_OK;
 }
 

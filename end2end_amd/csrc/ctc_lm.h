@@ -175,6 +175,7 @@ struct e2e_lm {
   // the lexicon (e2e_lm_enable_lexicon): folded spelling -> bit 0 a word, bit 1 a proper prefix of a longer word.  Once it is
   // built, the vocabulary tables above also hold the prefixes that are no words, with id 0.
   bool has_lexicon = false;
+  bool words_only = false;                               // e2e_lm_load_words: the model that scores nothing
   std::unordered_map<std::string, unsigned char> lex_class;
   int device = -1;                                       // HIP device that holds the tables (-1: host only)
   std::vector<std::string> words;                        // id -> word as the model lists it (e2e_lm_word_string)

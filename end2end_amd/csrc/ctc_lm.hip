@@ -338,6 +338,7 @@ extern "C" int e2e_lm_load_words(const char* const* words_in, int n_words, const
   e2e_lm* lm = new e2e_lm();
   lm->fold_case = case_sensitive ? 0 : 1;
   lm->order = 1;
+  lm->words_only = true;
   std::vector<std::string> words;
   std::vector<Entry> entries;
   auto add = [&](const std::string& w) {

@@ -1,16 +1,20 @@
 """GramCTCDecoder: greedy and prefix beam-search decoding for models trained with GramCTCLoss.  The constructor takes the
 loss's table (``num_base_labels, total_labels, label2ids``) and CTCDecoder's decoding arguments; the return conventions are
 CTCDecoder's.  Upstream has no such decoder (its Gram-CTC engine is empty); the definition is in include/e2e_ctc.h.
+After ``configure(lm_path=..., lmwt=..., wip=..., oov_penalty=...)`` the beam search ranks by the acoustic score together
+with a word language model, a word insertion penalty and an out-of-vocabulary penalty (e2e_gram_ctc_beam_nbest_lm): the
+base labels spell the words, the space among them separates them, and a gram may end one word and begin the next.
 
-Not provided for Gram-CTC: language model, lexicon, timestamps, streaming, a column segmentation per beam hypothesis
-(several segmentations spell one hypothesis), ``blank_idx != 0``.
+Not provided for Gram-CTC: a vocabulary restriction or lexicon, custom transcriptions, timestamps, streaming, a column
+segmentation per beam hypothesis (several segmentations spell one hypothesis), ``blank_idx != 0``.
 """
+import os
 from collections import namedtuple
 
 import torch
 
 from ..engines import GramCTCDecoderEngine
-from .ctc_decoder import CTCDecoderError, DecoderResults
+from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults
 
 # decode_nbest(): (B, N, ...) per utterance and hypothesis, ranked by `scores` (the log-probability of the labelling within
 # the beam); `decoded_sentences[b]` lists the num_hypotheses[b] sentences of utterance b
@@ -38,7 +42,7 @@ class GramCTCDecoder:
     def __init__(self, blank_idx=0, num_base_labels=None, total_labels=None, label2ids=None, beam_width=100, labels=None,
                  after_logsoftmax=False, time_major=False, keep_on_device=False, transcriptions=None):
         if transcriptions is not None:
-            raise CTCDecoderError("GramCTCDecoder does not support custom transcriptions: its search carries no word model")
+            raise CTCDecoderError("GramCTCDecoder does not support custom transcriptions: its search spells words from the base labels")
         if num_base_labels is None or total_labels is None:
             raise CTCDecoderError("GramCTCDecoder needs num_base_labels and total_labels (the arguments of GramCTCLoss)")
         self._beam_width = beam_width
@@ -46,6 +50,25 @@ class GramCTCDecoder:
         self._time_major = time_major
         self._decoder = GramCTCDecoderEngine(blank_idx, num_base_labels, total_labels, label2ids or {}, beam_width,
                                              labels, keep_on_device=keep_on_device)
+
+    def configure(self, lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True):
+        """Set up the beam search with a word language model, before decoding; returns self.  The names and defaults are
+        ``CTCDecoder``'s.  A decoder that was never configured searches on the labellings' probabilities alone.
+
+        :param lm_path: ARPA (optionally gzipped) language model; ``None``: no model, ``wip`` still applies per word
+        :param lmwt: language-model weight
+        :param wip: word insertion penalty
+        :param oov_penalty: penalty per out-of-vocabulary word
+        :param case_sensitive: look words up in the language model with their case
+
+        The decoder needs ``labels`` (they spell the words; ``" "`` among them separates the words, without it a hypothesis
+        is one word) and ``beam_width > 1``: a ``ValueError`` otherwise.  A later ``configure()`` replaces the former one.
+        """
+        lm_path = os.path.abspath(lm_path) if lm_path else ""
+        if lm_path and not os.path.isfile(lm_path):
+            raise CTCDecoderError("Can't find a model: {}".format(lm_path))
+        self._decoder.configure(lm_path, lmwt, wip, oov_penalty, case_sensitive)
+        return self
 
     def _batch_major(self, logits, logits_lengths):
         if self._time_major:
@@ -88,7 +111,10 @@ class GramCTCDecoder:
         :param nbest: how many to return per utterance, at most ``beam_width`` (the default)
         :return: ``GramNBestResults(decoded_targets (batch, nbest, longest), decoded_targets_lengths (batch, nbest),
             decoded_sentences (a list per utterance), scores (batch, nbest), num_hypotheses (batch))``; hypothesis 0 is
-            what ``decode`` returns, slots beyond ``num_hypotheses[b]`` are empty (length 0, score -inf)
+            what ``decode`` returns, slots beyond ``num_hypotheses[b]`` are empty (length 0, score -inf).  After
+            ``configure()``: ``CTCDecoder``'s ``NBestResults`` -- ``scores = ctc_scores + lmwt * lm_scores - wip * num_words +
+            oov_penalty * num_oov_words``, ``ctc_scores`` what ``scores`` is without ``configure()``, ``timesteps`` ``None``
         """
         logits, logits_lengths = self._batch_major(self._logprobs(logits), logits_lengths)
-        return GramNBestResults(*self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest))
+        r = self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest)
+        return NBestResults(*r) if self._decoder.configured else GramNBestResults(*r)

@@ -790,7 +790,9 @@ class GramCTCDecoderEngine:
     decode_nbest for Gram-CTC (e2e_gram_ctc_greedy, e2e_gram_ctc_beam_nbest; the definition: include/e2e_ctc.h).  The table
     check is GramCTCLossEngine's (gram_columns); the decoders take the table spelled out -- (V,8) base ids and (V) lengths
     -- copied to a device on first use and kept per device.  `labels`: the R base-label strings (index 0 the blank's).
-    The width limit is checked here, not at the first decode.  Results are CPU tensors unless `keep_on_device`."""
+    The width limit is checked here, not at the first decode.  `configure()` sets up the search with a word language
+    model (e2e_gram_ctc_beam_nbest_lm); an engine that was never configured is the search on the masses alone.  Results are
+    CPU tensors unless `keep_on_device`."""
 
     def __init__(self, blank_idx, num_base_labels, total_labels, label2ids, beam_width_=100, labels=None,
                  keep_on_device=False):
@@ -815,6 +817,32 @@ class GramCTCDecoderEngine:
             raise ValueError("beam_width %d is not supported for a Gram-CTC table of %d columns (max_order %d): 1 to %d"
                              % (self.beam_width, self.total_labels, self.max_order, cap))
         self._per_device = {}
+        self.configured = False                      # configure(): the search with the LM fields (e2e_gram_ctc_beam_nbest_lm)
+        self.lm = None
+
+    def configure(self, lm_path="", lmwt_=1.0, wip_=0.0, oov_penalty_=-1000.0, case_sensitive=False):
+        """Set up the beam search with a word language model (e2e_gram_ctc_beam_nbest_lm; the definition: include/e2e_ctc.h);
+        returns self.  The names and defaults are CTCDecoderEngine's.  The model is loaded here, once, over the
+        num_base_labels label strings (LanguageModel keeps a copy per device); `lm_path` empty: no model -- `lmwt_` counts
+        as 0, `wip_` still applies per word.  decode_nbest then returns CTCDecoderEngine.decode_nbest's tuple.  A later call
+        replaces the former one."""
+        if not self.labels:
+            raise ValueError("a configured Gram-CTC search needs the labels: the base labels' strings spell the language "
+                             "model's words, and the space among them separates the words")
+        if self.beam_width == 1:
+            raise ValueError("beam_width 1 is greedy decoding, which carries no language model: configure() needs beam_width > 1")
+        lm_path = lm_path or ""
+        self.lm = None
+        if lm_path:
+            R.require_gpu()
+            self.lm = LanguageModel(lm_path, self.labels, bool(case_sensitive))
+        self.lmwt = float(lmwt_) if lm_path else 0.0
+        self.wip = float(wip_)
+        self.oov_penalty = float(oov_penalty_)
+        self.case_sensitive = bool(case_sensitive)
+        self.space_id = self.labels.index(" ") if " " in self.labels else -1
+        self.configured = True
+        return self
 
     def _table(self, dev):
         t = self._per_device.get(dev.index)
@@ -873,11 +901,15 @@ class GramCTCDecoderEngine:
     def decode_nbest(self, logits_, logits_lengths_, nbest=None):
         """Prefix beam search on LOG-PROBABILITIES, read out as an n-best list -> (base ids (B,N,maxlen) int64, lengths
         (B,N), sentences [B][n_hyp], scores (B,N) f64 = log probability of the labelling within the beam, num_hypotheses
-        (B)).  Ranked by score, ties by the prefix key; slots beyond num_hypotheses[b] are empty (length 0, -inf)."""
+        (B)).  Ranked by score, ties by the prefix key; slots beyond num_hypotheses[b] are empty (length 0, -inf).
+        After configure(): CTCDecoderEngine.decode_nbest's tuple (ids, lengths, sentences, scores, acoustic scores, lm_scores,
+        num_words, num_oov, num_hypotheses, None), ranked by scores = acoustic + lmwt * lm - wip * words + oov_penalty * oovs."""
         N = self.beam_width if nbest is None else int(nbest)
         if not 1 <= N <= self.beam_width:
             raise ValueError("nbest=%d outside [1, beam_width=%d]" % (N, self.beam_width))
         x, xl, dev = self._prep(logits_, logits_lengths_, _F32_F64)
+        if self.configured:
+            return self._decode_nbest_lm(x, xl, dev, N)
         B, T, V = x.shape
         max_out = max(T * self.max_order, 1)
         out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
@@ -896,14 +928,48 @@ class GramCTCDecoderEngine:
                                        ids.data_ptr(), lens.data_ptr(), self.max_order, self.beam_width, N,
                                        out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
                                        ws.data_ptr(), ws.numel(), R.stream_handle(dev))
-        nh = n_hyp.tolist()
-        lens_host = out_len.tolist()
-        for b in range(B):
-            if nh[b] < 0:
-                raise R.E2EError("Gram-CTC beam search: utterance %d ran out of candidate entries" % b)
-        ids_out, sentences, _ = _pack_nbest(out, lens_host, nh, self._strings, self.keep_on_device)
+        ids_out, sentences = self._pack(out, out_len, n_hyp)
         r = self._result
         return (ids_out, r(out_len), sentences, r(scores), r(n_hyp))
+
+    def _pack(self, out, out_len, n_hyp):
+        """The ids packed to the longest hypothesis and the sentences; an utterance whose search ran out of entries raises."""
+        nh = n_hyp.tolist()
+        for b, n in enumerate(nh):
+            if n < 0:
+                raise R.E2EError("Gram-CTC beam search: utterance %d ran out of candidate entries" % b)
+        ids_out, sentences, _ = _pack_nbest(out, out_len.tolist(), nh, self._strings, self.keep_on_device)
+        return ids_out, sentences
+
+    def _decode_nbest_lm(self, x, xl, dev, N):
+        """decode_nbest after configure(): the search on the totals (e2e_gram_ctc_beam_nbest_lm)."""
+        B, T, V = x.shape
+        max_out = max(T * self.max_order, 1)
+        out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
+        out_len = torch.empty((B, N), dtype=torch.long, device=dev)
+        n_hyp = torch.empty(B, dtype=torch.long, device=dev)
+        scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
+        counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+        if B:
+            stream = R.stream_handle(dev)
+            with torch.cuda.device(dev):
+                ids, lens = self._table(dev)
+                lm = self.lm.on(dev).handle if self.lm is not None else 0
+                nbytes = _C.gram_beam_workspace_bytes_lm(B, T, V, self.max_order, self.beam_width, self.lm is not None)
+                if not nbytes:
+                    raise ValueError("Gram-CTC beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
+                ws = R.workspace(dev, nbytes, stream)
+                sB, sT, sV = x.stride()
+                _C.gram_ctc_beam_nbest_lm(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
+                                          ids.data_ptr(), lens.data_ptr(), self.max_order, self.num_base_labels,
+                                          self.beam_width, self.space_id, lm, self.lmwt, self.wip, self.oov_penalty, N,
+                                          out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                                          counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        ids_out, sentences = self._pack(out, out_len, n_hyp)
+        r = self._result
+        return (ids_out, r(out_len), sentences, r(scores[:, :, 0].contiguous()), r(scores[:, :, 1].contiguous()),
+                r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()), r(counts[:, :, 1].contiguous()),
+                r(n_hyp), None)
 
     def decode(self, logits_, logits_lengths_):
         """Hypothesis 0 of decode_nbest -> (base ids (B,maxlen) int64, lengths (B), sentences)."""

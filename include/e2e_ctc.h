@@ -346,8 +346,9 @@ int e2e_asg_viterbi(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV
  * Limits: beam_width <= e2e_gram_beam_max_width(V, max_order) = min(128, 131072 / V) -- 128 up to V = 1024, 100 fits the
  * loss's headline table V = 379, 16 at V = 8000 --, T <= 2^22; beyond them E2E_ERR_UNSUPPORTED, found on the host before
  * any launch (e2e_gram_beam_workspace_bytes then returns 0).  The call is asynchronous on `stream`, allocates nothing,
- * never synchronises and is capturable.  Not provided for Gram-CTC: language model, lexicon, timestamps, streaming, a
- * column segmentation per beam hypothesis (several exist), blank_idx != 0.
+ * never synchronises and is capturable.  With a word language model: e2e_gram_ctc_beam_nbest_lm, below.  Not provided
+ * for Gram-CTC: a vocabulary restriction or lexicon, custom transcriptions, timestamps, streaming, a column segmentation
+ * per beam hypothesis (several exist), blank_idx != 0.
  */
 int e2e_gram_ctc_greedy(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
                         int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
@@ -360,6 +361,53 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
                             int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
                             int beam_width, int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
                             double* scores, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Gram-CTC beam search with a word language model (additive, ABI 4: nothing above changes meaning).  The search, its slots,
+ * its stay and extend rules, the key and the per-frame power-of-two rescale are e2e_gram_ctc_beam_nbest's, unchanged; a
+ * hypothesis is still a base-id sequence, whichever columns spelled it.  What changes is what the cut and the ranking compare.
+ *   LM fields    lm_score, num_words, num_oov and the LM state are functions of the base-id sequence alone: e2e_ctc_beam's
+ *                rules (as e2e_asg_beam_nbest states them) applied to the base ids one at a time, as if each had been appended
+ *                on its own.  A word starts at a non-space id after the empty prefix or after the space; at every non-space id
+ *                the model is asked with the partial word as if it were complete: lm_score = lm_before +
+ *                base_score(state_before, idx(word)) / ln 10, num_oov = oov_before + (idx == 0); a space copies the fields;
+ *                case folding and byte comparison as in e2e_ctc_beam.  An extension by a gram of k ids applies the rule k
+ *                times (a gram may hold the space: it can end one word and begin the next).  Only the queries at a word's
+ *                last id inside the gram and at the gram's last id can influence the result; the others may be skipped,
+ *                the result is the same bits.  A hypothesis reached from several (parent, column) pairs has identical
+ *                fields from each -- same bits, same chain of additions: no result depends on which pair is used
+ *   totals, cut  for the frame's cut and for the final ranking a candidate's total is
+ *                log(tot) + lmwt * lm_score - wip * num_words + oov_penalty * num_oov, evaluated left to right, tot the
+ *                candidate's mass in the frame's scaling (without the common exponent sum).  A candidate with tot <= 0, or
+ *                with a NaN or -inf total, is no candidate.  The beam_width largest totals are kept, exactly equal totals
+ *                by key ascending.  The rescale uses the rank-0 survivor's tot.  The n-best list is in the last cut's order
+ *   space_id     the space's base id, or negative: none -- the whole sequence is then one word (>= num_base_labels:
+ *                E2E_ERR_ARG)
+ *   lm           NULL or a model of e2e_lm_load_arpa on the current device, loaded with exactly num_base_labels label
+ *                strings (index 0, the blank's, is never spelled; gram columns have no strings of their own); order <= 6.
+ *                NULL: lmwt counts as 0, wip still applies (num_words needs only space_id).  A model with custom
+ *                transcriptions (e2e_lm_load_transcriptions) or one that is only a word list (e2e_lm_load_words) is
+ *                refused with E2E_ERR_ARG
+ *   scores       (B,nbest,3) f64: total, ac, lm_score.  ac = log tot + e ln 2 is e2e_gram_ctc_beam_nbest's score, total the
+ *                formula above with ac in place of log(tot).  Slots >= n_hyp[b]: -inf, -inf, 0
+ *   counts       (B,nbest,2) int32: num_words, num_oov -- the layout of e2e_asg_beam_nbest
+ *   x_len[b] = 0 gives the empty hypothesis with all scores 0 and both counts 0
+ *   workspace    >= e2e_gram_beam_workspace_bytes_lm(..., with_lm): with_lm = 0 is e2e_gram_beam_workspace_bytes, and serves
+ *                a call with lm == NULL as well; with_lm = 1 adds, per utterance, the children's answers of 2 * beam_width
+ *                prefixes: 16 bytes per (prefix, column) (B=64, T=1000, V=379, beam_width=100: + 78 MB)
+ * Everything else -- lp, x_len, the table, nbest, out, out_len, n_hyp, the limits (e2e_gram_beam_max_width) -- is
+ * e2e_gram_ctc_beam_nbest's.  Every argument error is found on the host before any launch.  Asynchronous on `stream`,
+ * allocates nothing, never synchronises, capturable.  Two calls on the same input agree bit for bit.
+ */
+struct e2e_lm;   /* (e2e_lm_load_arpa, below) */
+size_t e2e_gram_beam_workspace_bytes_lm(int B, int T, int V, int max_order, int beam_width, int with_lm);
+
+int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                               int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                               int num_base_labels, int beam_width, int space_id, const struct e2e_lm* lm, double lmwt,
+                               double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
+                               int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
+                               void* stream);
 
 /* ------------------------------------------------------------------------
  * ASG decoding: n-best prefix beam search with transitions and a word language model (additive, ABI 4: nothing above
