@@ -41,6 +41,11 @@ class AsgBeamOpts(C.Structure):
     _fields_ = [("restrict_to_lexicon", C.c_int), ("timesteps", C.c_void_p)]
 
 
+class GramBeamOpts(C.Structure):
+    """e2e_gram_beam_opts (include/e2e_ctc.h)."""
+    _fields_ = [("restrict_to_lexicon", C.c_int), ("timesteps", C.c_void_p)]
+
+
 class E2EError(RuntimeError):
     """An error reported by the native library (message from e2e_last_error())."""
 
@@ -117,6 +122,8 @@ def load():
         L.e2e_gram_ctc_beam_nbest_lm.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
                                                  C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
                                                  C.c_int, i64p, i64, i64p, i64p, vp, vp, vp, C.c_size_t, vp]
+        L.e2e_gram_ctc_beam_nbest_opt.restype = C.c_int
+        L.e2e_gram_ctc_beam_nbest_opt.argtypes = L.e2e_gram_ctc_beam_nbest_lm.argtypes + [C.POINTER(GramBeamOpts)]
         L.e2e_asg_beam_max_width.restype = C.c_int
         L.e2e_asg_beam_max_width.argtypes = [C.c_int]
         L.e2e_asg_beam_workspace_bytes.restype = C.c_size_t

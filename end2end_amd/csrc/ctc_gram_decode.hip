@@ -23,6 +23,11 @@
 // computed once and kept in a row of the workspace for as long as the prefix stays in the beam (2 W rows, a member keeps its
 // row's index).  The cut then runs on okey(log tot + lmwt lm - wip words + oov_penalty oovs) as the ASG
 // kernel's does.  The no-LM instance is the kernel as it was, instruction for instruction (tools/diag/isa_compare.py).
+//
+// Restricted to the model's lexicon, and with label timestamps (e2e_gram_ctc_beam_nbest_opt, the LEX and TS instances): the
+// rule of the header is applied per base id, which walk_gram<LEX> decides at the places where it asks the model anyway; a
+// member's answer row also says which of its children exist, and a pair without a child is dropped before it claims a table
+// entry, so an inadmissible sequence never has one.  The timesteps are read off the nodes' numbers in the read-out.
 #include <cstring>
 #include <type_traits>
 
@@ -182,15 +187,26 @@ struct LmState {
   int n_stay, n_new, n_free;
 };
 struct Answer { double lm; int nw, oov; };                       // what the cut needs of a child: 16 bytes per (row, column)
+constexpr int kNoChild = -1;                                     // Answer::nw of a child that a restricted search does not form
 
 struct GramLmParams {
   GramBeamParams b;
   LmView lm; int has_lm, space_id, R; double lmwt, wip, oov;    // R: the base labels, the model's label strings
   int32_t* counts; size_t off_cache;
 };
-template <bool LM> using GramKernelParams = typename std::conditional<LM, GramLmParams, GramBeamParams>::type;
+// the parameter block of the instances of e2e_gram_ctc_beam_nbest_opt (LEX or TS): the LM instance's and what it lacks.  A
+// block of its own, so that the two instances that were there before keep theirs, and with it their code.
+struct GramOptParams { GramLmParams l; int64_t* timesteps; };   // (B,nbest,max_out): the TS instances only
+template <bool LM, bool OPT> using GramKernelParams =
+    typename std::conditional<OPT, GramOptParams, typename std::conditional<LM, GramLmParams, GramBeamParams>::type>::type;
 __device__ __forceinline__ const GramBeamParams& beam_of(const GramBeamParams& q) { return q; }
 __device__ __forceinline__ const GramBeamParams& beam_of(const GramLmParams& q) { return q.b; }
+__device__ __forceinline__ const GramBeamParams& search_of(const GramBeamParams& q) { return q; }
+__device__ __forceinline__ const GramLmParams& search_of(const GramLmParams& q) { return q; }
+__device__ __forceinline__ const GramLmParams& search_of(const GramOptParams& q) { return q.l; }
+__device__ __forceinline__ int64_t* timesteps_of(const GramBeamParams&) { return nullptr; }
+__device__ __forceinline__ int64_t* timesteps_of(const GramLmParams&) { return nullptr; }
+__device__ __forceinline__ int64_t* timesteps_of(const GramOptParams& q) { return q.timesteps; }
 
 // the fields of one sequence, in registers
 struct LmWalk {
@@ -231,11 +247,20 @@ __device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned l
 // (asg_beam.hip's child_lm and what follows it there) applied id by id.  The model is asked where a word ends inside the
 // gram and at the gram's last id; the answers in between would be overwritten (each is lm_before + one score, state_before
 // + one word), so leaving them out changes no bit.  Without a model only the words are counted.
-__device__ __forceinline__ void walk_gram(const GramLmParams& q, LmWalk& w, int c, int k) {
+// LEX: the search restricted to the model's lexicon (e2e_gram_ctc_beam_nbest_opt).  The rule is applied id by id, but Pref(L)
+// is prefix-closed, so the places where the model is asked anyway decide it: a word that ends inside the gram must be a word
+// of L (an id, not the 0 of a mere prefix), the spelling at the gram's last id must be listed at all, and a gram that begins
+// with the space needs the sequence's own last word to be one of L -- its last lookup counted no OOV.  -> false: the extended
+// sequence is not admissible (there is no child; w is then of no use), found before the n-gram walk.  Without LEX: true.
+template <bool LEX = false>
+__device__ __forceinline__ bool walk_gram(const GramLmParams& q, LmWalk& w, int c, int k) {
   const int32_t* ids = q.b.gram_ids + c * kMaxK;
   int id = ids[0];
   for (int j = 0; j < k; j++) {
     const int nxt = j + 1 < k ? ids[j + 1] : -1;
+    if constexpr (LEX) {                                          // a space after a word that the gram did not spell itself
+      if (id == q.space_id && j == 0 && w.last >= 0 && w.last != q.space_id && w.oov != w.oovb) return false;
+    }
     if (id != q.space_id) {                                       // (a space copies the fields)
       if (w.last < 0 || w.last == q.space_id) {                   // the id begins a word
         w.nw++;
@@ -246,7 +271,10 @@ __device__ __forceinline__ void walk_gram(const GramLmParams& q, LmWalk& w, int 
       if (q.has_lm) {
         if ((unsigned)id < (unsigned)q.R) w.hash = spell(q.lm, w.hash, id);   // (the host cannot see the table: no id spells outside the strings)
         if (j + 1 == k || nxt == q.space_id) {
-          const uint32_t wi = lm_word_lookup(q.lm, w.hash);
+          uint32_t wi;
+          if constexpr (LEX) {
+            if (!lm_word_find(q.lm, w.hash, wi) || (nxt == q.space_id && wi == 0)) return false;
+          } else wi = lm_word_lookup(q.lm, w.hash);
           const float sc = lm_base_score(q.lm, w.stb, w.stbn, wi, nullptr, nullptr);
           w.lm = w.lmb + (double)sc / 2.302585092994045684;       // quirk Q8: divides by ln 10
           w.oov = w.oovb + (wi == 0 ? 1 : 0);
@@ -262,6 +290,7 @@ __device__ __forceinline__ void walk_gram(const GramLmParams& q, LmWalk& w, int 
     w.last = id;
     id = nxt;
   }
+  return true;
 }
 // total = log tot + lmwt * lm_score - wip * num_words + oov_penalty * num_oov, in this order
 __device__ __forceinline__ double total_of(const GramLmParams& q, double ac, double lm, int nw, int noov) {
@@ -270,8 +299,14 @@ __device__ __forceinline__ double total_of(const GramLmParams& q, double ac, dou
 
 // LM = false: the search on the masses alone (e2e_gram_ctc_beam_nbest), the parameter block GramBeamParams.  LM = true: the
 // cut and the ranking on the totals with the language model's fields (e2e_gram_ctc_beam_nbest_lm).
-template <bool LM>
-__global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParams<LM> q) {
+// LEX (with LM): the search restricted to the model's lexicon -- the answer row of a member's children also says which of
+// them there are (nw = kNoChild: none), and a pair without a child is dropped before it claims a table entry.  TS (with LM):
+// the read-out also writes the frame each id's node was created at.  Instances of their own with a parameter block of their
+// own: without LEX and TS the two kernels are the code they were, instruction for instruction (tools/diag/isa_compare.py).
+template <bool LM, bool LEX = false, bool TS = false>
+__global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParams<LM, LEX || TS> kp) {
+  static_assert(LM || !(LEX || TS), "the restricted search and the timesteps are the LM instance's");
+  const auto& q = search_of(kp);
   const GramBeamParams& p = beam_of(q);
   __shared__ Members mem[2];
   __shared__ BeamCut cut;
@@ -316,8 +351,8 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
     if (q.has_lm && Tb > 0)
       for (int c = 1 + tid; c < V; c += kBeamThreads) {
         LmWalk w = load_walk(S->lms[0], 0);
-        walk_gram(q, w, c, order_of(p.gram_len, c, K));
-        cache[c] = Answer{w.lm, w.nw, w.oov};
+        const bool child = walk_gram<LEX>(q, w, c, order_of(p.gram_len, c, K));
+        cache[c] = Answer{w.lm, child ? w.nw : kNoChild, w.oov};
       }
   }
 
@@ -351,6 +386,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
       if (c != 0) {
         const int k = order_of(p.gram_len, (int)c, K);
         go = ext_source(M, (int)m, k, (int)c, K) * y[c] > 0.0;
+        if constexpr (LEX) go = go && cache[(size_t)S->lms[cur].row[m] * V + c].nw != kNoChild;   // (no child: no candidate)
         if (go) for (int j = 0; j < k; j++) key = (key ^ (unsigned long long)(unsigned)p.gram_ids[c * kMaxK + j]) * kKeyPrime;
       }
       if (!go) continue;
@@ -484,7 +520,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
         N.node[r] = node; N.len[r] = M.len[pm] + order_of(p.gram_len, (int)pc, K);
         if constexpr (LM) {                                      // a new prefix: its parent's fields walked through the gram
           LmWalk w = load_walk(S->lms[cur], (int)pm);
-          walk_gram(q, w, (int)pc, order_of(p.gram_len, (int)pc, K));
+          (void)walk_gram<LEX>(q, w, (int)pc, order_of(p.gram_len, (int)pc, K));   // (a pair that was not dropped: a child)
           store_walk(S->lms[cur ^ 1], r, w);
           S->new_list[atomicAdd(&S->n_new, 1)] = (unsigned char)r;
         }
@@ -508,8 +544,8 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
           if (c == 0) continue;
           const int r = S->new_list[j];
           LmWalk w = load_walk(O, r);
-          walk_gram(q, w, c, order_of(p.gram_len, c, K));
-          cache[(size_t)O.row[r] * V + c] = Answer{w.lm, w.nw, w.oov};
+          const bool child = walk_gram<LEX>(q, w, c, order_of(p.gram_len, c, K));
+          cache[(size_t)O.row[r] * V + c] = Answer{w.lm, child ? w.nw : kNoChild, w.oov};
         }
       }
     }
@@ -522,8 +558,12 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
   const int nbest = p.nbest;
   const int64_t max_out = p.max_out;
   int64_t* out = p.out + (int64_t)b * nbest * max_out;
+  int64_t* ts = nullptr;
+  if constexpr (TS) ts = timesteps_of(kp) + (int64_t)b * nbest * max_out;
   if (tid < nbest) {
     int64_t* row = out + (int64_t)tid * max_out;
+    int64_t* trow = nullptr;
+    if constexpr (TS) trow = ts + (int64_t)tid * max_out;
     int len = 0; double score = -__builtin_huge_val();
     if (tid < n_mem) {
       len = F.len[tid];
@@ -532,7 +572,13 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
       for (int hops = 0; node > 0 && hops <= p.T; hops++) {
         const int2 nd = nodes[node];
         const int k = order_of(p.gram_len, nd.y, K);
-        for (int j = k - 1; j >= 0; j--) { --at; if (at >= 0 && at < max_out) row[at] = (int64_t)p.gram_ids[nd.y * kMaxK + j]; }
+        for (int j = k - 1; j >= 0; j--) {
+          --at;
+          if (at >= 0 && at < max_out) {
+            row[at] = (int64_t)p.gram_ids[nd.y * kMaxK + j];
+            if constexpr (TS) trow[at] = (int64_t)((node - 1) / W);   // node = 1 + t * W + rank: a gram's ids share the frame
+          }
+        }
         node = nd.x;
       }
     }
@@ -556,6 +602,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
   for (int j = 0; j < nbest; j++) {
     int64_t* row = out + (int64_t)j * max_out;
     for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kBeamThreads) row[i] = 0;
+    if constexpr (TS) for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kBeamThreads) ts[(int64_t)j * max_out + i] = -1;
   }
   if (tid == 0) p.n_hyp[b] = overflow ? -1 : (n_mem < nbest ? n_mem : nbest);
 }
@@ -661,19 +708,22 @@ size_t e2e_gram_beam_workspace_bytes_lm(int B, int T, int V, int max_order, int 
   return (size_t)B * L.per_utt + 256;
 }
 
-int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
-                               int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
-                               int num_base_labels, int beam_width, int space_id, const e2e_lm* lm, double lmwt,
-                               double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
-                               int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
-                               void* stream) {
+int e2e_gram_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                                int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                                int num_base_labels, int beam_width, int space_id, const e2e_lm* lm, double lmwt,
+                                double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
+                                int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                void* stream, const e2e_gram_beam_opts* opts) {
+  const bool restricted = opts && opts->restrict_to_lexicon != 0;
+  int64_t* timesteps = opts ? opts->timesteps : nullptr;
   if (const int rc = check_beam_args(dtype, B, T, V, max_order, beam_width, nbest, max_out)) return rc;
   if (num_base_labels < 1 || num_base_labels > V) { set_error("num_base_labels=%d outside [1, V=%d]", num_base_labels, V); return E2E_ERR_ARG; }
   if (space_id >= num_base_labels) { set_error("space_id=%d is not one of the %d base labels", space_id, num_base_labels); return E2E_ERR_ARG; }
   if (lm) {
-    if (lm->transcribed || lm->words_only) {
-      set_error("the Gram-CTC search spells its words from the base labels' strings and has no restricted search: a model with "
-                "custom transcriptions (e2e_lm_load_transcriptions) or a word list (e2e_lm_load_words) is not supported");
+    if (lm->transcribed || (lm->words_only && !restricted)) {
+      set_error("the Gram-CTC search spells its words from the base labels' strings: a model with custom transcriptions "
+                "(e2e_lm_load_transcriptions) is not supported, and a word list (e2e_lm_load_words) only by a search that is "
+                "restricted to it (e2e_gram_ctc_beam_nbest_opt, restrict_to_lexicon)");
       return E2E_ERR_ARG;
     }
     if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_ARG; }
@@ -682,6 +732,10 @@ int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT
                 (int)lm->label_off.size() - 1, num_base_labels);
       return E2E_ERR_ARG;
     }
+  }
+  if (restricted && (!lm || !lm->has_lexicon)) {
+    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+    return E2E_ERR_ARG;
   }
   BeamLayout L;
   if (!beam_layout(T, V, max_order, beam_width, L, lm != nullptr)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
@@ -702,7 +756,8 @@ int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT
     set_error("workspace too small: %zu bytes, e2e_gram_beam_workspace_bytes_lm() = %zu", workspace_bytes, (size_t)B * L.per_utt + 256);
     return E2E_ERR_WORKSPACE;
   }
-  GramLmParams q;
+  GramOptParams o;
+  GramLmParams& q = o.l;
   q.b = GramBeamParams{lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
                        out, max_out, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
                        L.per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, L.off_nodes, L.logH};
@@ -710,9 +765,26 @@ int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT
   q.has_lm = lm ? 1 : 0; q.space_id = space_id < 0 ? -1 : space_id; q.R = num_base_labels;
   q.lmwt = lm ? lmwt : 0.0; q.wip = wip; q.oov = oov_penalty;
   q.counts = counts; q.off_cache = L.off_cache;
-  hipLaunchKernelGGL(gram_beam_kernel<true>, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, q);
+  o.timesteps = timesteps;
+  hipStream_t s = (hipStream_t)stream;
+  // (neither option: the kernel and the parameter block of e2e_gram_ctc_beam_nbest_lm)
+  if (!restricted && !timesteps) hipLaunchKernelGGL(gram_beam_kernel<true>, dim3(B), dim3(kBeamThreads), 0, s, q);
+  else if (!restricted) hipLaunchKernelGGL((gram_beam_kernel<true, false, true>), dim3(B), dim3(kBeamThreads), 0, s, o);
+  else if (!timesteps) hipLaunchKernelGGL((gram_beam_kernel<true, true, false>), dim3(B), dim3(kBeamThreads), 0, s, o);
+  else hipLaunchKernelGGL((gram_beam_kernel<true, true, true>), dim3(B), dim3(kBeamThreads), 0, s, o);
   E2E_HIP_CHECK(hipGetLastError(), "gram_beam_kernel (LM) launch");
   return E2E_OK;
+}
+
+int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                               int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                               int num_base_labels, int beam_width, int space_id, const e2e_lm* lm, double lmwt,
+                               double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
+                               int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  return e2e_gram_ctc_beam_nbest_opt(lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, num_base_labels,
+                                     beam_width, space_id, lm, lmwt, wip, oov_penalty, nbest, out, max_out, out_len, n_hyp,
+                                     scores, counts, workspace, workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"

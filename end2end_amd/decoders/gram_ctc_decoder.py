@@ -4,8 +4,10 @@ CTCDecoder's.  Upstream has no such decoder (its Gram-CTC engine is empty); the 
 After ``configure(lm_path=..., lmwt=..., wip=..., oov_penalty=...)`` the beam search ranks by the acoustic score together
 with a word language model, a word insertion penalty and an out-of-vocabulary penalty (e2e_gram_ctc_beam_nbest_lm): the
 base labels spell the words, the space among them separates them, and a gram may end one word and begin the next.
+``restrict_to_vocabulary()`` then restricts the search to the model's words or to a word list, and
+``decode_nbest(..., timesteps=True)`` also returns the frame at which each id entered the beam (e2e_gram_ctc_beam_nbest_opt).
 
-Not provided for Gram-CTC: a vocabulary restriction or lexicon, custom transcriptions, timestamps, streaming, a column
+Not provided for Gram-CTC: custom transcriptions, a word list together with a language model, streaming, a column
 segmentation per beam hypothesis (several segmentations spell one hypothesis), ``blank_idx != 0``.
 """
 import os
@@ -62,12 +64,31 @@ class GramCTCDecoder:
         :param case_sensitive: look words up in the language model with their case
 
         The decoder needs ``labels`` (they spell the words; ``" "`` among them separates the words, without it a hypothesis
-        is one word) and ``beam_width > 1``: a ``ValueError`` otherwise.  A later ``configure()`` replaces the former one.
+        is one word) and ``beam_width > 1``: a ``ValueError`` otherwise.  A later ``configure()`` replaces the former one
+        and drops a restriction to a vocabulary.
         """
         lm_path = os.path.abspath(lm_path) if lm_path else ""
         if lm_path and not os.path.isfile(lm_path):
             raise CTCDecoderError("Can't find a model: {}".format(lm_path))
         self._decoder.configure(lm_path, lmwt, wip, oov_penalty, case_sensitive)
+        return self
+
+    def restrict_to_vocabulary(self, lexicon=None):
+        """Restrict the beam search to a vocabulary, after ``configure()``; returns self.  Only sequences whose every word is
+        a word of the vocabulary, the last one possibly unfinished (a prefix of a word), are formed; a gram is taken only if
+        all its ids may follow, a gram with an inner space only if the word it closes is one.
+
+        :param lexicon: ``None``: the words of the language model given to ``configure(lm_path=...)``.  A path to a text file
+            of words or an iterable of words: the vocabulary without a model -- ``lmwt`` and ``oov_penalty`` then count as 0,
+            ``wip`` applies; not together with ``lm_path``.
+
+        A ``ValueError`` before ``configure()``, without any vocabulary, or with both.  A later ``configure()`` drops the
+        restriction.  ``decode`` then returns hypothesis 0 of the restricted search.
+        """
+        if not self._decoder.configured:
+            raise ValueError("restrict_to_vocabulary() comes after configure(): configure(lm_path=...) for a model's words, "
+                             "configure(wip=...) and a lexicon for a word list")
+        self._decoder.restrict(lexicon)
         return self
 
     def _batch_major(self, logits, logits_lengths):
@@ -105,16 +126,24 @@ class GramCTCDecoder:
         logits, logits_lengths = self._batch_major(self._logprobs(logits), logits_lengths)
         return DecoderResults(*self._decoder.decode(logits_=logits, logits_lengths_=logits_lengths))
 
-    def decode_nbest(self, logits, logits_lengths=None, nbest=None):
+    def decode_nbest(self, logits, logits_lengths=None, nbest=None, timesteps=False):
         """The hypotheses the beam search ends with, best first.
 
         :param nbest: how many to return per utterance, at most ``beam_width`` (the default)
+        :param timesteps: after ``configure()`` only: also fill ``NBestResults.timesteps``, ``(batch, nbest, longest)``,
+            -1 padded -- for every id the frame at which the sequence that ends in its gram entered the beam (the ids of one
+            gram share it; in a wide beam that can be before the label is heard).  An unconfigured decoder returns
+            ``GramNBestResults``, which has no such field: a ``ValueError`` that names ``configure(wip=0)``
         :return: ``GramNBestResults(decoded_targets (batch, nbest, longest), decoded_targets_lengths (batch, nbest),
             decoded_sentences (a list per utterance), scores (batch, nbest), num_hypotheses (batch))``; hypothesis 0 is
             what ``decode`` returns, slots beyond ``num_hypotheses[b]`` are empty (length 0, score -inf).  After
             ``configure()``: ``CTCDecoder``'s ``NBestResults`` -- ``scores = ctc_scores + lmwt * lm_scores - wip * num_words +
             oov_penalty * num_oov_words``, ``ctc_scores`` what ``scores`` is without ``configure()``, ``timesteps`` ``None``
+            unless asked for
         """
+        if timesteps and not self._decoder.configured:
+            raise ValueError("timesteps are a field of NBestResults, which a configured decoder returns: call configure(wip=0) "
+                             "for the same search with timesteps")
         logits, logits_lengths = self._batch_major(self._logprobs(logits), logits_lengths)
-        r = self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest)
+        r = self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest, timesteps=timesteps)
         return NBestResults(*r) if self._decoder.configured else GramNBestResults(*r)

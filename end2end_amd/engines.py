@@ -791,8 +791,9 @@ class GramCTCDecoderEngine:
     check is GramCTCLossEngine's (gram_columns); the decoders take the table spelled out -- (V,8) base ids and (V) lengths
     -- copied to a device on first use and kept per device.  `labels`: the R base-label strings (index 0 the blank's).
     The width limit is checked here, not at the first decode.  `configure()` sets up the search with a word language
-    model (e2e_gram_ctc_beam_nbest_lm); an engine that was never configured is the search on the masses alone.  Results are
-    CPU tensors unless `keep_on_device`."""
+    model (e2e_gram_ctc_beam_nbest_lm); an engine that was never configured is the search on the masses alone.  `restrict()`,
+    after `configure()`, restricts the search to a vocabulary (e2e_gram_ctc_beam_nbest_opt).  Results are CPU tensors unless
+    `keep_on_device`."""
 
     def __init__(self, blank_idx, num_base_labels, total_labels, label2ids, beam_width_=100, labels=None,
                  keep_on_device=False):
@@ -819,13 +820,14 @@ class GramCTCDecoderEngine:
         self._per_device = {}
         self.configured = False                      # configure(): the search with the LM fields (e2e_gram_ctc_beam_nbest_lm)
         self.lm = None
+        self.restricted = False                      # restrict(): only admissible sequences (e2e_gram_ctc_beam_nbest_opt)
 
     def configure(self, lm_path="", lmwt_=1.0, wip_=0.0, oov_penalty_=-1000.0, case_sensitive=False):
         """Set up the beam search with a word language model (e2e_gram_ctc_beam_nbest_lm; the definition: include/e2e_ctc.h);
         returns self.  The names and defaults are CTCDecoderEngine's.  The model is loaded here, once, over the
         num_base_labels label strings (LanguageModel keeps a copy per device); `lm_path` empty: no model -- `lmwt_` counts
         as 0, `wip_` still applies per word.  decode_nbest then returns CTCDecoderEngine.decode_nbest's tuple.  A later call
-        replaces the former one."""
+        replaces the former one, and drops a restriction (restrict())."""
         if not self.labels:
             raise ValueError("a configured Gram-CTC search needs the labels: the base labels' strings spell the language "
                              "model's words, and the space among them separates the words")
@@ -833,6 +835,8 @@ class GramCTCDecoderEngine:
             raise ValueError("beam_width 1 is greedy decoding, which carries no language model: configure() needs beam_width > 1")
         lm_path = lm_path or ""
         self.lm = None
+        self.restricted = False
+        self._lm_path = lm_path
         if lm_path:
             R.require_gpu()
             self.lm = LanguageModel(lm_path, self.labels, bool(case_sensitive))
@@ -842,6 +846,38 @@ class GramCTCDecoderEngine:
         self.case_sensitive = bool(case_sensitive)
         self.space_id = self.labels.index(" ") if " " in self.labels else -1
         self.configured = True
+        return self
+
+    def restrict(self, lexicon=None):
+        """Restrict the configured search to a vocabulary (the definition: e2e_gram_ctc_beam_nbest_opt); returns self.
+        `lexicon` None: the words of the language model of configure()'s `lm_path`, whose lexicon is enabled.  `lexicon` a path
+        (a text file, one word per line or white space between the words) or an iterable of words: the model that scores
+        nothing is built from them (e2e_lm_load_words) -- `lmwt` and `oov_penalty` then count as 0, `wip` applies; not together
+        with `lm_path`.  A later configure() drops the restriction."""
+        if not self.configured:
+            raise ValueError("restrict needs a configured search: call configure() first (configure(wip=0) for no model and no penalty)")
+        if lexicon is not None and self._lm_path:
+            raise ValueError("lm_path and lexicon exclude each other (a lexicon together with a language model is not supported)")
+        if lexicon is None and self.lm is None:
+            raise ValueError("restrict needs a vocabulary: configure(lm_path=...) or lexicon")
+        if lexicon is not None:
+            if isinstance(lexicon, (str, bytes, os.PathLike)):
+                path = os.fsdecode(lexicon)
+                if not os.path.isfile(path):
+                    raise ValueError("Can't find a lexicon: {}".format(path))
+                with open(path, encoding="utf-8") as f:
+                    words = f.read().split()
+            else:
+                words = [str(w) for w in lexicon]
+            if not words:
+                raise ValueError("the lexicon is empty")
+            R.require_gpu()
+            self.lm = LanguageModel(None, self.labels, self.case_sensitive, words=words, lexicon=True)
+            self.lmwt = 0.0
+            self.oov_penalty = 0.0
+        elif not self.lm.has_lexicon():
+            self.lm.enable_lexicon()
+        self.restricted = True
         return self
 
     def _table(self, dev):
@@ -898,18 +934,23 @@ class GramCTCDecoderEngine:
         res = (out, out_len, self._strings(out.cpu(), out_len.tolist()))
         return res + (self._result(cols), self._result(cols_len)) if return_columns else res
 
-    def decode_nbest(self, logits_, logits_lengths_, nbest=None):
+    def decode_nbest(self, logits_, logits_lengths_, nbest=None, timesteps=False):
         """Prefix beam search on LOG-PROBABILITIES, read out as an n-best list -> (base ids (B,N,maxlen) int64, lengths
         (B,N), sentences [B][n_hyp], scores (B,N) f64 = log probability of the labelling within the beam, num_hypotheses
         (B)).  Ranked by score, ties by the prefix key; slots beyond num_hypotheses[b] are empty (length 0, -inf).
         After configure(): CTCDecoderEngine.decode_nbest's tuple (ids, lengths, sentences, scores, acoustic scores, lm_scores,
-        num_words, num_oov, num_hypotheses, None), ranked by scores = acoustic + lmwt * lm - wip * words + oov_penalty * oovs."""
+        num_words, num_oov, num_hypotheses, timesteps), ranked by scores = acoustic + lmwt * lm - wip * words + oov_penalty * oovs.
+        `timesteps` (a configured search only): (B,N,maxlen) int64, the frame at which the node that carries each id was created
+        (the ids of one gram share it), -1 behind a sequence, cut to the longest result as the ids are; None unless asked for."""
         N = self.beam_width if nbest is None else int(nbest)
         if not 1 <= N <= self.beam_width:
             raise ValueError("nbest=%d outside [1, beam_width=%d]" % (N, self.beam_width))
+        if timesteps and not self.configured:
+            raise ValueError("timesteps are part of the configured search's results: call configure() first "
+                             "(configure(wip=0) is the search without a model and without penalties)")
         x, xl, dev = self._prep(logits_, logits_lengths_, _F32_F64)
         if self.configured:
-            return self._decode_nbest_lm(x, xl, dev, N)
+            return self._decode_nbest_lm(x, xl, dev, N, bool(timesteps))
         B, T, V = x.shape
         max_out = max(T * self.max_order, 1)
         out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
@@ -941,8 +982,9 @@ class GramCTCDecoderEngine:
         ids_out, sentences, _ = _pack_nbest(out, out_len.tolist(), nh, self._strings, self.keep_on_device)
         return ids_out, sentences
 
-    def _decode_nbest_lm(self, x, xl, dev, N):
-        """decode_nbest after configure(): the search on the totals (e2e_gram_ctc_beam_nbest_lm)."""
+    def _decode_nbest_lm(self, x, xl, dev, N, timesteps=False):
+        """decode_nbest after configure(): the search on the totals (e2e_gram_ctc_beam_nbest_lm; restricted or with timesteps:
+        e2e_gram_ctc_beam_nbest_opt)."""
         B, T, V = x.shape
         max_out = max(T * self.max_order, 1)
         out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
@@ -950,6 +992,7 @@ class GramCTCDecoderEngine:
         n_hyp = torch.empty(B, dtype=torch.long, device=dev)
         scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
         counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+        ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if timesteps else None
         if B:
             stream = R.stream_handle(dev)
             with torch.cuda.device(dev):
@@ -960,16 +1003,22 @@ class GramCTCDecoderEngine:
                     raise ValueError("Gram-CTC beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
                 ws = R.workspace(dev, nbytes, stream)
                 sB, sT, sV = x.stride()
-                _C.gram_ctc_beam_nbest_lm(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
-                                          ids.data_ptr(), lens.data_ptr(), self.max_order, self.num_base_labels,
-                                          self.beam_width, self.space_id, lm, self.lmwt, self.wip, self.oov_penalty, N,
-                                          out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
-                                          counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
+                        ids.data_ptr(), lens.data_ptr(), self.max_order, self.num_base_labels,
+                        self.beam_width, self.space_id, lm, self.lmwt, self.wip, self.oov_penalty, N,
+                        out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                        counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                if self.restricted or ts is not None:
+                    _C.gram_ctc_beam_nbest_opt(*args, (self.restricted, ts.data_ptr() if ts is not None else 0))
+                else:
+                    _C.gram_ctc_beam_nbest_lm(*args)
         ids_out, sentences = self._pack(out, out_len, n_hyp)
         r = self._result
+        if ts is not None:
+            ts = r(ts[:, :, :ids_out.shape[2]].contiguous())
         return (ids_out, r(out_len), sentences, r(scores[:, :, 0].contiguous()), r(scores[:, :, 1].contiguous()),
                 r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()), r(counts[:, :, 1].contiguous()),
-                r(n_hyp), None)
+                r(n_hyp), ts)
 
     def decode(self, logits_, logits_lengths_):
         """Hypothesis 0 of decode_nbest -> (base ids (B,maxlen) int64, lengths (B), sentences)."""

@@ -346,9 +346,10 @@ int e2e_asg_viterbi(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV
  * Limits: beam_width <= e2e_gram_beam_max_width(V, max_order) = min(128, 131072 / V) -- 128 up to V = 1024, 100 fits the
  * loss's headline table V = 379, 16 at V = 8000 --, T <= 2^22; beyond them E2E_ERR_UNSUPPORTED, found on the host before
  * any launch (e2e_gram_beam_workspace_bytes then returns 0).  The call is asynchronous on `stream`, allocates nothing,
- * never synchronises and is capturable.  With a word language model: e2e_gram_ctc_beam_nbest_lm, below.  Not provided
- * for Gram-CTC: a vocabulary restriction or lexicon, custom transcriptions, timestamps, streaming, a column segmentation
- * per beam hypothesis (several exist), blank_idx != 0.
+ * never synchronises and is capturable.  With a word language model: e2e_gram_ctc_beam_nbest_lm, below; restricted to
+ * a vocabulary, and with label timestamps: e2e_gram_ctc_beam_nbest_opt, below that.  Not provided for Gram-CTC: custom
+ * transcriptions, a word list together with a language model, streaming, a column
+ * segmentation per beam hypothesis (several exist), blank_idx != 0.
  */
 int e2e_gram_ctc_greedy(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
                         int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
@@ -408,6 +409,60 @@ int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT
                                double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
                                int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
                                void* stream);
+
+/* ------------------------------------------------------------------------
+ * Gram-CTC beam search restricted to a vocabulary, and label timestamps (additive, ABI 4: nothing above changes meaning).
+ *
+ * e2e_gram_ctc_beam_nbest_opt is e2e_gram_ctc_beam_nbest_lm with options; opts == NULL, or both fields zero, is
+ * e2e_gram_ctc_beam_nbest_lm bit for bit.  The workspace (e2e_gram_beam_workspace_bytes_lm) and the width limits do not change.
+ *
+ * restrict_to_lexicon   L and Pref(L) are those of e2e_ctc_beam_nbest_opt: the model's words, folded as the lookup folds them,
+ *                       and every non-empty byte prefix of a word.  A hypothesis is a base-id sequence, as before; its LAST WORD
+ *                       is the run of ids after its last space, spelled as the LM lookup of e2e_gram_ctc_beam_nbest_lm spells it.
+ *                       A step y -> y + (i) by one base id i obeys the rule if
+ *                         - i is not the space and the last word of y + (i) is spelled in Pref(L); or
+ *                         - i is the space and y is empty, ends in the space, or ends in a word of L (e2e_ctc_beam_nbest_opt's
+ *                           space rule, not ASG's: base-id sequences can repeat an id, so a space can follow a space).
+ *                       A sequence is ADMISSIBLE if every one of its base-id prefixes obeys the rule; an extension by a gram of k
+ *                       ids applies the rule k times.  Admissibility is a function of the sequence alone, not of the columns
+ *                       that spelled it: `a`,`b` and the gram `ab` agree.  A restricted search forms only admissible sequences:
+ *                       a (member, column) pair whose extension is inadmissible gives nothing and creates no candidate.  Slots,
+ *                       stay shares, keys, the rescale, LM fields, totals, the cut, tie order and the read-out are
+ *                       e2e_gram_ctc_beam_nbest_lm's.  The last word of a result may be a proper prefix that is no word: it
+ *                       counts as out of vocabulary, as it always did.  If no first label is admissible and the blank has no
+ *                       mass, no hypothesis is left: n_hyp[b] = 0.
+ *                       Pref(L) is prefix-closed, so the rule is decided where the model is asked anyway: a word that ends
+ *                       before a space inside the gram must be a word of L; the spelling at the gram's last id, if that is no
+ *                       space, must be in Pref(L); a gram that begins with the space needs the parent's last word to be a word
+ *                       of L (its last lookup counted no OOV).
+ *                       != 0 with lm == NULL or a model without a lexicon (e2e_lm_enable_lexicon): E2E_ERR_ARG, before any
+ *                       launch.  A transcription model stays refused (E2E_ERR_ARG).  A word-list model (e2e_lm_load_words) is
+ *                       accepted by this entry, and only together with restrict_to_lexicon; e2e_gram_ctc_beam_nbest_lm keeps
+ *                       refusing it.
+ * timesteps             NULL, or (B,nbest,max_out) int64: for every id written to `out`, the creation frame of the pool node
+ *                       that carries it, (node - 1) / beam_width, read during the read-out's backward walk: no workspace, no
+ *                       per-frame work.  All ids of one gram column share a frame.  Values lie in [0, x_len[b]) and never
+ *                       decrease along a sequence; from one node to the next they increase strictly.  Behind a sequence, and in
+ *                       slots >= n_hyp[b]: -1; x_len[b] = 0 gives -1 throughout.  The first value need not be 0: the empty
+ *                       prefix is a member and may stay.  A member that stays keeps its node.  A new sequence's node records the
+ *                       pair with the least m * V + c among the (member at beam position m, column c) pairs that gave it a
+ *                       non-zero share in that frame, and through it the parent's node: this is what makes the earlier labels'
+ *                       frames well defined when several pairs spell one sequence.
+ *                       The caveat of e2e_ctc_beam_nbest's timesteps holds here too: in a wide beam a sequence can enter the
+ *                       beam before its last label becomes likely, so a value can precede the frame where the label is heard.
+ * Asynchronous on `stream`, allocates nothing, never synchronises, capturable.
+ */
+typedef struct e2e_gram_beam_opts {
+  int restrict_to_lexicon;   /* 0: the plain search */
+  int64_t* timesteps;        /* NULL, or (B,nbest,max_out) int64 */
+} e2e_gram_beam_opts;
+
+int e2e_gram_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                                int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                                int num_base_labels, int beam_width, int space_id, const struct e2e_lm* lm, double lmwt,
+                                double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
+                                int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                void* stream, const e2e_gram_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
  * ASG decoding: n-best prefix beam search with transitions and a word language model (additive, ABI 4: nothing above
