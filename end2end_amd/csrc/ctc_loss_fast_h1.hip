@@ -22,8 +22,9 @@ namespace {
 //     one value (2 DPP moves) per lane in either direction (the (blank j, label j) pairing costs beta a fifth operation);
 //   * a wave without an upstream neighbour reads a wave slot that holds no cells (progress "idle", zero records), and lanes
 //     with nothing to publish store to a dump row: no case distinctions, no exec masks around the stores;
-//   * the neighbour's progress word and edge record, and the checkpoint wave's progress, are asked for two steps / four
-//     steps before they are needed and only looked at then;
+//   * the neighbour's progress word and edge record, the checkpoint wave's progress and the producers' progress words are
+//     asked for two steps / four steps before they are needed and only looked at then (the producers' words read and used
+//     at once were 7-8 of a wave's 143 cycles per step: profiles/chain_stream/);
 //   * a half block's probabilities are requested so that what is used first is asked for LAST: one wait covers the half.
 // Two waves per direction, 12 waves: the default for targets of 128..223 labels.  Tried and dropped (the code is in 904eb5c):
 // one pair per lane on four waves per direction, 16 waves (halving a wave's lattice work is not the lever), and eight waves
@@ -36,40 +37,35 @@ constexpr int kHxOwn = kHxNP * kHxOwnLanes;   // pairs a wave owns
 constexpr int kHxMaxW = 4 / kHxNP;            // chain waves per direction: 224 pairs, S <= 223
 constexpr int kHxWaves = 2 * kHxMaxW + 2 + 2 * kHxProducers + 2;
 
+// Everything but the ring has a size that does not depend on the alphabet, so it sits in FRONT of the ring at offsets known
+// at compile time: a hand-off word's address is then a constant, which a DS instruction carries in its offset field on top
+// of a register that holds zero -- with the ring in front the words sat at run-time offsets and every look at one began
+// with a v_mov_b32 from the SGPR that held the base.  The (yb, wb) rows, which the chain waves read at a wave-uniform
+// address, are out of the ring's blocks for the same reason.
 struct HxLds {
   static constexpr int kCkPad = 4;                                   // cells in front of a checkpoint buffer (beta's first slot writes cell -1)
   static constexpr int kCkCells = 2 * 4 * kHxOwnLanes + 2 * kCkPad;  // cells of one checkpoint row buffer
-  int ring;        // [2][kRingBlks] blocks of blk_bytes: (V+1) label rows of kRow doubles (row V: zeros) + 16 doubles (yb, wb) x 8 steps
+  static constexpr int bw = 4;                                       // wave slots of bnd
+  static constexpr int prog = 0;                                     // [2][8] ints
+  static constexpr int exw = prog + 2 * 8 * 4;                       // [2][kHaloSlots] ints
+  static constexpr int filled = exw + 2 * kHaloSlots * 4;            // [2][kRingBlks] ints; used: [dir][f] = the next block producer f of the direction has not finished yet
+  static constexpr int ckdone = filled + 2 * kRingBlks * 4;          // [2] ints (+ 2 of padding)
+  static constexpr int zacc = ckdone + 16;                           // [8] doubles
+  static constexpr int sortcnt = zacc + 64;                          // [130] ints (cellinfo_wave)
+  static constexpr int yw = (sortcnt + 130 * 4 + 15) & ~15;          // [2][kRingBlks] x 16 doubles: (yb, wb) of a block's 8 steps
+  static constexpr int bnd = yw + 2 * kRingBlks * 128;               // [2][bw][kHaloSlots][kHxHalo] x 4 doubles: wave w's edge lanes after block n (wave slots that hold no
+                                                                     //  cells stay zero: what the first / last wave of a direction reads as its neighbour's); bw = 4 wave slots
+                                                                     //  (waves 0, 1; slot 2: beta's "wave above the last", 3: alpha's "below the first")
+  static constexpr int dump = bnd + 2 * bw * kHaloSlots * kHxHalo * 32;   // 12 KB nobody reads: where lanes that have nothing to publish store
+  static constexpr int mxl = dump + 12288;                           // [2][kHaloSlots][4][64] ints
+  static constexpr int ckb = mxl + 2 * kHaloSlots * 4 * 64 * 4;      // [2][2][kCkCells] doubles: a checkpoint row's true cells in lattice order, double-buffered
+  static constexpr int ring = ckb + 2 * 2 * kCkCells * 8;            // [2][kRingBlks] blocks of blk_bytes: (V+1) label rows of kRow doubles (row V: zeros)
+  static_assert(filled % 8 == 0 && yw % 16 == 0 && bnd % 16 == 0 && dump % 16 == 0 && ckb % 16 == 0 && ring % 16 == 0, "alignment of the wide accesses");
   int blk_bytes;
-  int filled;      // [2][kRingBlks] ints; used: [dir][f] = the next block producer f of the direction has not finished yet
-  int sortcnt;     // [130] ints (cellinfo_wave)
-  int bnd;         // [2][bw][kHaloSlots][kHxHalo] x 4 doubles: wave w's edge lanes after block n (wave slots that hold no
-                   //  cells stay zero: what the first / last wave of a direction reads as its neighbour's); bw = 4 wave slots
-                   //  (waves 0, 1; slot 2: beta's "wave above the last", 3: alpha's "below the first")
-  int bw;          // (a field rather than a constant: as a constant it moves the chain wave's register allocation)
-  int dump;        // 12 KB nobody reads: where lanes that have nothing to publish store
-  int zacc;        // [8] doubles
-  int prog;        // [2][8] ints
-  int exw;         // [2][kHaloSlots] ints
-  int mxl;         // [2][kHaloSlots][4][64] ints
-  int ckb;         // [2][2][kCkCells] doubles: a checkpoint row's true cells in lattice order, double-buffered
-  int ckdone;      // [2] ints
   int total;
   __host__ __device__ HxLds(int V) {
-    bw = 4;
-    ring = 0;
-    blk_bytes = ((V + 1) * kRow + 16) * 8;
-    filled = ring + 2 * kRingBlks * blk_bytes;
-    sortcnt = filled + 2 * kRingBlks * 4;
-    bnd = (sortcnt + 130 * 4 + 15) & ~15;
-    dump = bnd + 2 * bw * kHaloSlots * kHxHalo * 32;
-    zacc = dump + 12288;
-    prog = zacc + 64;
-    exw = prog + 2 * 8 * 4;
-    mxl = exw + 2 * kHaloSlots * 4;
-    ckb = mxl + 2 * kHaloSlots * 4 * 64 * 4;
-    ckdone = ckb + 2 * 2 * kCkCells * 8;
-    total = ckdone + 16;
+    blk_bytes = (V + 1) * kRow * 8;
+    total = ring + 2 * kRingBlks * blk_bytes;
   }
 };
 
@@ -124,9 +120,16 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
   if (DIR == 0 && __any(badlab)) { if (lane == 0) atomicOr(&p.flags[b], 2); }
   const bool cond = (T > 1 || L == 1);            // ctc_loss.cpp:39,76
 
-  // LDS addresses that do not change: everything a block touches is one of these plus a constant
-  const int a_sync = hl.prog;                                                      // (uniform) the words of both directions
+  // LDS addresses that do not change: everything a block touches is one of these plus a constant.  The wave-uniform ones are
+  // constants (HxLds) on top of a VGPR that holds zero, which the compiler must take for a value it does not know: it then
+  // keeps the one register and puts the constant into the instruction, where it would otherwise move each address from an
+  // SGPR into a VGPR in front of its use.
+  int vz;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
+  const int a_sync = vz + hl.prog;                                                 // (uniform) the words of both directions
   const int o_prog = DIR * 32, o_exw = hl.exw - hl.prog + DIR * (kHaloSlots * 4), o_ckdone = hl.ckdone - hl.prog + 4 * DIR;
+  const int o_filled = hl.filled - hl.prog + DIR * (kRingBlks * 4);
+  const int a_up = a_sync + o_prog + 4 * up, a_me = a_sync + o_prog + 4 * w;        // the neighbour's progress word, the wave's own
   const int a_mxl = hl.mxl + ((DIR * kHaloSlots * 4 + w) * 64 + lane) * 4;         // + slot * 1024
   const int up_rec = DIR == 0 ? (w > 0 ? w - 1 : hl.bw - 1) : w + 1;          // (its edge records: the last wave slot is alpha's empty one)
   const int a_bnd_up = hl.bnd + ((DIR * hl.bw + up_rec) * kHaloSlots * kHxHalo + (lane & (kHxHalo - 1))) * 32;     // + slot * 256
@@ -139,16 +142,22 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
   int a_lab[kHxNP];
 #pragma unroll
   for (int r = 0; r < kHxNP; r++) a_lab[r] = ring_off + lab[r] * (kRow * 8);         // + slot * blk_bytes
-  const int a_yw = ring_off + (V + 1) * (kRow * 8);                                // (uniform)
+  const int a_yw = vz + hl.yw + DIR * (kRingBlks * 128);                           // (uniform) + slot * 128
 
   double Bc[kHxNP], Lc[kHxNP];                    // B~ (blank cells before their emission), L^ (label cells, tilted)
 #pragma unroll
   for (int r = 0; r < kHxNP; r++) { Bc[r] = 0.0; Lc[r] = 0.0; }
   double yb_prev = 0.0, wb_prev = 0.0;
   int e_total = 0;
-  int nck = 0, ckbuf = 0;
+  // checkpoint rows alternate between the two buffers by the parity of their slot k: alpha's first is row 15 (k = 1), beta's
+  // first the largest 16 k <= 8 M (k = M >> 1)
+  int nck = 0, ckoff = (DIR == 0 ? 1 : (M >> 1) & 1) * (HxLds::kCkCells * 8);
   int lead = 0;
-  auto need_blocks = [&](int k) {
+  static_assert(kHxProducers == 2, "the early look reads the two producers' words as one 8-byte pair");
+  // `early`: the producers' words as read two steps ago (a lower bound of where they are now: the words only grow); the
+  // spin re-reads them only if that is not enough
+  auto need_blocks = [&](int k, h_i2 early) {
+    if (lead < k) lead = __builtin_amdgcn_readfirstlane(min(early.x, early.y));
     if (lead < k) {
       PROF_SPIN_BEGIN
       for (;;) {
@@ -167,9 +176,10 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
   double e[kHxNP][kBlk], ybw[2 * kBlk];
   // steps 4H .. 4H+3 of the block in ring slot `slot`.  The reads are issued so that what is used FIRST (step 4H) is asked for
   // LAST: the wait in front of that first use then covers the whole half, instead of one wait per register pair
-  auto load_half = [&](int slot_bytes, auto half_tag) {
+  auto load_half = [&](int slot, auto half_tag) {
     constexpr int H = decltype(half_tag)::value;
-    lds_u8* py = L0 + (a_yw + slot_bytes);
+    const int slot_bytes = slot * hl.blk_bytes;
+    lds_u8* py = L0 + (a_yw + slot * 128);
 #pragma unroll
     for (int q = 3; q >= 1; q--) {
       const h_d2 y = *(volatile lds_d2*)(py + 64 * H + 16 * q);
@@ -207,10 +217,10 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
     const int pslot = SLOT >= 0 ? ((SLOT + 7) & (kRingBlks - 1)) : ((n + 7) & (kRingBlks - 1));
     const bool refill = SLOT >= 0 ? (SLOT % kHxNP) == 0 : (n % kHxNP) == 0;
     const bool publish = SLOT >= 0 ? (SLOT % kHxNP) == kHxNP - 1 : (n % kHxNP) == kHxNP - 1;
-    load_half(slot * hl.blk_bytes, std::integral_constant<int, 1>{});
+    load_half(slot, std::integral_constant<int, 1>{});
     if (refill && (STEADY || n > 0)) {
       if (__builtin_amdgcn_readfirstlane(hprog) < n) {
-        PROF_SPIN_BEGIN HALO_WAIT(__builtin_amdgcn_readfirstlane(*(volatile lds_int*)(L0 + a_sync + o_prog + 4 * up)) >= n); PROF_SPIN_END(prof_nb)
+        PROF_SPIN_BEGIN HALO_WAIT(__builtin_amdgcn_readfirstlane(*(volatile lds_int*)(L0 + a_up)) >= n); PROF_SPIN_END(prof_nb)
         read_edge(pslot, hv);
       }
       if (halo) {
@@ -221,18 +231,23 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
     const bool want_next = STEADY ? true : n + 1 < nblk;
     const int tbase = block_time(DIR, n, 0, T);
     int xw = 0;
+    h_i2 fill2 = h_i2{0, 0};
 #pragma unroll
     for (int tt = 0; tt < kBlk; tt++) {
       const int t = DIR == 0 ? tbase + tt : tbase - tt;
       const double yb = ybw[2 * tt], wb = ybw[2 * tt + 1];
+      if (tt == 2 && want_next) {                  // (looked at in step 4; the barrier keeps the scheduler from sinking the read to there)
+        fill2 = *(volatile lds_i2*)(L0 + a_sync + o_filled);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       if (tt == 4) {
         xw = *(volatile lds_int*)(L0 + a_sync + o_exw + 4 * slot);
         if (CK != 0) ckd = *(volatile lds_int*)(L0 + a_sync + o_ckdone);
-        if (want_next) need_blocks(n + 2);
-        load_half(nslot * hl.blk_bytes, std::integral_constant<int, 0>{});
+        if (want_next) need_blocks(n + 2, fill2);
+        load_half(nslot, std::integral_constant<int, 0>{});
       }
       if (tt == 6 && publish) {                    // (speculative: valid if the neighbour has finished block n by now)
-        hprog = *(volatile lds_int*)(L0 + a_sync + o_prog + 4 * up);
+        hprog = *(volatile lds_int*)(L0 + a_up);
         read_edge(slot, hv);
       }
       if (STEADY || t < T) {
@@ -293,19 +308,20 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
           const int kk = DIR == 0 ? (t + 1) : t;            // alpha row 16k-1 / beta row 16k -> slot k
           if ((CK >= 0 ? CK == 1 : ((kk & (kSeg - 1)) == 0 && kk > 0 && kk < T))) {
             // (two buffers: the checkpoint wave has 16 steps for each and is normally long done with the row before last)
-            if (nck >= 2 && __builtin_amdgcn_readfirstlane(ckd) < nck - 1)
+            // (ckd >= 0: the first two rows never wait)
+            if (__builtin_amdgcn_readfirstlane(ckd) < nck - 1)
               HALO_WAIT(__builtin_amdgcn_readfirstlane(*(volatile lds_int*)(L0 + a_sync + o_ckdone)) >= nck - 1);
-            if (nck == 0) ckbuf = (kk / kSeg) & 1;
             nck++;
-            // the true cells (blank with its emission, label without the tilt), in lattice order
-            lds_u8* dst = L0 + (a_ck + ckbuf * (HxLds::kCkCells * 8));
+            // the true cells (blank with its emission, label without the tilt), in lattice order: one 16-byte store per pair
+            // (beta's pairs begin with the label cell, at 8 bytes past a 16-byte boundary: the 8-byte aligned form)
+            lds_u8* dst = L0 + (a_ck + ckoff);
 #pragma unroll
             for (int r = 0; r < kHxNP; r++) {
               const double cb = Bc[r] * yb_prev, cl = Lc[r] * inv_rr;
-              if (DIR == 0) { *(volatile lds_f64*)(dst + 16 * r) = cb; *(volatile lds_f64*)(dst + 16 * r + 8) = cl; }
-              else { *(volatile lds_f64*)(dst + 16 * r) = cl; *(volatile lds_f64*)(dst + 16 * r + 8) = cb; }
+              if (DIR == 0) { h_d2 c; c.x = cb; c.y = cl; *(volatile lds_d2*)(dst + 16 * r) = c; }
+              else { h_d2 c; c.x = cl; c.y = cb; *(volatile lds_d2_a8*)(dst + 16 * r) = c; }
             }
-            ckbuf ^= 1;
+            ckoff ^= HxLds::kCkCells * 8;
           }
         }
       }
@@ -314,11 +330,11 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
 #pragma unroll
       for (int r = 0; r < kHxNP; r++) { h_d2 v; v.x = Bc[r]; v.y = Lc[r]; *(volatile lds_d2*)(L0 + a_bnd_my + slot * 256 + 16 * r) = v; }
     }
-    *(volatile lds_int*)(L0 + a_sync + o_prog + 4 * w) = n + 1;
+    *(volatile lds_int*)(L0 + a_me) = n + 1;
   };
   {
     typedef std::integral_constant<int, -1> Any;
-    need_blocks(1);
+    need_blocks(1, h_i2{0, 0});
     HX_TL(2)
     load_half(0, std::integral_constant<int, 0>{});
     const int steady_end = DIR == 0 ? T / kBlk : nblk;         // blocks [1, steady_end - 1) are steady (live, with a successor)
@@ -414,7 +430,7 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
   lds_u8* prog = L0 + hl.prog + DIR * 32;
   const int a_fill = hl.filled + (DIR * kRingBlks + first) * 4;
   const int a_row = hl.ring + DIR * kRingBlks * hl.blk_bytes + (l8 * kRow + tt) * 8;       // + slot * blk_bytes + k * 8 * kRow * 8
-  const int a_yw = hl.ring + DIR * kRingBlks * hl.blk_bytes + ((V + 1) * kRow + 2 * tt) * 8;
+  const int a_yw = hl.yw + DIR * (kRingBlks * 128) + 2 * tt * 8;                   // + slot * 128
   const int kb = p.blank >> 3;
   const bool blank_lane = l8 == (p.blank & 7);
 
@@ -507,7 +523,7 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
       float ybl = y[0];
 #pragma unroll
       for (int k = 1; k < NV; k++) ybl = kb == k ? y[k] : ybl;
-      if (blank_lane) { h_d2 yw; yw.x = (double)ybl; yw.y = rr2 * (double)ybl; *(volatile lds_d2*)(L0 + (a_yw + sb)) = yw; }
+      if (blank_lane) { h_d2 yw; yw.x = (double)ybl; yw.y = rr2 * (double)ybl; *(volatile lds_d2*)(L0 + (a_yw + (n & (kRingBlks - 1)) * 128)) = yw; }
     }
     if (DIR == 0 && row_live) {
       float* yrow = yl + (size_t)(t >> 4) * V * kSeg + (t & (kSeg - 1));

@@ -290,6 +290,9 @@ typedef int h_i4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) h_d2 lds_d2;      // (every LDS access of these waves is a DS operation: a wave's DS
 typedef __attribute__((address_space(3))) double lds_f64;   //  operations execute in order, which the hand-off words rely on)
 typedef __attribute__((address_space(3))) h_i4 lds_i4;
+typedef int h_i2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) h_i2 lds_i2;
+typedef __attribute__((address_space(3), aligned(8))) h_d2 lds_d2_a8;    // a pair of doubles at an 8-byte aligned address
 
 // smallest / largest of the eight words at a 32-byte aligned LDS address (wave-uniform)
 __device__ __forceinline__ int lds_min8(lds_u8* a) {

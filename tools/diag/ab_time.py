@@ -45,4 +45,5 @@ for rnd in range(12):
         e1.record(); torch.cuda.synchronize()
         res[k].append(e0.elapsed_time(e1) / 20 * 1e3)
 for k, v in res.items():
-    print("%-28s median %.1f us  min %.1f us" % (k, statistics.median(v), min(v)))
+    q = statistics.quantiles(v, n=4)
+    print("%-28s median %.1f us  min %.1f us  max %.1f us  quartiles %.1f .. %.1f us" % (k, statistics.median(v), min(v), max(v), q[0], q[2]))
