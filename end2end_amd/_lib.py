@@ -124,6 +124,16 @@ def load():
                                                  C.c_int, i64p, i64, i64p, i64p, vp, vp, vp, C.c_size_t, vp]
         L.e2e_gram_ctc_beam_nbest_opt.restype = C.c_int
         L.e2e_gram_ctc_beam_nbest_opt.argtypes = L.e2e_gram_ctc_beam_nbest_lm.argtypes + [C.POINTER(GramBeamOpts)]
+        L.e2e_gram_beam_stream_row_bytes.restype = C.c_size_t
+        L.e2e_gram_beam_stream_row_bytes.argtypes = [C.c_int] * 6
+        L.e2e_gram_beam_stream_workspace_bytes.restype = C.c_size_t
+        L.e2e_gram_beam_stream_workspace_bytes.argtypes = [C.c_int] * 6
+        L.e2e_gram_ctc_beam_stream.restype = C.c_int
+        L.e2e_gram_ctc_beam_stream.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
+                                               vp, C.c_size_t, C.c_int,
+                                               C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p,
+                                               vp, C.c_size_t, vp, C.POINTER(GramBeamOpts)]
         L.e2e_asg_beam_max_width.restype = C.c_int
         L.e2e_asg_beam_max_width.argtypes = [C.c_int]
         L.e2e_asg_beam_workspace_bytes.restype = C.c_size_t

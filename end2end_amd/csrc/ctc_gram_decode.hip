@@ -28,6 +28,13 @@
 // rule of the header is applied per base id, which walk_gram<LEX> decides at the places where it asks the model anyway; a
 // member's answer row also says which of its children exist, and a pair without a child is dropped before it claims a table
 // entry, so an inadmissible sequence never has one.  The timesteps are read off the nodes' numbers in the read-out.
+//
+// Fed in chunks (e2e_gram_ctc_beam_stream, the ST instances): between two frames the search is one Members set, with the LM
+// fields one LmMembers set, n_mem, esum, the overflow flag and the node pool -- that is an utterance's state row, which the
+// caller owns (header | Members | LmMembers | nodes).  The candidate table is empty between frames, the pair buffers are a
+// frame's scratch, and the answer cache is refilled at resume from the members' own sequences (rows 0 .. n_mem - 1), as the
+// per-frame refill fills a new member's row.  Node numbers count the frames of the stream.  DESIGN.md 4.7, Streaming.
+#include <cstddef>
 #include <cstring>
 #include <type_traits>
 
@@ -197,8 +204,33 @@ struct GramLmParams {
 // the parameter block of the instances of e2e_gram_ctc_beam_nbest_opt (LEX or TS): the LM instance's and what it lacks.  A
 // block of its own, so that the two instances that were there before keep theirs, and with it their code.
 struct GramOptParams { GramLmParams l; int64_t* timesteps; };   // (B,nbest,max_out): the TS instances only
-template <bool LM, bool OPT> using GramKernelParams =
-    typename std::conditional<OPT, GramOptParams, typename std::conditional<LM, GramLmParams, GramBeamParams>::type>::type;
+
+// ---- the state row of a stream (e2e_gram_ctc_beam_stream): header (256 bytes) | Members | LmMembers (scored) | node pool ----
+// Indices only, never an address: a row may be moved or copied.  magic == 0 -- what a zeroed header has -- is a fresh utterance.
+// A status (too many frames, another configuration) stores nothing, so a stored row carries no error flag.  The layout of the
+// header is part of the interface (include/e2e_ctc.h): 4-byte fields in this order, esum at byte 56.
+constexpr unsigned kGramStreamMagic = 0x4d415247u;
+constexpr int kGramStreamHeaderBytes = 256;
+struct GramStreamHeader {
+  unsigned magic;
+  int V, K, R, W, scored, has_lm, restricted, max_frames;   // the configuration the row was written under (R: 0 unless scored)
+  int n, frames, overflow, dead;         // members, frames consumed, the sticky overflow flag, 1: no hypothesis is left (n == 0)
+  int pad;
+  long long esum;                        // exponents taken out of the frames so far
+};
+static_assert(sizeof(GramStreamHeader) <= kGramStreamHeaderBytes && offsetof(GramStreamHeader, esum) == 56, "stream header");
+constexpr int kGramStreamTooManyFrames = -2, kGramStreamOtherConfig = -3;
+// what the streaming call adds to the whole call's parameters (whose x_len is then the chunk's lengths, T its width; ws holds
+// no nodes).  cfg: the header a row of this call's configuration has, the run-time fields zero
+struct GramStream {
+  unsigned char* rows; size_t row_bytes, off_lm, off_nodes;   // (B,row_bytes); the LM fields and the node pool inside a row
+  int64_t* frames_done;                  // (B): frames consumed so far, or the in-band status
+  GramStreamHeader cfg;
+};
+// one block for the three ST instances: the plain one reads o.l.b alone
+struct GramStreamParams { GramOptParams o; GramStream s; };
+template <bool LM, bool OPT, bool ST = false> using GramKernelParams = typename std::conditional<ST, GramStreamParams,
+    typename std::conditional<OPT, GramOptParams, typename std::conditional<LM, GramLmParams, GramBeamParams>::type>::type>::type;
 __device__ __forceinline__ const GramBeamParams& beam_of(const GramBeamParams& q) { return q; }
 __device__ __forceinline__ const GramBeamParams& beam_of(const GramLmParams& q) { return q.b; }
 __device__ __forceinline__ const GramBeamParams& search_of(const GramBeamParams& q) { return q; }
@@ -207,6 +239,17 @@ __device__ __forceinline__ const GramLmParams& search_of(const GramOptParams& q)
 __device__ __forceinline__ int64_t* timesteps_of(const GramBeamParams&) { return nullptr; }
 __device__ __forceinline__ int64_t* timesteps_of(const GramLmParams&) { return nullptr; }
 __device__ __forceinline__ int64_t* timesteps_of(const GramOptParams& q) { return q.timesteps; }
+__device__ __forceinline__ int64_t* timesteps_of(const GramStreamParams& q) { return q.o.timesteps; }
+__device__ __forceinline__ GramStream stream_of(const GramBeamParams&) { return GramStream{}; }
+__device__ __forceinline__ GramStream stream_of(const GramLmParams&) { return GramStream{}; }
+__device__ __forceinline__ GramStream stream_of(const GramOptParams&) { return GramStream{}; }
+__device__ __forceinline__ const GramStream& stream_of(const GramStreamParams& q) { return q.s; }
+// the search's own block inside the kernel's: the stream's block holds the widest, of which an instance reads its part
+template <bool LM, typename P> __device__ __forceinline__ const auto& search_in(const P& kp) {
+  if constexpr (std::is_same<P, GramStreamParams>::value) {
+    if constexpr (LM) return kp.o.l; else return kp.o.l.b;
+  } else return search_of(kp);
+}
 
 // the fields of one sequence, in registers
 struct LmWalk {
@@ -297,17 +340,54 @@ __device__ __forceinline__ double total_of(const GramLmParams& q, double ac, dou
   return ac + lm * q.lmwt - (double)nw * q.wip + (double)noov * q.oov;
 }
 
+// ---- the phases of a streaming call, compiled into the ST instances only ----
+// What the row says before a chunk of Tc frames: the frames consumed so far (a fresh row: 0, resume = false) or a status < 0;
+// n, esum, ovf: what the search resumes with.  The same for every thread of the workgroup (returned wave-uniform).
+__device__ __forceinline__ int gram_stream_open(const GramStream& sp, const unsigned char* row, int Tc, bool& resume, int& n,
+                                                long long& esum, int& ovf) {
+  const GramStreamHeader h = *reinterpret_cast<const GramStreamHeader*>(row);
+  const GramStreamHeader& c = sp.cfg;
+  int st = 0, res = 0, nn = 1, ov = 0;
+  long long es = 0;
+  if (h.magic != 0u) {
+    const bool same = h.magic == c.magic && h.V == c.V && h.K == c.K && h.R == c.R && h.W == c.W && h.scored == c.scored &&
+                      h.has_lm == c.has_lm && h.restricted == c.restricted && h.max_frames == c.max_frames &&
+                      h.n >= 0 && h.n <= c.W && h.dead == (h.n == 0 ? 1 : 0) && (h.overflow == 0 || h.overflow == 1) &&
+                      h.frames >= 1 && h.frames <= c.max_frames;
+    if (same) { st = h.frames; res = 1; nn = h.n; ov = h.overflow; es = h.esum; } else st = kGramStreamOtherConfig;
+  }
+  if (st >= 0 && st + Tc > c.max_frames) st = kGramStreamTooManyFrames;
+  resume = __builtin_amdgcn_readfirstlane(res) != 0;
+  n = __builtin_amdgcn_readfirstlane(nn);
+  ovf = __builtin_amdgcn_readfirstlane(ov);
+  esum = ((long long)__builtin_amdgcn_readfirstlane((int)(es >> 32)) << 32) |
+         (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)es);
+  return __builtin_amdgcn_readfirstlane(st);
+}
+// a member set between LDS and the row, as it stands (all threads; plain vector loads and stores)
+__device__ __forceinline__ void gram_stream_copy(void* dst, const void* src, size_t bytes) {
+  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(dst);
+  for (size_t i = threadIdx.x; i < bytes / 8; i += kBeamThreads) d[i] = s[i];
+}
+static_assert(sizeof(Members) % 8 == 0 && sizeof(LmMembers) % 8 == 0, "the member sets are copied in 8-byte words");
+
 // LM = false: the search on the masses alone (e2e_gram_ctc_beam_nbest), the parameter block GramBeamParams.  LM = true: the
 // cut and the ranking on the totals with the language model's fields (e2e_gram_ctc_beam_nbest_lm).
 // LEX (with LM): the search restricted to the model's lexicon -- the answer row of a member's children also says which of
 // them there are (nw = kNoChild: none), and a pair without a child is dropped before it claims a table entry.  TS (with LM):
 // the read-out also writes the frame each id's node was created at.  Instances of their own with a parameter block of their
 // own: without LEX and TS the two kernels are the code they were, instruction for instruction (tools/diag/isa_compare.py).
-template <bool LM, bool LEX = false, bool TS = false>
-__global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParams<LM, LEX || TS> kp) {
+// ST: the search fed in chunks (e2e_gram_ctc_beam_stream): resume from the state row, run the chunk's frames as frames f0 .. of
+// the stream, suspend; the timesteps are then a run-time test on the pointer (TS is not read).  Without ST the code the kernel
+// had before it could stream, instruction for instruction (profiles/gram_decode/isa_identity_stream.txt).
+template <bool LM, bool LEX = false, bool TS = false, bool ST = false>
+__global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParams<LM, LEX || TS, ST> kp) {
   static_assert(LM || !(LEX || TS), "the restricted search and the timesteps are the LM instance's");
-  const auto& q = search_of(kp);
+  static_assert(!(ST && TS), "a stream tests the timesteps' pointer");
+  const auto& q = search_in<LM>(kp);
   const GramBeamParams& p = beam_of(q);
+  const GramStream& sp = stream_of(kp);
   __shared__ Members mem[2];
   __shared__ BeamCut cut;
   __shared__ int n_cand, n_surv, overflow;
@@ -332,23 +412,52 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
   double* ctot = reinterpret_cast<double*>(ws + p.off_tot);
   unsigned long long* sval = reinterpret_cast<unsigned long long*>(ws + p.off_sval);
   int* spos = reinterpret_cast<int*>(ws + p.off_spos);
-  int2* nodes = reinterpret_cast<int2*>(ws + p.off_nodes);
+  unsigned char* row = ST ? sp.rows + (size_t)b * sp.row_bytes : nullptr;   // the utterance's state row
+  int2* nodes = reinterpret_cast<int2*>(ST ? row + sp.off_nodes : ws + p.off_nodes);
   const unsigned H = 1u << p.logH, hmask = H - 1u;
   const int64_t Tq = p.x_len[b];
   const int Tb = Tq < 0 ? 0 : (Tq > p.T ? p.T : (int)Tq);
+  int f0 = 0, n0 = 1, ovf0 = 0;                                   // the stream's frames before this chunk; what it resumes with
+  long long esum0 = 0;
+  bool resume = false;
+  if constexpr (ST) {
+    f0 = gram_stream_open(sp, row, Tb, resume, n0, esum0, ovf0);
+    // a status: nothing of the row or the utterance is touched
+    if (f0 < 0) {
+      if (tid == 0) { sp.frames_done[b] = f0; if (p.nbest) p.n_hyp[b] = f0; }
+      return;
+    }
+  }
 
   for (unsigned i = tid; i < H; i += kBeamThreads) { table[i].key = 0ull; table[i].head = -1; }
   if constexpr (LM) { if (tid < kMaxW) { S->lms[0].row[tid] = 0; S->lms[1].row[tid] = 0; } }   // (never a row outside the cache)
-  if (tid == 0) {
+  if (ST && resume) {                                            // the row's members become set 0
+    gram_stream_copy(&mem[0], row + kGramStreamHeaderBytes, sizeof(Members));
+    if constexpr (LM) gram_stream_copy(&S->lms[0], row + sp.off_lm, sizeof(LmMembers));
+    if (tid == 0) overflow = ovf0;
+  } else if (tid == 0) {
     for (int k = 0; k <= kMaxK; k++) { mem[0].p[k][0] = k == 0 ? 1.0 : 0.0; mem[0].col[k][0] = 0; }
     mem[0].key[0] = kKeyBasis; mem[0].tot[0] = 1.0; mem[0].node[0] = 0; mem[0].len[0] = 0;
-    nodes[0] = make_int2(-1, 0);
+    if (!ST || Tb > 0) nodes[0] = make_int2(-1, 0);              // (a chunk of no frames stores nothing)
     overflow = 0;
     if constexpr (LM) { store_walk(S->lms[0], 0, root_walk(q)); S->lms[0].row[0] = 0; }
   }
   __syncthreads();
-  if constexpr (LM) {                                            // the root's children, into row 0
-    if (q.has_lm && Tb > 0)
+  if constexpr (LM) {
+    if (ST && resume) {
+      // the answer cache is not stored: the resumed members take rows 0 .. n - 1 and their children's answers are computed as
+      // the per-frame refill computes a new member's.  They are functions of the sequence, so no bit depends on the row
+      if (tid < kMaxW) S->lms[0].row[tid] = tid < n0 ? tid : 0;
+      __syncthreads();
+      if (q.has_lm && Tb > 0)
+        for (int i = tid; i < n0 * V; i += kBeamThreads) {
+          const int r = i / V, c = i - r * V;
+          if (c == 0) continue;
+          LmWalk w = load_walk(S->lms[0], r);
+          const bool child = walk_gram<LEX>(q, w, c, order_of(p.gram_len, c, K));
+          cache[(size_t)r * V + c] = Answer{w.lm, child ? w.nw : kNoChild, w.oov};
+        }
+    } else if (q.has_lm && Tb > 0)                                // the root's children, into row 0
       for (int c = 1 + tid; c < V; c += kBeamThreads) {
         LmWalk w = load_walk(S->lms[0], 0);
         const bool child = walk_gram<LEX>(q, w, c, order_of(p.gram_len, c, K));
@@ -356,8 +465,8 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
       }
   }
 
-  int cur = 0, n_mem = 1;
-  long long esum = 0;                                           // exponents taken out of the frames so far
+  int cur = 0, n_mem = ST ? n0 : 1;
+  long long esum = ST ? esum0 : 0;                              // exponents taken out of the frames so far
   for (int t = 0; t < Tb && n_mem > 0; t++) {
     const Members& M = mem[cur];
     Members& N = mem[cur ^ 1];
@@ -515,7 +624,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
       } else {
         const unsigned pid = (unsigned)E.pair < n_ids ? (unsigned)E.pair : 0u;
         const unsigned pm = pid / (unsigned)V, pc = pid - pm * (unsigned)V;
-        const int node = 1 + t * W + r;
+        const int node = 1 + (ST ? f0 + t : t) * W + r;          // (a stream's nodes count the stream's frames)
         nodes[node] = make_int2(M.node[pm], (int)pc);
         N.node[r] = node; N.len[r] = M.len[pm] + order_of(p.gram_len, (int)pc, K);
         if constexpr (LM) {                                      // a new prefix: its parent's fields walked through the gram
@@ -553,30 +662,50 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
     __syncthreads();
   }
 
+  // ---- suspend, behind the chunk's last frame: the current set, then the header.  A chunk of no frames stores nothing ----
+  if constexpr (ST) {
+    if (Tb > 0) {
+      gram_stream_copy(row + kGramStreamHeaderBytes, &mem[cur], sizeof(Members));
+      if constexpr (LM) gram_stream_copy(row + sp.off_lm, &S->lms[cur], sizeof(LmMembers));
+    }
+    if (tid == 0) {
+      if (Tb > 0) {
+        GramStreamHeader h = sp.cfg;
+        h.n = n_mem; h.frames = f0 + Tb; h.overflow = overflow ? 1 : 0; h.dead = n_mem == 0 ? 1 : 0; h.pad = 0; h.esum = esum;
+        *reinterpret_cast<GramStreamHeader*>(row) = h;
+      }
+      sp.frames_done[b] = f0 + Tb;
+    }
+    if (p.nbest == 0) return;                                    // feed only
+  }
+
   // ---- read-out: the first nbest members, ranked already ----
   const Members& F = mem[cur];
   const int nbest = p.nbest;
   const int64_t max_out = p.max_out;
+  const bool want_ts = ST ? timesteps_of(kp) != nullptr : TS;
+  const int max_hops = ST ? f0 + Tb : p.T;                       // a sequence has at most one node per frame consumed
   int64_t* out = p.out + (int64_t)b * nbest * max_out;
   int64_t* ts = nullptr;
-  if constexpr (TS) ts = timesteps_of(kp) + (int64_t)b * nbest * max_out;
+  if (want_ts) ts = timesteps_of(kp) + (int64_t)b * nbest * max_out;
   if (tid < nbest) {
     int64_t* row = out + (int64_t)tid * max_out;
     int64_t* trow = nullptr;
-    if constexpr (TS) trow = ts + (int64_t)tid * max_out;
+    if (want_ts) trow = ts + (int64_t)tid * max_out;
     int len = 0; double score = -__builtin_huge_val();
     if (tid < n_mem) {
       len = F.len[tid];
       score = log(F.tot[tid]) + (double)esum * 0.6931471805599453094;
       int at = len, node = F.node[tid];
-      for (int hops = 0; node > 0 && hops <= p.T; hops++) {
+      for (int hops = 0; node > 0 && hops <= max_hops; hops++) {
+        if constexpr (ST) { if (node > W * sp.cfg.max_frames) break; }   // (no node of this row's pool: the row is not this call's)
         const int2 nd = nodes[node];
         const int k = order_of(p.gram_len, nd.y, K);
         for (int j = k - 1; j >= 0; j--) {
           --at;
           if (at >= 0 && at < max_out) {
             row[at] = (int64_t)p.gram_ids[nd.y * kMaxK + j];
-            if constexpr (TS) trow[at] = (int64_t)((node - 1) / W);   // node = 1 + t * W + rank: a gram's ids share the frame
+            if (want_ts) trow[at] = (int64_t)((node - 1) / W);   // node = 1 + t * W + rank: a gram's ids share the frame
           }
         }
         node = nd.x;
@@ -602,7 +731,7 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
   for (int j = 0; j < nbest; j++) {
     int64_t* row = out + (int64_t)j * max_out;
     for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kBeamThreads) row[i] = 0;
-    if constexpr (TS) for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kBeamThreads) ts[(int64_t)j * max_out + i] = -1;
+    if (want_ts) for (int64_t i = cut.sel_pos[j] + tid; i < max_out; i += kBeamThreads) ts[(int64_t)j * max_out + i] = -1;
   }
   if (tid == 0) p.n_hyp[b] = overflow ? -1 : (n_mem < nbest ? n_mem : nbest);
 }
@@ -629,7 +758,7 @@ bool beam_layout(int T, int V, int K, int W, BeamLayout& L, bool with_lm = false
 }
 
 // every argument error of the two n-best calls that the host can see, before any launch
-int check_beam_args(int dtype, int B, int T, int V, int max_order, int beam_width, int nbest, int64_t max_out) {
+int check_beam_args(int dtype, int B, int T, int V, int max_order, int beam_width, int nbest, int64_t max_out, int min_nbest = 1) {
   if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
   if (B < 0 || T < 1 || V < 1 || max_out < 0) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
   if (max_order < 1 || max_order > kMaxK) { set_error("max_order %d is not in [1, %d]", max_order, kMaxK); return E2E_ERR_ARG; }
@@ -639,8 +768,59 @@ int check_beam_args(int dtype, int B, int T, int V, int max_order, int beam_widt
               e2e_gram_beam_max_width(V, max_order));
     return E2E_ERR_UNSUPPORTED;
   }
-  if (nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (nbest < min_nbest || nbest > beam_width) { set_error("nbest=%d outside [%d, beam_width=%d]", nbest, min_nbest, beam_width); return E2E_ERR_ARG; }
   return E2E_OK;
+}
+
+// ... of the scored calls (e2e_gram_ctc_beam_nbest_opt and the scored stream): the base labels, the space, the model
+int check_scored_args(int V, int num_base_labels, int space_id, const e2e_lm* lm, bool restricted) {
+  if (num_base_labels < 1 || num_base_labels > V) { set_error("num_base_labels=%d outside [1, V=%d]", num_base_labels, V); return E2E_ERR_ARG; }
+  if (space_id >= num_base_labels) { set_error("space_id=%d is not one of the %d base labels", space_id, num_base_labels); return E2E_ERR_ARG; }
+  if (lm) {
+    if (lm->transcribed || (lm->words_only && !restricted)) {
+      set_error("the Gram-CTC search spells its words from the base labels' strings: a model with custom transcriptions "
+                "(e2e_lm_load_transcriptions) is not supported, and a word list (e2e_lm_load_words) only by a search that is "
+                "restricted to it (e2e_gram_ctc_beam_nbest_opt, restrict_to_lexicon)");
+      return E2E_ERR_ARG;
+    }
+    if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_ARG; }
+    if ((int)lm->label_off.size() - 1 != num_base_labels) {
+      set_error("the language model was loaded with %d labels but the table has num_base_labels=%d",
+                (int)lm->label_off.size() - 1, num_base_labels);
+      return E2E_ERR_ARG;
+    }
+  }
+  if (restricted && (!lm || !lm->has_lexicon)) {
+    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+    return E2E_ERR_ARG;
+  }
+  return E2E_OK;
+}
+// ... and the device the model's tables are on
+int check_model_device(const e2e_lm* lm) {
+  if (!lm) return E2E_OK;
+  if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
+  int dev = -1;
+  E2E_HIP_CHECK(hipGetDevice(&dev), "hipGetDevice");
+  if (dev != lm->device) {
+    set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, dev);
+    return E2E_ERR_ARG;
+  }
+  return E2E_OK;
+}
+
+// a state row of a stream: header | Members | LmMembers (scored) | node pool of max_frames frames, each part 256-aligned.  The
+// workspace of a streaming call: a frame's scratch (beam_layout's up to the nodes, which are the row's) and, with a model,
+// the answer cache in the nodes' place
+struct StreamLayout { size_t off_lm, off_nodes, total, ws_per_utt; };
+bool stream_layout(int max_frames, int V, int K, int W, bool scored, bool with_lm, StreamLayout& S, BeamLayout& L) {
+  if (max_frames < 1 || max_frames > (1 << 22) || (with_lm && !scored) || !beam_layout(1, V, K, W, L, with_lm)) return false;
+  S.off_lm = kGramStreamHeaderBytes + align_up(sizeof(Members), 256);
+  S.off_nodes = S.off_lm + (scored ? align_up(sizeof(LmMembers), 256) : 0);
+  S.total = S.off_nodes + align_up(((size_t)W * ((size_t)max_frames + 1) + 1) * 8, 256);
+  S.ws_per_utt = L.off_nodes + (L.per_utt - L.off_cache);
+  L.off_cache = L.off_nodes;
+  return true;
 }
 
 }  // namespace
@@ -717,41 +897,14 @@ int e2e_gram_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t s
   const bool restricted = opts && opts->restrict_to_lexicon != 0;
   int64_t* timesteps = opts ? opts->timesteps : nullptr;
   if (const int rc = check_beam_args(dtype, B, T, V, max_order, beam_width, nbest, max_out)) return rc;
-  if (num_base_labels < 1 || num_base_labels > V) { set_error("num_base_labels=%d outside [1, V=%d]", num_base_labels, V); return E2E_ERR_ARG; }
-  if (space_id >= num_base_labels) { set_error("space_id=%d is not one of the %d base labels", space_id, num_base_labels); return E2E_ERR_ARG; }
-  if (lm) {
-    if (lm->transcribed || (lm->words_only && !restricted)) {
-      set_error("the Gram-CTC search spells its words from the base labels' strings: a model with custom transcriptions "
-                "(e2e_lm_load_transcriptions) is not supported, and a word list (e2e_lm_load_words) only by a search that is "
-                "restricted to it (e2e_gram_ctc_beam_nbest_opt, restrict_to_lexicon)");
-      return E2E_ERR_ARG;
-    }
-    if (lm->order > kLmMaxOrder) { set_error("a language model of order %d: at most %d", lm->order, kLmMaxOrder); return E2E_ERR_ARG; }
-    if ((int)lm->label_off.size() - 1 != num_base_labels) {
-      set_error("the language model was loaded with %d labels but the table has num_base_labels=%d",
-                (int)lm->label_off.size() - 1, num_base_labels);
-      return E2E_ERR_ARG;
-    }
-  }
-  if (restricted && (!lm || !lm->has_lexicon)) {
-    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
-    return E2E_ERR_ARG;
-  }
+  if (const int rc = check_scored_args(V, num_base_labels, space_id, lm, restricted)) return rc;
   BeamLayout L;
   if (!beam_layout(T, V, max_order, beam_width, L, lm != nullptr)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
   if (B > 0 && (!lp || !x_len || !gram_ids || !gram_len || !out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
     set_error("null pointer argument"); return E2E_ERR_ARG;
   }
   if (B == 0) return E2E_OK;
-  if (lm) {
-    if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
-    int dev = -1;
-    E2E_HIP_CHECK(hipGetDevice(&dev), "hipGetDevice");
-    if (dev != lm->device) {
-      set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, dev);
-      return E2E_ERR_ARG;
-    }
-  }
+  if (const int rc = check_model_device(lm)) return rc;
   if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < (size_t)B * L.per_utt) {
     set_error("workspace too small: %zu bytes, e2e_gram_beam_workspace_bytes_lm() = %zu", workspace_bytes, (size_t)B * L.per_utt + 256);
     return E2E_ERR_WORKSPACE;
@@ -785,6 +938,80 @@ int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT
   return e2e_gram_ctc_beam_nbest_opt(lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, num_base_labels,
                                      beam_width, space_id, lm, lmwt, wip, oov_penalty, nbest, out, max_out, out_len, n_hyp,
                                      scores, counts, workspace, workspace_bytes, stream, nullptr);
+}
+
+size_t e2e_gram_beam_stream_row_bytes(int max_frames, int V, int max_order, int beam_width, int scored, int with_lm) {
+  StreamLayout S;
+  BeamLayout L;
+  return stream_layout(max_frames, V, max_order, beam_width, scored != 0, with_lm != 0, S, L) ? S.total : 0;
+}
+
+size_t e2e_gram_beam_stream_workspace_bytes(int B, int V, int max_order, int beam_width, int scored, int with_lm) {
+  StreamLayout S;
+  BeamLayout L;
+  if (B < 0 || !stream_layout(1, V, max_order, beam_width, scored != 0, with_lm != 0, S, L)) return 0;
+  return (size_t)B * S.ws_per_utt + 256;
+}
+
+int e2e_gram_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* chunk_len,
+                             int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                             int num_base_labels, int beam_width, int scored, int space_id, const e2e_lm* lm, double lmwt,
+                             double wip, double oov_penalty, void* state, size_t row_bytes, int max_frames,
+                             int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                             int32_t* counts, int64_t* frames_done, void* workspace, size_t workspace_bytes, void* stream,
+                             const e2e_gram_beam_opts* opts) {
+  const bool sc = scored != 0;
+  const bool restricted = sc && opts && opts->restrict_to_lexicon != 0;
+  // every argument error the host can see, before any launch
+  if (const int rc = check_beam_args(dtype, B, T, V, max_order, beam_width, nbest, nbest > 0 ? max_out : 0, 0)) return rc;
+  if (!sc && (lm || counts || opts)) {
+    set_error("scored = 0 is the search of e2e_gram_ctc_beam_nbest: lm, counts and opts must be NULL");
+    return E2E_ERR_ARG;
+  }
+  if (sc) { if (const int rc = check_scored_args(V, num_base_labels, space_id, lm, restricted)) return rc; }
+  if (max_frames < 1 || max_frames > (1 << 22)) { set_error("max_frames=%d outside [1, %d]", max_frames, 1 << 22); return E2E_ERR_ARG; }
+  StreamLayout S;
+  BeamLayout L;
+  if (!stream_layout(max_frames, V, max_order, beam_width, sc, lm != nullptr, S, L)) {
+    set_error("max_frames=%d frames are more than the search takes", max_frames); return E2E_ERR_UNSUPPORTED;
+  }
+  if (row_bytes < S.total || row_bytes % 8) {
+    set_error("row_bytes = %zu: a state row needs %zu bytes (e2e_gram_beam_stream_row_bytes) and a multiple of 8", row_bytes, S.total);
+    return E2E_ERR_ARG;
+  }
+  if (B > 0 && (!lp || !chunk_len || !gram_ids || !gram_len || !state || !frames_done)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  if (B > 0 && nbest > 0 && (!out_len || !n_hyp || !scores || (sc && !counts) || (max_out > 0 && !out))) {
+    set_error("null pointer argument"); return E2E_ERR_ARG;
+  }
+  if (B > 0 && reinterpret_cast<uintptr_t>(state) % 8) { set_error("the state must be 8-byte aligned"); return E2E_ERR_ARG; }
+  if (B == 0) return E2E_OK;
+  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < (size_t)B * S.ws_per_utt) {
+    set_error("workspace too small: %zu bytes, e2e_gram_beam_stream_workspace_bytes() = %zu", workspace_bytes, (size_t)B * S.ws_per_utt + 256);
+    return E2E_ERR_WORKSPACE;
+  }
+  if (const int rc = check_model_device(lm)) return rc;
+  GramStreamParams sp;
+  memset(&sp, 0, sizeof(sp));
+  GramLmParams& q = sp.o.l;
+  q.b = GramBeamParams{lp, dtype, sB, sT, sV, chunk_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
+                       out, nbest > 0 ? max_out : 0, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
+                       S.ws_per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, 0, L.logH};
+  if (lm) q.lm = lm->dev_view();
+  q.has_lm = lm ? 1 : 0; q.space_id = space_id < 0 ? -1 : space_id; q.R = num_base_labels;
+  q.lmwt = lm ? lmwt : 0.0; q.wip = wip; q.oov = oov_penalty;
+  q.counts = counts; q.off_cache = L.off_cache;
+  sp.o.timesteps = sc && nbest > 0 && opts ? opts->timesteps : nullptr;
+  GramStream& s = sp.s;
+  s.rows = reinterpret_cast<unsigned char*>(state); s.row_bytes = row_bytes; s.off_lm = S.off_lm; s.off_nodes = S.off_nodes;
+  s.frames_done = frames_done;
+  s.cfg.magic = kGramStreamMagic; s.cfg.V = V; s.cfg.K = max_order; s.cfg.R = sc ? num_base_labels : 0; s.cfg.W = beam_width;
+  s.cfg.scored = sc ? 1 : 0; s.cfg.has_lm = lm ? 1 : 0; s.cfg.restricted = restricted ? 1 : 0; s.cfg.max_frames = max_frames;
+  hipStream_t hs = (hipStream_t)stream;
+  if (!sc) hipLaunchKernelGGL((gram_beam_kernel<false, false, false, true>), dim3(B), dim3(kBeamThreads), 0, hs, sp);
+  else if (!restricted) hipLaunchKernelGGL((gram_beam_kernel<true, false, false, true>), dim3(B), dim3(kBeamThreads), 0, hs, sp);
+  else hipLaunchKernelGGL((gram_beam_kernel<true, true, false, true>), dim3(B), dim3(kBeamThreads), 0, hs, sp);
+  E2E_HIP_CHECK(hipGetLastError(), "gram_beam_kernel (stream) launch");
+  return E2E_OK;
 }
 
 }  // extern "C"

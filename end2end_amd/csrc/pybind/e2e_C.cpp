@@ -325,6 +325,44 @@ PYBIND11_MODULE(_C, m) {
         py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("workspace"), py::arg("workspace_bytes"),
         py::arg("stream"), py::arg("opts") = py::none());
 
+  m.def("gram_beam_stream_row_bytes", [](int max_frames, int V, int max_order, int beam_width, bool scored, bool with_lm) {
+    return e2e_gram_beam_stream_row_bytes(max_frames, V, max_order, beam_width, scored ? 1 : 0, with_lm ? 1 : 0);
+  });
+  m.def("gram_beam_stream_workspace_bytes", [](int B, int V, int max_order, int beam_width, bool scored, bool with_lm) {
+    return e2e_gram_beam_stream_workspace_bytes(B, V, max_order, beam_width, scored ? 1 : 0, with_lm ? 1 : 0);
+  });
+
+  // opts: None passes NULL; else (restrict_to_lexicon, timesteps), as gram_ctc_beam_nbest_opt takes them
+  m.def("gram_ctc_beam_stream",
+        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t chunk_len, int B, int T, int V,
+           uintptr_t gram_ids, uintptr_t gram_len, int max_order, int num_base_labels, int beam_width, bool scored,
+           int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, uintptr_t state, size_t row_bytes,
+           int max_frames, int nbest, uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores,
+           uintptr_t counts, uintptr_t frames_done, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
+           py::object opts) {
+          e2e_gram_beam_opts o{0, nullptr};
+          if (!opts.is_none()) {
+            auto t = opts.cast<std::pair<bool, uintptr_t>>();
+            o.restrict_to_lexicon = t.first ? 1 : 0;
+            o.timesteps = ptr<int64_t>(t.second);
+          }
+          check(e2e_gram_ctc_beam_stream(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(chunk_len), B, T, V,
+                                         ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
+                                         num_base_labels, beam_width, scored ? 1 : 0, space_id, ptr<const e2e_lm>(lm), lmwt,
+                                         wip, oov_penalty, ptr<void>(state), row_bytes, max_frames, nbest,
+                                         ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
+                                         ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(frames_done),
+                                         ptr<void>(workspace), workspace_bytes, ptr<void>(stream),
+                                         opts.is_none() ? nullptr : &o));
+        },
+        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("chunk_len"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"),
+        py::arg("num_base_labels"), py::arg("beam_width"), py::arg("scored"), py::arg("space_id"), py::arg("lm"),
+        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"), py::arg("row_bytes"),
+        py::arg("max_frames"), py::arg("nbest"), py::arg("out"), py::arg("max_out"), py::arg("out_len"), py::arg("n_hyp"),
+        py::arg("scores"), py::arg("counts"), py::arg("frames_done"), py::arg("workspace"), py::arg("workspace_bytes"),
+        py::arg("stream"), py::arg("opts") = py::none());
+
   m.def("asg_beam_max_width", [](int V) { return e2e_asg_beam_max_width(V); });
   m.def("asg_beam_workspace_bytes", [](int B, int T, int V, int beam_width, bool with_lm) {
     return e2e_asg_beam_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0);

@@ -6,8 +6,10 @@ with a word language model, a word insertion penalty and an out-of-vocabulary pe
 base labels spell the words, the space among them separates them, and a gram may end one word and begin the next.
 ``restrict_to_vocabulary()`` then restricts the search to the model's words or to a word list, and
 ``decode_nbest(..., timesteps=True)`` also returns the frame at which each id entered the beam (e2e_gram_ctc_beam_nbest_opt).
+``open_stream(batch_size, max_frames)`` is the same search, configured or not, fed in chunks with the beams kept on the GPU in
+between (e2e_gram_ctc_beam_stream): after every chunk the result of ``decode`` / ``decode_nbest`` on everything fed so far.
 
-Not provided for Gram-CTC: custom transcriptions, a word list together with a language model, streaming, a column
+Not provided for Gram-CTC: custom transcriptions, a word list together with a language model, a column
 segmentation per beam hypothesis (several segmentations spell one hypothesis), ``blank_idx != 0``.
 """
 import os
@@ -147,3 +149,67 @@ class GramCTCDecoder:
         logits, logits_lengths = self._batch_major(self._logprobs(logits), logits_lengths)
         r = self._decoder.decode_nbest(logits_=logits, logits_lengths_=logits_lengths, nbest=nbest, timesteps=timesteps)
         return NBestResults(*r) if self._decoder.configured else GramNBestResults(*r)
+
+    def open_stream(self, batch_size, max_frames, device=None, timesteps=False):
+        """Streaming beam search (``beam_width > 1``): a ``GramCTCDecoderStream`` that is fed the logits in chunks and keeps
+        the beams of ``batch_size`` utterances of up to ``max_frames`` frames on the GPU in between.  After every chunk the
+        result is that of ``decode`` / ``decode_nbest`` on everything fed so far; the decoder's settings at this moment --
+        ``configure()`` and ``restrict_to_vocabulary()`` included -- are the stream's.
+
+        :param device: the GPU of the state; by default that of the first chunk
+        :param timesteps: after ``configure()`` only: ``feed_nbest`` returns the frames of the ids, counted from the stream's
+            start, unless told otherwise per call
+        """
+        if self._beam_width == 1:
+            raise CTCDecoderError("a stream needs beam_width > 1: greedy decoding has no beam to keep")
+        try:
+            return GramCTCDecoderStream(self, self._decoder.open_stream(batch_size, max_frames, device=device, timesteps=timesteps))
+        except ValueError as e:
+            raise CTCDecoderError(str(e))
+
+
+class GramCTCDecoderStream:
+    """What ``GramCTCDecoder.open_stream`` returns: ``CTCDecoderStream``'s surface.  ``feed`` / ``feed_nbest`` take a chunk of
+    logits shaped as ``decode`` takes them (``logits_lengths``: the frames of this chunk per utterance, all by default, 0
+    allowed; the log-softmax is per frame, so it is applied per chunk) and return ``DecoderResults`` / ``GramNBestResults``
+    (``NBestResults`` after ``configure()``) for everything fed so far; ``frames`` are the per-utterance totals, ``state`` the
+    (batch, row_bytes) uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts utterances anew."""
+
+    def __init__(self, decoder, stream):
+        self._owner, self._stream = decoder, stream
+
+    @property
+    def frames(self):
+        return self._stream.frames
+
+    @property
+    def state(self):
+        return self._stream.state
+
+    @property
+    def row_bytes(self):
+        return self._stream.row_bytes
+
+    def reset(self, rows=None):
+        self._stream.reset(rows)
+
+    def _chunk(self, logits, logits_lengths):
+        if logits.dim() != 3:
+            raise ValueError("logits must be (batch, time, alphabet)")
+        logits, logits_lengths = self._owner._batch_major(logits, logits_lengths)
+        self._stream.check_chunk(tuple(logits.shape))             # (before any device work)
+        return self._owner._logprobs(logits), logits_lengths
+
+    def feed(self, logits, logits_lengths=None):
+        logits, logits_lengths = self._chunk(logits, logits_lengths)
+        return DecoderResults(*self._stream.feed(logits, logits_lengths))
+
+    def feed_nbest(self, logits, logits_lengths=None, nbest=None, timesteps=None):
+        if timesteps and not self._stream.scored:
+            raise ValueError("timesteps are a field of NBestResults, which a configured decoder returns: call configure(wip=0) "
+                             "for the same search with timesteps")
+        logits, logits_lengths = self._chunk(logits, logits_lengths)
+        r = self._stream.feed_nbest(logits, logits_lengths, nbest=nbest, timesteps=timesteps)
+        if r is None:
+            return None
+        return NBestResults(*r) if self._stream.scored else GramNBestResults(*r)

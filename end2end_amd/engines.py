@@ -1012,6 +1012,10 @@ class GramCTCDecoderEngine:
                     _C.gram_ctc_beam_nbest_opt(*args, (self.restricted, ts.data_ptr() if ts is not None else 0))
                 else:
                     _C.gram_ctc_beam_nbest_lm(*args)
+        return self._nbest_result_lm(out, out_len, n_hyp, scores, counts, ts)
+
+    def _nbest_result_lm(self, out, out_len, n_hyp, scores, counts, ts):
+        """What the configured decode_nbest returns, from the buffers the read-out has filled (ts: None without timesteps)."""
         ids_out, sentences = self._pack(out, out_len, n_hyp)
         r = self._result
         if ts is not None:
@@ -1024,6 +1028,13 @@ class GramCTCDecoderEngine:
         """Hypothesis 0 of decode_nbest -> (base ids (B,maxlen) int64, lengths (B), sentences)."""
         r = self.decode_nbest(logits_, logits_lengths_, nbest=1)
         return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+
+    def open_stream(self, batch_size, max_frames, device=None, timesteps=False):
+        """Streaming beam search (e2e_gram_ctc_beam_stream, include/e2e_ctc.h): a GramBeamStream that is fed log-probabilities
+        in chunks and keeps the beams of `batch_size` utterances of up to `max_frames` frames on the GPU between the chunks.
+        After every chunk the result is, bit for bit, that of decode / decode_nbest on all the frames fed so far.  The
+        configuration and the restriction in force now are the stream's.  `timesteps` needs a configured engine."""
+        return GramBeamStream(self, batch_size, max_frames, device=device, timesteps=timesteps)
 
 
 def read_transcriptions(transcriptions, labels, blank_idx=None):
@@ -1521,3 +1532,109 @@ class CTCBeamStream:
         """Feed a chunk and return what decode returns for everything fed so far: (indices, lengths, sentences)."""
         r = self.feed_nbest(logits_, logits_lengths_, nbest=1)
         return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] for s in r[2]]
+
+
+class GramBeamStream(CTCBeamStream):
+    """The Gram-CTC beams of `batch_size` utterances, kept on the GPU between chunks (GramCTCDecoderEngine.open_stream):
+    CTCBeamStream's surface -- `frames`, `state`, `check_chunk`, `reset(rows)` are its own.  The engine's configuration
+    (configure(), restrict()) at the time the stream was opened is the stream's: an engine that was never configured streams
+    the search on the masses (e2e_gram_ctc_beam_stream with scored = 0), a configured one the search on the totals."""
+
+    def __init__(self, engine, batch_size, max_frames, device=None, timesteps=False):
+        super().__init__(engine, batch_size, max_frames, device=device, timesteps=timesteps)
+        e = engine
+        if self.timesteps and not e.configured:
+            raise ValueError("timesteps are part of the configured search's results: call configure() first "
+                             "(configure(wip=0) is the search without a model and without penalties)")
+        self.scored = bool(e.configured)
+        self.lm = e.lm if self.scored else None
+        self.restricted = bool(e.restricted) if self.scored else False
+        self._knobs = (e.space_id, e.lmwt, e.wip, e.oov_penalty) if self.scored else (-1, 0.0, 0.0, 0.0)
+
+    def _state_for(self, V, dev):
+        e = self.engine
+        if self.state is None:
+            self.row_bytes = _C.gram_beam_stream_row_bytes(self.max_frames, V, e.max_order, e.beam_width, self.scored,
+                                                           self.lm is not None)
+            if not self.row_bytes:
+                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported" % (self.max_frames, e.beam_width))
+            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
+            self.state[:, : self.HEADER_BYTES].zero_()
+            self.device = dev
+        return self.state
+
+    def feed_nbest(self, logits_, logits_lengths_=None, nbest=None, timesteps=None):
+        """Feed a chunk of LOG-PROBABILITIES (batch, frames, alphabet) -- logits_lengths_: the frames of this chunk per
+        utterance, 0 allowed, all of them by default -- and read the beams out: what decode_nbest returns for everything
+        fed so far.  timesteps: None -- as the stream was opened -- or whether this read-out returns them (a configured search
+        only; they cost the stream nothing: the nodes' numbers carry them).  nbest=0 feeds only and returns None."""
+        e = self.engine
+        want_ts = self.timesteps if timesteps is None else bool(timesteps)
+        if want_ts and not self.scored:
+            raise ValueError("timesteps are part of the configured search's results: call configure() first "
+                             "(configure(wip=0) is the search without a model and without penalties)")
+        N = e.beam_width if nbest is None else int(nbest)
+        if not 0 <= N <= e.beam_width:
+            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
+        self.check_chunk(tuple(logits_.shape))
+        B, Tc = logits_.shape[0], logits_.shape[1]
+        if logits_lengths_ is None:
+            logits_lengths_ = torch.full((B,), Tc, dtype=torch.long)
+        if self.device is not None and logits_.device != self.device:
+            logits_ = logits_.to(self.device)
+        x, xl, dev = e._prep(logits_, logits_lengths_, _F32_F64)
+        V = x.shape[2]
+        state = self._state_for(V, dev)
+        if dev != state.device:
+            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
+        max_out = max((max(self._frames) + Tc) * e.max_order, 1)
+        frames_done = torch.empty(B, dtype=torch.long, device=dev)
+        out = out_len = n_hyp = scores = counts = ts = None
+        if N:
+            out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
+            out_len = torch.empty((B, N), dtype=torch.long, device=dev)
+            n_hyp = torch.empty(B, dtype=torch.long, device=dev)
+            scores = torch.empty((B, N, 3) if self.scored else (B, N), dtype=torch.float64, device=dev)
+            counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev) if self.scored else None
+            ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if want_ts else None
+        space_id, lmwt, wip, oov_penalty = self._knobs
+        stream = R.stream_handle(dev)
+        with torch.cuda.device(dev):
+            ids, lens = e._table(dev)
+            lm = self.lm.on(dev).handle if self.lm is not None else 0
+            ws = R.workspace(dev, _C.gram_beam_stream_workspace_bytes(B, V, e.max_order, e.beam_width, self.scored,
+                                                                      self.lm is not None), stream)
+            sB, sT, sV = x.stride()
+            opts = (self.restricted, ts.data_ptr() if ts is not None else 0) if self.scored else None
+            _C.gram_ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V,
+                                    ids.data_ptr(), lens.data_ptr(), e.max_order, e.num_base_labels, e.beam_width,
+                                    self.scored, space_id, lm, lmwt, wip, oov_penalty,
+                                    state.data_ptr(), self.row_bytes, self.max_frames, N,
+                                    out.data_ptr() if N else 0, max_out, out_len.data_ptr() if N else 0,
+                                    n_hyp.data_ptr() if N else 0, scores.data_ptr() if N else 0,
+                                    counts.data_ptr() if counts is not None else 0, frames_done.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), stream, opts)
+        done = frames_done.tolist()
+        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
+        bad = None
+        for b, f in enumerate(done):
+            if f >= 0:
+                self._frames[b] = f
+            elif bad is None:
+                bad = (b, f)
+        if bad is not None:
+            why = {-2: "would pass max_frames=%d with this chunk" % self.max_frames,
+                   -3: "has a state row that was written under another configuration"}
+            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
+        if not N:
+            return None
+        if self.scored:
+            return e._nbest_result_lm(out, out_len, n_hyp, scores, counts, ts)
+        ids_out, sentences = e._pack(out, out_len, n_hyp)
+        r = e._result
+        return (ids_out, r(out_len), sentences, r(scores), r(n_hyp))
+
+    def feed(self, logits_, logits_lengths_=None):
+        """Feed a chunk and return what decode returns for everything fed so far: (base ids, lengths, sentences)."""
+        r = self.feed_nbest(logits_, logits_lengths_, nbest=1)
+        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]

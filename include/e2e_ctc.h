@@ -347,8 +347,9 @@ int e2e_asg_viterbi(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV
  * loss's headline table V = 379, 16 at V = 8000 --, T <= 2^22; beyond them E2E_ERR_UNSUPPORTED, found on the host before
  * any launch (e2e_gram_beam_workspace_bytes then returns 0).  The call is asynchronous on `stream`, allocates nothing,
  * never synchronises and is capturable.  With a word language model: e2e_gram_ctc_beam_nbest_lm, below; restricted to
- * a vocabulary, and with label timestamps: e2e_gram_ctc_beam_nbest_opt, below that.  Not provided for Gram-CTC: custom
- * transcriptions, a word list together with a language model, streaming, a column
+ * a vocabulary, and with label timestamps: e2e_gram_ctc_beam_nbest_opt, below that; both fed in chunks:
+ * e2e_gram_ctc_beam_stream, below that.  Not provided for Gram-CTC: custom
+ * transcriptions, a word list together with a language model, a column
  * segmentation per beam hypothesis (several exist), blank_idx != 0.
  */
 int e2e_gram_ctc_greedy(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
@@ -463,6 +464,75 @@ int e2e_gram_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t s
                                 double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
                                 int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
                                 void* stream, const e2e_gram_beam_opts* opts);
+
+/* ------------------------------------------------------------------------
+ * Streaming Gram-CTC beam search: e2e_gram_ctc_beam_nbest / e2e_gram_ctc_beam_nbest_opt fed in chunks, the beam kept on the
+ * device between the calls (additive, ABI 4: nothing above changes meaning).  The conventions are e2e_asg_beam_stream's and
+ * e2e_ctc_beam_stream's.
+ *
+ *   scored       0: the search and the outputs of e2e_gram_ctc_beam_nbest -- the cut on the bits of the masses, scores
+ *                (B,nbest); lm, counts and opts must be NULL (E2E_ERR_ARG), num_base_labels, space_id and the knobs are not read.
+ *                != 0: e2e_gram_ctc_beam_nbest_opt -- the cut on the totals' order keys, scores (B,nbest,3), counts (B,nbest,2),
+ *                lm NULL or a model, opts NULL or restrict_to_lexicon / timesteps.  The two searches need not break ties
+ *                alike (the bits of tot against the bits of log tot), so neither stands in for the other.
+ * An utterance's search lives in one STATE ROW of device memory that the caller owns.  Its parts, each rounded up to 256
+ * bytes: a 256-byte header, the beam's current members as they stand in the kernel's LDS (slot masses, slot columns, key,
+ * tot, node, length: 16896 bytes), with `scored` their language-model fields (11776 bytes), and the pool of
+ * beam_width * (max_frames + 1) + 1 (parent, column) nodes of 8 bytes.  The header holds 4-byte fields in this order: a magic
+ * value; the configuration V, max_order, num_base_labels (0 unless scored), beam_width, scored, model or not, restricted or not,
+ * max_frames; the member count, the frames consumed, the sticky overflow flag (byte 44), whether the beam is dead; and at byte
+ * 56 the 8-byte sum of the exponents taken out so far.  A call resumes every utterance from its row, runs chunk_len[b] further
+ * frames, stores the row and reads the current beam out.  What a frame rebuilds anyway is not stored: the candidate table is
+ * empty between frames, the pair buffers are a frame's scratch, and the cache of the children's answers is recomputed at
+ * resume -- the resumed members take its rows 0 .. n - 1 and their children's answers are computed as the per-frame refill
+ * computes a new member's; they are functions of the sequence alone, so no output bit depends on the row a member holds.
+ * A node's index, 1 + frame * beam_width + rank, counts the frames of the STREAM, so the timesteps need no storage.
+ *   - A row whose first 256 bytes are zero is a fresh utterance: hipMemsetAsync (or zeroing the header) opens or resets a
+ *     stream, no other call is needed.  The rest of a fresh row may hold anything.
+ *   - Rows are self-contained: indices, no addresses.  They may be moved, permuted, gathered or reordered between calls,
+ *     and a batch may mix fresh rows with rows of any age.
+ *   - The call is asynchronous on `stream`, allocates nothing, does not synchronise and is capturable.
+ *   - Every argument error the host can see is found before any launch, with the whole calls' codes; in addition nbest
+ *     outside [0, beam_width], max_frames outside [1, 2^22], row_bytes below the query or no multiple of 8, and scored = 0
+ *     together with a model, counts or opts (all E2E_ERR_ARG).
+ * CONTRACT.  After chunks whose lengths for utterance b sum to f_b >= 0 -- fed with the same table, beam_width, model, lmwt /
+ * wip / oov_penalty and options throughout -- every output of the read-out (out, out_len, n_hyp, scores, counts,
+ * opts->timesteps) equals, bit for bit, what the whole call writes for the concatenated frames with x_len[b] = f_b and the
+ * same nbest, max_out and options.  f_b = 0 is the whole call's utterance of length 0: a fresh row read out before any frame
+ * gives the one empty hypothesis with acoustic score 0.  Timesteps are frames of the stream, not of the chunk.  A beam that
+ * died (n_hyp = 0) stays dead over later chunks; a stream whose candidate table ran out reads out n_hyp = -1 from then on.
+ *   lp           (B,T,V) log-probabilities of this chunk, strides sB,sT,sV, E2E_F32 or E2E_F64 (chunks may differ in dtype)
+ *   chunk_len    (B) int64, device: frames of this chunk per utterance, clamped to 0..T.  0 runs no frame and stores
+ *                nothing: the read-out repeats the utterance's last result
+ *   state        (B,row_bytes) device, 8-byte aligned; row_bytes >= e2e_gram_beam_stream_row_bytes(...), a multiple of 8
+ *   max_frames   the longest stream a row can hold, 1 .. 2^22; part of the row's configuration, checked at resume
+ *   nbest        0: feed only, no read-out: the outputs up to counts (and opts->timesteps) may be NULL and are not touched;
+ *                else 1 .. beam_width
+ *   frames_done  (B) int64, device.  What only the device knows is reported here per utterance, and mirrored in n_hyp[b]
+ *                when nbest > 0:
+ *                  >= 0  frames consumed so far
+ *                  -2    this chunk would pass max_frames
+ *                  -3    the row was not written under this configuration
+ *                Both statuses are found before anything of the row is touched: they leave the whole row byte for byte and
+ *                write none of the utterance's other outputs, and the other utterances advance.
+ *   workspace    >= e2e_gram_beam_stream_workspace_bytes(...): the whole call's per utterance without the node pool, which
+ *                is the row's; it does not depend on the frames
+ *   opts         NULL or e2e_gram_beam_opts (scored only); restrict_to_lexicon the same for every chunk, timesteps NULL or
+ *                (B,nbest,max_out) per call
+ * Row size: 256 + 16896 + (11776 scored) + 8 * (beam_width * (max_frames + 1) + 1) rounded up to 256, whatever the alphabet
+ * and with or without a model; 0 for a width, alphabet or max_frames that is not supported, and for with_lm without scored.
+ * beam_width 100, max_frames 30 000: 24 029 952 bytes scored, 24 MB per utterance, the node pool being all but 29 KB of it.
+ */
+size_t e2e_gram_beam_stream_row_bytes(int max_frames, int V, int max_order, int beam_width, int scored, int with_lm);
+size_t e2e_gram_beam_stream_workspace_bytes(int B, int V, int max_order, int beam_width, int scored, int with_lm);
+
+int e2e_gram_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* chunk_len,
+                             int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                             int num_base_labels, int beam_width, int scored, int space_id, const struct e2e_lm* lm, double lmwt,
+                             double wip, double oov_penalty, void* state, size_t row_bytes, int max_frames,
+                             int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                             int32_t* counts, int64_t* frames_done, void* workspace, size_t workspace_bytes, void* stream,
+                             const e2e_gram_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
  * ASG decoding: n-best prefix beam search with transitions and a word language model (additive, ABI 4: nothing above

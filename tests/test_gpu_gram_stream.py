@@ -1,0 +1,455 @@
+"""GPU: the streaming Gram-CTC beam search (e2e_gram_ctc_beam_stream; GramCTCDecoder.open_stream) against the whole calls
+e2e_gram_ctc_beam_nbest (scored = 0) and e2e_gram_ctc_beam_nbest_opt (scored = 1) on the frames fed so far: np.array_equal on
+every output -- ids, lengths, n_hyp, scores, counts, timesteps -- after every chunk (tests/gram_stream_util.py).  The stream
+does the same arithmetic in the same order, so there is no tolerance.  Final read-outs are also pinned to the plain-Python
+restatements, as the whole calls' own tests compare them."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import gram_decode_lm_ref as LR
+import gram_decode_ref as DR
+import gram_lexicon_ref as XR
+import gram_stream_util as S
+from test_gpu_gram_decode import check_against_restatement
+from test_gpu_gram_decode_lm import check_rows as check_lm_rows
+from test_gpu_gram_lexicon import check_rows as check_lexicon_rows
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+DTYPES = {"f32": torch.float32, "f64": torch.float64}
+_caches = {}
+
+
+def cache(*key):
+    """The whole-call references of one case, shared by its chunkings."""
+    return _caches.setdefault(key, {})
+
+
+# ---- the chunkings ---------------------------------------------------------------------------------------------------------
+def ragged3(lens):
+    """Three utterances of at least 30 frames: some get no frame in some calls, and they end in different chunks."""
+    plan = [[5, 0, 3], [0, 4, 0], [10, 10, 10], [0, 0, 0], [0, 0, 7]]
+    rest = [int(n) - sum(c[b] for c in plan) for b, n in enumerate(lens)]
+    assert min(rest) >= 10
+    return plan + [[rest[0], 0, 9], [0, rest[1], rest[2] - 9]]
+
+
+RAGGED4 = [[3, 0, 1, 0], [0, 4, 0, 0], [5, 5, 0, 0], [0, 0, 0, 0], [6, 0, 0, 0]]     # sums 14, 9, 1, 0: the scored cases' lengths
+
+
+def chunkings(lens, T):
+    """name -> (chunking, layout of the chunks): one frame at a time, sizes 5 and 16, the whole, a ragged plan."""
+    return {"every_frame": (S.regular(lens, T, 1), None), "fives": (S.regular(lens, T, 5), "time_major"),
+            "sixteens": (S.regular(lens, T, 16), "strided"), "whole": (S.regular(lens, T, T), None),
+            "ragged": (ragged3(lens) if len(lens) == 3 else RAGGED4, None)}
+
+
+# ---- 1. scored = 0: the search on the masses ---------------------------------------------------------------------------------
+def plain_case(W, dt):
+    R, V, l2i, batches = DR.pruned_cases()
+    x, xl = batches[(W, 1.0 if dt == "f32" else 3.0)]
+    return S.Search(R, V, l2i, W), torch.from_numpy(DR.log_softmax(x)).to(DTYPES[dt]), [int(n) for n in xl]
+
+
+@pytest.mark.parametrize("dt", sorted(DTYPES))
+@pytest.mark.parametrize("name", ["every_frame", "fives", "sixteens", "whole", "ragged"])
+@pytest.mark.parametrize("W", [2, 7, 32, 100])
+def test_plain(W, name, dt):
+    s, lp, lens = plain_case(W, dt)
+    chunking, layout = chunkings(lens, 60)[name]
+    assert [sum(c[b] for c in chunking) for b in range(3)] == lens
+    r = S.check_stream(lp, lens, chunking, s, cache=cache("plain", W, dt), layout=layout)
+    assert r["n_hyp"].tolist() == [W] * 3 and r["counts"] is None and r["scores"].shape == (3, W)
+
+
+def test_headline_table_in_two_chunks():
+    R, V, l2i, x, xl, W = DR.headline_case()
+    lens = [int(n) for n in xl]
+    for dt in ("f32", "f64"):
+        lp = torch.from_numpy(DR.log_softmax(x)).to(DTYPES[dt])
+        S.check_stream(lp, lens, S.cuts(lens, [16, 14]), S.Search(R, V, l2i, W))
+
+
+# ---- 2. scored = 1: the totals, with and without a model; restricted ---------------------------------------------------------
+def scored_case(model, W, with_lm=True, case_sensitive=True):
+    from end2end_amd.engines import LanguageModel
+    R, V, l2i, x = LR.pruned_case(model)
+    labels = LR.PRUNED[model]["labels"] if case_sensitive else LR.upper(LR.PRUNED[model]["labels"])
+    if with_lm:
+        s = S.Search(R, V, l2i, W, True, labels, LanguageModel(os.path.join(LR.GOLDEN, model), labels, case_sensitive), **LR.KNOBS)
+    else:
+        s = S.Search(R, V, l2i, W, True, labels, wip=LR.KNOBS["wip"])
+    return s, torch.log_softmax(torch.from_numpy(x), -1)
+
+
+@pytest.mark.parametrize("case_sensitive", [True, False])
+@pytest.mark.parametrize("with_lm", [True, False])
+@pytest.mark.parametrize("W", LR.PRUNED_WIDTHS)
+@pytest.mark.parametrize("model", sorted(LR.PRUNED))
+def test_scored(model, W, with_lm, case_sensitive):
+    s, lp = scored_case(model, W, with_lm, case_sensitive)
+    c = {}
+    for name, (chunking, layout) in chunkings(LR.PRUNED_LENS, LR.PRUNED_T).items():
+        r = S.check_stream(lp, LR.PRUNED_LENS, chunking, s, cache=c, layout=layout)
+        assert r["n_hyp"][3] == 1 and r["lens"][3, 0] == 0 and (r["scores"][3, 0] == 0).all(), name   # no frame: the empty one
+        assert int(r["n_hyp"].min()) > 0 and r["scores"].shape == (4, W, 3)
+
+
+def restricted_case(name, W):
+    from end2end_amd.engines import LanguageModel
+    R, V, l2i, x = XR.pruned_case(name)
+    m = XR.PRUNED[name]
+    labels = m["labels"]
+    if isinstance(m["source"], str):
+        lm, knobs = LanguageModel(os.path.join(LR.GOLDEN, m["source"]), labels, True, lexicon=True), XR.KNOBS
+    else:
+        lm, knobs = LanguageModel(None, labels, True, words=list(m["source"]), lexicon=True), XR.LIST_KNOBS
+    return S.Search(R, V, l2i, W, True, labels, lm, True, **knobs), torch.log_softmax(torch.from_numpy(x), -1)
+
+
+@pytest.mark.parametrize("name,W", [c for c in XR.PRUNED_CASES if c not in XR.LEFT_OUT])
+def test_restricted(name, W):
+    s, lp = restricted_case(name, W)
+    c = {}
+    for what, (chunking, layout) in chunkings(XR.PRUNED_LENS, XR.PRUNED_T).items():
+        r = S.check_stream(lp, XR.PRUNED_LENS, chunking, s, cache=c, layout=layout)
+    # (the restriction bites: the unrestricted search over the same model ends elsewhere)
+    R, V, l2i, _ = XR.pruned_case(name)
+    words_only = not isinstance(XR.PRUNED[name]["source"], str)         # (a word list serves a restricted search only)
+    free = S.Search(R, V, l2i, W, True, XR.PRUNED[name]["labels"], None if words_only else s.lm, False,
+                    lmwt=s.lmwt, wip=s.wip, oov_penalty=s.oov)
+    assert not np.array_equal(r["ids"], S.reference(lp, XR.PRUNED_LENS, free)["ids"])
+
+
+# ---- 3. the final read-out against the restatements --------------------------------------------------------------------------
+def decoder(R, V, l2i, width, labels=None, **kw):
+    from end2end_amd.decoders import GramCTCDecoder
+    kw.setdefault("after_logsoftmax", True)
+    return GramCTCDecoder(0, R, V, l2i, beam_width=width, labels=labels, **kw)
+
+
+def fed_in(st, lp, lens, size, **kw):
+    """lp (B,T,V) through the module's stream in chunks of `size` frames -> the last feed_nbest."""
+    r = None
+    for a, cl in zip(range(0, lp.shape[1], size), S.regular(lens, lp.shape[1], size)):
+        r = st.feed_nbest(lp[:, a:a + size], torch.tensor(cl), **kw)
+    return r
+
+
+def test_final_read_out_equals_the_restatement_of_the_search_on_the_masses():
+    """gram_decode_ref.beam_search, with the whole call's test's tolerance on the scores (1e-9)."""
+    import gram_ref as GR
+    W = 7
+    R, V, l2i, batches = DR.pruned_cases()
+    x, xl = batches[(W, 3.0)]
+    lp = DR.log_softmax(x)
+    grams = GR.grams_of(R, V, l2i)
+    want = [DR.beam_search(lp[b, :int(xl[b])], grams, W) for b in range(3)]     # (this width and scale only: a second)
+    res = fed_in(decoder(R, V, l2i, W).open_stream(3, 60), torch.from_numpy(lp).to(DEV), xl.tolist(), 16)
+    assert type(res).__name__ == "GramNBestResults"
+    check_against_restatement(res, want)
+
+
+@pytest.mark.parametrize("model", sorted(LR.PRUNED))
+def test_final_read_out_equals_the_restatement_with_a_model(model):
+    """gram_decode_lm_ref.beam_search, where its cuts are decided by MIN_GAP or more."""
+    W = 7
+    want, gap = LR.pruned_ref(model, W)
+    assert gap >= LR.MIN_GAP
+    R, V, l2i, x = LR.pruned_case(model)
+    labels = LR.PRUNED[model]["labels"]
+    lp = torch.log_softmax(torch.from_numpy(x).double(), -1).to(DEV)
+    dec = decoder(R, V, l2i, W, labels).configure(lm_path=os.path.join(LR.GOLDEN, model), **LR.KNOBS)
+    res = fed_in(dec.open_stream(4, LR.PRUNED_T), lp, LR.PRUNED_LENS, 5)
+    assert type(res).__name__ == "NBestResults"
+    for b in range(4):
+        check_lm_rows(res, b, want[b], labels)
+
+
+@pytest.mark.parametrize("name", [n for n in XR.PRUNED if (n, 7) not in XR.LEFT_OUT])
+def test_final_read_out_equals_the_restatement_restricted(name):
+    """gram_lexicon_ref.beam_search, timesteps included; none of its cases is left out."""
+    W = 7
+    assert XR.LEFT_OUT == ()
+    want, gap = XR.pruned_ref(name, W)
+    assert gap >= XR.MIN_GAP
+    R, V, l2i, x = XR.pruned_case(name)
+    m = XR.PRUNED[name]
+    lp = torch.log_softmax(torch.from_numpy(x).double(), -1).to(DEV)
+    dec = decoder(R, V, l2i, W, m["labels"])
+    if isinstance(m["source"], str):
+        dec.configure(lm_path=os.path.join(LR.GOLDEN, m["source"]), **XR.KNOBS).restrict_to_vocabulary()
+    else:
+        dec.configure(wip=XR.KNOBS["wip"]).restrict_to_vocabulary(list(m["source"]))
+    res = fed_in(dec.open_stream(4, XR.PRUNED_T, timesteps=True), lp, XR.PRUNED_LENS, 5)
+    for b in range(4):
+        check_lexicon_rows(res, b, want[b], m["labels"])
+
+
+# ---- 4. the edges of the contract --------------------------------------------------------------------------------------------
+def test_timesteps_are_frames_of_the_stream():
+    s, lp = restricted_case("lm_order4.arpa", 32)
+    r = S.check_stream(lp, XR.PRUNED_LENS, S.regular(XR.PRUNED_LENS, XR.PRUNED_T, 5), s)
+    late = 0
+    for b in range(3):
+        for k in range(int(r["n_hyp"][b])):
+            n = int(r["lens"][b, k])
+            ts = r["ts"][b, k, :n].tolist()
+            assert all(p <= q for p, q in zip(ts, ts[1:])) and (not ts or 0 <= ts[0] and ts[-1] < XR.PRUNED_LENS[b])
+            assert (r["ts"][b, k, n:] == -1).all()
+            late += bool(ts) and ts[-1] >= 5
+    assert late                                                         # (frames beyond the first chunk: not the chunk's own count)
+
+
+@pytest.mark.parametrize("scored", [False, True])
+def test_a_dead_beam_stays_dead(scored):
+    """A frame whose log-probabilities are all -inf has probability zero: no hypothesis is left, then or later."""
+    if scored:
+        s, lp = scored_case("lm_order4.arpa", 7)
+        lp = lp[:2].clone()
+    else:
+        s, lp, _ = plain_case(7, "f32")
+        lp = lp[:2, :14].clone()
+    lp[0, 5, :] = -math.inf
+    lens = [14, 14]
+    c = {}
+    for size in (1, 4):
+        S.check_stream(lp, lens, S.regular(lens, 14, size), s, cache=c)
+    assert c[(4, 4)]["n_hyp"].tolist() == [7, 7] and c[(8, 8)]["n_hyp"].tolist() == [0, 7] and c[(14, 14)]["n_hyp"].tolist() == [0, 7]
+    last = c[(14, 14)]
+    assert (last["lens"][0] == 0).all() and (last["scores"][0].reshape(7, -1)[:, 0] == -math.inf).all()
+
+
+def test_short_max_out():
+    s, lp, lens = plain_case(7, "f32")
+    r = S.check_stream(lp, lens, S.regular(lens, 60, 16), s, max_out=5)
+    assert int(r["lens"].max()) > 5 and r["ids"].shape[2] == 5
+    s, lp = restricted_case("word list", 7)
+    r = S.check_stream(lp, XR.PRUNED_LENS, S.regular(XR.PRUNED_LENS, XR.PRUNED_T, 5), s, max_out=3)
+    assert int(r["lens"].max()) > 3 and r["ts"].shape[2] == 3
+
+
+@pytest.mark.parametrize("scored", [False, True])
+def test_feed_only(scored):
+    if scored:
+        s, lp = scored_case("tiny_3gram.arpa", 7)
+        lens, T = LR.PRUNED_LENS, LR.PRUNED_T
+    else:
+        s, lp, lens = plain_case(7, "f32")
+        T = 60
+    B = len(lens)
+    st = S.RawStream(B, T, s)
+    dx = lp.to(DEV)
+    o = S.garbage(B, 1, st.max_out, DEV, scored, True)
+    before = S.host(o)
+    for a, cl in zip(range(0, T, 5), S.regular(lens, T, 5)):
+        r = st.feed(dx[:, a:a + 5], cl, nbest=0, outputs=o)
+        assert r["done"].tolist() == [min(n, a + 5) for n in lens]
+        S.same(r, before, "feed only wrote an output")
+    r = st.feed(dx[:, :1], [0] * B)                                     # a read-out alone
+    S.same(r, S.reference(lp, lens, s))
+    assert r["done"].tolist() == lens
+
+
+@pytest.mark.parametrize("scored", [False, True])
+def test_a_fresh_row_reads_out_the_empty_hypothesis(scored):
+    """f_b = 0 is the whole call's utterance of length 0, and nothing of the row is written."""
+    s, lp = scored_case("tiny_3gram.arpa", 7) if scored else plain_case(7, "f32")[:2]
+    B = lp.shape[0]
+    st = S.RawStream(B, 14, s)
+    before = st.state.clone()
+    r = st.feed(lp[:, :3].to(DEV), [0] * B)
+    S.same(r, S.reference(lp[:, :14], [0] * B, s))
+    assert r["done"].tolist() == [0] * B and r["n_hyp"].tolist() == [1] * B and (r["lens"] == 0).all()
+    assert (r["scores"].reshape(B, 7, -1)[:, 0] == 0).all() and torch.equal(st.state, before)
+
+
+def test_rows_permuted_and_reset():
+    s, lp = scored_case("lm_order4.arpa", 7)
+    lp = torch.cat([lp[:3], lp[:3].flip(1)], 1)                         # three utterances of 28 frames
+    st = S.RawStream(3, 28, s)
+    dx = lp.to(DEV)
+    ref = lambda lens: S.reference(lp, lens, s)   # noqa: E731
+    S.same(st.feed(dx[:, :10], [10, 10, 10]), ref([10, 10, 10]))
+    perm = [2, 0, 1]
+    st.state = st.state[perm].contiguous()                              # the rows move, and the chunks with them
+    r = st.feed(dx[perm, 10:17], [7, 7, 7])
+    want = ref([17, 17, 17])
+    S.same({k: (v[perm] if v is not None else None) for k, v in want.items()}, {k: r[k] for k in S.KEYS}, "permuted")
+    # row 1 (utterance 0) starts anew, on utterance 1's frames; the others go on
+    st.state[1, :S.HEADER] = 0
+    chunk = torch.stack([dx[2, 17:25], dx[1, :8], dx[1, 17:25]])
+    r = st.feed(chunk, [8, 8, 8])
+    assert r["done"].tolist() == [25, 8, 25]
+    a, fresh = ref([25, 25, 25]), ref([8, 8, 8])
+    for k in S.KEYS:
+        assert np.array_equal(r[k][0], a[k][2]) and np.array_equal(r[k][2], a[k][1]), k
+        assert np.array_equal(r[k][1], fresh[k][1]), k
+
+
+def test_statuses():
+    from end2end_amd.engines import LanguageModel
+    R, V, l2i, x = LR.pruned_case("lm_order4.arpa")
+    labels = LR.PRUNED["lm_order4.arpa"]["labels"]
+    lp = torch.log_softmax(torch.from_numpy(x), -1)[:3]
+    lp = torch.cat([lp, lp.flip(1)], 1)                                 # 28 frames
+    W = 7
+    lm = LanguageModel(os.path.join(LR.GOLDEN, "lm_order4.arpa"), labels, True, lexicon=True)
+    kinds = dict(scored=S.Search(R, V, l2i, W, True, labels, wip=0.4),
+                 narrower=S.Search(R, V, l2i, 6, True, labels, wip=0.4),
+                 plain=S.Search(R, V, l2i, W),
+                 model=S.Search(R, V, l2i, W, True, labels, lm, **LR.KNOBS),
+                 restricted=S.Search(R, V, l2i, W, True, labels, lm, True, **LR.KNOBS),
+                 shorter_table=S.Search(R, V - 1, {c: g for c, g in l2i.items() if c < V - 1}, W, True, labels, wip=0.4))
+    s = kinds["scored"]
+    st = S.RawStream(3, 20, kinds["model"])                             # (rows long enough for every kind)
+    dx = lp.to(DEV)
+    ref = lambda lens: S.reference(lp, lens, s, max_out=st.max_out)   # noqa: E731
+    S.same(st.feed(dx[:, :12], [12, 5, 12], s=s), ref([12, 5, 12]))
+
+    def refused(r, rows, status, want_lens, others=True):
+        """The rows `rows` answer `status` and are left alone, outputs and state; the others advanced."""
+        assert torch.equal(st.state[rows], before[rows])
+        want = ref(want_lens) if want_lens else None
+        for b in range(3):
+            if b in rows:
+                assert r["done"][b] == status and r["n_hyp"][b] == status
+                assert (r["ids"][b] == -7).all() and (r["lens"][b] == -7).all() and (r["scores"][b] == 7.0).all()
+                assert r["counts"] is None or (r["counts"][b] == -7).all()
+                assert r["ts"] is None or (r["ts"][b] == -7).all()
+            elif others:
+                assert r["done"][b] == want_lens[b]
+                for k in S.KEYS:
+                    assert np.array_equal(r[k][b], want[k][b]), (k, b)
+
+    # -2: 12 + 9 > max_frames = 20 for utterances 0 and 2; utterance 1 advances
+    before = st.state.clone()
+    refused(st.feed(torch.stack([dx[0, 12:21], dx[1, 5:14], dx[2, 12:21]]), [9, 9, 9], s=s), [0, 2], -2, [12, 14, 12])
+    assert not torch.equal(st.state[1], before[1])
+    # ... and what fits is taken afterwards
+    S.same(st.feed(dx[:, 12:20], [8, 0, 8], s=s), ref([20, 14, 20]))
+    # -3: the rows were written at width 7, scored, without a model, for 20 frames
+    before = st.state.clone()
+    for kind in ("narrower", "plain", "model", "restricted"):
+        refused(st.feed(dx[:, :1], [1, 1, 1], s=kinds[kind]), [0, 1, 2], -3, None)
+    refused(st.feed(dx[:, :1, :V - 1], [1, 1, 1], s=kinds["shorter_table"]), [0, 1, 2], -3, None)
+    refused(st.feed(dx[:, :1], [1, 1, 1], s=s, max_frames=19), [0, 1, 2], -3, None)
+    # a fresh row beside them is served
+    st.state[1, :S.HEADER] = 0
+    before = st.state.clone()
+    r = st.feed(dx[:, :6], [6, 6, 6], s=kinds["narrower"])
+    refused(r, [0, 2], -3, None, others=False)
+    fresh = S.reference(lp, [6, 6, 6], kinds["narrower"], max_out=st.max_out)
+    assert r["done"][1] == 6 and all(np.array_equal(r[k][1], fresh[k][1]) for k in S.KEYS)
+
+
+@pytest.mark.parametrize("scored", [False, True])
+def test_the_overflow_flag_is_sticky(scored):
+    """A table of 2 W V entries cannot run out, so the flag is set in the row by hand: from then on every read-out of that
+    utterance is n_hyp = -1, over chunks fed only and chunks of no frames as well, and the flag stays in the row."""
+    s, lp = scored_case("tiny_3gram.arpa", 7) if scored else plain_case(7, "f32")[:2]
+    lp = lp[:2, :14]
+    st = S.RawStream(2, 14, s)
+    dx = lp.to(DEV)
+    st.feed(dx[:, :4], [4, 4])
+    assert st.field(0, S.H_OVERFLOW) == 0 and st.field(0, S.H_FRAMES) == 4 and st.field(0, S.H_N) == 7 and st.field(0, S.H_DEAD) == 0
+    st.state[0, S.H_OVERFLOW] = 1
+    fed = 4
+    for n, nbest in ((3, None), (2, 0), (0, None), (5, 1)):
+        r = st.feed(dx[:, fed:fed + max(n, 1)], [n, n], nbest=nbest)
+        fed += n
+        assert r["done"].tolist() == [fed, fed] and st.field(0, S.H_OVERFLOW) == 1 and st.field(1, S.H_OVERFLOW) == 0
+        if nbest != 0:
+            want = S.reference(lp, [fed, fed], s, nbest=nbest)
+            assert r["n_hyp"][0] == -1 and r["n_hyp"][1] == want["n_hyp"][1] == (7 if nbest is None else nbest)
+            assert np.array_equal(r["scores"][1], want["scores"][1]) and np.array_equal(r["ids"][1], want["ids"][1])
+    assert fed == 14 and st.field(0, S.H_FRAMES) == 14
+
+
+def test_the_header_carries_the_exponents():
+    """esum is what the frames' rescaling took out: after enough frames it is far from 0, and the score needs it."""
+    s, lp, lens = plain_case(7, "f32")
+    st = S.RawStream(3, 60, s)
+    r = st.feed(lp[:, :30].to(DEV), [30, 30, 30])
+    esum = st.field(0, S.H_ESUM, 8)
+    assert esum < -30 and abs(float(r["scores"][0, 0]) - esum * math.log(2.0)) < 2.0      # (tot of the best is in [0.5, 1))
+
+
+# ---- 5. the module -------------------------------------------------------------------------------------------------------------
+FIELDS = ("decoded_targets", "decoded_targets_lengths", "scores", "ctc_scores", "lm_scores", "num_words", "num_oov_words",
+          "num_hypotheses", "timesteps")
+
+
+@pytest.mark.parametrize("keep_on_device,time_major", [(False, False), (True, True)])
+def test_module_configured(keep_on_device, time_major):
+    from end2end_amd._runtime import E2EError
+    model = "lm_order4.arpa"
+    R, V, l2i, x = XR.pruned_case(model)
+    labels = XR.PRUNED[model]["labels"]
+    x = torch.from_numpy(x).to(DEV)                                     # raw logits: the log-softmax is the decoder's, per chunk
+    d = decoder(R, V, l2i, 7, labels, after_logsoftmax=False, time_major=time_major, keep_on_device=keep_on_device)
+    d.configure(lm_path=os.path.join(LR.GOLDEN, model), **XR.KNOBS).restrict_to_vocabulary()
+    shaped = (lambda t: t.transpose(0, 1)) if time_major else (lambda t: t)
+    T, lens = XR.PRUNED_T, XR.PRUNED_LENS
+    st = d.open_stream(4, T)
+    fed = [0] * 4
+    for a, cl in zip(range(0, T, 5), S.regular(lens, T, 5)):
+        chunk, cl = shaped(x[:, a:a + 5]), torch.tensor(cl)
+        fed = [f + int(n) for f, n in zip(fed, cl)]
+        if a == 5:
+            best = st.feed(chunk, cl)
+            want = d.decode(shaped(x), torch.tensor(fed))
+            assert torch.equal(best.decoded_targets, want.decoded_targets) and best.decoded_sentences == want.decoded_sentences
+            assert torch.equal(best.decoded_targets_lengths, want.decoded_targets_lengths)
+        else:
+            got = st.feed_nbest(chunk, cl, timesteps=True)
+            want = d.decode_nbest(shaped(x), torch.tensor(fed), timesteps=True)
+            assert type(got) is type(want) and type(got).__name__ == "NBestResults"
+            for f in FIELDS:
+                assert torch.equal(getattr(got, f), getattr(want, f)), (f, fed)
+            assert got.decoded_sentences == want.decoded_sentences
+            assert got.decoded_targets.is_cuda == keep_on_device
+        assert st.frames == fed
+    assert fed == lens and st.state.shape == (4, st.row_bytes)
+    assert st.feed_nbest(shaped(x[:, :1]), torch.tensor([0, 0, 0, 0]), nbest=2).timesteps is None    # (asked for per call)
+    # a later configure() of the decoder does not reach the stream: its rows go on under the configuration they were opened with
+    d.configure(wip=0.0)
+    got = st.feed_nbest(shaped(x[:, :1]), torch.tensor([0, 0, 0, 0]), timesteps=True)
+    for f in FIELDS:
+        assert torch.equal(getattr(got, f), getattr(want, f)), f
+    # a status surfaces as an error that names the utterance; the others have advanced
+    with pytest.raises(E2EError, match="utterance 0 would pass max_frames=%d" % T):
+        st.feed(shaped(x[:, :2]), torch.tensor([1, 2, 0, 0]))
+    assert st.frames == [lens[0], lens[1] + 2, lens[2], lens[3]]
+    st.reset([0])
+    assert st.frames[0] == 0
+    assert st.feed_nbest(shaped(x[:, :1]), torch.tensor([1, 0, 0, 0]), nbest=0) is None and st.frames[0] == 1
+
+
+def test_module_unconfigured():
+    R, V, l2i, batches = DR.pruned_cases()
+    x, xl = batches[(7, 1.0)]
+    lp = torch.from_numpy(DR.log_softmax(x)).float().to(DEV)
+    d = decoder(R, V, l2i, 7)
+    st = d.open_stream(3, 60)
+    first = st.feed_nbest(lp[:, :1], torch.tensor([0, 0, 0]))           # before any frame: the empty hypothesis
+    assert first.num_hypotheses.tolist() == [1, 1, 1] and first.scores[:, 0].tolist() == [0.0, 0.0, 0.0]
+    assert first.decoded_sentences == [[""], [""], [""]]
+    fed = [0, 0, 0]
+    for a, cl in zip(range(0, 60, 16), S.regular(xl.tolist(), 60, 16)):
+        fed = [f + n for f, n in zip(fed, cl)]
+        got = st.feed_nbest(lp[:, a:a + 16], torch.tensor(cl), nbest=5)
+        want = d.decode_nbest(lp, torch.tensor(fed), nbest=5)
+        assert type(got) is type(want) and type(got).__name__ == "GramNBestResults"
+        for f in ("decoded_targets", "decoded_targets_lengths", "scores", "num_hypotheses"):
+            assert torch.equal(getattr(got, f), getattr(want, f)), (f, fed)
+        assert st.frames == fed
+    one, want = st.feed(lp[:, :1], torch.tensor([0, 0, 0])), d.decode(lp, torch.from_numpy(xl))
+    assert torch.equal(one.decoded_targets, want.decoded_targets) and one.decoded_sentences == want.decoded_sentences
+    with pytest.raises(ValueError, match="configure"):
+        st.feed_nbest(lp[:, :1], torch.tensor([0, 0, 0]), timesteps=True)

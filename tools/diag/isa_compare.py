@@ -12,7 +12,8 @@ another namespace or another source).  Of each kernel two things are compared, l
   * the .amdhsa_* descriptor block (registers, scratch, LDS, next_free_*), as it stands.
   tools/diag/isa_compare.py A B 'REGEX=REPLACEMENT'   the same after renaming on both sides: for a kernel whose name changed
       but whose code should not have (a template argument more, with a default: asg_beam.hip's ST,
-      'asg_beam_kernel<(\w+, \w+, \w+), false>\(.*?\)=asg_beam_kernel<\1>(AsgBeamParams)')
+      'asg_beam_kernel<(\w+, \w+, \w+), false>\(.*?\)=asg_beam_kernel<\1>(AsgBeamParams)'; ctc_gram_decode.hip's ST, whose
+      parameter type is spelled as a nest of conditionals: 'gram_beam_kernel<(\w+, \w+, \w+)(, false)?>\(.*?::type\)=gram_beam_kernel<\1>(P)')
 One line per kernel, then the counts; the exit status is 0 only if every kernel is on both sides and identical.
 It compares two dumps with each other and nothing more."""
 import os
