@@ -116,14 +116,6 @@ __device__ __forceinline__ bool spellable(const AsgBeamParams& p, int a, int c) 
 // what the pair (member m, label c != space) asks of the model: the expanded word's hash, its id, its score in the context
 // (`listed`, the restricted search's: the spelling is in the table at all -- a word, or with id 0 a prefix of one)
 struct LmAnswer { unsigned long long h; uint32_t wi; float sc; bool listed; };
-__device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned long long h, int c) {
-  for (int bi = lm.label_off[c]; bi < lm.label_off[c + 1]; bi++) {
-    unsigned char ch = lm.label_bytes[bi];
-    if (lm.fold_case && ch >= 'A' && ch <= 'Z') ch += 32;
-    h = fnv_step(h, ch);
-  }
-  return h;
-}
 template <bool LEX = false>
 __device__ __forceinline__ LmAnswer lm_query(const AsgBeamParams& p, const LmMembers& L, int m, int a, int c, bool new_word) {
   LmAnswer ans;
@@ -206,12 +198,6 @@ __device__ __forceinline__ int asg_stream_open(const AsgBeamParams& p, const Asg
   n = __builtin_amdgcn_readfirstlane(nn);
   return __builtin_amdgcn_readfirstlane(st);
 }
-// a member set between LDS and the row, as it stands (all threads; plain vector loads and stores)
-__device__ __forceinline__ void asg_stream_copy(void* dst, const void* src, size_t bytes) {
-  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
-  unsigned long long* d = reinterpret_cast<unsigned long long*>(dst);
-  for (size_t i = threadIdx.x; i < bytes / 8; i += kThreads) d[i] = s[i];
-}
 
 // The search of one utterance, whole (ST = false: the parameter block is AsgBeamParams and sp is not read) or streamed: one
 // piece of source, and without ST the code the kernel had before it could stream, instruction for instruction
@@ -263,8 +249,8 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgKernelParams<ST> 
   int2* nodes = reinterpret_cast<int2*>(ST ? row + sp.off_nodes : ws + p.off_nodes);
 
   if (ST && resume) {                                             // the row's members become set 0
-    asg_stream_copy(&mem[0], row + kAsgStreamHeaderBytes, sizeof(Members));
-    if constexpr (LM) asg_stream_copy(&lms[0], row + sp.off_lm, sizeof(LmMembers));
+    stream_copy<kThreads>(&mem[0], row + kAsgStreamHeaderBytes, sizeof(Members));
+    if constexpr (LM) stream_copy<kThreads>(&lms[0], row + sp.off_lm, sizeof(LmMembers));
   } else if (tid == 0) {
     mem[0].s[0] = 0.0; mem[0].key[0] = kKeyBasis; mem[0].last[0] = -1; mem[0].node[0] = 0; mem[0].len[0] = 0; mem[0].nw[0] = 0;
     if constexpr (LM) {
@@ -421,8 +407,8 @@ __global__ __launch_bounds__(kThreads) void asg_beam_kernel(AsgKernelParams<ST> 
   // ---- suspend, behind the chunk's last frame: the current set, then the header.  A chunk of no frames stores nothing ----
   if constexpr (ST) {
     if (Tb > 0) {
-      asg_stream_copy(row + kAsgStreamHeaderBytes, &mem[cur], sizeof(Members));
-      if constexpr (LM) asg_stream_copy(row + sp.off_lm, &lms[cur], sizeof(LmMembers));
+      stream_copy<kThreads>(row + kAsgStreamHeaderBytes, &mem[cur], sizeof(Members));
+      if constexpr (LM) stream_copy<kThreads>(row + sp.off_lm, &lms[cur], sizeof(LmMembers));
     }
     if (tid == 0) {
       if (Tb > 0) {
@@ -538,16 +524,53 @@ int check_model(const e2e_lm* lm, int V, bool restricted) {
   }
   return E2E_OK;
 }
-// ... and the device its tables are on
-int check_model_device(const e2e_lm* lm) {
-  if (!lm) return E2E_OK;
-  if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
-  int cur = -1;
-  E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
-  if (cur != lm->device) {
-    set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, cur);
-    return E2E_ERR_ARG;
+// (... and the device its tables are on: check_model_device, ctc_lm.h)
+
+// every argument error that the whole call (min_nbest = 1) and the stream (0: feed only) have in common, in the order they are
+// reported; without a read-out max_out is not looked at
+int check_beam_args(int dtype, int B, int T, int V, int num_replabels, int space_id, int beam_width, int nbest, int64_t max_out,
+                    int min_nbest = 1) {
+  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
+  if (B < 0 || T < 1 || V < 1 || ((min_nbest > 0 || nbest > 0) && max_out < 0)) {
+    set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG;
   }
+  if (V > e2e_asg_max_labels()) { set_error("V=%d exceeds e2e_asg_max_labels() = %d", V, e2e_asg_max_labels()); return E2E_ERR_UNSUPPORTED; }
+  if (num_replabels < 0 || num_replabels >= V) { set_error("num_replabels=%d outside [0, V=%d)", num_replabels, V); return E2E_ERR_ARG; }
+  if (space_id >= V - num_replabels) { set_error("space_id=%d is not one of the %d characters", space_id, V - num_replabels); return E2E_ERR_ARG; }
+  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
+  if (beam_width > e2e_asg_beam_max_width(V)) {
+    set_error("beam_width %d exceeds e2e_asg_beam_max_width(V=%d) = %d", beam_width, V, e2e_asg_beam_max_width(V));
+    return E2E_ERR_UNSUPPORTED;
+  }
+  if (nbest < min_nbest || nbest > beam_width) { set_error("nbest=%d outside [%d, beam_width=%d]", nbest, min_nbest, beam_width); return E2E_ERR_ARG; }
+  return E2E_OK;
+}
+
+// the search's parameter block, the whole call's and the stream's alike; where the nodes lie (per_utt, off_nodes) is the caller's
+void fill_params(AsgBeamParams& p, const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len, int B, int T,
+                 int V, int num_replabels, int beam_width, int space_id, const e2e_lm* lm, double lmwt, double wip,
+                 double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                 int32_t* counts, int64_t* timesteps, void* workspace, const Layout& L, size_t per_utt, size_t off_nodes) {
+  p.x = x; p.dtype = dtype; p.sB = sB; p.sT = sT; p.sV = sV; p.x_len = x_len;
+  p.B = B; p.T = T; p.V = V; p.R = num_replabels; p.W = beam_width; p.space_id = space_id < 0 ? -1 : space_id; p.nbest = nbest;
+  if (lm) p.lm = lm->dev_view(); else memset(&p.lm, 0, sizeof(p.lm));
+  p.lmwt = lm ? lmwt : 0.0; p.wip = wip; p.oov = oov_penalty;
+  p.out = out; p.max_out = max_out; p.out_len = out_len; p.n_hyp = n_hyp; p.scores = scores; p.counts = counts;
+  p.timesteps = timesteps;
+  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
+  p.At = reinterpret_cast<const double*>(base);
+  p.ws = base + L.head; p.per_utt = per_utt; p.off_sval = L.off_sval; p.off_spos = L.off_spos; p.off_nodes = off_nodes;
+}
+
+// the transitions into the head of the workspace, then the search: q is the kernel's parameter block, p the search's in it
+template <typename Kernel, typename Params>
+int launch(Kernel kernel, const Params& q, const AsgBeamParams& p, const void* transitions, void* stream, const char* what) {
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(asg_beam_transpose_kernel, dim3((p.V * p.V + 255) / 256), dim3(256), 0, s, transitions, p.dtype, p.V,
+                     const_cast<double*>(p.At));
+  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_transpose_kernel launch");
+  hipLaunchKernelGGL(kernel, dim3(p.B), dim3(kThreads), 0, s, q);
+  E2E_HIP_CHECK(hipGetLastError(), what);
   return E2E_OK;
 }
 
@@ -579,17 +602,7 @@ int e2e_asg_beam_nbest_opt(const void* x, int dtype, int64_t sB, int64_t sT, int
                            const e2e_asg_beam_opts* opts) {
   const bool restricted = opts && opts->restrict_to_lexicon != 0;
   int64_t* timesteps = opts ? opts->timesteps : nullptr;
-  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
-  if (B < 0 || T < 1 || V < 1 || max_out < 0) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
-  if (V > e2e_asg_max_labels()) { set_error("V=%d exceeds e2e_asg_max_labels() = %d", V, e2e_asg_max_labels()); return E2E_ERR_UNSUPPORTED; }
-  if (num_replabels < 0 || num_replabels >= V) { set_error("num_replabels=%d outside [0, V=%d)", num_replabels, V); return E2E_ERR_ARG; }
-  if (space_id >= V - num_replabels) { set_error("space_id=%d is not one of the %d characters", space_id, V - num_replabels); return E2E_ERR_ARG; }
-  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
-  if (beam_width > e2e_asg_beam_max_width(V)) {
-    set_error("beam_width %d exceeds e2e_asg_beam_max_width(V=%d) = %d", beam_width, V, e2e_asg_beam_max_width(V));
-    return E2E_ERR_UNSUPPORTED;
-  }
-  if (nbest < 1 || nbest > beam_width) { set_error("nbest=%d outside [1, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (const int rc = check_beam_args(dtype, B, T, V, num_replabels, space_id, beam_width, nbest, max_out)) return rc;
   Layout L;
   if (!layout(T, V, beam_width, L)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
   if (const int rc = check_model(lm, V, restricted)) return rc;
@@ -603,26 +616,13 @@ int e2e_asg_beam_nbest_opt(const void* x, int dtype, int64_t sB, int64_t sT, int
     return E2E_ERR_WORKSPACE;
   }
   AsgBeamParams p;
-  p.x = x; p.dtype = dtype; p.sB = sB; p.sT = sT; p.sV = sV; p.x_len = x_len;
-  p.B = B; p.T = T; p.V = V; p.R = num_replabels; p.W = beam_width; p.space_id = space_id < 0 ? -1 : space_id; p.nbest = nbest;
-  if (lm) p.lm = lm->dev_view(); else memset(&p.lm, 0, sizeof(p.lm));
-  p.lmwt = lm ? lmwt : 0.0; p.wip = wip; p.oov = oov_penalty;
-  p.out = out; p.max_out = max_out; p.out_len = out_len; p.n_hyp = n_hyp; p.scores = scores; p.counts = counts;
-  p.timesteps = timesteps;
-  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
-  p.At = reinterpret_cast<const double*>(base);
-  p.ws = base + L.head; p.per_utt = L.per_utt; p.off_sval = L.off_sval; p.off_spos = L.off_spos; p.off_nodes = L.off_nodes;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(asg_beam_transpose_kernel, dim3((V * V + 255) / 256), dim3(256), 0, s, transitions, dtype, V,
-                     reinterpret_cast<double*>(base));
-  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_transpose_kernel launch");
+  fill_params(p, x, dtype, sB, sT, sV, x_len, B, T, V, num_replabels, beam_width, space_id, lm, lmwt, wip, oov_penalty, nbest,
+              out, max_out, out_len, n_hyp, scores, counts, timesteps, workspace, L, L.per_utt, L.off_nodes);
   auto kernel = asg_beam_kernel<false, false, false>;
   if (timesteps) kernel = restricted ? asg_beam_kernel<true, true, true> : lm ? asg_beam_kernel<true, false, true> : asg_beam_kernel<false, false, true>;
   else if (restricted) kernel = asg_beam_kernel<true, true, false>;
   else if (lm) kernel = asg_beam_kernel<true, false, false>;
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(kThreads), 0, s, p);
-  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_kernel launch");
-  return E2E_OK;
+  return launch(kernel, p, p, transitions, stream, "asg_beam_kernel launch");
 }
 
 int e2e_asg_beam_nbest(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
@@ -656,17 +656,7 @@ int e2e_asg_beam_stream(const void* x, int dtype, int64_t sB, int64_t sT, int64_
                         void* workspace, size_t workspace_bytes, void* stream, const e2e_asg_beam_opts* opts) {
   const bool restricted = opts && opts->restrict_to_lexicon != 0;
   // every argument error the host can see, before any launch
-  if (dtype != E2E_F32 && dtype != E2E_F64) { set_error("dtype must be E2E_F32 or E2E_F64"); return E2E_ERR_ARG; }
-  if (B < 0 || T < 1 || V < 1 || (nbest > 0 && max_out < 0)) { set_error("bad sizes B=%d T=%d V=%d max_out=%lld", B, T, V, (long long)max_out); return E2E_ERR_ARG; }
-  if (V > e2e_asg_max_labels()) { set_error("V=%d exceeds e2e_asg_max_labels() = %d", V, e2e_asg_max_labels()); return E2E_ERR_UNSUPPORTED; }
-  if (num_replabels < 0 || num_replabels >= V) { set_error("num_replabels=%d outside [0, V=%d)", num_replabels, V); return E2E_ERR_ARG; }
-  if (space_id >= V - num_replabels) { set_error("space_id=%d is not one of the %d characters", space_id, V - num_replabels); return E2E_ERR_ARG; }
-  if (beam_width < 1) { set_error("beam_width %d must be at least 1", beam_width); return E2E_ERR_ARG; }
-  if (beam_width > e2e_asg_beam_max_width(V)) {
-    set_error("beam_width %d exceeds e2e_asg_beam_max_width(V=%d) = %d", beam_width, V, e2e_asg_beam_max_width(V));
-    return E2E_ERR_UNSUPPORTED;
-  }
-  if (nbest < 0 || nbest > beam_width) { set_error("nbest=%d outside [0, beam_width=%d]", nbest, beam_width); return E2E_ERR_ARG; }
+  if (const int rc = check_beam_args(dtype, B, T, V, num_replabels, space_id, beam_width, nbest, max_out, 0)) return rc;
   if (max_frames < 1 || max_frames > (1 << 22)) { set_error("max_frames=%d outside [1, %d]", max_frames, 1 << 22); return E2E_ERR_ARG; }
   StreamLayout S;
   Layout L;
@@ -684,35 +674,22 @@ int e2e_asg_beam_stream(const void* x, int dtype, int64_t sB, int64_t sT, int64_
   }
   if (B > 0 && reinterpret_cast<uintptr_t>(state) % 8) { set_error("the state must be 8-byte aligned"); return E2E_ERR_ARG; }
   if (B == 0) return E2E_OK;
-  const size_t per_utt = L.off_nodes;
+  const size_t per_utt = L.off_nodes;                             // (the node pool lives in the row)
   if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < L.head + (size_t)B * per_utt) {
     set_error("workspace too small: %zu bytes, e2e_asg_beam_stream_workspace_bytes() = %zu", workspace_bytes, L.head + (size_t)B * per_utt + 256);
     return E2E_ERR_WORKSPACE;
   }
   if (const int rc = check_model_device(lm)) return rc;
   AsgStreamParams sp;
-  AsgBeamParams& p = sp.b;
-  p.x = x; p.dtype = dtype; p.sB = sB; p.sT = sT; p.sV = sV; p.x_len = chunk_len;
-  p.B = B; p.T = T; p.V = V; p.R = num_replabels; p.W = beam_width; p.space_id = space_id < 0 ? -1 : space_id; p.nbest = nbest;
-  if (lm) p.lm = lm->dev_view(); else memset(&p.lm, 0, sizeof(p.lm));
-  p.lmwt = lm ? lmwt : 0.0; p.wip = wip; p.oov = oov_penalty;
-  p.out = out; p.max_out = nbest > 0 ? max_out : 0; p.out_len = out_len; p.n_hyp = n_hyp; p.scores = scores; p.counts = counts;
-  p.timesteps = nbest > 0 && opts ? opts->timesteps : nullptr;
-  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
-  p.At = reinterpret_cast<const double*>(base);
-  p.ws = base + L.head; p.per_utt = per_utt; p.off_sval = L.off_sval; p.off_spos = L.off_spos; p.off_nodes = 0;
+  fill_params(sp.b, x, dtype, sB, sT, sV, chunk_len, B, T, V, num_replabels, beam_width, space_id, lm, lmwt, wip, oov_penalty, nbest,
+              out, nbest > 0 ? max_out : 0, out_len, n_hyp, scores, counts, nbest > 0 && opts ? opts->timesteps : nullptr,
+              workspace, L, per_utt, 0);
   sp.s.rows = reinterpret_cast<unsigned char*>(state); sp.s.row_bytes = row_bytes; sp.s.off_lm = S.off_lm; sp.s.off_nodes = S.off_nodes;
   sp.s.max_frames = max_frames; sp.s.frames_done = frames_done;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(asg_beam_transpose_kernel, dim3((V * V + 255) / 256), dim3(256), 0, s, transitions, dtype, V,
-                     reinterpret_cast<double*>(base));
-  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_transpose_kernel launch");
   auto kernel = asg_beam_kernel<false, false, false, true>;
   if (restricted) kernel = asg_beam_kernel<true, true, false, true>;
   else if (lm) kernel = asg_beam_kernel<true, false, false, true>;
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(kThreads), 0, s, sp);
-  E2E_HIP_CHECK(hipGetLastError(), "asg_beam_kernel (stream) launch");
-  return E2E_OK;
+  return launch(kernel, sp, sp.b, transitions, stream, "asg_beam_kernel (stream) launch");
 }
 
 }  // extern "C"

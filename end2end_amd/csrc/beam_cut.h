@@ -27,6 +27,15 @@ __device__ __forceinline__ unsigned long long okey(double d) {
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
+// a streaming search's member set between LDS and its state row, as it stands: `bytes` (a multiple of 8) copied by all
+// kThreads threads of the workgroup in plain vector loads and stores
+template <int kThreads>
+__device__ __forceinline__ void stream_copy(void* dst, const void* src, size_t bytes) {
+  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(dst);
+  for (size_t i = threadIdx.x; i < bytes / 8; i += kThreads) d[i] = s[i];
+}
+
 // the cut's LDS state: a kernel declares one __shared__ and zeroes n_sel (behind a barrier) before every beam_cut
 struct BeamCut {
   double sel_tot[kMaxW];                                // the survivors: total,

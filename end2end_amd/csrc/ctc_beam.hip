@@ -149,21 +149,12 @@ static int beam_call(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
   if (B < 0 || T < 1 || V < 1 || beam_width < 1 || max_out < 1) { set_error("bad sizes"); return E2E_ERR_ARG; }
   if (blank < 0 || blank >= V) { set_error("blank=%d outside [0,%d)", blank, V); return E2E_ERR_ARG; }
   if (B > 0 && (!lp || !x_len || ((!out || !out_len) && !(st && nb->nbest == 0)))) { set_error("null pointer argument"); return E2E_ERR_ARG; }
-  if (lm && !lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
-  if (lm) {
-    int cur = -1;
-    E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
-    if (cur != lm->device) {
-      set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device",
-                lm->device, cur);
-      return E2E_ERR_ARG;
-    }
-    // the kernel spells words with label_off[0..V]: the model must have been loaded with exactly this alphabet
-    if ((int)lm->label_off.size() - 1 != V) {
-      set_error("the language model was loaded with %d labels but the log-probabilities have %d columns",
-                (int)lm->label_off.size() - 1, V);
-      return E2E_ERR_ARG;
-    }
+  if (const int rc = check_model_device(lm)) return rc;
+  // the kernel spells words with label_off[0..V]: the model must have been loaded with exactly this alphabet
+  if (lm && (int)lm->label_off.size() - 1 != V) {
+    set_error("the language model was loaded with %d labels but the log-probabilities have %d columns",
+              (int)lm->label_off.size() - 1, V);
+    return E2E_ERR_ARG;
   }
   // (a stream: the node pool is the row's, sized by max_frames; the workspace holds the general kernel's share alone)
   const BeamLayout l = beam_layout(B, st ? st->max_frames : T, V, beam_width, lm != nullptr);

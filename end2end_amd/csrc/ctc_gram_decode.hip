@@ -278,14 +278,6 @@ __device__ __forceinline__ LmWalk root_walk(const GramLmParams& q) {
   w.st[0] = q.has_lm ? q.lm.bos : 0u; w.stb[0] = w.st[0]; w.stn = 1; w.stbn = 1;
   return w;
 }
-__device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned long long h, int c) {
-  for (int bi = lm.label_off[c]; bi < lm.label_off[c + 1]; bi++) {
-    unsigned char ch = lm.label_bytes[bi];
-    if (lm.fold_case && ch >= 'A' && ch <= 'Z') ch += 32;
-    h = fnv_step(h, ch);
-  }
-  return h;
-}
 // w: the fields of a sequence -> those of the sequence extended by column c's k base ids: get_next_prefix's LM part
 // (asg_beam.hip's child_lm and what follows it there) applied id by id.  The model is asked where a word ends inside the
 // gram and at the gram's last id; the answers in between would be overwritten (each is lm_before + one score, state_before
@@ -364,12 +356,6 @@ __device__ __forceinline__ int gram_stream_open(const GramStream& sp, const unsi
          (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)es);
   return __builtin_amdgcn_readfirstlane(st);
 }
-// a member set between LDS and the row, as it stands (all threads; plain vector loads and stores)
-__device__ __forceinline__ void gram_stream_copy(void* dst, const void* src, size_t bytes) {
-  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
-  unsigned long long* d = reinterpret_cast<unsigned long long*>(dst);
-  for (size_t i = threadIdx.x; i < bytes / 8; i += kBeamThreads) d[i] = s[i];
-}
 static_assert(sizeof(Members) % 8 == 0 && sizeof(LmMembers) % 8 == 0, "the member sets are copied in 8-byte words");
 
 // LM = false: the search on the masses alone (e2e_gram_ctc_beam_nbest), the parameter block GramBeamParams.  LM = true: the
@@ -432,8 +418,8 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
   for (unsigned i = tid; i < H; i += kBeamThreads) { table[i].key = 0ull; table[i].head = -1; }
   if constexpr (LM) { if (tid < kMaxW) { S->lms[0].row[tid] = 0; S->lms[1].row[tid] = 0; } }   // (never a row outside the cache)
   if (ST && resume) {                                            // the row's members become set 0
-    gram_stream_copy(&mem[0], row + kGramStreamHeaderBytes, sizeof(Members));
-    if constexpr (LM) gram_stream_copy(&S->lms[0], row + sp.off_lm, sizeof(LmMembers));
+    stream_copy<kBeamThreads>(&mem[0], row + kGramStreamHeaderBytes, sizeof(Members));
+    if constexpr (LM) stream_copy<kBeamThreads>(&S->lms[0], row + sp.off_lm, sizeof(LmMembers));
     if (tid == 0) overflow = ovf0;
   } else if (tid == 0) {
     for (int k = 0; k <= kMaxK; k++) { mem[0].p[k][0] = k == 0 ? 1.0 : 0.0; mem[0].col[k][0] = 0; }
@@ -665,8 +651,8 @@ __global__ __launch_bounds__(kBeamThreads) void gram_beam_kernel(GramKernelParam
   // ---- suspend, behind the chunk's last frame: the current set, then the header.  A chunk of no frames stores nothing ----
   if constexpr (ST) {
     if (Tb > 0) {
-      gram_stream_copy(row + kGramStreamHeaderBytes, &mem[cur], sizeof(Members));
-      if constexpr (LM) gram_stream_copy(row + sp.off_lm, &S->lms[cur], sizeof(LmMembers));
+      stream_copy<kBeamThreads>(row + kGramStreamHeaderBytes, &mem[cur], sizeof(Members));
+      if constexpr (LM) stream_copy<kBeamThreads>(row + sp.off_lm, &S->lms[cur], sizeof(LmMembers));
     }
     if (tid == 0) {
       if (Tb > 0) {
@@ -796,18 +782,7 @@ int check_scored_args(int V, int num_base_labels, int space_id, const e2e_lm* lm
   }
   return E2E_OK;
 }
-// ... and the device the model's tables are on
-int check_model_device(const e2e_lm* lm) {
-  if (!lm) return E2E_OK;
-  if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
-  int dev = -1;
-  E2E_HIP_CHECK(hipGetDevice(&dev), "hipGetDevice");
-  if (dev != lm->device) {
-    set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, dev);
-    return E2E_ERR_ARG;
-  }
-  return E2E_OK;
-}
+// (... and the device the model's tables are on: check_model_device, ctc_lm.h)
 
 // a state row of a stream: header | Members | LmMembers (scored) | node pool of max_frames frames, each part 256-aligned.  The
 // workspace of a streaming call: a frame's scratch (beam_layout's up to the nodes, which are the row's) and, with a model,

@@ -67,6 +67,16 @@ __host__ __device__ inline bool is_hom_ref(uint32_t val) { return (val & kHomMar
 
 __host__ __device__ inline uint64_t fnv_step(uint64_t h, unsigned char b) { return (h ^ b) * 1099511628211ULL; }
 constexpr uint64_t kFnvInit = 1469598103934665603ULL;
+// the hash h of a spelling, extended by label c's bytes (the searches that spell from the model's own strings: asg_beam.hip,
+// ctc_gram_decode.hip)
+__device__ __forceinline__ unsigned long long spell(const LmView& lm, unsigned long long h, int c) {
+  for (int bi = lm.label_off[c]; bi < lm.label_off[c + 1]; bi++) {
+    unsigned char ch = lm.label_bytes[bi];
+    if (lm.fold_case && ch >= 'A' && ch <= 'Z') ch += 32;
+    h = fnv_step(h, ch);
+  }
+  return h;
+}
 
 // hash of an n-gram of word ids (table placement and signature; internal to the LM code): one multiply per id
 __host__ __device__ inline uint64_t ng_mix(uint64_t h, uint32_t id) { h = (h ^ id) * 0x9E3779B97F4A7C15ULL; return h ^ (h >> 32); }
@@ -197,3 +207,9 @@ struct e2e_lm {
             nwords, unk_prob, d_homs};
   }
 };
+
+namespace e2e {
+// E2E_OK if a call on the current device may read the model's tables (lm null: no model, nothing to read), else the error
+// set: no device tables, or tables on another device (ctc_lm.hip)
+int check_model_device(const e2e_lm* lm);
+}  // namespace e2e

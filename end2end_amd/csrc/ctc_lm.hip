@@ -308,6 +308,18 @@ extern "C" void e2e_lm_free(e2e_lm* lm) {
 extern "C" int e2e_lm_order(const e2e_lm* lm) { return lm ? lm->order : 0; }
 extern "C" int e2e_lm_device(const e2e_lm* lm) { return lm ? lm->device : -1; }
 
+int e2e::check_model_device(const e2e_lm* lm) {
+  if (!lm) return E2E_OK;
+  if (!lm->d_ng) { set_error("the language model has no device tables (it was loaded without a GPU)"); return E2E_ERR_HIP; }
+  int cur = -1;
+  E2E_HIP_CHECK(hipGetDevice(&cur), "hipGetDevice");
+  if (cur != lm->device) {
+    set_error("the language model's tables are on device %d but the call runs on device %d: load it once per device", lm->device, cur);
+    return E2E_ERR_ARG;
+  }
+  return E2E_OK;
+}
+
 // get_idx(string), ctc_decoder.cpp:77-82: exact lookup when case sensitive, else lower-cased lookup
 extern "C" uint32_t e2e_lm_word_index(const e2e_lm* lm, const char* word) {
   if (!lm || !word) return 0;

@@ -19,7 +19,7 @@ from collections import namedtuple
 import torch
 
 from ..engines import ASGBeamEngine, ASGViterbiEngine
-from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults, read_lexicon
+from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults, _DecoderStream, read_lexicon
 
 # decode_path(): the label of every frame, -100 past an utterance's length (as get_alignment_3d pads), and the paths' scores
 ASGPathResults = namedtuple("ASGPathResults", ["paths", "scores"])
@@ -186,41 +186,11 @@ class ASGDecoder:
             raise CTCDecoderError(str(e))
 
 
-class ASGDecoderStream:
-    """What ``ASGDecoder.open_stream`` returns: ``CTCDecoderStream``'s surface.  ``feed`` / ``feed_nbest`` take a chunk of
-    emissions shaped as ``decode`` takes them (``logits_lengths``: the frames of this chunk per utterance, all by default, 0
-    allowed) and return ``DecoderResults`` / ``NBestResults`` for everything fed so far; ``frames`` are the per-utterance
-    totals, ``state`` the (batch, row_bytes) uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts
-    utterances anew."""
-
-    def __init__(self, decoder, stream):
-        self._owner, self._stream = decoder, stream
-
-    @property
-    def frames(self):
-        return self._stream.frames
-
-    @property
-    def state(self):
-        return self._stream.state
-
-    @property
-    def row_bytes(self):
-        return self._stream.row_bytes
-
-    def reset(self, rows=None):
-        self._stream.reset(rows)
+class ASGDecoderStream(_DecoderStream):
+    """What ``ASGDecoder.open_stream`` returns: ``_DecoderStream`` (``CTCDecoderStream``'s surface), fed emissions as they
+    are."""
 
     def _chunk(self, emissions, logits_lengths):
         emissions, logits_lengths = self._owner._batch_major(emissions, logits_lengths)
         self._stream.check_chunk(tuple(emissions.shape))          # (before any device work)
         return emissions, logits_lengths
-
-    def feed(self, emissions, logits_lengths=None):
-        emissions, logits_lengths = self._chunk(emissions, logits_lengths)
-        return DecoderResults(*self._stream.feed(emissions, logits_lengths))
-
-    def feed_nbest(self, emissions, logits_lengths=None, nbest=None):
-        emissions, logits_lengths = self._chunk(emissions, logits_lengths)
-        r = self._stream.feed_nbest(emissions, logits_lengths, nbest=nbest)
-        return None if r is None else NBestResults(*r)

@@ -198,11 +198,14 @@ class CTCDecoder:
         return DecoderResults(*self._decoder.decode_greedy(logits_=logits, logits_lengths_=logits_lengths))
 
 
-class CTCDecoderStream:
-    """What ``CTCDecoder.open_stream`` returns.  ``feed`` / ``feed_nbest`` take a chunk of logits shaped as ``decode`` takes them
+class _DecoderStream:
+    """What the decoders' ``open_stream`` return.  ``feed`` / ``feed_nbest`` take a chunk shaped as ``decode`` takes it
     (``logits_lengths``: the frames of this chunk per utterance, all by default, 0 allowed) and return ``DecoderResults`` /
     ``NBestResults`` for everything fed so far; ``frames`` are the per-utterance totals, ``state`` the (batch, row_bytes)
-    uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts utterances anew."""
+    uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts utterances anew.  A decoder's stream says how
+    a chunk becomes what its engine's stream takes (``_chunk``)."""
+
+    _nbest_type = NBestResults
 
     def __init__(self, decoder, stream):
         self._owner, self._stream = decoder, stream
@@ -215,8 +218,29 @@ class CTCDecoderStream:
     def state(self):
         return self._stream.state
 
+    @property
+    def row_bytes(self):
+        return self._stream.row_bytes
+
     def reset(self, rows=None):
         self._stream.reset(rows)
+
+    def feed(self, logits, logits_lengths=None):
+        logits, logits_lengths = self._chunk(logits, logits_lengths)
+        return DecoderResults(*self._stream.feed(logits, logits_lengths))
+
+    def feed_nbest(self, logits, logits_lengths=None, nbest=None):
+        return self._read_out(logits, logits_lengths, nbest=nbest)
+
+    def _read_out(self, logits, logits_lengths, **read_out):
+        logits, logits_lengths = self._chunk(logits, logits_lengths)
+        r = self._stream.feed_nbest(logits, logits_lengths, **read_out)
+        return None if r is None else self._nbest_type(*r)
+
+
+class CTCDecoderStream(_DecoderStream):
+    """What ``CTCDecoder.open_stream`` returns: ``_DecoderStream``, fed logits; the log-softmax is per frame, so it is applied
+    per chunk."""
 
     def _chunk(self, logits, logits_lengths):
         d = self._owner
@@ -226,12 +250,3 @@ class CTCDecoderStream:
             if not d._after_logsoftmax:
                 logits = torch.log_softmax(logits, -1)            # per frame: the same numbers whatever the chunking
         return logits, logits_lengths
-
-    def feed(self, logits, logits_lengths=None):
-        logits, logits_lengths = self._chunk(logits, logits_lengths)
-        return DecoderResults(*self._stream.feed(logits, logits_lengths))
-
-    def feed_nbest(self, logits, logits_lengths=None, nbest=None):
-        logits, logits_lengths = self._chunk(logits, logits_lengths)
-        r = self._stream.feed_nbest(logits, logits_lengths, nbest=nbest)
-        return None if r is None else NBestResults(*r)

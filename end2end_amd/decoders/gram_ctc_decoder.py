@@ -18,7 +18,7 @@ from collections import namedtuple
 import torch
 
 from ..engines import GramCTCDecoderEngine
-from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults
+from .ctc_decoder import CTCDecoderError, DecoderResults, NBestResults, _DecoderStream
 
 # decode_nbest(): (B, N, ...) per utterance and hypothesis, ranked by `scores` (the log-probability of the labelling within
 # the beam); `decoded_sentences[b]` lists the num_hypotheses[b] sentences of utterance b
@@ -168,30 +168,14 @@ class GramCTCDecoder:
             raise CTCDecoderError(str(e))
 
 
-class GramCTCDecoderStream:
-    """What ``GramCTCDecoder.open_stream`` returns: ``CTCDecoderStream``'s surface.  ``feed`` / ``feed_nbest`` take a chunk of
-    logits shaped as ``decode`` takes them (``logits_lengths``: the frames of this chunk per utterance, all by default, 0
-    allowed; the log-softmax is per frame, so it is applied per chunk) and return ``DecoderResults`` / ``GramNBestResults``
-    (``NBestResults`` after ``configure()``) for everything fed so far; ``frames`` are the per-utterance totals, ``state`` the
-    (batch, row_bytes) uint8 tensor on the GPU that holds the beams, ``reset(rows=None)`` starts utterances anew."""
-
-    def __init__(self, decoder, stream):
-        self._owner, self._stream = decoder, stream
+class GramCTCDecoderStream(_DecoderStream):
+    """What ``GramCTCDecoder.open_stream`` returns: ``_DecoderStream`` (``CTCDecoderStream``'s surface), fed logits -- the
+    log-softmax is per frame, so it is applied per chunk.  ``feed_nbest`` returns ``GramNBestResults``, after ``configure()``
+    ``NBestResults``, and takes ``timesteps`` per read-out."""
 
     @property
-    def frames(self):
-        return self._stream.frames
-
-    @property
-    def state(self):
-        return self._stream.state
-
-    @property
-    def row_bytes(self):
-        return self._stream.row_bytes
-
-    def reset(self, rows=None):
-        self._stream.reset(rows)
+    def _nbest_type(self):
+        return NBestResults if self._stream.scored else GramNBestResults
 
     def _chunk(self, logits, logits_lengths):
         if logits.dim() != 3:
@@ -200,16 +184,8 @@ class GramCTCDecoderStream:
         self._stream.check_chunk(tuple(logits.shape))             # (before any device work)
         return self._owner._logprobs(logits), logits_lengths
 
-    def feed(self, logits, logits_lengths=None):
-        logits, logits_lengths = self._chunk(logits, logits_lengths)
-        return DecoderResults(*self._stream.feed(logits, logits_lengths))
-
     def feed_nbest(self, logits, logits_lengths=None, nbest=None, timesteps=None):
         if timesteps and not self._stream.scored:
             raise ValueError("timesteps are a field of NBestResults, which a configured decoder returns: call configure(wip=0) "
                              "for the same search with timesteps")
-        logits, logits_lengths = self._chunk(logits, logits_lengths)
-        r = self._stream.feed_nbest(logits, logits_lengths, nbest=nbest, timesteps=timesteps)
-        if r is None:
-            return None
-        return NBestResults(*r) if self._stream.scored else GramNBestResults(*r)
+        return self._read_out(logits, logits_lengths, nbest=nbest, timesteps=timesteps)

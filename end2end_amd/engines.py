@@ -64,6 +64,68 @@ def _pack_nbest(out, lens, nh, strings, keep_on_device):
     return ids if keep_on_device else ids_host, sentences, width
 
 
+def _nbest_buffers(B, N, max_out, dev, scored=True, timesteps=False, prefill=None):
+    """The buffers an n-best read-out fills -> (out (B,N,max_out) int64, out_len (B,N), n_hyp (B), scores (B,N,3) f64, counts
+    (B,N,2) int32, ts (B,N,max_out) int64 or None); not scored (Gram-CTC's search on the masses): scores (B,N) and no counts.
+    `prefill` None: nothing (the call writes every slot); "ts": the timesteps with -1; "all": every buffer with the empty
+    result -- length 0, -inf, an LM score of 0, timesteps -1 -- for a call that leaves some utterances untouched."""
+    new = torch.zeros if prefill == "all" else torch.empty
+    out = new((B, N, max_out), dtype=torch.long, device=dev)
+    out_len = new((B, N), dtype=torch.long, device=dev)
+    n_hyp = new(B, dtype=torch.long, device=dev)
+    if prefill == "all":
+        scores = torch.full((B, N, 3) if scored else (B, N), float("-inf"), dtype=torch.float64, device=dev)
+        if scored:
+            scores[:, :, 2] = 0.0
+    else:
+        scores = torch.empty((B, N, 3) if scored else (B, N), dtype=torch.float64, device=dev)
+    counts = new((B, N, 2), dtype=torch.int32, device=dev) if scored else None
+    ts = None
+    if timesteps:
+        ts = (torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if prefill
+              else torch.empty((B, N, max_out), dtype=torch.long, device=dev))
+    return out, out_len, n_hyp, scores, counts, ts
+
+
+def _nbest_result(engine, out, out_len, n_hyp, scores, counts, ts):
+    """What decode_nbest and a stream's feed_nbest return, from the buffers the read-out has filled: (ids, lengths, sentences,
+    scores, acoustic scores, lm_scores, num_words, num_oov, num_hypotheses, timesteps or None) -- without counts (not scored):
+    (ids, lengths, sentences, scores, num_hypotheses).  The status that rides on the counts and lengths is the engine's to
+    read (`_check_nbest`), its spelling `_strings`."""
+    nh, lens = n_hyp.tolist(), out_len.tolist()
+    engine._check_nbest(nh, lens, out.shape[2])
+    ids, sentences, width = _pack_nbest(out, lens, nh, engine._strings, engine.keep_on_device)
+    r = (lambda t: t) if engine.keep_on_device else (lambda t: t.cpu())
+    if counts is None:
+        return (ids, r(out_len), sentences, r(scores), r(n_hyp))
+    if ts is not None:
+        ts = r(ts[:, :, :width].contiguous())
+    return (ids, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
+            r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
+            r(counts[:, :, 1].contiguous()), r(n_hyp), ts)
+
+
+def _first_hypothesis(r):
+    """Hypothesis 0 of an n-best result -> (ids (B,maxlen) int64, lengths (B), sentences), what decode / feed return."""
+    return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+
+
+def _lexicon_words(lexicon):
+    """The words of a lexicon given as an iterable of words or as the path of a text file of them (white space between the
+    words) -> a list; a ValueError for a file that is not there and for no words at all."""
+    if isinstance(lexicon, (str, bytes, os.PathLike)):
+        path = os.fsdecode(lexicon)
+        if not os.path.isfile(path):
+            raise ValueError("Can't find a lexicon: {}".format(path))
+        with open(path, encoding="utf-8") as f:
+            words = f.read().split()
+    else:
+        words = [str(w) for w in lexicon]
+    if not words:
+        raise ValueError("the lexicon is empty")
+    return words
+
+
 class _NullCtx:
     def __enter__(self):
         return None
@@ -73,6 +135,118 @@ class _NullCtx:
 
 
 _NULL_CTX = _NullCtx()
+
+
+class _BeamStream:
+    """The beams of `batch_size` utterances, kept on the GPU between chunks: what the engines' open_stream return.  Owns the
+    (batch_size, row_bytes) uint8 state tensor `state`: one self-contained row per utterance, allocated at the first chunk
+    (on `device`, else on the chunk's GPU, else on the current one).  Rows may be reordered or copied by the caller; a row
+    whose first 256 bytes are zero starts a new utterance.  A family says how large a row is (`_row_bytes`), how a chunk is
+    checked and converted (`_prepare`), how many ids a hypothesis of so many frames can have (`_max_out`), makes its one C
+    call (`_launch`) and names the statuses that are its own (`_STATUS`)."""
+
+    HEADER_BYTES = 256
+    _INPUT = "logits"                    # what check_chunk calls a chunk
+    _PREFILL = None                      # _nbest_buffers' prefill
+    _STATUS = {}                         # frames_done < 0, beside -2 and -3: what it says of the utterance
+    _scored = True
+
+    def __init__(self, engine, batch_size, max_frames, device=None, timesteps=False):
+        if int(batch_size) < 1 or int(max_frames) < 1:
+            raise ValueError("batch_size and max_frames must be at least 1")
+        self.engine = engine
+        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
+        self.timesteps = bool(timesteps)
+        self.device = None if device is None else torch.device(device)
+        self.state = None
+        self.row_bytes = 0
+        self._frames = [0] * self.batch_size
+
+    @property
+    def frames(self):
+        """Frames consumed so far, per utterance."""
+        return list(self._frames)
+
+    def check_chunk(self, shape):
+        """The chunk's shape (batch, frames, alphabet) against the stream: a ValueError before any device work."""
+        if len(shape) != 3:
+            raise ValueError("%s must be (batch, time, alphabet)" % self._INPUT)
+        if shape[0] != self.batch_size:
+            raise ValueError("the chunk has %d utterances, the stream was opened for %d" % (shape[0], self.batch_size))
+        if not 1 <= shape[1] <= self.max_frames:
+            raise ValueError("a chunk of %d frames: the stream takes 1 .. max_frames = %d" % (shape[1], self.max_frames))
+
+    def reset(self, rows=None):
+        """Start the given utterances (all: None) anew: their headers are zeroed, nothing else is touched."""
+        idx = range(self.batch_size) if rows is None else [int(r) for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
+        for b in idx:
+            if not 0 <= b < self.batch_size:
+                raise ValueError("row %d outside the stream's %d utterances" % (b, self.batch_size))
+        if self.state is not None:
+            if rows is None:
+                self.state[:, : self.HEADER_BYTES].zero_()
+            else:
+                self.state[torch.as_tensor(list(idx), dtype=torch.long, device=self.state.device), : self.HEADER_BYTES] = 0
+        for b in idx:
+            self._frames[b] = 0
+
+    def _state_for(self, V, dev):
+        if self.state is None:
+            self.row_bytes = self._row_bytes(V)
+            if not self.row_bytes:
+                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported"
+                                 % (self.max_frames, self.engine.beam_width))
+            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
+            self.state[:, : self.HEADER_BYTES].zero_()
+            self.device = dev
+        return self.state
+
+    def feed_nbest(self, logits_, logits_lengths_=None, nbest=None):
+        """Feed a chunk (batch, frames, alphabet) -- of LOG-PROBABILITIES; an ASG stream: of emissions -- and read the beams out:
+        what the engine's decode_nbest returns for everything fed so far (timesteps if the stream was opened with them).
+        logits_lengths_: the frames of this chunk per utterance, 0 allowed, all of them by default.  nbest=0 feeds only and
+        returns None."""
+        return self._feed_nbest(logits_, logits_lengths_, nbest, self.timesteps)
+
+    def _feed_nbest(self, chunk, lengths, nbest, timesteps):
+        e = self.engine
+        N = e.beam_width if nbest is None else int(nbest)
+        if not 0 <= N <= e.beam_width:
+            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
+        self.check_chunk(tuple(chunk.shape))
+        B, Tc = chunk.shape[0], chunk.shape[1]
+        if lengths is None:
+            lengths = torch.full((B,), Tc, dtype=torch.long)
+        if self.device is not None and chunk.device != self.device:
+            chunk = chunk.to(self.device)
+        x, xl, dev = self._prepare(chunk, lengths)
+        state = self._state_for(x.shape[2], dev)
+        if dev != state.device:
+            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
+        max_out = self._max_out(max(self._frames) + Tc)
+        frames_done = torch.empty(B, dtype=torch.long, device=dev)
+        # (a buffer the read-out does not fill -- none at all with nbest=0 -- goes to the call as a null pointer)
+        bufs = _nbest_buffers(B, N, max_out, dev, self._scored, timesteps, self._PREFILL) if N else (None,) * 6
+        stream = R.stream_handle(dev)
+        with _on_device(dev):
+            self._launch(x, xl, state, N, max_out, [t.data_ptr() if t is not None else 0 for t in bufs],
+                         frames_done.data_ptr(), stream)
+        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
+        bad = None
+        for b, f in enumerate(frames_done.tolist()):
+            if f >= 0:
+                self._frames[b] = f
+            elif bad is None:
+                bad = (b, f)
+        if bad is not None:
+            why = {-2: "would pass max_frames=%d with this chunk" % self.max_frames,
+                   -3: "has a state row that was written under another configuration", **self._STATUS}
+            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
+        return _nbest_result(e, *bufs) if N else None
+
+    def feed(self, logits_, logits_lengths_=None):
+        """Feed a chunk and return what the engine's decode returns for everything fed so far: (ids, lengths, sentences)."""
+        return _first_hypothesis(self.feed_nbest(logits_, logits_lengths_, nbest=1))
 
 
 class _ForwardBackwardEngine:
@@ -406,9 +580,7 @@ class ASGBeamEngine:
         if lexicon is None and not self._lm_path and self._words is None:
             raise ValueError("restrict needs a vocabulary: lm_path or lexicon")
         if lexicon is not None:
-            words = [str(w) for w in lexicon]
-            if not words:
-                raise ValueError("the lexicon is empty")
+            words = _lexicon_words(lexicon)
             R.require_gpu()
             self._words = words
             self.lmwt = 0.0
@@ -493,13 +665,7 @@ class ASGBeamEngine:
             raise ValueError("logits_lengths must have one entry per utterance")
         max_out = max(T, 1)
         # (an utterance whose length is outside [1, T] is not touched by the call: its slots are the empty ones from here)
-        out = torch.zeros((B, N, max_out), dtype=torch.long, device=dev)
-        out_len = torch.zeros((B, N), dtype=torch.long, device=dev)
-        n_hyp = torch.zeros(B, dtype=torch.long, device=dev)
-        scores = torch.full((B, N, 3), float("-inf"), dtype=torch.float64, device=dev)
-        scores[:, :, 2] = 0.0
-        counts = torch.zeros((B, N, 2), dtype=torch.int32, device=dev)
-        ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if timesteps else None
+        bufs = out, out_len, n_hyp, scores, counts, ts = _nbest_buffers(B, N, max_out, dev, timesteps=timesteps, prefill="all")
         if B and T:
             stream = R.stream_handle(dev)
             with _on_device(dev):
@@ -514,22 +680,14 @@ class ASGBeamEngine:
                                   self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
                                   n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream,
                                   self.restricted, ts.data_ptr() if ts is not None else 0)
-        return self._nbest_result(out, out_len, n_hyp, scores, counts, ts)
+        return _nbest_result(self, *bufs)
 
-    def _nbest_result(self, out, out_len, n_hyp, scores, counts, ts):
-        """What decode_nbest returns, from the buffers the read-out has filled (ts: None without timesteps)."""
-        ids, sentences, width = _pack_nbest(out, out_len.tolist(), n_hyp.tolist(), self._strings, self.keep_on_device)
-        r = (lambda t: t) if self.keep_on_device else (lambda t: t.cpu())
-        if ts is not None:
-            ts = r(ts[:, :, :width].contiguous())
-        return (ids, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
-                r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
-                r(counts[:, :, 1].contiguous()), r(n_hyp), ts)
+    def _check_nbest(self, nh, lens, max_out):
+        pass                                         # (no status rides on the results: the search cannot run out of anything)
 
     def decode(self, emissions, transitions, logits_lengths):
         """Hypothesis 0 of decode_nbest -> (ids (B,maxlen) int64, lengths (B), sentences)."""
-        r = self.decode_nbest(emissions, transitions, logits_lengths, nbest=1)
-        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+        return _first_hypothesis(self.decode_nbest(emissions, transitions, logits_lengths, nbest=1))
 
     def open_stream(self, transitions, batch_size, max_frames, device=None, timesteps=False):
         """Streaming beam search (e2e_asg_beam_stream, include/e2e_ctc.h): an ASGBeamStream that is fed emissions in chunks
@@ -539,66 +697,21 @@ class ASGBeamEngine:
         return ASGBeamStream(self, transitions, batch_size, max_frames, device=device, timesteps=timesteps)
 
 
-class ASGBeamStream:
-    """The beams of `batch_size` utterances, kept on the GPU between chunks (ASGBeamEngine.open_stream): CTCBeamStream's
-    surface.  Owns the (batch_size, row_bytes) uint8 state tensor `state`: one self-contained row per utterance, allocated
-    at the first chunk (on `device`, else on the chunk's GPU, else on the current one).  Rows may be reordered or copied by
-    the caller; a row whose first 256 bytes are zero starts a new utterance.  The transitions are the stream's: converted to
-    a chunk's dtype on first use and kept."""
+class ASGBeamStream(_BeamStream):
+    """The ASG beams of `batch_size` utterances, kept on the GPU between chunks (ASGBeamEngine.open_stream): _BeamStream, fed
+    emissions.  The transitions are the stream's: converted to a chunk's dtype on first use and kept."""
 
-    HEADER_BYTES = 256
+    _INPUT = "emissions"
+    _PREFILL = "all"                     # (an utterance that has been fed no frame is not touched by the call)
 
     def __init__(self, engine, transitions, batch_size, max_frames, device=None, timesteps=False):
-        if int(batch_size) < 1 or int(max_frames) < 1:
-            raise ValueError("batch_size and max_frames must be at least 1")
-        self.engine = engine
+        super().__init__(engine, batch_size, max_frames, device=device, timesteps=timesteps)
         self.transitions = None if transitions is None else transitions.detach()
-        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
-        self.timesteps = bool(timesteps)
-        self.device = None if device is None else torch.device(device)
-        self.state = None
-        self.row_bytes = 0
-        self._frames = [0] * self.batch_size
         self._A = {}                              # dtype -> the transitions on the stream's device
 
-    @property
-    def frames(self):
-        """Frames consumed so far, per utterance."""
-        return list(self._frames)
-
-    def check_chunk(self, shape):
-        """The chunk's shape (batch, frames, alphabet) against the stream: a ValueError before any device work."""
-        if len(shape) != 3:
-            raise ValueError("emissions must be (batch, time, alphabet)")
-        if shape[0] != self.batch_size:
-            raise ValueError("the chunk has %d utterances, the stream was opened for %d" % (shape[0], self.batch_size))
-        if not 1 <= shape[1] <= self.max_frames:
-            raise ValueError("a chunk of %d frames: the stream takes 1 .. max_frames = %d" % (shape[1], self.max_frames))
-
-    def reset(self, rows=None):
-        """Start the given utterances (all: None) anew: their headers are zeroed, nothing else is touched."""
-        idx = range(self.batch_size) if rows is None else [int(r) for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
-        for b in idx:
-            if not 0 <= b < self.batch_size:
-                raise ValueError("row %d outside the stream's %d utterances" % (b, self.batch_size))
-        if self.state is not None:
-            if rows is None:
-                self.state[:, : self.HEADER_BYTES].zero_()
-            else:
-                self.state[torch.as_tensor(list(idx), dtype=torch.long, device=self.state.device), : self.HEADER_BYTES] = 0
-        for b in idx:
-            self._frames[b] = 0
-
-    def _state_for(self, V, dev):
+    def _row_bytes(self, V):
         e = self.engine
-        if self.state is None:
-            self.row_bytes = _C.asg_beam_stream_row_bytes(self.max_frames, V, e.beam_width, e.lm is not None)
-            if not self.row_bytes:
-                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported" % (self.max_frames, e.beam_width))
-            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
-            self.state[:, : self.HEADER_BYTES].zero_()
-            self.device = dev
-        return self.state
+        return _C.asg_beam_stream_row_bytes(self.max_frames, V, e.beam_width, e.lm is not None)
 
     def _transitions_for(self, V, dev, dtype):
         if self.transitions is None:
@@ -608,76 +721,33 @@ class ASGBeamStream:
             A = self._A[dtype] = _asg_transitions(self.transitions, V, dev, dtype)
         return A
 
-    def feed_nbest(self, emissions, lengths=None, nbest=None):
-        """Feed a chunk of emissions (batch, frames, alphabet) -- lengths: the frames of this chunk per utterance, 0 allowed,
-        all of them by default -- and read the beams out: what decode_nbest returns for everything fed so far (timesteps if
-        the stream was opened with them).  nbest=0 feeds only and returns None."""
-        e = self.engine
-        N = e.beam_width if nbest is None else int(nbest)
-        if not 0 <= N <= e.beam_width:
-            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
-        self.check_chunk(tuple(emissions.shape))
-        B, Tc, V = emissions.shape
-        e._bind(V)
-        if lengths is None:
-            lengths = torch.full((B,), Tc, dtype=torch.long)
-        if self.device is not None and emissions.device != self.device:
-            emissions = emissions.to(self.device)
+    def _prepare(self, emissions, lengths):
+        self.engine._bind(emissions.shape[2])
         dev = R.compute_device(emissions)
         x = emissions.detach().to(dev)
         if x.dtype not in _F32_F64:
             x = x.to(torch.float32)
         xl = _as_long(lengths, dev)
-        if xl.numel() != B:
+        if xl.numel() != x.shape[0]:
             raise ValueError("lengths must have one entry per utterance")
-        state = self._state_for(V, dev)
-        if dev != state.device:
-            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
-        A = self._transitions_for(V, dev, x.dtype)
-        max_out = max(self._frames) + Tc
-        frames_done = torch.empty(B, dtype=torch.long, device=dev)
-        out = out_len = n_hyp = scores = counts = ts = None
-        if N:
-            # (an utterance that has been fed no frame is not touched by the call: its slots are the empty ones from here)
-            out = torch.zeros((B, N, max_out), dtype=torch.long, device=dev)
-            out_len = torch.zeros((B, N), dtype=torch.long, device=dev)
-            n_hyp = torch.zeros(B, dtype=torch.long, device=dev)
-            scores = torch.full((B, N, 3), float("-inf"), dtype=torch.float64, device=dev)
-            scores[:, :, 2] = 0.0
-            counts = torch.zeros((B, N, 2), dtype=torch.int32, device=dev)
-            ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if self.timesteps else None
-        stream = R.stream_handle(dev)
-        with _on_device(dev):
-            lm = e.lm.on(dev).handle if e.lm is not None else 0
-            ws = R.workspace(dev, _C.asg_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None), stream)
-            sB, sT, sV = x.stride()
-            _C.asg_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
-                               xl.data_ptr(), B, Tc, V, e.num_replabels, e.beam_width, e.space_id, lm,
-                               e.lmwt, e.wip, e.oov_penalty, state.data_ptr(), self.row_bytes, self.max_frames, N,
-                               out.data_ptr() if N else 0, max_out, out_len.data_ptr() if N else 0,
-                               n_hyp.data_ptr() if N else 0, scores.data_ptr() if N else 0, counts.data_ptr() if N else 0,
-                               frames_done.data_ptr(), ws.data_ptr(), ws.numel(), stream,
-                               e.restricted, ts.data_ptr() if ts is not None else 0)
-        done = frames_done.tolist()
-        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
-        bad = None
-        for b, f in enumerate(done):
-            if f >= 0:
-                self._frames[b] = f
-            elif bad is None:
-                bad = (b, f)
-        if bad is not None:
-            why = {-2: "would pass max_frames=%d with this chunk" % self.max_frames,
-                   -3: "has a state row that was written under another configuration"}
-            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
-        if not N:
-            return None
-        return e._nbest_result(out, out_len, n_hyp, scores, counts, ts)
+        return x, xl, dev
 
-    def feed(self, emissions, lengths=None):
-        """Feed a chunk and return what decode returns for everything fed so far: (ids, lengths, sentences)."""
-        r = self.feed_nbest(emissions, lengths, nbest=1)
-        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+    def _max_out(self, frames):
+        return frames
+
+    def _launch(self, x, xl, state, N, max_out, bufs, frames_done, stream):
+        e, dev = self.engine, x.device
+        B, Tc, V = x.shape
+        out, out_len, n_hyp, scores, counts, ts = bufs
+        A = self._transitions_for(V, dev, x.dtype)
+        lm = e.lm.on(dev).handle if e.lm is not None else 0
+        ws = R.workspace(dev, _C.asg_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None), stream)
+        sB, sT, sV = x.stride()
+        _C.asg_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
+                           xl.data_ptr(), B, Tc, V, e.num_replabels, e.beam_width, e.space_id, lm,
+                           e.lmwt, e.wip, e.oov_penalty, state.data_ptr(), self.row_bytes, self.max_frames, N,
+                           out, max_out, out_len, n_hyp, scores, counts, frames_done, ws.data_ptr(), ws.numel(), stream,
+                           e.restricted, ts)
 
 
 GRAM_MAX_ORDER = 8
@@ -861,16 +931,7 @@ class GramCTCDecoderEngine:
         if lexicon is None and self.lm is None:
             raise ValueError("restrict needs a vocabulary: configure(lm_path=...) or lexicon")
         if lexicon is not None:
-            if isinstance(lexicon, (str, bytes, os.PathLike)):
-                path = os.fsdecode(lexicon)
-                if not os.path.isfile(path):
-                    raise ValueError("Can't find a lexicon: {}".format(path))
-                with open(path, encoding="utf-8") as f:
-                    words = f.read().split()
-            else:
-                words = [str(w) for w in lexicon]
-            if not words:
-                raise ValueError("the lexicon is empty")
+            words = _lexicon_words(lexicon)
             R.require_gpu()
             self.lm = LanguageModel(None, self.labels, self.case_sensitive, words=words, lexicon=True)
             self.lmwt = 0.0
@@ -953,10 +1014,7 @@ class GramCTCDecoderEngine:
             return self._decode_nbest_lm(x, xl, dev, N, bool(timesteps))
         B, T, V = x.shape
         max_out = max(T * self.max_order, 1)
-        out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
-        out_len = torch.empty((B, N), dtype=torch.long, device=dev)
-        n_hyp = torch.empty(B, dtype=torch.long, device=dev)
-        scores = torch.empty((B, N), dtype=torch.float64, device=dev)
+        bufs = out, out_len, n_hyp, scores, _, _ = _nbest_buffers(B, N, max_out, dev, scored=False)
         if B:
             with torch.cuda.device(dev):
                 ids, lens = self._table(dev)
@@ -969,30 +1027,20 @@ class GramCTCDecoderEngine:
                                        ids.data_ptr(), lens.data_ptr(), self.max_order, self.beam_width, N,
                                        out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
                                        ws.data_ptr(), ws.numel(), R.stream_handle(dev))
-        ids_out, sentences = self._pack(out, out_len, n_hyp)
-        r = self._result
-        return (ids_out, r(out_len), sentences, r(scores), r(n_hyp))
+        return _nbest_result(self, *bufs)
 
-    def _pack(self, out, out_len, n_hyp):
-        """The ids packed to the longest hypothesis and the sentences; an utterance whose search ran out of entries raises."""
-        nh = n_hyp.tolist()
+    def _check_nbest(self, nh, lens, max_out):
+        """An utterance whose search ran out of entries raises (the status rides on num_hypotheses)."""
         for b, n in enumerate(nh):
             if n < 0:
                 raise R.E2EError("Gram-CTC beam search: utterance %d ran out of candidate entries" % b)
-        ids_out, sentences, _ = _pack_nbest(out, out_len.tolist(), nh, self._strings, self.keep_on_device)
-        return ids_out, sentences
 
     def _decode_nbest_lm(self, x, xl, dev, N, timesteps=False):
         """decode_nbest after configure(): the search on the totals (e2e_gram_ctc_beam_nbest_lm; restricted or with timesteps:
         e2e_gram_ctc_beam_nbest_opt)."""
         B, T, V = x.shape
         max_out = max(T * self.max_order, 1)
-        out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
-        out_len = torch.empty((B, N), dtype=torch.long, device=dev)
-        n_hyp = torch.empty(B, dtype=torch.long, device=dev)
-        scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-        counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
-        ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if timesteps else None
+        bufs = out, out_len, n_hyp, scores, counts, ts = _nbest_buffers(B, N, max_out, dev, timesteps=timesteps, prefill="ts")
         if B:
             stream = R.stream_handle(dev)
             with torch.cuda.device(dev):
@@ -1012,22 +1060,11 @@ class GramCTCDecoderEngine:
                     _C.gram_ctc_beam_nbest_opt(*args, (self.restricted, ts.data_ptr() if ts is not None else 0))
                 else:
                     _C.gram_ctc_beam_nbest_lm(*args)
-        return self._nbest_result_lm(out, out_len, n_hyp, scores, counts, ts)
-
-    def _nbest_result_lm(self, out, out_len, n_hyp, scores, counts, ts):
-        """What the configured decode_nbest returns, from the buffers the read-out has filled (ts: None without timesteps)."""
-        ids_out, sentences = self._pack(out, out_len, n_hyp)
-        r = self._result
-        if ts is not None:
-            ts = r(ts[:, :, :ids_out.shape[2]].contiguous())
-        return (ids_out, r(out_len), sentences, r(scores[:, :, 0].contiguous()), r(scores[:, :, 1].contiguous()),
-                r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()), r(counts[:, :, 1].contiguous()),
-                r(n_hyp), ts)
+        return _nbest_result(self, *bufs)
 
     def decode(self, logits_, logits_lengths_):
         """Hypothesis 0 of decode_nbest -> (base ids (B,maxlen) int64, lengths (B), sentences)."""
-        r = self.decode_nbest(logits_, logits_lengths_, nbest=1)
-        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+        return _first_hypothesis(self.decode_nbest(logits_, logits_lengths_, nbest=1))
 
     def open_stream(self, batch_size, max_frames, device=None, timesteps=False):
         """Streaming beam search (e2e_gram_ctc_beam_stream, include/e2e_ctc.h): a GramBeamStream that is fed log-probabilities
@@ -1239,7 +1276,7 @@ class CTCDecoderEngine:
         elif lexicon is not None:
             self._check_width(True)
             R.require_gpu()
-            self.lm = LanguageModel(None, self.labels, self.case_sensitive, words=list(lexicon), lexicon=True)
+            self.lm = LanguageModel(None, self.labels, self.case_sensitive, words=_lexicon_words(lexicon), lexicon=True)
             self.lmwt = 0.0
             self.oov_penalty = 0.0
         if restrict and not self.lm.has_lexicon():
@@ -1313,8 +1350,7 @@ class CTCDecoderEngine:
         """Prefix beam search on LOG-PROBABILITIES -> (indices (B,maxlen) int64, lengths (B), sentences)."""
         if self.restrict:
             # hypothesis 0 of the restricted n-best list (the restriction is an option of that call: e2e_ctc_beam_nbest_opt)
-            r = self.decode_nbest(logits_, logits_lengths_, nbest=1)
-            return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] for s in r[2]]
+            return _first_hypothesis(self.decode_nbest(logits_, logits_lengths_, nbest=1))
         x, xl, dev = self._prep(logits_, logits_lengths_)
         B, T, V = x.shape
         max_out = T + 1
@@ -1353,12 +1389,7 @@ class CTCDecoderEngine:
         x, xl, dev = self._prep(logits_, logits_lengths_)
         B, T, V = x.shape
         max_out = T + 1
-        out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
-        out_len = torch.empty((B, N), dtype=torch.long, device=dev)
-        n_hyp = torch.empty(B, dtype=torch.long, device=dev)
-        scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-        counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
-        ts = torch.empty((B, N, max_out), dtype=torch.long, device=dev) if timesteps else None
+        bufs = out, out_len, n_hyp, scores, counts, ts = _nbest_buffers(B, N, max_out, dev, timesteps=timesteps)
         if B:
             with torch.cuda.device(dev):
                 lm = self.lm.on(dev).handle if self.lm is not None else 0
@@ -1371,25 +1402,15 @@ class CTCDecoderEngine:
                                   out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
                                   counts.data_ptr(), ts.data_ptr() if timesteps else 0,
                                   ws.data_ptr(), ws.numel(), R.stream_handle(dev), restrict_to_lexicon=self.restrict)
-        return self._nbest_result(out, out_len, n_hyp, scores, counts, ts, max_out)
+        return _nbest_result(self, *bufs)
 
-    def _nbest_result(self, out, out_len, n_hyp, scores, counts, ts, max_out):
-        """What decode_nbest returns, from the buffers the n-best read-out has filled (ts: None without timestamps)."""
-        B, N = out_len.shape
-        timesteps = ts is not None
-        nh = n_hyp.tolist()
-        lens = out_len.tolist()
-        # per-utterance and per-hypothesis status ride on the counts and lengths, as in decode()
-        for b in range(B):
-            if nh[b] < 0:
+    def _check_nbest(self, nh, lens, max_out):
+        """Per-utterance and per-hypothesis status ride on the counts and lengths, as in decode()."""
+        for b, n in enumerate(nh):
+            if n < 0:
                 raise R.E2EError("beam search: utterance %d ran out of prefix-tree nodes" % b)
             if max(lens[b]) > max_out:
                 raise R.E2EError("beam search: utterance %d needs %d output ids, %d provided" % (b, max(lens[b]), max_out))
-        ids, sentences, width = _pack_nbest(out, lens, nh, self._strings, self.keep_on_device)
-        r = self._result
-        return (ids, r(out_len), sentences, r(scores[:, :, 0].contiguous()),
-                r(scores[:, :, 1].contiguous()), r(scores[:, :, 2].contiguous()), r(counts[:, :, 0].contiguous()),
-                r(counts[:, :, 1].contiguous()), r(n_hyp), r(ts[:, :, :width].contiguous()) if timesteps else None)
 
     def open_stream(self, batch_size, max_frames, device=None, timesteps=False):
         """Streaming beam search (e2e_ctc_beam_stream, include/e2e_ctc.h): a CTCBeamStream that is fed log-probabilities in
@@ -1410,231 +1431,96 @@ class CTCDecoderEngine:
             ctx = ([idx] + ctx)[: max(order - 1, 0)]
 
 
-class CTCBeamStream:
-    """The beams of `batch_size` utterances, kept on the GPU between chunks (CTCDecoderEngine.open_stream).  Owns the
-    (batch_size, row_bytes) uint8 state tensor `state`: one self-contained row per utterance, allocated at the first chunk
-    (on `device`, else on the chunk's GPU, else on the current one).  Rows may be reordered or copied by the caller; a row
-    whose first 256 bytes are zero starts a new utterance."""
+class CTCBeamStream(_BeamStream):
+    """The CTC beams of `batch_size` utterances, kept on the GPU between chunks (CTCDecoderEngine.open_stream): _BeamStream,
+    fed log-probabilities."""
 
-    HEADER_BYTES = 256
+    _STATUS = {-1: "ran out of prefix-tree nodes"}
 
     def __init__(self, engine, batch_size, max_frames, device=None, timesteps=False):
         if engine.beam_width < 2:
             raise ValueError("a stream needs beam_width > 1: greedy decoding has no beam to keep")
-        if int(batch_size) < 1 or int(max_frames) < 1:
-            raise ValueError("batch_size and max_frames must be at least 1")
-        self.engine = engine
-        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
-        self.timesteps = bool(timesteps)
-        self.device = None if device is None else torch.device(device)
-        self.state = None
-        self.row_bytes = 0
-        self._frames = [0] * self.batch_size
+        super().__init__(engine, batch_size, max_frames, device=device, timesteps=timesteps)
 
-    @property
-    def frames(self):
-        """Frames consumed so far, per utterance."""
-        return list(self._frames)
-
-    def check_chunk(self, shape):
-        """The chunk's shape (batch, frames, alphabet) against the stream: a ValueError before any device work."""
-        if len(shape) != 3:
-            raise ValueError("logits must be (batch, time, alphabet)")
-        if shape[0] != self.batch_size:
-            raise ValueError("the chunk has %d utterances, the stream was opened for %d" % (shape[0], self.batch_size))
-        if not 1 <= shape[1] <= self.max_frames:
-            raise ValueError("a chunk of %d frames: the stream takes 1 .. max_frames = %d" % (shape[1], self.max_frames))
-
-    def reset(self, rows=None):
-        """Start the given utterances (all: None) anew: their headers are zeroed, nothing else is touched."""
-        idx = range(self.batch_size) if rows is None else [int(r) for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
-        for b in idx:
-            if not 0 <= b < self.batch_size:
-                raise ValueError("row %d outside the stream's %d utterances" % (b, self.batch_size))
-        if self.state is not None:
-            if rows is None:
-                self.state[:, : self.HEADER_BYTES].zero_()
-            else:
-                self.state[torch.as_tensor(list(idx), dtype=torch.long, device=self.state.device), : self.HEADER_BYTES] = 0
-        for b in idx:
-            self._frames[b] = 0
-
-    def _state_for(self, V, dev):
+    def _row_bytes(self, V):
         e = self.engine
-        if self.state is None:
-            self.row_bytes = _C.ctc_beam_stream_row_bytes(self.max_frames, V, e.beam_width, e.lm is not None, self.timesteps)
-            if not self.row_bytes:
-                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported" % (self.max_frames, e.beam_width))
-            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
-            self.state[:, : self.HEADER_BYTES].zero_()
-            self.device = dev
-        return self.state
+        return _C.ctc_beam_stream_row_bytes(self.max_frames, V, e.beam_width, e.lm is not None, self.timesteps)
 
-    def feed_nbest(self, logits_, logits_lengths_=None, nbest=None):
-        """Feed a chunk of LOG-PROBABILITIES (batch, frames, alphabet) -- logits_lengths_: the frames of this chunk per
-        utterance, 0 allowed, all of them by default -- and read the beams out: what decode_nbest returns for everything
-        fed so far (timestamps if the stream was opened with them).  nbest=0 feeds only and returns None."""
-        e = self.engine
-        N = e.beam_width if nbest is None else int(nbest)
-        if not 0 <= N <= e.beam_width:
-            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
-        self.check_chunk(tuple(logits_.shape))
-        B, Tc = logits_.shape[0], logits_.shape[1]
-        if logits_lengths_ is None:
-            logits_lengths_ = torch.full((B,), Tc, dtype=torch.long)
-        if self.device is not None and logits_.device != self.device:
-            logits_ = logits_.to(self.device)
-        x, xl, dev = e._prep(logits_, logits_lengths_)
-        V = x.shape[2]
-        state = self._state_for(V, dev)
-        if dev != state.device:
-            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
-        max_out = max(self._frames) + Tc + 1
-        frames_done = torch.empty(B, dtype=torch.long, device=dev)
-        out = out_len = n_hyp = scores = counts = ts = None
-        if N:
-            out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
-            out_len = torch.empty((B, N), dtype=torch.long, device=dev)
-            n_hyp = torch.empty(B, dtype=torch.long, device=dev)
-            scores = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-            counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
-            ts = torch.empty((B, N, max_out), dtype=torch.long, device=dev) if self.timesteps else None
-        with torch.cuda.device(dev):
-            lm = e.lm.on(dev).handle if e.lm is not None else 0
-            nbytes = _C.ctc_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
-            ws = R.workspace(dev, nbytes) if nbytes else None
-            sB, sT, sV = x.stride()
-            _C.ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V, e.blank_idx,
-                               e.beam_width, e.space_id, lm, e.lmwt, e.wip, e.oov_penalty,
-                               state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
-                               out.data_ptr() if N else 0, max_out, out_len.data_ptr() if N else 0,
-                               n_hyp.data_ptr() if N else 0, scores.data_ptr() if N else 0, counts.data_ptr() if N else 0,
-                               ts.data_ptr() if ts is not None else 0, frames_done.data_ptr(),
-                               ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, R.stream_handle(dev),
-                               restrict_to_lexicon=e.restrict)
-        done = frames_done.tolist()
-        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
-        bad = None
-        for b, f in enumerate(done):
-            if f >= 0:
-                self._frames[b] = f
-            elif bad is None:
-                bad = (b, f)
-        if bad is not None:
-            why = {-1: "ran out of prefix-tree nodes", -2: "would pass max_frames=%d with this chunk" % self.max_frames,
-                   -3: "has a state row that was written under another configuration"}
-            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
-        if not N:
-            return None
-        return e._nbest_result(out, out_len, n_hyp, scores, counts, ts, max_out)
+    def _prepare(self, logits_, logits_lengths_):
+        return self.engine._prep(logits_, logits_lengths_)
 
-    def feed(self, logits_, logits_lengths_=None):
-        """Feed a chunk and return what decode returns for everything fed so far: (indices, lengths, sentences)."""
-        r = self.feed_nbest(logits_, logits_lengths_, nbest=1)
-        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] for s in r[2]]
+    def _max_out(self, frames):
+        return frames + 1
+
+    def _launch(self, x, xl, state, N, max_out, bufs, frames_done, stream):
+        e, dev = self.engine, x.device
+        B, Tc, V = x.shape
+        out, out_len, n_hyp, scores, counts, ts = bufs
+        lm = e.lm.on(dev).handle if e.lm is not None else 0
+        nbytes = _C.ctc_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
+        ws = R.workspace(dev, nbytes, stream) if nbytes else None     # (the one-workgroup kernel needs none: a null pointer)
+        sB, sT, sV = x.stride()
+        _C.ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V, e.blank_idx,
+                           e.beam_width, e.space_id, lm, e.lmwt, e.wip, e.oov_penalty,
+                           state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
+                           out, max_out, out_len, n_hyp, scores, counts, ts, frames_done,
+                           ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, stream,
+                           restrict_to_lexicon=e.restrict)
 
 
-class GramBeamStream(CTCBeamStream):
+class GramBeamStream(_BeamStream):
     """The Gram-CTC beams of `batch_size` utterances, kept on the GPU between chunks (GramCTCDecoderEngine.open_stream):
-    CTCBeamStream's surface -- `frames`, `state`, `check_chunk`, `reset(rows)` are its own.  The engine's configuration
-    (configure(), restrict()) at the time the stream was opened is the stream's: an engine that was never configured streams
-    the search on the masses (e2e_gram_ctc_beam_stream with scored = 0), a configured one the search on the totals."""
+    _BeamStream, fed log-probabilities.  The engine's configuration (configure(), restrict()) at the time the stream was
+    opened is the stream's: an engine that was never configured streams the search on the masses (e2e_gram_ctc_beam_stream with
+    scored = 0), a configured one the search on the totals."""
+
+    _PREFILL = "ts"
+    _NEEDS_CONFIGURE = ("timesteps are part of the configured search's results: call configure() first "
+                        "(configure(wip=0) is the search without a model and without penalties)")
 
     def __init__(self, engine, batch_size, max_frames, device=None, timesteps=False):
+        if engine.beam_width < 2:
+            raise ValueError("a stream needs beam_width > 1: greedy decoding has no beam to keep")
         super().__init__(engine, batch_size, max_frames, device=device, timesteps=timesteps)
         e = engine
         if self.timesteps and not e.configured:
-            raise ValueError("timesteps are part of the configured search's results: call configure() first "
-                             "(configure(wip=0) is the search without a model and without penalties)")
-        self.scored = bool(e.configured)
+            raise ValueError(self._NEEDS_CONFIGURE)
+        self.scored = self._scored = bool(e.configured)
         self.lm = e.lm if self.scored else None
         self.restricted = bool(e.restricted) if self.scored else False
         self._knobs = (e.space_id, e.lmwt, e.wip, e.oov_penalty) if self.scored else (-1, 0.0, 0.0, 0.0)
 
-    def _state_for(self, V, dev):
-        e = self.engine
-        if self.state is None:
-            self.row_bytes = _C.gram_beam_stream_row_bytes(self.max_frames, V, e.max_order, e.beam_width, self.scored,
-                                                           self.lm is not None)
-            if not self.row_bytes:
-                raise ValueError("a stream of max_frames=%d at beam_width=%d is not supported" % (self.max_frames, e.beam_width))
-            self.state = torch.empty((self.batch_size, self.row_bytes), dtype=torch.uint8, device=dev)
-            self.state[:, : self.HEADER_BYTES].zero_()
-            self.device = dev
-        return self.state
-
     def feed_nbest(self, logits_, logits_lengths_=None, nbest=None, timesteps=None):
-        """Feed a chunk of LOG-PROBABILITIES (batch, frames, alphabet) -- logits_lengths_: the frames of this chunk per
-        utterance, 0 allowed, all of them by default -- and read the beams out: what decode_nbest returns for everything
-        fed so far.  timesteps: None -- as the stream was opened -- or whether this read-out returns them (a configured search
-        only; they cost the stream nothing: the nodes' numbers carry them).  nbest=0 feeds only and returns None."""
-        e = self.engine
+        """_BeamStream.feed_nbest; timesteps: None -- as the stream was opened -- or whether this read-out returns them (a
+        configured search only; they cost the stream nothing: the nodes' numbers carry them)."""
         want_ts = self.timesteps if timesteps is None else bool(timesteps)
         if want_ts and not self.scored:
-            raise ValueError("timesteps are part of the configured search's results: call configure() first "
-                             "(configure(wip=0) is the search without a model and without penalties)")
-        N = e.beam_width if nbest is None else int(nbest)
-        if not 0 <= N <= e.beam_width:
-            raise ValueError("nbest=%d outside [0, beam_width=%d]" % (N, e.beam_width))
-        self.check_chunk(tuple(logits_.shape))
-        B, Tc = logits_.shape[0], logits_.shape[1]
-        if logits_lengths_ is None:
-            logits_lengths_ = torch.full((B,), Tc, dtype=torch.long)
-        if self.device is not None and logits_.device != self.device:
-            logits_ = logits_.to(self.device)
-        x, xl, dev = e._prep(logits_, logits_lengths_, _F32_F64)
-        V = x.shape[2]
-        state = self._state_for(V, dev)
-        if dev != state.device:
-            raise ValueError("the chunk is on %s, the stream's state on %s" % (dev, state.device))
-        max_out = max((max(self._frames) + Tc) * e.max_order, 1)
-        frames_done = torch.empty(B, dtype=torch.long, device=dev)
-        out = out_len = n_hyp = scores = counts = ts = None
-        if N:
-            out = torch.empty((B, N, max_out), dtype=torch.long, device=dev)
-            out_len = torch.empty((B, N), dtype=torch.long, device=dev)
-            n_hyp = torch.empty(B, dtype=torch.long, device=dev)
-            scores = torch.empty((B, N, 3) if self.scored else (B, N), dtype=torch.float64, device=dev)
-            counts = torch.empty((B, N, 2), dtype=torch.int32, device=dev) if self.scored else None
-            ts = torch.full((B, N, max_out), -1, dtype=torch.long, device=dev) if want_ts else None
-        space_id, lmwt, wip, oov_penalty = self._knobs
-        stream = R.stream_handle(dev)
-        with torch.cuda.device(dev):
-            ids, lens = e._table(dev)
-            lm = self.lm.on(dev).handle if self.lm is not None else 0
-            ws = R.workspace(dev, _C.gram_beam_stream_workspace_bytes(B, V, e.max_order, e.beam_width, self.scored,
-                                                                      self.lm is not None), stream)
-            sB, sT, sV = x.stride()
-            opts = (self.restricted, ts.data_ptr() if ts is not None else 0) if self.scored else None
-            _C.gram_ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V,
-                                    ids.data_ptr(), lens.data_ptr(), e.max_order, e.num_base_labels, e.beam_width,
-                                    self.scored, space_id, lm, lmwt, wip, oov_penalty,
-                                    state.data_ptr(), self.row_bytes, self.max_frames, N,
-                                    out.data_ptr() if N else 0, max_out, out_len.data_ptr() if N else 0,
-                                    n_hyp.data_ptr() if N else 0, scores.data_ptr() if N else 0,
-                                    counts.data_ptr() if counts is not None else 0, frames_done.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), stream, opts)
-        done = frames_done.tolist()
-        # what only the device knows rides on frames_done (include/e2e_ctc.h); the other utterances have advanced
-        bad = None
-        for b, f in enumerate(done):
-            if f >= 0:
-                self._frames[b] = f
-            elif bad is None:
-                bad = (b, f)
-        if bad is not None:
-            why = {-2: "would pass max_frames=%d with this chunk" % self.max_frames,
-                   -3: "has a state row that was written under another configuration"}
-            raise R.E2EError("beam search stream: utterance %d %s" % (bad[0], why.get(bad[1], "status %d" % bad[1])))
-        if not N:
-            return None
-        if self.scored:
-            return e._nbest_result_lm(out, out_len, n_hyp, scores, counts, ts)
-        ids_out, sentences = e._pack(out, out_len, n_hyp)
-        r = e._result
-        return (ids_out, r(out_len), sentences, r(scores), r(n_hyp))
+            raise ValueError(self._NEEDS_CONFIGURE)
+        return self._feed_nbest(logits_, logits_lengths_, nbest, want_ts)
 
-    def feed(self, logits_, logits_lengths_=None):
-        """Feed a chunk and return what decode returns for everything fed so far: (base ids, lengths, sentences)."""
-        r = self.feed_nbest(logits_, logits_lengths_, nbest=1)
-        return r[0][:, 0, :].contiguous(), r[1][:, 0].contiguous(), [s[0] if s else "" for s in r[2]]
+    def _row_bytes(self, V):
+        e = self.engine
+        return _C.gram_beam_stream_row_bytes(self.max_frames, V, e.max_order, e.beam_width, self.scored, self.lm is not None)
+
+    def _prepare(self, logits_, logits_lengths_):
+        return self.engine._prep(logits_, logits_lengths_, _F32_F64)
+
+    def _max_out(self, frames):
+        return max(frames * self.engine.max_order, 1)
+
+    def _launch(self, x, xl, state, N, max_out, bufs, frames_done, stream):
+        e, dev = self.engine, x.device
+        B, Tc, V = x.shape
+        out, out_len, n_hyp, scores, counts, ts = bufs
+        space_id, lmwt, wip, oov_penalty = self._knobs
+        ids, lens = e._table(dev)
+        lm = self.lm.on(dev).handle if self.lm is not None else 0
+        ws = R.workspace(dev, _C.gram_beam_stream_workspace_bytes(B, V, e.max_order, e.beam_width, self.scored,
+                                                                  self.lm is not None), stream)
+        sB, sT, sV = x.stride()
+        _C.gram_ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V,
+                                ids.data_ptr(), lens.data_ptr(), e.max_order, e.num_base_labels, e.beam_width,
+                                self.scored, space_id, lm, lmwt, wip, oov_penalty,
+                                state.data_ptr(), self.row_bytes, self.max_frames, N,
+                                out, max_out, out_len, n_hyp, scores, counts, frames_done,
+                                ws.data_ptr(), ws.numel(), stream, (self.restricted, ts) if self.scored else None)

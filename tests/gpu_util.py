@@ -153,3 +153,20 @@ def c_abi_beam(lp, x_len=None, blank=0, beam_width=100, labels=None, lm=None, lm
     assert ((lens >= 0) & (lens <= max_out)).all(), lens
     width = int(lens.max()) if B else 0
     return out[:, :width].cpu().numpy(), lens
+
+
+class DeviceWords:
+    """`count` int64 words of device memory at a raw address, for torch.as_tensor(..., device="cuda"): a test that stands in
+    for a C call writes the status the kernel would have written."""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = {"shape": (count,), "typestr": "<i8", "data": (ptr, False), "version": 2}
+
+
+def poison_allocator(device, sizes=(1 << 8, 1 << 10, 1 << 12, 1 << 14), copies=8):
+    """Leave freed blocks full of 0x5a bytes in torch's caching allocator, so that a buffer that should have been prefilled
+    and was only allocated shows."""
+    import torch
+    blocks = [torch.full((n,), 0x5a, dtype=torch.uint8, device=device) for n in sizes for _ in range(copies)]
+    torch.cuda.synchronize(device)
+    del blocks

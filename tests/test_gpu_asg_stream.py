@@ -300,3 +300,58 @@ def test_module_zero_transitions_and_half():
     for f in FIELDS[:-1]:
         assert torch.equal(getattr(got, f), getattr(want, f)), f
     assert got.decoded_sentences == want.decoded_sentences
+
+
+# ---- 5. what the engine's host layer adds to the calls -----------------------------------------------------------------------
+def _empty_slot(r, b, N):
+    """Utterance b of an n-best tuple is the empty result: no hypothesis, length 0, -inf, an LM score of 0, timesteps -1."""
+    assert int(r[8][b]) == 0 and r[2][b] == [] and r[1][b].tolist() == [0] * N and r[0][b].tolist() == [[0] * r[0].shape[2]] * N
+    assert r[3][b].tolist() == [-math.inf] * N and r[4][b].tolist() == [-math.inf] * N and r[5][b].tolist() == [0.0] * N
+    assert r[6][b].tolist() == [0] * N and r[7][b].tolist() == [0] * N
+    assert r[9][b].tolist() == [[-1] * r[9].shape[2]] * N
+
+
+def test_engine_leaves_an_utterance_without_frames_empty():
+    """The call does not touch an utterance of length 0, nor a stream's utterance that has been fed no frame: the engine's
+    buffers are the empty result beforehand.  No frames at all: no launch, the same empty result."""
+    from end2end_amd.engines import ASGBeamEngine
+    from gpu_util import poison_allocator
+    e = ASGBeamEngine(["a", "b", " ", "c", "d"], 0, 4)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(3, 6, 5, generator=g).to(DEV)
+    poison_allocator(DEV)
+    r = e.decode_nbest(x, None, torch.tensor([6, 0, 3]), timesteps=True)
+    _empty_slot(r, 1, 4)
+    assert r[8].tolist() == [4, 0, 4]
+    st = e.open_stream(None, 3, 12, timesteps=True)
+    poison_allocator(DEV)
+    s = st.feed_nbest(x[:, :5], torch.tensor([5, 0, 2]))
+    _empty_slot(s, 1, 4)
+    assert st.frames == [5, 0, 2] and s[8].tolist() == [4, 0, 4]
+    want = e.decode_nbest(x[:, :5], None, torch.tensor([5, 0, 2]), timesteps=True)
+    for i in (0, 1, 3, 4, 5, 6, 7, 8, 9):
+        assert torch.equal(s[i], want[i]), i
+    assert s[2] == want[2]
+    z = e.decode_nbest(torch.zeros(2, 0, 5, device=DEV), None, torch.tensor([0, 0]), timesteps=True)
+    assert z[0].shape == (2, 4, 0) and z[9].shape == (2, 4, 0)
+    for b in range(2):
+        _empty_slot(z, b, 4)
+
+
+def test_engine_stream_keeps_its_transitions_per_dtype():
+    """Chunks of either dtype in one stream: each reads the transitions in its own dtype (f32 values are exact in f64, so the
+    result is the whole f32 call's)."""
+    from end2end_amd.engines import ASGBeamEngine
+    e = ASGBeamEngine(["a", "b", " ", "c", "d"], 0, 4)
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(2, 10, 5, generator=g).to(DEV)
+    A = torch.randn(5, 5, generator=g)
+    want = e.decode_nbest(x, A, torch.tensor([10, 10]))
+    st = e.open_stream(A, 2, 10)
+    st.feed_nbest(x[:, :3].double(), nbest=0)
+    st.feed_nbest(x[:, 3:6], nbest=0)
+    st.feed_nbest(x[:, 6:8].double(), nbest=0)
+    got = st.feed_nbest(x[:, 8:])
+    for i in (0, 1, 3, 4, 5, 6, 7, 8):
+        assert torch.equal(got[i], want[i]), i
+    assert got[2] == want[2] and got[9] is None and st.frames == [10, 10]

@@ -453,3 +453,52 @@ def test_module_unconfigured():
     assert torch.equal(one.decoded_targets, want.decoded_targets) and one.decoded_sentences == want.decoded_sentences
     with pytest.raises(ValueError, match="configure"):
         st.feed_nbest(lp[:, :1], torch.tensor([0, 0, 0]), timesteps=True)
+
+
+@pytest.mark.parametrize("scored", [False, True])
+def test_engine_raises_the_status_that_rides_on_num_hypotheses(monkeypatch, scored):
+    """n_hyp < 0 is an error that names the utterance, in decode_nbest and in a stream's read-out."""
+    from end2end_amd.engines import GramCTCDecoderEngine
+    from end2end_amd._runtime import E2EError
+    from test_gpu_nbest import _status_after
+    B, T, V, W = 2, 6, 4, 4
+    g = torch.Generator().manual_seed(4)
+    x = torch.log_softmax(torch.randn(B, T, V, generator=g, dtype=torch.float64), -1).to(DEV)
+    e = GramCTCDecoderEngine(0, 3, V, {3: [1, 2]}, W, ["_", "a", "b"])
+    if scored:
+        e.configure(wip_=0.0)
+    text = "Gram-CTC beam search: utterance 0 ran out of candidate entries"
+    # n_hyp among the arguments: (x, dtype, sB, sT, sV, x_len, B, T, V, ids, lens, max_order, ...
+    #   e2e_gram_ctc_beam_nbest:     W, N, out, max_out, out_len, n_hyp
+    #   e2e_gram_ctc_beam_nbest_lm:  R, W, space, lm, lmwt, wip, oov, N, out, max_out, out_len, n_hyp
+    #   e2e_gram_ctc_beam_stream:    R, W, scored, space, lm, lmwt, wip, oov, state, row_bytes, max_frames, N, out, max_out, out_len, n_hyp
+    _status_after(monkeypatch, "gram_ctc_beam_nbest_lm" if scored else "gram_ctc_beam_nbest", 23 if scored else 17, B, -1)
+    with pytest.raises(E2EError, match=text):
+        e.decode_nbest(x, torch.tensor([T, T]))
+    _status_after(monkeypatch, "gram_ctc_beam_stream", 27, B, -1)
+    with pytest.raises(E2EError, match=text):
+        e.open_stream(B, T).feed_nbest(x)
+
+
+def test_engine_pads_the_timesteps_behind_every_hypothesis():
+    """Behind every hypothesis the timesteps are -1, whatever the buffers held before, in decode_nbest and in a stream's
+    read-out asked for per call."""
+    from end2end_amd.engines import GramCTCDecoderEngine
+    from gpu_util import poison_allocator
+    B, T, V, W = 2, 6, 4, 4
+    g = torch.Generator().manual_seed(4)
+    x = torch.log_softmax(torch.randn(B, T, V, generator=g, dtype=torch.float64), -1).to(DEV)
+    e = GramCTCDecoderEngine(0, 3, V, {3: [1, 2]}, W, ["_", "a", "b"]).configure(wip_=0.0)
+    poison_allocator(DEV)
+    whole = e.decode_nbest(x, torch.tensor([T, 2]), timesteps=True)
+    st = e.open_stream(B, T)
+    poison_allocator(DEV)
+    fed = st.feed_nbest(x, torch.tensor([T, 2]), timesteps=True)
+    for r in (whole, fed):
+        lens, ts = r[1].tolist(), r[9]
+        assert ts.shape == r[0].shape and max(max(row) for row in lens) == ts.shape[2] > min(min(row) for row in lens)
+        for b in range(B):
+            for k in range(W):
+                assert ts[b, k, lens[b][k]:].tolist() == [-1] * (ts.shape[2] - lens[b][k]), (b, k)
+                assert min(ts[b, k, :lens[b][k]].tolist(), default=0) >= 0
+    assert torch.equal(whole[9], fed[9])

@@ -311,3 +311,50 @@ def test_module_decode_nbest(keep):
     eng = cpp_ctc_decoder.CTCDecoder(0, 8, LABELS7, wip_=1.0)
     out = eng.decode_nbest(torch.log_softmax(logits.transpose(0, 1), -1), xl)
     assert out[0].shape[:2] == (4, 8) and out[9] is None and torch.equal(out[0][:, :5, : ids.shape[2]], ids)
+
+
+def _status_after(monkeypatch, name, at, count, value):
+    """Let the C call `name` run, then write `value` over the first int64 word of its argument `at` (a buffer of `count`
+    words): the status a search that ran out of room reports there."""
+    from end2end_amd import engines
+    real = getattr(engines._C, name)
+
+    def call(*args, **kw):
+        real(*args, **kw)
+        torch.cuda.synchronize()
+        torch.as_tensor(U.DeviceWords(args[at], count), device="cuda")[0] = value
+    monkeypatch.setattr(engines._C, name, call)
+
+
+@pytest.mark.parametrize("what", ["nodes", "max_out"])
+def test_engine_raises_the_status_that_rides_on_the_results(monkeypatch, what):
+    """n_hyp < 0 and a length beyond max_out are errors that name the utterance, in decode_nbest and in a stream's read-out."""
+    from end2end_amd.engines import CTCDecoderEngine
+    from end2end_amd._runtime import E2EError
+    B, T, V, W = 2, 6, 4, 4
+    x = rand_lp(3, B, T, V).to("cuda")
+    e = CTCDecoderEngine(0, W, ["_", "a", "b", " "])
+    text = {"nodes": "beam search: utterance 0 ran out of prefix-tree nodes",
+            "max_out": "beam search: utterance 0 needs %d output ids, %d provided" % (T + 2, T + 1)}[what]
+    # (x, dtype, sB, sT, sV, x_len, B, T, V, blank, W, space, lm, lmwt, wip, oov, N, out, max_out, out_len, n_hyp, ...)
+    at, count, value = {"nodes": (20, B, -1), "max_out": (19, B * W, T + 2)}[what]
+    _status_after(monkeypatch, "ctc_beam_nbest", at, count, value)
+    with pytest.raises(E2EError, match=text):
+        e.decode_nbest(x, torch.tensor([T, T]))
+    # (..., oov, state, row_bytes, max_frames, with_timesteps, N, out, max_out, out_len, n_hyp, ...)
+    _status_after(monkeypatch, "ctc_beam_stream", at + 4, count, value)
+    with pytest.raises(E2EError, match=text):
+        e.open_stream(B, T).feed_nbest(x)
+
+
+def test_engine_stream_names_the_status_of_its_own(monkeypatch):
+    """frames_done = -1: the CTC stream alone can run out of prefix-tree nodes; the other utterance has advanced."""
+    from end2end_amd.engines import CTCDecoderEngine
+    from end2end_amd._runtime import E2EError
+    B, T, V, W = 2, 6, 4, 4
+    st = CTCDecoderEngine(0, W, ["_", "a", "b", " "]).open_stream(B, T)
+    # (..., N, out, max_out, out_len, n_hyp, scores, counts, timesteps, frames_done, ...)
+    _status_after(monkeypatch, "ctc_beam_stream", 28, B, -1)
+    with pytest.raises(E2EError, match="beam search stream: utterance 0 ran out of prefix-tree nodes"):
+        st.feed_nbest(rand_lp(3, B, T, V).to("cuda"))
+    assert st.frames == [0, T]

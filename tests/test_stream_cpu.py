@@ -147,3 +147,51 @@ def test_python_surface():
     e.reset()
     with pytest.raises(ValueError):
         cpp_ctc_decoder.CTCDecoder(0, 8, ["_", "a", "b"]).open_stream(0, 10)
+
+
+def _engine_streams():
+    """One stream of each family, opened for 2 utterances of up to 10 frames at beam_width 4: no GPU is asked for."""
+    from end2end_amd.engines import ASGBeamEngine, CTCDecoderEngine, GramCTCDecoderEngine
+    labels = ["_", "a", "b"]
+    return {"ctc": (CTCDecoderEngine(0, 4, labels).open_stream(2, 10), "logits"),
+            "asg": (ASGBeamEngine(labels, 0, 4).open_stream(None, 2, 10), "emissions"),
+            "gram": (GramCTCDecoderEngine(0, 3, 4, {3: [1, 2]}, 4, labels).open_stream(2, 10), "logits")}
+
+
+def test_the_three_streams_share_one_base_and_its_errors():
+    import inspect
+    import torch
+    from end2end_amd.engines import ASGBeamStream, CTCBeamStream, GramBeamStream, _BeamStream
+    shared = ("feed_nbest", "feed", "reset", "check_chunk", "frames")
+    for cls in (CTCBeamStream, ASGBeamStream, GramBeamStream):
+        assert cls.__bases__ == (_BeamStream,)
+        for name in shared:
+            assert name in vars(_BeamStream)
+            if (cls, name) != (GramBeamStream, "feed_nbest"):
+                assert name not in vars(cls), (cls.__name__, name)
+    # Gram's feed_nbest is the base's with `timesteps` per read-out, and hands the work to the base
+    base, gram = inspect.signature(_BeamStream.feed_nbest), inspect.signature(GramBeamStream.feed_nbest)
+    assert list(gram.parameters) == list(base.parameters) + ["timesteps"]
+    names = GramBeamStream.feed_nbest.__code__.co_names
+    assert "_feed_nbest" in names and not {"check_chunk", "_launch", "_prepare", "_state_for"} & set(names)
+    for family, (s, what) in _engine_streams().items():
+        assert isinstance(s, _BeamStream) and s.HEADER_BYTES == 256 and s.frames == [0, 0] and s.state is None and s.row_bytes == 0
+        for nbest in (-1, 5):
+            with pytest.raises(ValueError, match=re.escape("nbest=%d outside [0, beam_width=4]" % nbest)):
+                s.feed_nbest(torch.zeros(2, 4, 4), nbest=nbest)
+        for call in (s.feed, s.feed_nbest, lambda x: s.check_chunk(tuple(x.shape))):
+            with pytest.raises(ValueError, match=re.escape("%s must be (batch, time, alphabet)" % what)):
+                call(torch.zeros(2, 4))
+            with pytest.raises(ValueError, match=re.escape("the chunk has 3 utterances, the stream was opened for 2")):
+                call(torch.zeros(3, 4, 4))
+            for frames in (0, 11):
+                with pytest.raises(ValueError, match=re.escape("a chunk of %d frames: the stream takes 1 .. max_frames = 10" % frames)):
+                    call(torch.zeros(2, frames, 4))
+        for rows in ([2], [-1], torch.tensor([0, 2])):
+            with pytest.raises(ValueError, match=re.escape("outside the stream's 2 utterances")):
+                s.reset(rows)
+        with pytest.raises(ValueError, match=re.escape("row 2 outside the stream's 2 utterances")):
+            s.reset([1, 2])
+        s.reset()
+        s.reset([1])
+        assert s.frames == [0, 0], family
