@@ -308,7 +308,8 @@ __device__ __forceinline__ bool walk_gram(const GramLmParams& q, LmWalk& w, int 
         if (j + 1 == k || nxt == q.space_id) {
           uint32_t wi;
           if constexpr (LEX) {
-            if (!lm_word_find(q.lm, w.hash, wi) || (nxt == q.space_id && wi == 0)) return false;
+            // (j + 1 < k: behind the gram's last id nxt is -1, which is also the space_id of a table without a space)
+            if (!lm_word_find(q.lm, w.hash, wi) || (j + 1 < k && nxt == q.space_id && wi == 0)) return false;
           } else wi = lm_word_lookup(q.lm, w.hash);
           const float sc = lm_base_score(q.lm, w.stb, w.stbn, wi, nullptr, nullptr);
           w.lm = w.lmb + (double)sc / 2.302585092994045684;       // quirk Q8: divides by ln 10
