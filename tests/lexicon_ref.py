@@ -6,6 +6,9 @@ and by each living child's strong `parent`; a parent's `children[c]` is a weakre
 pruned child that a descendant keeps alive is still found and not re-created (quirk Q7).  The functions below therefore keep
 no stray strong reference to a prefix beyond the beam: no prefix survives in a local variable across a pruning.
 
+A prefix records the frame at which it was created (run() returns them per label as `frames`), and margin() says by how
+little the search was decided (tests/ctc_beam_fuzz_util.py leaves out what f64 round-off could decide otherwise).
+
 LM numbers come from oracle_lib.OracleLM (base_score / word_index): the arithmetic is the oracle's, bit for bit.
 """
 import math
@@ -75,7 +78,7 @@ class WordListLM:
 
 class Prefix:
     __slots__ = ("pb", "pnb", "prev_pb", "prev_pnb", "last_char", "lm_score", "lm_before", "num_words", "num_oov",
-                 "num_oov_before", "last_word", "st", "st_before", "parent", "children", "__weakref__")
+                 "num_oov_before", "last_word", "st", "st_before", "parent", "children", "frame", "__weakref__")
 
     def __init__(self):
         self.pb = self.pnb = self.prev_pb = self.prev_pnb = NEG_INF
@@ -86,6 +89,7 @@ class Prefix:
         self.st = self.st_before = ()
         self.parent = None
         self.children = {}
+        self.frame = -1                          # the frame at which it was created (the root: none)
 
 
 class Search:
@@ -96,6 +100,9 @@ class Search:
         self.lmwt = lmwt if lm is not None else 0.0                     # .cpp:72-74
         self.wip, self.oov, self.lexicon = wip, oov, lexicon
         self.min_gap = math.inf                  # smallest positive gap between the W-th and (W+1)-th score over all cuts
+        self.t, self.row = -1, None              # the frame being searched and its row
+        self.final_gap = math.inf                # smallest gap between neighbours of the final rankings whose totals differ
+        self.odd_tie = False                     # a zero gap, at a cut or in a final ranking, that is not the same arithmetic
 
     def spell(self, chars):
         return "".join(self.labels[c] for c in chars)
@@ -156,9 +163,29 @@ class Search:
                 n.num_oov, n.num_oov_before = p.num_oov, p.num_oov_before
                 n.st, n.st_before = p.st, p.st_before
         n.parent = p
+        n.frame = self.t
         return n, True
 
-    def step(self, beam, row):
+    def same_arithmetic(self, a, b):
+        """An exact tie of two scores is decided by position (Q9).  It is the same on any machine only where both numbers come
+        out of the same operations on the same operands: both -inf, or two children of one parent created in this frame by
+        bit-equal emissions (neither repeats the parent's label), with the same words behind them."""
+        if self.score(a) == NEG_INF and self.score(b) == NEG_INF:
+            return True
+        p = a.parent
+        if p is None or p is not b.parent or a.frame != self.t or b.frame != self.t or self.row is None:
+            return False
+        if a.last_char == p.last_char or b.last_char == p.last_char or self.row[a.last_char] != self.row[b.last_char]:
+            return False
+        return (a.lm_score, a.num_words, a.num_oov) == (b.lm_score, b.num_words, b.num_oov)
+
+    def margin(self):
+        """The smaller of the smallest positive gap at any cut and the smallest gap between neighbours of the final rankings
+        whose totals differ; 0 where an exact tie was met that is not the same arithmetic."""
+        return 0.0 if self.odd_tie else min(self.min_gap, self.final_gap)
+
+    def step(self, beam, row, t=-1):
+        self.t, self.row = t, row
         fresh = []
         for ch in range(len(row)):                                       # char outer, prefix inner, :370-395
             cur = row[ch]
@@ -189,6 +216,8 @@ class Search:
             gap = sc[order[self.W - 1]] - sc[order[self.W]]
             if gap > 0:
                 self.min_gap = min(self.min_gap, gap)
+            elif not self.same_arithmetic(beam[order[self.W - 1]], beam[order[self.W]]):
+                self.odd_tie = True
         return [beam[i] for i in order]
 
     def run(self, lp, x_len):
@@ -199,16 +228,24 @@ class Search:
             root.st = root.st_before = (self.lm.word_index("<s>"),)
         beam = [root]
         for t in range(int(x_len)):
-            beam = self.step(beam, [float(v) for v in lp[t]])
+            beam = self.step(beam, [float(v) for v in lp[t]], t)
         out = []
-        for p in self.ranked(beam):
-            ids, q = [], p
+        final = self.ranked(beam)
+        for hi, lo in zip(final, final[1:]):
+            gap = self.score(hi) - self.score(lo)
+            if gap > 0:
+                self.final_gap = min(self.final_gap, gap)
+            elif not self.same_arithmetic(hi, lo):
+                self.odd_tie = True
+        for p in final:
+            ids, frames, q = [], [], p
             while q is not None:                                         # get_sentence, :232-245
                 if q is p or q.parent is not None:
                     ids.append(q.last_char)
+                    frames.append(q.frame)
                 q = q.parent
             out.append(dict(ids=tuple(reversed(ids)), total=self.score(p), ctc=lse(p.prev_pnb, p.prev_pb), lm=p.lm_score,
-                            words=p.num_words, oov=p.num_oov))
+                            words=p.num_words, oov=p.num_oov, frames=tuple(reversed(frames))))
         return out
 
 

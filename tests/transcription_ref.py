@@ -30,6 +30,8 @@ class _Chooser:
 
     def __init__(self, lm):
         self.lm = lm
+        self.min_choice = float("inf")    # smallest non-zero difference (log10 p) between the best and the second word of a key
+        self.choices = {}                 # key (the tuple of candidates) -> the words chosen for it, by any query
 
     def word_index(self, w):
         return self.lm.word_index(w)
@@ -37,18 +39,27 @@ class _Chooser:
     def base_score(self, ctx, word):
         if not isinstance(word, tuple):
             return self.lm.base_score(ctx, word)
-        best = None
+        best, scores = None, []
         for w in word:
             s, st = self.lm.base_score(ctx, w)
+            scores.append(s)
             if best is None or s > best[0]:                    # (strictly greater: a tie stays with the earliest)
-                best = (s, st)
-        return best
+                best = (s, st, w)
+        top = sorted(scores, reverse=True)
+        if top[0] != top[1]:
+            self.min_choice = min(self.min_choice, top[0] - top[1])
+        self.choices.setdefault(word, set()).add(best[2])
+        return best[:2]
 
 
 class Search(LR.Search):
     def __init__(self, labels, blank, W, lm, table, restrict=False, lmwt=1.0, wip=0.0, oov=-1000.0):
         super().__init__(labels, blank, W, _Chooser(lm), True, lmwt, wip, oov, lexicon=table if restrict else None)
         self.table = table
+
+    def margin(self):
+        """lexicon_ref.Search.margin, and the closest choice among homophones: less is f32 against f64 rounding."""
+        return min(super().margin(), self.lm.min_choice)
 
     def word_idx(self, chars):
         ids = self.table.keys.get(tuple(chars), ())
