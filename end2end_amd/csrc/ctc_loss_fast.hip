@@ -1019,6 +1019,7 @@ __device__ __forceinline__ void finish_rows(const P& p, int b, int t0, int n, in
   const float dev = __builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(my_st)) - zfrac + (float)(__builtin_amdgcn_frexp_expf(my_st) + u);
   const bool live = lane < rows;
 #ifdef E2E_FAST_PROFILE
+  // (the banded kernel's grid is (utterance, segment): wg is seg * B + b there, b * NS + seg for the other segment kernels)
   { const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
     if (wg < 16384 && live) atomicMax(reinterpret_cast<int*>(&g_zdev[wg]), __float_as_int(fminf(fabsf(dev), 1e30f))); }
 #endif
@@ -1820,7 +1821,9 @@ __device__ __forceinline__ bool band_group_matters(const FastParams& p, int b, i
 template <typename P>
 __device__ __forceinline__ void segment_wave_band(const P& p, unsigned char* smem) {
   constexpr int PPL = 2;
-  const int b = blockIdx.y, seg = blockIdx.x, lane = threadIdx.x & 63;
+  // (utterance fastest; the segment index is folded over grid y and z, and the last z plane may be short: launch_segments_band)
+  const int b = blockIdx.x, seg = blockIdx.z * gridDim.y + blockIdx.y, lane = threadIdx.x & 63;
+  if (seg >= p.NS) return;
   const int V = p.V, Tmax = p.T, t0 = seg * kSeg;
   const F2Lds<PPL> lds(smem, V);
   typedef float f4 __attribute__((ext_vector_type(4)));
@@ -1981,8 +1984,16 @@ __global__ E2E_KERNEL_ALIGN __launch_bounds__(64, kSegMinWaves2) void ctc_fast_s
 }
 
 // The banded form behind the chains of a call with targets of 128..255 labels and at most kMaxSmallV columns.
+// Grid: the utterance is the FAST index.  Workgroups are handed to the XCDs round-robin -- observed, not promised, and nothing
+// but the speed depends on it --, so with the segment as the fast index an utterance's segments were spread over all XCDs,
+// while this way the segments of utterance b mostly run on the XCD whose L2 the chain workgroup b wrote its probabilities and
+// checkpoints through (profiles/chain_entry/item_d_ab.txt, final_ab.txt).  A grid's y and z extents end at 65 535 and NS =
+// ceil(T / 16) reaches 2^18 (fast_supported: T < 2^22), so the segment index is y + z * gridDim.y: one z plane up to
+// kBandGridY segments, which is every call of up to 1 048 560 frames; beyond that the last plane's surplus workgroups leave at once.
+constexpr int kBandGridY = 65535;
 int launch_segments_band(const FastParams& p, hipStream_t stream) {
-  const dim3 grid(p.NS, p.B), block(64);
+  const int nz = (p.NS + kBandGridY - 1) / kBandGridY, ny = (p.NS + nz - 1) / nz;
+  const dim3 grid(p.B, ny, nz), block(64);
   const size_t lds = F2Lds<2>::bytes(p.V);
   if (dtype_is_16bit(p.xdt)) hipLaunchKernelGGL((ctc_fast_segment_band_kernel<true>), grid, block, lds, stream, p);
   else hipLaunchKernelGGL((ctc_fast_segment_band_kernel<false>), grid, block, lds, stream, p);

@@ -256,6 +256,8 @@ __shared__ unsigned long long s_prof_acc[8];
 #define F2_STAMP(i) { unsigned long long _t; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); \
     if (threadIdx.x == 0) { if ((i) < 0) { for (int _k = 0; _k < 8; _k++) s_prof_acc[_k] = 0; } else s_prof_acc[(i) < 0 ? 0 : (i)] += _t - s_prof_prev; } \
     asm volatile("s_waitcnt lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); if (threadIdx.x == 0) s_prof_prev = _t; asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// (F2_FLUSH's workgroup index: y * gridDim.x + x -- b * NS + seg for the segment kernels launched as (segment, utterance),
+//  seg * B + b for the banded one, whose grid is (utterance, segment))
 #define F2_FLUSH { const unsigned _wg = blockIdx.y * gridDim.x + blockIdx.x; if (threadIdx.x < 8 && _wg < 16384) g_prof2[_wg * 8 + threadIdx.x] = s_prof_acc[threadIdx.x]; }
 #define PROF_SPIN_BEGIN unsigned long long _t0 = __builtin_amdgcn_s_memtime();
 #define PROF_SPIN_END(acc) acc += __builtin_amdgcn_s_memtime() - _t0;
