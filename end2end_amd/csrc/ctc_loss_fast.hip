@@ -2108,7 +2108,7 @@ int launch_fast_ppl(const FastParams& p, hipStream_t stream) {
     c = hf_chains<PPL, ChainF32>(p.V);
     q.ztol = kZTolF32;
   } else if (rule == 4) {
-    c = h1_chains(PPL, p.V);
+    c = h1_chains(PPL, p);
   } else if (rule == 5) {
     c = hf_chains<PPL, ChainF64>(p.V);
   } else {

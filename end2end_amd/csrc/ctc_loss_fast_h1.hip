@@ -407,7 +407,13 @@ __device__ __forceinline__ void hx_chain_wave(const FastParams& p, int b, int T,
 // address is one clamp and one multiply-add from the block number, only the last column groups of a bracket are tested,
 // steady blocks (all rows live) have no row tests, the blank's (probability, tilted probability) pair is one masked store
 // after the columns, and only the alpha side tracks the smallest log-probability.
-template <int NV, int DIR>
+// LEAN (chosen by the host, h1_lean_input): f32 logits whose columns are adjacent and whose byte offsets inside an utterance,
+// like those into its part of ytab, fit 31 bits.  A row's address is then the utterance's base, which is the same in every
+// lane and stays in scalar registers, plus one 32-bit lane offset -- a 24-bit multiply-add from the clamped row, and for ytab
+// a scalar product of the segment number on top of a lane constant -- where the general form multiplies and adds in 64 bits
+// per row and per column group (loads and their addresses 19.7 -> 11.0 / 22.7 -> 16.3 instructions per block on the alpha /
+// beta side, ytab's 22 -> 20: profiles/chain_producers/static_counts*.txt).
+template <int NV, int DIR, bool LEAN>
 __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, int first, unsigned char* smem, const HxLds hl,
                                              int lane, double rr2) {
   constexpr int stride = kHxProducers;
@@ -426,6 +432,13 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
   const int64_t xl = (int64_t)b * p.sB + (int64_t)l8 * p.sV;        // this lane's first column (element offset)
   const int64_t cstep = 8 * p.sV;
   float* yl = p.ytab + ((size_t)b * p.NS * V + l8) * kSeg;          // [segment][label][16 steps]
+  // LEAN: the utterance's bases and the lane's byte offsets on top of them (a dead column reads the lane's first one)
+  const char* xu = reinterpret_cast<const char*>(reinterpret_cast<const float*>(p.x) + (int64_t)b * p.sB);
+  char* yu = reinterpret_cast<char*>(p.ytab + (size_t)b * p.NS * V * kSeg);
+  const unsigned sT4 = (unsigned)p.sT * 4u, l84 = 4u * l8, ylane = (unsigned)(l8 * kSeg + tt) * 4u;
+  unsigned cb[NV];
+#pragma unroll
+  for (int k = 0; k < NV; k++) cb[k] = (k < kFull || live[k]) ? 32u * k : 0u;
   const int t_first = DIR == 0 ? tt : 8 * M + 7 - tt;                // the lane's row in block 0; block n: t_first +- 8 n
   lds_u8* prog = L0 + hl.prog + DIR * 32;
   const int a_fill = hl.filled + (DIR * kRingBlks + first) * 4;
@@ -442,6 +455,14 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
     constexpr bool F32IN = decltype(f32_tag)::value;
     const int t = row_of(n);
     const int tc = min(max(t, 0), T - 1);
+    if (LEAN) {
+      const unsigned ob = __umul24((unsigned)tc, sT4) + l84;
+      const char* src = xu + ob;
+#pragma unroll
+      for (int k = 0; k < NV; k++)
+        out[k] = k < kFull ? *reinterpret_cast<const float*>(src + 32 * k) : *reinterpret_cast<const float*>(xu + (ob + cb[k]));
+      return;
+    }
     const int64_t xr = xl + (int64_t)tc * p.sT;
     int64_t off[NV];
 #pragma unroll
@@ -471,10 +492,12 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
 #pragma unroll
     for (int k = 0; k < NV; k++) xv[k] = (row_live && (k < kFull || live[k])) ? xraw[k] : ninf;
     if (n >= kRingBlks) {
-      // (the readers' progress is looked at again only when the last look does not cover this block)
+      // (the readers' progress is looked at again only when the last look does not cover this block.  A producer is a
+      // block's time ahead of the slot it waits for and the chains read six blocks behind it: it sleeps 512 cycles between
+      // looks, not 64 -- every look is ~15 instructions on a SIMD it shares with a chain wave, 0.9-1.5 us of the headline call)
       while (consumed < n - kRingBlks + 1) {
         consumed = __builtin_amdgcn_readfirstlane(lds_min8(prog));
-        if (consumed < n - kRingBlks + 1) __builtin_amdgcn_s_sleep(1);
+        if (consumed < n - kRingBlks + 1) __builtin_amdgcn_s_sleep(8);
       }
       asm volatile("" ::: "memory");
     }
@@ -526,10 +549,19 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
       if (blank_lane) { h_d2 yw; yw.x = (double)ybl; yw.y = rr2 * (double)ybl; *(volatile lds_d2*)(L0 + (a_yw + (n & (kRingBlks - 1)) * 128)) = yw; }
     }
     if (DIR == 0 && row_live) {
-      float* yrow = yl + (size_t)(t >> 4) * V * kSeg + (t & (kSeg - 1));
+      if (LEAN) {
+        // t = 8 n + tt: segment n >> 1, step 8 (n & 1) + tt of it
+        char* yrow = yu + ((unsigned)(n >> 1) * (unsigned)(V * (kSeg * 4)) + (unsigned)((n & 1) * 32) + ylane);
 #pragma unroll
-      for (int k = 0; k < NV; k++) {
-        if (k < kFull || live[k]) yrow[8 * k * kSeg] = y[k];
+        for (int k = 0; k < NV; k++) {
+          if (k < kFull || live[k]) *reinterpret_cast<float*>(yrow + k * (8 * kSeg * 4)) = y[k];
+        }
+      } else {
+        float* yrow = yl + (size_t)(t >> 4) * V * kSeg + (t & (kSeg - 1));
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+          if (k < kFull || live[k]) yrow[8 * k * kSeg] = y[k];
+        }
       }
     }
     // every lane stores the same word ("my blocks up to n are there"): no divergence, one LDS write
@@ -545,7 +577,7 @@ __device__ __forceinline__ void hx_prep_wave(const FastParams& p, int b, int T, 
       load_block(f32_tag, n + 4 * stride, xb); if (n + 2 * stride < nblk) process(n + 2 * stride, xc);
     }
   };
-  if (p.xdt == E2E_F32) run(std::true_type{}); else run(std::false_type{});
+  if (LEAN || p.xdt == E2E_F32) run(std::true_type{}); else run(std::false_type{});
   // (see prep_wave: emissions near the end of f32 -> the utterance is recomputed entirely by the exact kernel)
   { const bool t1 = __any(lpmin < -69.f), t2 = __any(lpmin < -78.f);      // (both votes by the whole wave, outside the lane test)
     if (DIR == 0 && t1 && lane == 0) atomicOr(&p.flags[b], t2 ? 64 | 256 : 64); }       // e^-69 = 2^-100
@@ -602,7 +634,7 @@ __device__ __forceinline__ void hx_ckpt_wave(const FastParams& p, int b, int T, 
 // Waves: 2 * kHxMaxW chain waves (alpha0, beta0, alpha1, beta1, ...: waves of a workgroup land on the SIMDs in the order 0,2,1,3),
 // the two frame waves, four probability-row waves (alternating alpha side / beta side), the two checkpoint waves (the second
 // writes the lattice description first).
-template <int PPL>
+template <int PPL, bool LEAN>
 __global__ E2E_KERNEL_ALIGN __launch_bounds__(kHxWaves * 64) void ctc_fast_chain_hx_kernel(FastParams p) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -651,7 +683,7 @@ __global__ E2E_KERNEL_ALIGN __launch_bounds__(kHxWaves * 64) void ctc_fast_chain
     const int d = (wave - kProd) & 1;                    // alternating: alpha rows, beta rows
     const int first = (wave - kProd) >> 1;               // the producers of a direction take every kHxProducers-th block
     const double rr2 = (double)fast_tilt(S, T) * (double)fast_tilt(S, T);        // (the chain waves' own expression)
-#define HX_PREP(NVV) { if (d == 0) hx_prep_wave<NVV, 0>(p, b, T, first, smem, hl, lane, rr2); else hx_prep_wave<NVV, 1>(p, b, T, first, smem, hl, lane, rr2); }
+#define HX_PREP(NVV) { if (d == 0) hx_prep_wave<NVV, 0, LEAN>(p, b, T, first, smem, hl, lane, rr2); else hx_prep_wave<NVV, 1, LEAN>(p, b, T, first, smem, hl, lane, rr2); }
     if (V <= 16) HX_PREP(2) else if (V <= 32) HX_PREP(4) else if (V <= 48) HX_PREP(6) else if (V <= 64) HX_PREP(8) else HX_PREP(12)
 #undef HX_PREP
   }
@@ -663,12 +695,29 @@ bool h1_supported(int V, int Smax, int ppl) {
   return (ppl == 2 || ppl == 4) && Smax + 1 <= 4 * kHxOwnLanes && HxLds(V).total <= 160 * 1024;
 }
 
-Chains h1_chains(int ppl, int V) {           // (ppl: 2 or 4, see h1_supported)
-  return Chains{ppl == 4 ? &ctc_fast_chain_hx_kernel<4> : &ctc_fast_chain_hx_kernel<2>, kHxWaves * 64, (size_t)HxLds(V).total};
+// Whether the producers take the logits by their lean form (hx_prep_wave): f32, adjacent columns, and every byte offset inside
+// an utterance -- into the logits, the reads of dead columns included, and into its part of ytab -- below 2^31, with four
+// times the row stride a 24-bit factor.  Everything else keeps 64-bit offsets.
+bool h1_lean_input(int dtype, int T, int V, int64_t sT, int64_t sV) {
+  if (dtype != E2E_F32 || sV != 1 || sT < 0 || sT >= (int64_t)1 << 22 || T < 1 || T >= 1 << 24) return false;
+  const int64_t x_bytes = ((int64_t)(T - 1) * sT + V + 8) * 4;
+  const int64_t y_bytes = (int64_t)((T + kSeg - 1) / kSeg) * kSeg * V * 4;
+  return x_bytes < (int64_t)1 << 31 && y_bytes < (int64_t)1 << 31;
+}
+
+Chains h1_chains(int ppl, const FastParams& p) {           // (ppl: 2 or 4, see h1_supported)
+  const bool lean = h1_lean_input(p.xdt, p.T, p.V, p.sT, p.sV);
+  void (*k)(FastParams) = ppl == 4 ? (lean ? &ctc_fast_chain_hx_kernel<4, true> : &ctc_fast_chain_hx_kernel<4, false>)
+                                   : (lean ? &ctc_fast_chain_hx_kernel<2, true> : &ctc_fast_chain_hx_kernel<2, false>);
+  return Chains{k, kHxWaves * 64, (size_t)HxLds(p.V).total};
 }
 
 }  // namespace fastk
 }  // namespace e2e
+
+extern "C" int e2e_debug_chain_lean_input(int dtype, int T, int V, int64_t sT, int64_t sV) {
+  return e2e::fastk::h1_lean_input(dtype, T, V, sT, sV) ? 1 : 0;
+}
 
 #ifdef E2E_FAST_PROFILE
 extern "C" int e2e_debug_fast_timeline_h1(unsigned long long* host) {

@@ -760,7 +760,8 @@ struct Chains { void (*kernel)(FastParams); int threads; size_t lds; };
 
 // the lean halo chain kernel (ctc_loss_fast_h1.hip); h1_supported: whether it takes the shape
 bool h1_supported(int V, int Smax, int ppl);
-Chains h1_chains(int ppl, int V);
+Chains h1_chains(int ppl, const FastParams& p);
+bool h1_lean_input(int dtype, int T, int V, int64_t sT, int64_t sV);      // the producers' lean form of the logits (ctc_loss_fast_h1.hip)
 
 }  // namespace fastk
 }  // namespace e2e

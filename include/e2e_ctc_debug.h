@@ -42,6 +42,13 @@ int e2e_debug_occupy(int workgroups, int threads, int lds_bytes, long long nanos
 int e2e_debug_loss_route(int dtype, int algo, int B, int T, int V, int Smax, int chains,
                          int64_t sB, int64_t sT, int64_t sV, const void* x, const void* grads);
 
+/* Whether the producers of the lean halo chain kernel (rule 4 above) take logits of this dtype, frame count, alphabet and
+ * strides by their lean form -- an utterance's base address plus 32-bit byte offsets -- (1) or keep 64-bit offsets (0): the
+ * host's choice, computed by the function the launch follows; no GPU is touched.  1 needs f32, sV == 1, 0 <= sT < 2^22,
+ * 1 <= T < 2^24, and ((T - 1) sT + V + 8) * 4 as well as an utterance's part of the probability table,
+ * ceil(T / 16) * 16 * V * 4 bytes, below 2^31. */
+int e2e_debug_chain_lean_input(int dtype, int T, int V, int64_t sT, int64_t sV);
+
 /* After an e2e_ctc_loss_fwd_bwd(ALGO_AUTO / ALGO_FAST) call that took the fast path: the per-utterance
  * flag words (0 = served by the fast path; bits: 1 bad lengths, 2 blank in targets, 4 infeasible,
  * 8 range / self-check, 16 non-finite, 32 log Z mismatch, 64 emissions near the end of f32) and the
