@@ -198,6 +198,23 @@ def load():
                                           vp, C.c_size_t, C.c_int, C.c_int,
                                           C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p, i64p,
                                           vp, C.c_size_t, vp, C.POINTER(BeamOpts)]
+        L.e2e_ctc_label_cut_max.restype = C.c_int
+        L.e2e_ctc_label_cut_max.argtypes = []
+        L.e2e_ctc_label_cut_workspace_bytes.restype = C.c_size_t
+        L.e2e_ctc_label_cut_workspace_bytes.argtypes = [C.c_int] * 4
+        L.e2e_ctc_label_cut.restype = C.c_int
+        L.e2e_ctc_label_cut.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_double, vp, vp, vp, C.c_size_t, vp]
+        L.e2e_ctc_beam_cut_max_width.restype = C.c_int
+        L.e2e_ctc_beam_cut_max_width.argtypes = [C.c_int, C.c_int]
+        L.e2e_ctc_beam_cut_workspace_bytes.restype = C.c_size_t
+        L.e2e_ctc_beam_cut_workspace_bytes.argtypes = [C.c_int] * 7
+        L.e2e_ctc_beam_cut_stream_workspace_bytes.restype = C.c_size_t
+        L.e2e_ctc_beam_cut_stream_workspace_bytes.argtypes = [C.c_int] * 6
+        L.e2e_ctc_beam_nbest_cut.restype = C.c_int
+        L.e2e_ctc_beam_nbest_cut.argtypes = L.e2e_ctc_beam_nbest_opt.argtypes + [C.c_int, C.c_double]
+        L.e2e_ctc_beam_stream_cut.restype = C.c_int
+        L.e2e_ctc_beam_stream_cut.argtypes = L.e2e_ctc_beam_stream.argtypes + [C.c_int, C.c_double]
         L.e2e_lm_load_words.restype = C.c_int
         L.e2e_lm_load_words.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(vp)]
         L.e2e_lm_enable_lexicon.restype = C.c_int

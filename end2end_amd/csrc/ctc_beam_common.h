@@ -41,8 +41,10 @@
 // kernels run (all __forceinline__: every kernel instance carries its own copy, none is a function of its own).
 //   ctc_beam_lds.hip      ctc_beam_kernel: the beam in LDS                   } each compiled once per input dtype
 //   ctc_beam_general.hip  ctc_beam_general_kernel: any alphabet width        } (-DE2E_BEAM_IO=<type>), 18 instances an object
+//                         ... and once more per dtype for the pruned calls (-DE2E_BEAM_CUT=true; per-frame label pruning)
+//   ctc_label_cut.hip     label_cut_kernel: which labels of a frame a pruned call expands
 //   ctc_beam.hip          the host side: layouts, kernel choice, the C entry points
-// A kernel object hands its instances out through lds_kernel<IO> / general_kernel<IO> below.
+// A kernel object hands its instances out through lds_kernel<IO> / general_kernel<IO, CUT> below.
 #pragma once
 #include "beam_cut.h"
 #include "ctc_lm.h"
@@ -776,25 +778,42 @@ constexpr int kGenMaxW = 1024;
 __host__ __device__ inline int gen_list_cap(int W) { return 4 * W + 64; }
 __host__ __device__ inline int gen_bitmap_words(int V) { return V <= 65536 ? (V + 31) / 32 : 1; }
 struct GenParams {
-  unsigned long long* gkey;      // [B][W + W*V]
-  LmAnswer* lmc;                 // [B][2][W][V]   (null without a language model)
+  unsigned long long* gkey;      // [B][gstride]
+  LmAnswer* lmc;                 // [B][2][W][V]   (null without a language model, and in a pruned call)
   unsigned char* gmem;           // [B][2][Members::bytes(W)]: both member sets, when they no longer fit LDS (else null)
   int CH;                        // child map slots (power of two >= 4W)
+  // A pruned call (e2e_ctc_beam_nbest_cut, the kernel's CUT instances): the frames' label lists, written by the selection
+  // kernel ahead of this one on the stream.  Every other call reads nothing below.
+  const int* cut_ids;            // [B][T][cut_k1] ascending, -1 behind
+  const int* cut_n;              // [B][T]
+  int cut_k1;                    // min(cutoff_top_n, V) + 1
+  size_t gstride;                // candidate keys of an utterance: W + W * V, pruned W + W * cut_k1
 };
+
+// ---- per-frame label pruning (ctc_label_cut.hip): what the pruned search's host side needs of it ----
+inline int label_cut_k(int V, int cutoff_top_n) { return cutoff_top_n < V ? cutoff_top_n : V; }
+// the argument errors of a selection (E2E_ERR_ARG, the limit: E2E_ERR_UNSUPPORTED), before any launch
+int label_cut_check(int dtype, int B, int T, int V, int blank, int cutoff_top_n, double cutoff_prob);
+int launch_label_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len, int B, int T, int V,
+                     int blank, int cutoff_top_n, double cutoff_prob, int* ids, int* n, hipStream_t s);
 
 // ---- the kernel objects ----
 // Instance <IO, lmk, st> of a kernel, for its launch.  Each specialisation is defined by the object of its dtype; an lmk
 // outside [0, kLmKinds) is the caller's error (lmk_of gives none).
 template <typename IO> const void* lds_kernel(int lmk, bool st);
-template <typename IO> const void* general_kernel(int lmk, bool st);
+template <typename IO, bool CUT> const void* general_kernel(int lmk, bool st);     // (CUT: the pruned calls' instances)
 template <> const void* lds_kernel<float>(int, bool);
 template <> const void* lds_kernel<double>(int, bool);
 template <> const void* lds_kernel<f16_t>(int, bool);
 template <> const void* lds_kernel<bf16_t>(int, bool);
-template <> const void* general_kernel<float>(int, bool);
-template <> const void* general_kernel<double>(int, bool);
-template <> const void* general_kernel<f16_t>(int, bool);
-template <> const void* general_kernel<bf16_t>(int, bool);
+template <> const void* general_kernel<float, false>(int, bool);
+template <> const void* general_kernel<double, false>(int, bool);
+template <> const void* general_kernel<f16_t, false>(int, bool);
+template <> const void* general_kernel<bf16_t, false>(int, bool);
+template <> const void* general_kernel<float, true>(int, bool);
+template <> const void* general_kernel<double, true>(int, bool);
+template <> const void* general_kernel<f16_t, true>(int, bool);
+template <> const void* general_kernel<bf16_t, true>(int, bool);
 
 }  // namespace beamk
 }  // namespace e2e

@@ -17,7 +17,8 @@
 // the same result (tests run the whole beam suite through it: E2E_BEAM_GENERAL=1).  beam_width <= kGenMaxW and what the
 // maps and the selection's arrays leave of one workgroup's LDS (the member sets move to the workspace beyond ~256): 512.
 //
-// Compiled once per input dtype like ctc_beam_lds.hip: ctc_beam_general.f32.o, ... with general_kernel<IO>.  GenParams, kGenMaxW
+// Compiled once per input dtype like ctc_beam_lds.hip, and once more for the pruned calls (-DE2E_BEAM_CUT=false / true):
+// ctc_beam_general.f32.o, ... with general_kernel<IO, false>, ctc_beam_general_cut.f32.o, ... with general_kernel<IO, true>.  GenParams, kGenMaxW
 // and the sizes of the character pre-selection are in ctc_beam_common.h: the host lays the workspace out with them.
 #include <utility>
 
@@ -35,7 +36,14 @@ __device__ __forceinline__ unsigned okey32(float f) {
 
 __device__ __forceinline__ void gsync() { __threadfence_block(); __syncthreads(); }
 
-template <typename IO, int LMK, bool ST>
+// is label c in the frame's ascending list l[0 .. n)?  (a pruned call: the member's own last label)
+__device__ __forceinline__ bool cut_has(const int* l, int n, int c) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int m = (lo + hi) >> 1; if (l[m] < c) lo = m + 1; else hi = m; }
+  return lo < n && l[lo] == c;
+}
+
+template <typename IO, int LMK, bool ST, bool CUT>
 __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p, GenParams g) {
   constexpr bool LM = LMK != 0, RS = lmk_restricted(LMK);
   extern __shared__ __align__(16) unsigned char smem[];
@@ -70,8 +78,13 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
   int* const node_t = ST ? (p.st_ts_off ? reinterpret_cast<int*>(st_row + p.st_ts_off) : nullptr)
                          : p.node_t ? p.node_t + (size_t)b * p.NCAP : nullptr;         // (uniform: null in the plain call)
   const IO* lp = reinterpret_cast<const IO*>(p.lp) + (int64_t)b * p.sB;
-  unsigned long long* const gkey = g.gkey + (size_t)b * ((size_t)W + (size_t)W * V);
-  LmAnswer* const lmc0 = LM ? g.lmc + (size_t)b * 2 * (size_t)W * V : nullptr;
+  // A pruned call (e2e_ctc_beam_nbest_cut: the CUT instances, objects of their own): a step expands the frame's label list and
+  // nothing of it scales with V -- no answer rows: the pair loop asks the LM for the pairs that have no living child, `place`
+  // asks again for the <= W children it creates (W queries a frame against a stash of W * (K+1) answers written for W read).
+  // (A run-time branch on g.cut_ids instead of the template argument cost the unpruned call 4 % at V = 8000, W = 100: DESIGN.md 4.4.)
+  constexpr bool cut = CUT;
+  unsigned long long* const gkey = g.gkey + (size_t)b * (CUT ? g.gstride : (size_t)W + (size_t)W * V);
+  LmAnswer* const lmc0 = LM && !cut ? g.lmc + (size_t)b * 2 * (size_t)W * V : nullptr;
   int64_t Tq = p.x_len[b];
   const int T = Tq < 0 ? 0 : (Tq > p.T ? p.T : (int)Tq);
   Members M0; M0.carve(mem0, W);
@@ -94,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
   gsync();
   if (!ST || !resume) {
     if (tid == 0) slot_map(0).insert(0, 0);
-    if (LM) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[0], -1, c);
+    if (LM && !cut) for (int c = tid; c < V; c += kThreads) if (c != blank && c != p.space_id) lmc0[c] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[0], -1, c);
   } else {
     // what a step rebuilds: the slot map, the child map (one entry per guard) and the members' LM answer rows
     const SlotMap map0 = slot_map(0);
@@ -104,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
       const int go = M0.gown[i];
       if (go >= 0) cm.insert(go * V + M0.gchar[i], M0.gnode[i]);
     }
-    if (LM) for (size_t e = tid; e < (size_t)n0 * V; e += kThreads) {
+    if (LM && !cut) for (size_t e = tid; e < (size_t)n0 * V; e += kThreads) {
       const int j2 = (int)(e / V), c = (int)(e - (size_t)j2 * V);
       if (c != blank && c != p.space_id) lmc0[e] = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, M0.lm[j2], M0.last[j2], c);
     }
@@ -127,8 +140,9 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
     Bm.carve(mem0 + (size_t)(cur ^ 1) * mbytes, W);
     const SlotMap mapA = slot_map(cur), mapB = slot_map(cur ^ 1);
     const ChildMap cmA = child_map(cur), cmB = child_map(cur ^ 1);
-    const LmAnswer* const lmcA = LM ? lmc0 + (size_t)cur * W * V : nullptr;
-    LmAnswer* const lmcB = LM ? lmc0 + (size_t)(cur ^ 1) * W * V : nullptr;
+    const LmAnswer* const lmcA = LM && !cut ? lmc0 + (size_t)cur * W * V : nullptr;
+    LmAnswer* const lmcB = LM && !cut ? lmc0 + (size_t)(cur ^ 1) * W * V : nullptr;
+    const int* const cl = cut ? g.cut_ids + ((size_t)b * p.T + t) * g.cut_k1 : nullptr;     // this frame's labels, ascending
     const IO* const row = lp + (int64_t)t * p.sT;
     auto LP = [&](int c) -> double { return (double)row[(int64_t)c * p.sV]; };
     if (tid == 0) { s_hi = 0u; s_lo = 0xffffffffu; s_total_new = 0; }
@@ -145,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
     // W = 100).  Exact unless two DIFFERENT lp values could round to the same score, i.e. unless |full| is within 2^24 of
     // their spacing: f32 inputs and |full| < 2^20 only; otherwise, with a language model, for tiny alphabets or if the ties
     // overflow the list, every character is taken as before.
-    bool pre = LMK == 0 && sizeof(IO) <= 4 && V <= 65536 && V - 1 > 3 * W + 2;      // (16-bit inputs are f32 numbers too)
+    bool pre = !cut && LMK == 0 && sizeof(IO) <= 4 && V <= 65536 && V - 1 > 3 * W + 2;      // (16-bit inputs are f32 numbers too)
     if (pre) {
       if (tid == 0) s_fmax = 0u;
       __syncthreads();
@@ -156,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
       __syncthreads();
       pre = __uint_as_float(s_fmax) < 1048576.f;
     }
-    int NL = V;
+    int NL = cut ? min(g.cut_n[(size_t)b * p.T + t], g.cut_k1) : V;
     if (pre) {
       // threshold: the key of the (2W)-th largest lp[c], c != blank -- radix select over V 32-bit keys, 11 bits per pass
       const int want = 2 * W;
@@ -205,7 +219,15 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
       NL = s_nl;
       if (NL > gen_list_cap(W)) { pre = false; NL = V; }        // (more ties than the list holds: every character)
     }
-    auto CH = [&](int sidx) -> int { return pre ? s_lst[sidx] : sidx; };
+    auto CH = [&](int sidx) -> int { return cut ? cl[sidx] : pre ? s_lst[sidx] : sidx; };
+    // (pruned: a member's last label outside the frame's list gives the member no repeated-label share)
+    auto LPm = [&](int c) -> double { return !cut || cut_has(cl, NL, c) ? LP(c) : ninf(); };
+    // (pruned: the LM's answer for the child (member i, label c), asked when it is needed; the space asks nothing)
+    auto cut_answer = [&](int i, int last, int c) -> LmAnswer {
+      LmAnswer a; a.sc = 0.f; a.wi = 0u;
+      if (c != p.space_id) a = lm_query<lmk_fast(LMK), RS, lmk_hom(LMK)>(p, lt, A.lm[i], last, c);
+      return a;
+    };
     // ---- pairs: candidate q = c*n + i is the reference's order (character outer, prefix inner, :370-395) ----
     // (the blank creates no candidate: its share of every member is taken first)
     for (int i = tid; i < n; i += kThreads) A.npb[i] = LP(blank) + A.full[i];      // :374-376 (prob_blank was -inf)
@@ -219,7 +241,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
       const int last = A.last[ii];
       const double curp = LP(ci);
       unsigned long long* const slot = gkey + n + e;
-      if (ci == blank) { *slot = kNoCandKey; continue; }
+      if (ci == blank || (cut && (unsigned)ci >= (unsigned)V)) { *slot = kNoCandKey; continue; }
       const double val = curp + (ci == last ? ppb : full);                     // :383-385 / :389-391
       const int k = cmA.find(ii * V + ci);
       unsigned long long uk = kNoCandKey;
@@ -229,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
         // else: alive but pruned (Q7) -- the probability is lost and the slot stays taken
       } else {
         const LmFields pr = score_fields<LM>(A.lm[ii]);
-        const LmAnswer ans = answer_at<LM>(lmcA, (size_t)ii * V + ci);
+        const LmAnswer ans = LM && cut ? cut_answer(ii, last, ci) : answer_at<LM>(lmcA, (size_t)ii * V + ci);
         if (!RS || !lexicon_forbids(p, pr, last, ci, ans)) {
           uk = child_key<LM>(p, pr, last, ci, ans, val);
           key_hi = max(key_hi, (unsigned)(uk >> 32));
@@ -243,7 +265,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
       if (lane == 63 && incl) atomicAdd(&s_total_new, incl);
     }
     gsync();
-    update_members<LM>(p, A, n, LP, gkey, key_hi, key_lo);
+    update_members<LM>(p, A, n, LPm, gkey, key_hi, key_lo);
     key_hi = (unsigned)wave_max_i((int)(key_hi ^ 0x80000000u)) ^ 0x80000000u;
     key_lo = ~((unsigned)wave_max_i((int)((~key_lo) ^ 0x80000000u)) ^ 0x80000000u);
     if (lane == 0) { atomicMax(&s_hi, key_hi); atomicMin(&s_lo, key_lo); }
@@ -268,7 +290,8 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
         const int si = div_n(q), i = q - si * n;
         const int c = CH(si);
         const double val = LP(c) + (c == A.last[i] ? A.ppb[i] : A.full[i]);
-        child_lm<LM>(p, lt, A.lm[i], A.last[i], c, answer_at<LM>(lmcA, (size_t)i * V + c), Bm.lm[j]);
+        child_lm<LM>(p, lt, A.lm[i], A.last[i], c,
+                     LM && cut ? cut_answer(i, A.last[i], c) : answer_at<LM>(lmcA, (size_t)i * V + c), Bm.lm[j]);
         int k = atomicAdd(&s_next_node, 1);                                       // make_shared<Prefix>, :254
         if (k >= p.NCAP) { s_err = 1; k = 0; }
         else {
@@ -355,7 +378,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
     }
     gsync();
     rebuild_guards(A, Bm, nsel, V, [&](int e, int node) { cmB.insert(e, node); });
-    if (LM) {
+    if (LM && !cut) {
       // the LM's answers for the new beam: rows copied with members that stay, asked for members that are new
       for (size_t e = tid; e < (size_t)nsel * V; e += kThreads) {
         const int j2 = (int)(e / V), c = (int)(e - (size_t)j2 * V);
@@ -377,17 +400,17 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_general_kernel(BeamParams p
 }
 
 // entry k of the table is instance k: the pack expands LMK = 0 .. kLmKinds - 1 in order
-template <typename IO, bool ST, int... LMK>
+template <typename IO, bool ST, bool CUT, int... LMK>
 const void* general_instance(int lmk, std::integer_sequence<int, LMK...>) {
-  static const void* const instances[] = { reinterpret_cast<const void*>(&ctc_beam_general_kernel<IO, LMK, ST>)... };
+  static const void* const instances[] = { reinterpret_cast<const void*>(&ctc_beam_general_kernel<IO, LMK, ST, CUT>)... };
   return instances[lmk];
 }
 
 }  // namespace
 
-template <> const void* general_kernel<E2E_BEAM_IO>(int lmk, bool st) {
+template <> const void* general_kernel<E2E_BEAM_IO, E2E_BEAM_CUT>(int lmk, bool st) {
   using Kinds = std::make_integer_sequence<int, kLmKinds>;
-  return st ? general_instance<E2E_BEAM_IO, true>(lmk, Kinds()) : general_instance<E2E_BEAM_IO, false>(lmk, Kinds());
+  return st ? general_instance<E2E_BEAM_IO, true, E2E_BEAM_CUT>(lmk, Kinds()) : general_instance<E2E_BEAM_IO, false, E2E_BEAM_CUT>(lmk, Kinds());
 }
 
 }  // namespace beamk

@@ -504,6 +504,72 @@ PYBIND11_MODULE(_C, m) {
         py::arg("frames_done"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"),
         py::arg("restrict_to_lexicon") = false);
 
+  // per-frame label pruning: the selection alone, and the pruned searches (cutoff_top_n, cutoff_prob behind the unpruned
+  // calls' arguments)
+  m.def("ctc_label_cut_max", [] { return e2e_ctc_label_cut_max(); });
+  m.def("ctc_label_cut_workspace_bytes",
+        [](int B, int T, int V, int cutoff_top_n) { return e2e_ctc_label_cut_workspace_bytes(B, T, V, cutoff_top_n); });
+  m.def("ctc_label_cut",
+        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
+           int cutoff_top_n, double cutoff_prob, uintptr_t ids, uintptr_t n, uintptr_t workspace, size_t workspace_bytes,
+           uintptr_t stream) {
+          check(e2e_ctc_label_cut(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
+                                  cutoff_top_n, cutoff_prob, ptr<int32_t>(ids), ptr<int32_t>(n), ptr<void>(workspace),
+                                  workspace_bytes, ptr<void>(stream)));
+        },
+        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("cutoff_top_n"), py::arg("cutoff_prob"), py::arg("ids"),
+        py::arg("n"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
+  m.def("ctc_beam_cut_max_width", [](int V, bool with_lm) { return e2e_ctc_beam_cut_max_width(V, with_lm ? 1 : 0); });
+  m.def("ctc_beam_cut_workspace_bytes",
+        [](int B, int T, int V, int beam_width, bool with_lm, bool with_timesteps, int cutoff_top_n) {
+          return e2e_ctc_beam_cut_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0, with_timesteps ? 1 : 0, cutoff_top_n);
+        });
+  m.def("ctc_beam_cut_stream_workspace_bytes", [](int B, int T, int V, int beam_width, bool with_lm, int cutoff_top_n) {
+    return e2e_ctc_beam_cut_stream_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0, cutoff_top_n);
+  });
+  m.def("ctc_beam_nbest_cut",
+        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
+           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, int nbest,
+           uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts,
+           uintptr_t timesteps, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon,
+           int cutoff_top_n, double cutoff_prob) {
+          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
+          check(e2e_ctc_beam_nbest_cut(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
+                                       beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, nbest,
+                                       ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
+                                       ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(timesteps),
+                                       ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o, cutoff_top_n, cutoff_prob));
+        },
+        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
+        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
+        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
+        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon"),
+        py::arg("cutoff_top_n"), py::arg("cutoff_prob"));
+  m.def("ctc_beam_stream_cut",
+        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t chunk_len, int B, int T, int V, int blank,
+           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, uintptr_t state,
+           size_t row_bytes, int max_frames, bool with_timesteps, int nbest, uintptr_t out, int64_t max_out,
+           uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t timesteps,
+           uintptr_t frames_done, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon,
+           int cutoff_top_n, double cutoff_prob) {
+          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
+          check(e2e_ctc_beam_stream_cut(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(chunk_len), B, T, V, blank,
+                                        beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, ptr<void>(state),
+                                        row_bytes, max_frames, with_timesteps ? 1 : 0, nbest, ptr<int64_t>(out), max_out,
+                                        ptr<int64_t>(out_len), ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<int32_t>(counts),
+                                        ptr<int64_t>(timesteps), ptr<int64_t>(frames_done), ptr<void>(workspace),
+                                        workspace_bytes, ptr<void>(stream), &o, cutoff_top_n, cutoff_prob));
+        },
+        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("chunk_len"), py::arg("B"),
+        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
+        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"), py::arg("row_bytes"),
+        py::arg("max_frames"), py::arg("with_timesteps"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
+        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
+        py::arg("frames_done"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"),
+        py::arg("restrict_to_lexicon"), py::arg("cutoff_top_n"), py::arg("cutoff_prob"));
+
   m.def("ctc_align_workspace_bytes",
         [](int B, int T, int V, int Smax, bool is_ctc) { return e2e_ctc_align_workspace_bytes(B, T, V, Smax, is_ctc ? 1 : 0); });
 

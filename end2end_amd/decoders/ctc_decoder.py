@@ -67,11 +67,16 @@ class CTCDecoder:
         its context.  Goes with ``lm_path`` (entries whose word the model does not list are dropped, with a warning) or
         alone (nothing is scored, the first listed homophone wins), and with ``restrict_to_vocabulary=True``.
         ``decoded_sentences`` are the chosen words joined by single spaces, ``<unk>`` for a piece that is no word.
+    :param cutoff_top_n: (extension) per-frame label pruning: a frame expands at most this many labels, the likeliest
+        (ties to the lower id), and the blank.  ``None`` or a value that is no less than the alphabet: no limit.  At most
+        1024 labels can be kept; needs ``beam_width > 1``.
+    :param cutoff_prob: (extension) ... and of those the fewest whose probabilities sum to this, in ``(0, 1]``; ``1.0``: all.
+        With both at their defaults the decoder is the unpruned one.
     """
 
     def __init__(self, beam_width=100, after_logsoftmax=False, blank_idx=0, time_major=False, labels=None,
                  lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True, keep_on_device=False,
-                 restrict_to_vocabulary=False, lexicon=None, transcriptions=None):
+                 restrict_to_vocabulary=False, lexicon=None, transcriptions=None, cutoff_top_n=None, cutoff_prob=1.0):
         self._beam_width = beam_width
         self._blank_idx = blank_idx
         self._after_logsoftmax = after_logsoftmax
@@ -85,22 +90,34 @@ class CTCDecoder:
         self._restrict = bool(restrict_to_vocabulary) or lexicon is not None
         self._lexicon = lexicon
         self._transcriptions = transcriptions
+        self._cutoff_top_n, self._cutoff_prob = cutoff_top_n, cutoff_prob
         self._check_params()
         # (a transcription model is loaded once, by configure: the engine's constructor would key it by spellings)
         self._decoder = CTCDecoderEngine(self._blank_idx, self._beam_width, self._labels,
                                          "" if transcriptions is not None else self._lm_path,
                                          self._lmwt, self._wip, self._oov_penalty, self._case_sensitive,
                                          keep_on_device=keep_on_device)
+        cut = dict(cutoff_top_n=cutoff_top_n, cutoff_prob=cutoff_prob)
         if transcriptions is not None:
             try:
                 self._decoder.configure(restrict_to_vocabulary=self._restrict, transcriptions=transcriptions,
-                                        lm_path=self._lm_path or None)
+                                        lm_path=self._lm_path or None, **cut)
             except ValueError as e:
                 raise CTCDecoderError(str(e)) from e
-        elif self._restrict:
-            self._decoder.configure(restrict_to_vocabulary=True, lexicon=self._lexicon)
+        elif self._restrict or cutoff_top_n is not None or cutoff_prob != 1.0:
+            try:
+                self._decoder.configure(restrict_to_vocabulary=self._restrict, lexicon=self._lexicon, **cut)
+            except ValueError as e:
+                raise CTCDecoderError(str(e)) from e
 
     def _check_params(self):
+        top_n, prob = self._cutoff_top_n, self._cutoff_prob
+        if top_n is not None and (isinstance(top_n, bool) or int(top_n) != top_n or top_n < 1):
+            raise CTCDecoderError("cutoff_top_n must be an integer >= 1 (or None), got {!r}".format(top_n))
+        if not isinstance(prob, (int, float)) or not 0.0 < prob <= 1.0:
+            raise CTCDecoderError("cutoff_prob must be in (0, 1], got {!r}".format(prob))
+        if (top_n is not None or prob != 1.0) and self._beam_width == 1:
+            raise CTCDecoderError("cutoff_top_n / cutoff_prob need beam_width > 1: greedy decoding expands nothing")
         if self._lm_path:
             # (upstream also tests `self._labels is None` here, which cannot hold after `labels or []`,
             # pytorch_end2end/decoders/ctc_decoder.py:53,69: a model without labels is accepted at construction;
@@ -129,6 +146,12 @@ class CTCDecoder:
         if self._time_major:
             logits = logits.transpose(1, 0)
         logits = logits.detach()
+        if not self._labels and self._beam_width > 1 and logits.dim() == 3:
+            # (without labels the alphabet is known at the first call only: the pruning's limit is checked here)
+            try:
+                self._decoder.check_cut_limit(logits.shape[2], self._cutoff_top_n, float(self._cutoff_prob))
+            except ValueError as e:
+                raise CTCDecoderError(str(e)) from e
         if logits_lengths is None:
             logits_lengths = torch.full((logits.size(0),), logits.size(1), dtype=torch.int32, device=logits.device)
         return logits, logits_lengths

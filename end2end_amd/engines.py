@@ -1223,6 +1223,7 @@ class CTCDecoderEngine:
                        if self.labels and all(len(c) == 1 and not 0xD800 <= ord(c) <= 0xDFFF for c in self.labels) else None)
         self.lm = None
         self.restrict = False
+        self.cutoff_top_n, self.cutoff_prob = None, 1.0          # per-frame label pruning (configure): off
         self._check_width(bool(lm_path))
         if lm_path:
             R.require_gpu()
@@ -1234,13 +1235,43 @@ class CTCDecoderEngine:
         if self.labels and self.beam_width > 1:
             # the beam lives in one workgroup's LDS: a width / alphabet it cannot hold is reported now, not at the first
             # decode (upstream has no such limit, ctc_decoder.cpp:353-441; see include/e2e_ctc.h)
-            cap = _C.ctc_beam_max_width(len(self.labels), with_lm)
+            # (a pruned search always takes the general kernel: its limit)
+            cap = (_C.ctc_beam_cut_max_width if self._cut(len(self.labels)) else _C.ctc_beam_max_width)(len(self.labels), with_lm)
             if self.beam_width > cap:
                 raise ValueError("beam_width %d is not supported for an alphabet of %d labels%s: at most %d"
                                  % (self.beam_width, len(self.labels), " with a language model" if with_lm else "", cap))
 
-    def configure(self, restrict_to_vocabulary=False, lexicon=None, lm=None, transcriptions=None, lm_path=None):
+    def _cut(self, V):
+        """(cutoff_top_n, cutoff_prob) as the C calls take them if the decoder prunes an alphabet of V labels, else None."""
+        top_n = V if self.cutoff_top_n is None else self.cutoff_top_n
+        return (top_n, self.cutoff_prob) if top_n < V or self.cutoff_prob < 1.0 else None
+
+    def _set_cut(self, cutoff_top_n, cutoff_prob):
+        if cutoff_top_n is not None and int(cutoff_top_n) < 1:
+            raise ValueError("cutoff_top_n=%r: at least 1" % (cutoff_top_n,))
+        if not 0.0 < float(cutoff_prob) <= 1.0:
+            raise ValueError("cutoff_prob=%r outside (0, 1]" % (cutoff_prob,))
+        if (cutoff_top_n is not None or float(cutoff_prob) < 1.0) and self.beam_width == 1:
+            raise ValueError("cutoff_top_n / cutoff_prob need beam_width > 1: greedy decoding expands nothing")
+        top_n = None if cutoff_top_n is None else int(cutoff_top_n)
+        if self.labels:
+            self.check_cut_limit(len(self.labels), top_n, float(cutoff_prob))
+        self.cutoff_top_n, self.cutoff_prob = top_n, float(cutoff_prob)
+
+    @staticmethod
+    def check_cut_limit(V, cutoff_top_n, cutoff_prob):
+        """A pruned frame keeps at most e2e_ctc_label_cut_max() labels besides the blank."""
+        K = V if cutoff_top_n is None else min(cutoff_top_n, V)
+        if (K < V or cutoff_prob < 1.0) and K > _C.ctc_label_cut_max():
+            raise ValueError("min(cutoff_top_n, alphabet) = %d: a pruned frame keeps at most %d labels (set cutoff_top_n)"
+                             % (K, _C.ctc_label_cut_max()))
+
+    def configure(self, restrict_to_vocabulary=False, lexicon=None, lm=None, transcriptions=None, lm_path=None,
+                  cutoff_top_n=None, cutoff_prob=1.0):
         """Extensions, set once before decoding; returns self.
+        `cutoff_top_n`, `cutoff_prob`: per-frame label pruning (the definition: e2e_ctc_label_cut, include/e2e_ctc.h) -- a frame
+        expands at most `cutoff_top_n` labels and of those the fewest whose probabilities sum to `cutoff_prob`, the blank always.
+        None / 1.0 (or a `cutoff_top_n` that is no less than the alphabet): not pruned.  A pruned search runs the general kernel.
         `restrict_to_vocabulary`: the beam search only forms words of the language model's vocabulary.
         `lexicon`: an iterable of words; the search is restricted to them without a language model -- a model that scores
         nothing is built from the list, `lmwt` and `oov_penalty` then count as 0 (as `lmwt` does upstream without a model),
@@ -1252,6 +1283,7 @@ class CTCDecoderEngine:
         here the model scores them; alone it is the model that scores nothing (every listed word at log10 p = 0)."""
         if lm_path is not None and transcriptions is None:
             raise ValueError("lm_path is the constructor's; configure takes it only together with transcriptions")
+        self._set_cut(cutoff_top_n, cutoff_prob)
         if transcriptions is not None:
             if lexicon is not None or lm is not None:
                 raise ValueError("transcriptions exclude lexicon and lm (restrict_to_vocabulary=True restricts to the transcriptions)")
@@ -1282,6 +1314,7 @@ class CTCDecoderEngine:
         if restrict and not self.lm.has_lexicon():
             self.lm.enable_lexicon()
         self.restrict = restrict
+        self._check_width(self.lm is not None)
         return self
 
     def _strings(self, rows, lens):
@@ -1348,8 +1381,8 @@ class CTCDecoderEngine:
 
     def decode(self, logits_, logits_lengths_):
         """Prefix beam search on LOG-PROBABILITIES -> (indices (B,maxlen) int64, lengths (B), sentences)."""
-        if self.restrict:
-            # hypothesis 0 of the restricted n-best list (the restriction is an option of that call: e2e_ctc_beam_nbest_opt)
+        if self.restrict or self._cut(logits_.shape[-1]):
+            # hypothesis 0 of the restricted / pruned n-best list (options of that call: e2e_ctc_beam_nbest_opt, _cut)
             return _first_hypothesis(self.decode_nbest(logits_, logits_lengths_, nbest=1))
         x, xl, dev = self._prep(logits_, logits_lengths_)
         B, T, V = x.shape
@@ -1393,15 +1426,24 @@ class CTCDecoderEngine:
         if B:
             with torch.cuda.device(dev):
                 lm = self.lm.on(dev).handle if self.lm is not None else 0
-                nbytes = _C.ctc_beam_nbest_workspace_bytes(B, T, V, self.beam_width, self.lm is not None, bool(timesteps))
+                cut = self._cut(V)
+                if cut:
+                    self.check_cut_limit(V, *cut)
+                    nbytes = _C.ctc_beam_cut_workspace_bytes(B, T, V, self.beam_width, self.lm is not None, bool(timesteps), cut[0])
+                else:
+                    nbytes = _C.ctc_beam_nbest_workspace_bytes(B, T, V, self.beam_width, self.lm is not None, bool(timesteps))
                 ws = R.workspace(dev, nbytes)
                 sB, sT, sV = x.stride()
-                _C.ctc_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(),
-                                  B, T, V, self.blank_idx, self.beam_width, self.space_id, lm,
-                                  self.lmwt, self.wip, self.oov_penalty, N,
-                                  out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
-                                  counts.data_ptr(), ts.data_ptr() if timesteps else 0,
-                                  ws.data_ptr(), ws.numel(), R.stream_handle(dev), restrict_to_lexicon=self.restrict)
+                args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(),
+                        B, T, V, self.blank_idx, self.beam_width, self.space_id, lm,
+                        self.lmwt, self.wip, self.oov_penalty, N,
+                        out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                        counts.data_ptr(), ts.data_ptr() if timesteps else 0,
+                        ws.data_ptr(), ws.numel(), R.stream_handle(dev), self.restrict)
+                if cut:
+                    _C.ctc_beam_nbest_cut(*args, *cut)
+                else:
+                    _C.ctc_beam_nbest(*args)
         return _nbest_result(self, *bufs)
 
     def _check_nbest(self, nh, lens, max_out):
@@ -1457,15 +1499,23 @@ class CTCBeamStream(_BeamStream):
         B, Tc, V = x.shape
         out, out_len, n_hyp, scores, counts, ts = bufs
         lm = e.lm.on(dev).handle if e.lm is not None else 0
-        nbytes = _C.ctc_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
+        cut = e._cut(V)                              # (the engine's knobs: the same for every chunk, as the restriction is)
+        if cut:
+            e.check_cut_limit(V, *cut)
+            nbytes = _C.ctc_beam_cut_stream_workspace_bytes(B, Tc, V, e.beam_width, e.lm is not None, cut[0])
+        else:
+            nbytes = _C.ctc_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
         ws = R.workspace(dev, nbytes, stream) if nbytes else None     # (the one-workgroup kernel needs none: a null pointer)
         sB, sT, sV = x.stride()
-        _C.ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V, e.blank_idx,
-                           e.beam_width, e.space_id, lm, e.lmwt, e.wip, e.oov_penalty,
-                           state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
-                           out, max_out, out_len, n_hyp, scores, counts, ts, frames_done,
-                           ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, stream,
-                           restrict_to_lexicon=e.restrict)
+        args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V, e.blank_idx,
+                e.beam_width, e.space_id, lm, e.lmwt, e.wip, e.oov_penalty,
+                state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
+                out, max_out, out_len, n_hyp, scores, counts, ts, frames_done,
+                ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, stream, e.restrict)
+        if cut:
+            _C.ctc_beam_stream_cut(*args, *cut)
+        else:
+            _C.ctc_beam_stream(*args)
 
 
 class GramBeamStream(_BeamStream):

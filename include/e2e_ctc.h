@@ -975,6 +975,72 @@ int e2e_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, int64
                         void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * Per-frame label pruning (cutoff_top_n, cutoff_prob) -- an extension (no counterpart upstream; the knobs of parlance
+ * ctcdecode, PaddlePaddle DeepSpeech, pyctcdecode, flashlight).  Additive, ABI 4.
+ *
+ * DEFINITION.  For a frame's row lp[0..V), taken as the numbers the search reads (16-bit inputs as their f32 images), and
+ * cutoff_top_n >= 1, 0 < cutoff_prob <= 1:
+ *   1. order the labels by lp descending, ties by label id ascending; NaN counts as -inf;
+ *   2. K = min(cutoff_top_n, V); take the first K of that order;
+ *   3. if cutoff_prob < 1: with P_j the f64 sum of exp(lp) over the first j, keep the first k, the smallest j with
+ *      P_j >= cutoff_prob, or all K if there is none.  cutoff_prob == 1 skips this step exactly: no sum is compared with 1;
+ *   4. the blank is always kept: if it is not among the k it is added and uses none of the K places, so a frame keeps
+ *      between 1 and k + 1 labels;
+ *   5. the kept set is written in ascending label id, the order in which the search expands it.
+ * In the search a label outside the frame's set does nothing in that frame: it creates no child, gives no share to a living
+ * child and no repeated-label share to the member itself.  Everything else is e2e_ctc_beam_nbest_opt's.
+ * cutoff_top_n >= V together with cutoff_prob == 1 is no pruning: the *_cut calls are then the unpruned calls.
+ * (P_j is summed by a scan of fixed shape, not one label after the other: a frame whose P_j comes within a few ulp of
+ * cutoff_prob may keep one label more or fewer than a sequential sum would; a call repeats bit for bit.)
+ *
+ * e2e_ctc_label_cut: the selection alone, one kernel over the B*T frames.
+ *   lp, dtype, sB, sT, sV, x_len, B, T, V, blank   as e2e_ctc_beam (E2E_F32 / F64 / F16 / BF16, any strides)
+ *   ids        (B,T,K+1) int32: a frame's kept labels ascending, -1 behind them
+ *   n          (B,T) int32: how many; 0 for t >= x_len[b] (the frame's ids are then not written)
+ *   workspace  >= e2e_ctc_label_cut_workspace_bytes(...) (the selection works in LDS: a token block, not read)
+ * Limits: min(cutoff_top_n, V) <= e2e_ctc_label_cut_max() = 1024, E2E_ERR_UNSUPPORTED beyond; any V.  Argument errors
+ * (sizes, null pointers, cutoff_top_n < 1, cutoff_prob outside (0, 1], blank outside [0, V)) are E2E_ERR_ARG before any
+ * launch.  Asynchronous on `stream`, allocates nothing, capturable.
+ *
+ * e2e_ctc_beam_nbest_cut / e2e_ctc_beam_stream_cut: e2e_ctc_beam_nbest_opt / e2e_ctc_beam_stream with the two knobs; the
+ * selection and the search run on `stream` in one call.  A pruned call always takes the general kernel (beam_width <=
+ * e2e_ctc_beam_cut_max_width(V, with_lm)); nothing of a frame's work scales with V, and the workspace
+ * (e2e_ctc_beam_cut_workspace_bytes; a stream: e2e_ctc_beam_cut_stream_workspace_bytes, T the chunk's) holds the frames'
+ * lists and beam_width * (K + 2) candidate keys per utterance instead of beam_width * (V + 1) keys and the LM's answer rows.
+ * A stream: the knobs are the same for every chunk (the caller's contract, as for opts), the selection runs on each chunk,
+ * the state row is e2e_ctc_beam_stream_row_bytes' unchanged, and the CONTRACT above holds: after any chunking the read-out
+ * equals the whole pruned call, bit for bit.
+ */
+int e2e_ctc_label_cut_max(void);
+size_t e2e_ctc_label_cut_workspace_bytes(int B, int T, int V, int cutoff_top_n);
+int e2e_ctc_label_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                      int B, int T, int V, int blank, int cutoff_top_n, double cutoff_prob,
+                      int32_t* ids, int32_t* n, void* workspace, size_t workspace_bytes, void* stream);
+
+int e2e_ctc_beam_cut_max_width(int V, int with_lm);
+size_t e2e_ctc_beam_cut_workspace_bytes(int B, int T, int V, int beam_width, int with_lm, int with_timesteps, int cutoff_top_n);
+size_t e2e_ctc_beam_cut_stream_workspace_bytes(int B, int T, int V, int beam_width, int with_lm, int cutoff_top_n);
+
+int e2e_ctc_beam_nbest_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                           const int64_t* x_len, int B, int T, int V, int blank,
+                           int beam_width, int space_id, const e2e_lm* lm,
+                           double lmwt, double wip, double oov_penalty,
+                           int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                           double* scores, int32_t* counts, int64_t* timesteps,
+                           void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts,
+                           int cutoff_top_n, double cutoff_prob);
+
+int e2e_ctc_beam_stream_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV,
+                            const int64_t* chunk_len, int B, int T, int V, int blank,
+                            int beam_width, int space_id, const e2e_lm* lm,
+                            double lmwt, double wip, double oov_penalty,
+                            void* state, size_t row_bytes, int max_frames, int with_timesteps,
+                            int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp,
+                            double* scores, int32_t* counts, int64_t* timesteps, int64_t* frames_done,
+                            void* workspace, size_t workspace_bytes, void* stream, const e2e_ctc_beam_opts* opts,
+                            int cutoff_top_n, double cutoff_prob);
+
+/* ------------------------------------------------------------------------
  * Viterbi forced alignment on the same lattice (max-plus instead of sum).
  * Replaces pytorch_end2end/utils/alignment.py:50-106 (_get_alignment_ctc_1d), :10-47
  * (_get_alignment_asg_1d, is_ctc = 0: no blanks) and the batch driver :109-138
