@@ -518,11 +518,7 @@ int check_model(const e2e_lm* lm, int V, bool restricted) {
       return E2E_ERR_ARG;
     }
   }
-  if (restricted && (!lm || !lm->has_lexicon)) {
-    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
-    return E2E_ERR_ARG;
-  }
-  return E2E_OK;
+  return check_lexicon(lm, restricted);
 }
 // (... and the device its tables are on: check_model_device, ctc_lm.h)
 
@@ -663,16 +659,13 @@ int e2e_asg_beam_stream(const void* x, int dtype, int64_t sB, int64_t sT, int64_
   if (!stream_layout(max_frames, V, beam_width, lm != nullptr, S) || !layout(1, V, beam_width, L)) {
     set_error("max_frames=%d frames are more than the search takes", max_frames); return E2E_ERR_UNSUPPORTED;
   }
-  if (row_bytes < S.total || row_bytes % 8) {
-    set_error("row_bytes = %zu: a state row needs %zu bytes (e2e_asg_beam_stream_row_bytes) and a multiple of 8", row_bytes, S.total);
-    return E2E_ERR_ARG;
-  }
+  if (const int rc = check_row_bytes(row_bytes, S.total, "e2e_asg_beam_stream_row_bytes")) return rc;
   if (const int rc = check_model(lm, V, restricted)) return rc;
   if (B > 0 && (!x || !chunk_len || !state || !frames_done)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
   if (B > 0 && nbest > 0 && (!out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
     set_error("null pointer argument"); return E2E_ERR_ARG;
   }
-  if (B > 0 && reinterpret_cast<uintptr_t>(state) % 8) { set_error("the state must be 8-byte aligned"); return E2E_ERR_ARG; }
+  if (const int rc = check_state_aligned(B, state)) return rc;
   if (B == 0) return E2E_OK;
   const size_t per_utt = L.off_nodes;                             // (the node pool lives in the row)
   if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < L.head + (size_t)B * per_utt) {

@@ -36,6 +36,7 @@
 // per-frame refill fills a new member's row.  Node numbers count the frames of the stream.  DESIGN.md 4.7, Streaming.
 #include <cstddef>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 
 #include "beam_cut.h"
@@ -777,13 +778,41 @@ int check_scored_args(int V, int num_base_labels, int space_id, const e2e_lm* lm
       return E2E_ERR_ARG;
     }
   }
-  if (restricted && (!lm || !lm->has_lexicon)) {
-    set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
-    return E2E_ERR_ARG;
-  }
-  return E2E_OK;
+  return check_lexicon(lm, restricted);
 }
 // (... and the device the model's tables are on: check_model_device, ctc_lm.h)
+
+// ... the null-pointer test of a call on B > 0 utterances: the pointers it needs, in any order.  (A pointer that this call does
+// not need -- out without room for an id, counts of an unscored search -- is given as `unused`)
+const void* const unused = &unused;
+int check_pointers(int B, std::initializer_list<const void*> needed) {
+  for (const void* p : needed) if (B > 0 && !p) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  return E2E_OK;
+}
+// ... and the workspace: aligned, then at least `need` bytes -- what the entry's query, named `query`, says, less its slack
+int check_workspace(void*& workspace, size_t& workspace_bytes, size_t need, const char* query) {
+  if (align_workspace(workspace, workspace_bytes) && workspace_bytes >= need) return E2E_OK;
+  set_error("workspace too small: %zu bytes, %s() = %zu", workspace_bytes, query, need + 256);
+  return E2E_ERR_WORKSPACE;
+}
+
+// the search's parameter block, the whole call's and the stream's alike; where the nodes lie (per_utt, off_nodes) is the caller's
+void fill_params(GramBeamParams& p, const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len, int B, int T,
+                 int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order, int beam_width, int nbest, int64_t* out,
+                 int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores, void* workspace, const BeamLayout& L,
+                 size_t per_utt, size_t off_nodes) {
+  p = GramBeamParams{lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
+                     out, max_out, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
+                     per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, off_nodes, L.logH};
+}
+// ... and what a scored search adds to it
+void fill_lm_params(GramLmParams& q, int num_base_labels, int space_id, const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                    int32_t* counts, const BeamLayout& L) {
+  if (lm) q.lm = lm->dev_view(); else memset(&q.lm, 0, sizeof(q.lm));
+  q.has_lm = lm ? 1 : 0; q.space_id = space_id < 0 ? -1 : space_id; q.R = num_base_labels;
+  q.lmwt = lm ? lmwt : 0.0; q.wip = wip; q.oov = oov_penalty;
+  q.counts = counts; q.off_cache = L.off_cache;
+}
 
 // a state row of a stream: header | Members | LmMembers (scored) | node pool of max_frames frames, each part 256-aligned.  The
 // workspace of a streaming call: a frame's scratch (beam_layout's up to the nodes, which are the row's) and, with a model,
@@ -830,9 +859,7 @@ int e2e_gram_beam_max_width(int V, int max_order) {
 }
 
 size_t e2e_gram_beam_workspace_bytes(int B, int T, int V, int max_order, int beam_width) {
-  BeamLayout L;
-  if (B < 0 || !beam_layout(T, V, max_order, beam_width, L)) return 0;
-  return (size_t)B * L.per_utt + 256;
+  return e2e_gram_beam_workspace_bytes_lm(B, T, V, max_order, beam_width, 0);
 }
 
 int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
@@ -842,17 +869,12 @@ int e2e_gram_ctc_beam_nbest(const void* lp, int dtype, int64_t sB, int64_t sT, i
   if (const int rc = check_beam_args(dtype, B, T, V, max_order, beam_width, nbest, max_out)) return rc;
   BeamLayout L;
   if (!beam_layout(T, V, max_order, beam_width, L)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
-  if (B > 0 && (!lp || !x_len || !gram_ids || !gram_len || !out_len || !n_hyp || !scores || (max_out > 0 && !out))) {
-    set_error("null pointer argument"); return E2E_ERR_ARG;
-  }
+  if (const int rc = check_pointers(B, {lp, x_len, gram_ids, gram_len, out_len, n_hyp, scores, max_out > 0 ? out : unused})) return rc;
   if (B == 0) return E2E_OK;
-  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < (size_t)B * L.per_utt) {
-    set_error("workspace too small: %zu bytes, e2e_gram_beam_workspace_bytes() = %zu", workspace_bytes, (size_t)B * L.per_utt + 256);
-    return E2E_ERR_WORKSPACE;
-  }
-  GramBeamParams p{lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
-                   out, max_out, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
-                   L.per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, L.off_nodes, L.logH};
+  if (const int rc = check_workspace(workspace, workspace_bytes, (size_t)B * L.per_utt, "e2e_gram_beam_workspace_bytes")) return rc;
+  GramBeamParams p;
+  fill_params(p, lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest, out, max_out, out_len,
+              n_hyp, scores, workspace, L, L.per_utt, L.off_nodes);
   hipLaunchKernelGGL(gram_beam_kernel<false>, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, p);
   E2E_HIP_CHECK(hipGetLastError(), "gram_beam_kernel launch");
   return E2E_OK;
@@ -876,24 +898,15 @@ int e2e_gram_ctc_beam_nbest_opt(const void* lp, int dtype, int64_t sB, int64_t s
   if (const int rc = check_scored_args(V, num_base_labels, space_id, lm, restricted)) return rc;
   BeamLayout L;
   if (!beam_layout(T, V, max_order, beam_width, L, lm != nullptr)) { set_error("T=%d frames are more than the search takes", T); return E2E_ERR_UNSUPPORTED; }
-  if (B > 0 && (!lp || !x_len || !gram_ids || !gram_len || !out_len || !n_hyp || !scores || !counts || (max_out > 0 && !out))) {
-    set_error("null pointer argument"); return E2E_ERR_ARG;
-  }
+  if (const int rc = check_pointers(B, {lp, x_len, gram_ids, gram_len, out_len, n_hyp, scores, counts, max_out > 0 ? out : unused})) return rc;
   if (B == 0) return E2E_OK;
   if (const int rc = check_model_device(lm)) return rc;
-  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < (size_t)B * L.per_utt) {
-    set_error("workspace too small: %zu bytes, e2e_gram_beam_workspace_bytes_lm() = %zu", workspace_bytes, (size_t)B * L.per_utt + 256);
-    return E2E_ERR_WORKSPACE;
-  }
+  if (const int rc = check_workspace(workspace, workspace_bytes, (size_t)B * L.per_utt, "e2e_gram_beam_workspace_bytes_lm")) return rc;
   GramOptParams o;
   GramLmParams& q = o.l;
-  q.b = GramBeamParams{lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
-                       out, max_out, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
-                       L.per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, L.off_nodes, L.logH};
-  if (lm) q.lm = lm->dev_view(); else memset(&q.lm, 0, sizeof(q.lm));
-  q.has_lm = lm ? 1 : 0; q.space_id = space_id < 0 ? -1 : space_id; q.R = num_base_labels;
-  q.lmwt = lm ? lmwt : 0.0; q.wip = wip; q.oov = oov_penalty;
-  q.counts = counts; q.off_cache = L.off_cache;
+  fill_params(q.b, lp, dtype, sB, sT, sV, x_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest, out, max_out, out_len,
+              n_hyp, scores, workspace, L, L.per_utt, L.off_nodes);
+  fill_lm_params(q, num_base_labels, space_id, lm, lmwt, wip, oov_penalty, counts, L);
   o.timesteps = timesteps;
   hipStream_t s = (hipStream_t)stream;
   // (neither option: the kernel and the parameter block of e2e_gram_ctc_beam_nbest_lm)
@@ -917,14 +930,12 @@ int e2e_gram_ctc_beam_nbest_lm(const void* lp, int dtype, int64_t sB, int64_t sT
 }
 
 size_t e2e_gram_beam_stream_row_bytes(int max_frames, int V, int max_order, int beam_width, int scored, int with_lm) {
-  StreamLayout S;
-  BeamLayout L;
+  StreamLayout S; BeamLayout L;
   return stream_layout(max_frames, V, max_order, beam_width, scored != 0, with_lm != 0, S, L) ? S.total : 0;
 }
 
 size_t e2e_gram_beam_stream_workspace_bytes(int B, int V, int max_order, int beam_width, int scored, int with_lm) {
-  StreamLayout S;
-  BeamLayout L;
+  StreamLayout S; BeamLayout L;
   if (B < 0 || !stream_layout(1, V, max_order, beam_width, scored != 0, with_lm != 0, S, L)) return 0;
   return (size_t)B * S.ws_per_utt + 256;
 }
@@ -946,36 +957,23 @@ int e2e_gram_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, 
   }
   if (sc) { if (const int rc = check_scored_args(V, num_base_labels, space_id, lm, restricted)) return rc; }
   if (max_frames < 1 || max_frames > (1 << 22)) { set_error("max_frames=%d outside [1, %d]", max_frames, 1 << 22); return E2E_ERR_ARG; }
-  StreamLayout S;
-  BeamLayout L;
+  StreamLayout S; BeamLayout L;
   if (!stream_layout(max_frames, V, max_order, beam_width, sc, lm != nullptr, S, L)) {
     set_error("max_frames=%d frames are more than the search takes", max_frames); return E2E_ERR_UNSUPPORTED;
   }
-  if (row_bytes < S.total || row_bytes % 8) {
-    set_error("row_bytes = %zu: a state row needs %zu bytes (e2e_gram_beam_stream_row_bytes) and a multiple of 8", row_bytes, S.total);
-    return E2E_ERR_ARG;
-  }
-  if (B > 0 && (!lp || !chunk_len || !gram_ids || !gram_len || !state || !frames_done)) { set_error("null pointer argument"); return E2E_ERR_ARG; }
-  if (B > 0 && nbest > 0 && (!out_len || !n_hyp || !scores || (sc && !counts) || (max_out > 0 && !out))) {
-    set_error("null pointer argument"); return E2E_ERR_ARG;
-  }
-  if (B > 0 && reinterpret_cast<uintptr_t>(state) % 8) { set_error("the state must be 8-byte aligned"); return E2E_ERR_ARG; }
+  if (const int rc = check_row_bytes(row_bytes, S.total, "e2e_gram_beam_stream_row_bytes")) return rc;
+  if (const int rc = check_pointers(B, {lp, chunk_len, gram_ids, gram_len, state, frames_done})) return rc;
+  if (nbest > 0) if (const int rc = check_pointers(B, {out_len, n_hyp, scores, sc ? counts : unused, max_out > 0 ? out : unused})) return rc;
+  if (const int rc = check_state_aligned(B, state)) return rc;
   if (B == 0) return E2E_OK;
-  if (!align_workspace(workspace, workspace_bytes) || workspace_bytes < (size_t)B * S.ws_per_utt) {
-    set_error("workspace too small: %zu bytes, e2e_gram_beam_stream_workspace_bytes() = %zu", workspace_bytes, (size_t)B * S.ws_per_utt + 256);
-    return E2E_ERR_WORKSPACE;
-  }
+  if (const int rc = check_workspace(workspace, workspace_bytes, (size_t)B * S.ws_per_utt, "e2e_gram_beam_stream_workspace_bytes")) return rc;
   if (const int rc = check_model_device(lm)) return rc;
   GramStreamParams sp;
   memset(&sp, 0, sizeof(sp));
   GramLmParams& q = sp.o.l;
-  q.b = GramBeamParams{lp, dtype, sB, sT, sV, chunk_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest,
-                       out, nbest > 0 ? max_out : 0, out_len, n_hyp, scores, reinterpret_cast<unsigned char*>(workspace),
-                       S.ws_per_utt, L.off_table, L.off_next, L.off_list, L.off_tot, L.off_sval, L.off_spos, 0, L.logH};
-  if (lm) q.lm = lm->dev_view();
-  q.has_lm = lm ? 1 : 0; q.space_id = space_id < 0 ? -1 : space_id; q.R = num_base_labels;
-  q.lmwt = lm ? lmwt : 0.0; q.wip = wip; q.oov = oov_penalty;
-  q.counts = counts; q.off_cache = L.off_cache;
+  fill_params(q.b, lp, dtype, sB, sT, sV, chunk_len, B, T, V, gram_ids, gram_len, max_order, beam_width, nbest, out,
+              nbest > 0 ? max_out : 0, out_len, n_hyp, scores, workspace, L, S.ws_per_utt, 0);     // (the nodes are the row's)
+  fill_lm_params(q, num_base_labels, space_id, lm, lmwt, wip, oov_penalty, counts, L);
   sp.o.timesteps = sc && nbest > 0 && opts ? opts->timesteps : nullptr;
   GramStream& s = sp.s;
   s.rows = reinterpret_cast<unsigned char*>(state); s.row_bytes = row_bytes; s.off_lm = S.off_lm; s.off_nodes = S.off_nodes;

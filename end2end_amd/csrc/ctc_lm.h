@@ -212,4 +212,11 @@ namespace e2e {
 // E2E_OK if a call on the current device may read the model's tables (lm null: no model, nothing to read), else the error
 // set: no device tables, or tables on another device (ctc_lm.hip)
 int check_model_device(const e2e_lm* lm);
+// The argument errors the three beam searches (ctc_beam.hip, asg_beam.hip, ctc_gram_decode.hip) word alike: E2E_OK, else the
+// error set.  A search restricted to the lexicon has a model, and one with a lexicon ...
+int check_lexicon(const e2e_lm* lm, bool restricted);
+// ... a stream's state rows are at least `want` bytes -- what the entry's own query, named `query`, says -- and a multiple of 8 ...
+int check_row_bytes(size_t row_bytes, size_t want, const char* query);
+// ... and the state is 8-byte aligned (not looked at for B = 0)
+int check_state_aligned(int B, const void* state);
 }  // namespace e2e

@@ -320,6 +320,24 @@ int e2e::check_model_device(const e2e_lm* lm) {
   return E2E_OK;
 }
 
+int e2e::check_lexicon(const e2e_lm* lm, bool restricted) {
+  if (!restricted || (lm && lm->has_lexicon)) return E2E_OK;
+  set_error(lm ? "restrict_to_lexicon: the model has no lexicon (e2e_lm_enable_lexicon)" : "restrict_to_lexicon needs a model: a language model or a word list (e2e_lm_load_words)");
+  return E2E_ERR_ARG;
+}
+
+int e2e::check_row_bytes(size_t row_bytes, size_t want, const char* query) {
+  if (row_bytes >= want && row_bytes % 8 == 0) return E2E_OK;
+  set_error("row_bytes = %zu: a state row needs %zu bytes (%s) and a multiple of 8", row_bytes, want, query);
+  return E2E_ERR_ARG;
+}
+
+int e2e::check_state_aligned(int B, const void* state) {
+  if (B <= 0 || reinterpret_cast<uintptr_t>(state) % 8 == 0) return E2E_OK;
+  set_error("the state must be 8-byte aligned");
+  return E2E_ERR_ARG;
+}
+
 // get_idx(string), ctc_decoder.cpp:77-82: exact lookup when case sensitive, else lower-cased lookup
 extern "C" uint32_t e2e_lm_word_index(const e2e_lm* lm, const char* word) {
   if (!lm || !word) return 0;

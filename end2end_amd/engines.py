@@ -1391,14 +1391,9 @@ class CTCDecoderEngine:
         out_len = torch.empty(B, dtype=torch.long, device=dev)
         if B:
             with torch.cuda.device(dev):
-                lm = self.lm.on(dev).handle if self.lm is not None else 0
                 nbytes = _C.ctc_beam_workspace_bytes_lm(B, T, V, self.beam_width, self.lm is not None)
                 ws = R.workspace(dev, nbytes)
-                sB, sT, sV = x.stride()
-                _C.ctc_beam(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(),
-                            B, T, V, self.blank_idx, self.beam_width, self.space_id, lm,
-                            self.lmwt, self.wip, self.oov_penalty,
-                            out.data_ptr(), max_out, out_len.data_ptr(),
+                _C.ctc_beam(*self._search_args(x, xl), out.data_ptr(), max_out, out_len.data_ptr(),
                             ws.data_ptr(), ws.numel(), R.stream_handle(dev))
         lens = out_len.tolist()
         # per-utterance status rides on the lengths (include/e2e_ctc.h): no extra call, no extra synchronisation
@@ -1425,26 +1420,35 @@ class CTCDecoderEngine:
         bufs = out, out_len, n_hyp, scores, counts, ts = _nbest_buffers(B, N, max_out, dev, timesteps=timesteps)
         if B:
             with torch.cuda.device(dev):
-                lm = self.lm.on(dev).handle if self.lm is not None else 0
-                cut = self._cut(V)
-                if cut:
-                    self.check_cut_limit(V, *cut)
-                    nbytes = _C.ctc_beam_cut_workspace_bytes(B, T, V, self.beam_width, self.lm is not None, bool(timesteps), cut[0])
-                else:
-                    nbytes = _C.ctc_beam_nbest_workspace_bytes(B, T, V, self.beam_width, self.lm is not None, bool(timesteps))
+                nbytes, entry, cut = self._entry(B, T, V, timesteps=timesteps)
                 ws = R.workspace(dev, nbytes)
-                sB, sT, sV = x.stride()
-                args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(),
-                        B, T, V, self.blank_idx, self.beam_width, self.space_id, lm,
-                        self.lmwt, self.wip, self.oov_penalty, N,
-                        out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
-                        counts.data_ptr(), ts.data_ptr() if timesteps else 0,
-                        ws.data_ptr(), ws.numel(), R.stream_handle(dev), self.restrict)
-                if cut:
-                    _C.ctc_beam_nbest_cut(*args, *cut)
-                else:
-                    _C.ctc_beam_nbest(*args)
+                entry(*self._search_args(x, xl), N,
+                      out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                      counts.data_ptr(), ts.data_ptr() if timesteps else 0,
+                      ws.data_ptr(), ws.numel(), R.stream_handle(dev), self.restrict, *cut)
         return _nbest_result(self, *bufs)
+
+    def _search_args(self, x, xl):
+        """What the arguments of every beam-search entry begin with: the input (pointer, dtype code, strides, lengths), the
+        sizes and the blank, the width, the space and the model's handle on x's device, the three weights."""
+        B, T, V = x.shape
+        sB, sT, sV = x.stride()
+        lm = self.lm.on(x.device).handle if self.lm is not None else 0
+        return (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V, self.blank_idx,
+                self.beam_width, self.space_id, lm, self.lmwt, self.wip, self.oov_penalty)
+
+    def _entry(self, B, T, V, stream=False, timesteps=False):
+        """(workspace bytes, the n-best entry to call, the arguments it takes behind the unpruned entry's) of a whole call on
+        T frames, or of a stream's chunk of T: pruned or not is decided here, and with it which query sizes the workspace."""
+        W, with_lm, cut = self.beam_width, self.lm is not None, self._cut(V)
+        if not cut:
+            if stream:
+                return _C.ctc_beam_stream_workspace_bytes(B, V, W, with_lm), _C.ctc_beam_stream, ()
+            return _C.ctc_beam_nbest_workspace_bytes(B, T, V, W, with_lm, bool(timesteps)), _C.ctc_beam_nbest, ()
+        self.check_cut_limit(V, *cut)
+        if stream:
+            return _C.ctc_beam_cut_stream_workspace_bytes(B, T, V, W, with_lm, cut[0]), _C.ctc_beam_stream_cut, cut
+        return _C.ctc_beam_cut_workspace_bytes(B, T, V, W, with_lm, bool(timesteps), cut[0]), _C.ctc_beam_nbest_cut, cut
 
     def _check_nbest(self, nh, lens, max_out):
         """Per-utterance and per-hypothesis status ride on the counts and lengths, as in decode()."""
@@ -1498,24 +1502,12 @@ class CTCBeamStream(_BeamStream):
         e, dev = self.engine, x.device
         B, Tc, V = x.shape
         out, out_len, n_hyp, scores, counts, ts = bufs
-        lm = e.lm.on(dev).handle if e.lm is not None else 0
-        cut = e._cut(V)                              # (the engine's knobs: the same for every chunk, as the restriction is)
-        if cut:
-            e.check_cut_limit(V, *cut)
-            nbytes = _C.ctc_beam_cut_stream_workspace_bytes(B, Tc, V, e.beam_width, e.lm is not None, cut[0])
-        else:
-            nbytes = _C.ctc_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
+        # (pruned or not: the engine's knobs, the same for every chunk, as the restriction is)
+        nbytes, entry, cut = e._entry(B, Tc, V, stream=True)
         ws = R.workspace(dev, nbytes, stream) if nbytes else None     # (the one-workgroup kernel needs none: a null pointer)
-        sB, sT, sV = x.stride()
-        args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V, e.blank_idx,
-                e.beam_width, e.space_id, lm, e.lmwt, e.wip, e.oov_penalty,
-                state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
-                out, max_out, out_len, n_hyp, scores, counts, ts, frames_done,
-                ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, stream, e.restrict)
-        if cut:
-            _C.ctc_beam_stream_cut(*args, *cut)
-        else:
-            _C.ctc_beam_stream(*args)
+        entry(*e._search_args(x, xl), state.data_ptr(), self.row_bytes, self.max_frames, self.timesteps, N,
+              out, max_out, out_len, n_hyp, scores, counts, ts, frames_done,
+              ws.data_ptr() if nbytes else 0, ws.numel() if nbytes else 0, stream, e.restrict, *cut)
 
 
 class GramBeamStream(_BeamStream):
