@@ -11,19 +11,19 @@ import threading
 
 import torch
 
+from ._runtime import _C, ABI_VERSION, dtype_code, require_gpu       # noqa: F401  (public names of this module too)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E2E_CTC_LIB") or os.path.join(_HERE, "csrc", "libe2e_ctc.so")      # (E2E_CTC_LIB: tools/diag A/B builds)
 
-F32, F64, F16, BF16 = 0, 1, 2, 3
-ALGO_AUTO, ALGO_EXACT, ALGO_FAST = 0, 1, 2
-ABI_VERSION = 4
+# (the codes are include/e2e_ctc.h's: the pybind layer, which is compiled against the header, carries them)
+F32, F64, F16, BF16 = _C.F32, _C.F64, _C.F16, _C.BF16
+ALGO_AUTO, ALGO_EXACT, ALGO_FAST = _C.ALGO_AUTO, _C.ALGO_EXACT, _C.ALGO_FAST
+REDUCE_NONE, REDUCE_SUM, REDUCE_MEAN = _C.REDUCE_NONE, _C.REDUCE_SUM, _C.REDUCE_MEAN
+CHAINS_F64, CHAINS_F32 = _C.CHAINS_F64, _C.CHAINS_F32
 
 _lib = None
 _lock = threading.Lock()
-
-
-REDUCE_NONE, REDUCE_SUM, REDUCE_MEAN = 0, 1, 2
-CHAINS_F64, CHAINS_F32 = 0, 1
 
 
 class LossOpts(C.Structure):
@@ -50,6 +50,29 @@ class E2EError(RuntimeError):
     """An error reported by the native library (message from e2e_last_error())."""
 
 
+# One character per type, as end2end_amd._C.SIGNATURES spells the parameters of include/e2e_ctc.h and e2e_ctc_debug.h
+# (type_code in csrc/pybind/e2e_C.cpp).  Lower case: values.  Upper case: pointers.
+_VALUES = {"v": None, "i": C.c_int, "q": C.c_int64, "z": C.c_size_t, "d": C.c_double, "u": C.c_uint32, "l": C.c_longlong,
+           "s": C.c_char_p}
+_POINTERS = {"S": C.POINTER(C.c_char_p), "M": C.POINTER(C.c_void_p), "O": C.POINTER(LossOpts), "C": C.POINTER(BeamOpts),
+             "A": C.POINTER(AsgBeamOpts), "G": C.POINTER(GramBeamOpts)}
+
+
+def _ctype(code, host):
+    """The ctypes type of one code.  A data pointer (void*, an e2e_lm handle, int64_t* ...) is c_void_p: callers pass
+    data_ptr() integers, arrays and byref().  `host`: the typed pointers of the e2e_lm_* calls, which point to host
+    arrays, keep their element type (I, Q, U, D: POINTER of i, q, u, d).  A struct of options is POINTER(its Structure),
+    so that an instance is passed by reference."""
+    if code in _VALUES:
+        return _VALUES[code]
+    if code in _POINTERS:
+        return _POINTERS[code]
+    if host and code in "IQUD":
+        return C.POINTER(_VALUES[code.lower()])
+    assert code in "pmIQUD", "end2end_amd._C.SIGNATURES has a type code that _lib.py does not know: %r" % code
+    return C.c_void_p
+
+
 def load():
     """Load libe2e_ctc.so once; raise loudly if it is absent or has the wrong ABI."""
     global _lib
@@ -63,208 +86,13 @@ def load():
                 "end2end_amd: native library %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C end2end_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        vp, i64, i64p = C.c_void_p, C.c_int64, C.c_void_p
-        L.e2e_ctc_abi_version.restype = C.c_int
         # (first of all: a library of another ABI may lack symbols bound below, and would fail with an AttributeError instead)
         if L.e2e_ctc_abi_version() != ABI_VERSION:
             raise ImportError("end2end_amd: %s has ABI %d, expected %d" % (LIB_PATH, L.e2e_ctc_abi_version(), ABI_VERSION))
-        L.e2e_last_error.restype = C.c_char_p
-        L.e2e_ctc_loss_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_loss_workspace_bytes.argtypes = [C.c_int] * 6
-        L.e2e_ctc_loss_takes_dtype.restype = C.c_int
-        L.e2e_ctc_loss_takes_dtype.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, i64, i64, vp, vp]
-        L.e2e_ctc_loss_fwd_bwd.restype = C.c_int
-        L.e2e_ctc_loss_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
-                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           vp, vp, vp, C.c_size_t, C.c_int, vp]
-        L.e2e_ctc_loss_fwd_bwd_opt.restype = C.c_int
-        L.e2e_ctc_loss_fwd_bwd_opt.argtypes = L.e2e_ctc_loss_fwd_bwd.argtypes + [C.POINTER(LossOpts)]
-        L.e2e_ctc_noblank_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_noblank_workspace_bytes.argtypes = [C.c_int] * 5
-        L.e2e_ctc_noblank_fwd_bwd.restype = C.c_int
-        L.e2e_ctc_noblank_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
-                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              vp, vp, vp, C.c_size_t, vp, C.POINTER(LossOpts)]
-        L.e2e_gram_ctc_workspace_bytes.restype = C.c_size_t
-        L.e2e_gram_ctc_workspace_bytes.argtypes = [C.c_int] * 6
-        L.e2e_gram_ctc_fwd_bwd.restype = C.c_int
-        L.e2e_gram_ctc_fwd_bwd.argtypes = [vp, C.c_int, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
-                                           C.c_int, C.c_int, C.c_int, C.c_int, i64p, vp, C.c_int, C.c_int, C.c_int,
-                                           vp, vp, vp, C.c_size_t, vp, C.POINTER(LossOpts)]
-        L.e2e_asg_max_labels.restype = C.c_int
-        L.e2e_asg_max_labels.argtypes = []
-        L.e2e_asg_max_target_length.restype = C.c_int
-        L.e2e_asg_max_target_length.argtypes = []
-        L.e2e_asg_workspace_bytes.restype = C.c_size_t
-        L.e2e_asg_workspace_bytes.argtypes = [C.c_int] * 5
-        L.e2e_asg_fwd_bwd.restype = C.c_int
-        L.e2e_asg_fwd_bwd.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, i64, i64p, i64p,
-                                      C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t, vp,
-                                      C.POINTER(LossOpts)]
-        L.e2e_asg_viterbi_workspace_bytes.restype = C.c_size_t
-        L.e2e_asg_viterbi_workspace_bytes.argtypes = [C.c_int] * 3
-        L.e2e_asg_viterbi.restype = C.c_int
-        L.e2e_asg_viterbi.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, C.c_int, C.c_int, C.c_int,
-                                      i64p, i64, vp, i64p, i64p, vp, C.c_size_t, vp]
-        L.e2e_gram_ctc_greedy.restype = C.c_int
-        L.e2e_gram_ctc_greedy.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
-                                          i64p, i64p, i64p, i64p, vp]
-        L.e2e_gram_beam_max_width.restype = C.c_int
-        L.e2e_gram_beam_max_width.argtypes = [C.c_int, C.c_int]
-        L.e2e_gram_beam_workspace_bytes.restype = C.c_size_t
-        L.e2e_gram_beam_workspace_bytes.argtypes = [C.c_int] * 5
-        L.e2e_gram_ctc_beam_nbest.restype = C.c_int
-        L.e2e_gram_ctc_beam_nbest.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
-                                              C.c_int, C.c_int, i64p, i64, i64p, i64p, vp, vp, C.c_size_t, vp]
-        L.e2e_gram_beam_workspace_bytes_lm.restype = C.c_size_t
-        L.e2e_gram_beam_workspace_bytes_lm.argtypes = [C.c_int] * 6
-        L.e2e_gram_ctc_beam_nbest_lm.restype = C.c_int
-        L.e2e_gram_ctc_beam_nbest_lm.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
-                                                 C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                                 C.c_int, i64p, i64, i64p, i64p, vp, vp, vp, C.c_size_t, vp]
-        L.e2e_gram_ctc_beam_nbest_opt.restype = C.c_int
-        L.e2e_gram_ctc_beam_nbest_opt.argtypes = L.e2e_gram_ctc_beam_nbest_lm.argtypes + [C.POINTER(GramBeamOpts)]
-        L.e2e_gram_beam_stream_row_bytes.restype = C.c_size_t
-        L.e2e_gram_beam_stream_row_bytes.argtypes = [C.c_int] * 6
-        L.e2e_gram_beam_stream_workspace_bytes.restype = C.c_size_t
-        L.e2e_gram_beam_stream_workspace_bytes.argtypes = [C.c_int] * 6
-        L.e2e_gram_ctc_beam_stream.restype = C.c_int
-        L.e2e_gram_ctc_beam_stream.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
-                                               C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                               vp, C.c_size_t, C.c_int,
-                                               C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p,
-                                               vp, C.c_size_t, vp, C.POINTER(GramBeamOpts)]
-        L.e2e_asg_beam_max_width.restype = C.c_int
-        L.e2e_asg_beam_max_width.argtypes = [C.c_int]
-        L.e2e_asg_beam_workspace_bytes.restype = C.c_size_t
-        L.e2e_asg_beam_workspace_bytes.argtypes = [C.c_int] * 5
-        L.e2e_asg_beam_nbest.restype = C.c_int
-        L.e2e_asg_beam_nbest.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int, i64p, i64, i64p, i64p,
-                                         vp, vp, vp, C.c_size_t, vp]
-        L.e2e_asg_beam_nbest_opt.restype = C.c_int
-        L.e2e_asg_beam_nbest_opt.argtypes = L.e2e_asg_beam_nbest.argtypes + [C.POINTER(AsgBeamOpts)]
-        L.e2e_asg_beam_stream_row_bytes.restype = C.c_size_t
-        L.e2e_asg_beam_stream_row_bytes.argtypes = [C.c_int] * 4
-        L.e2e_asg_beam_stream_workspace_bytes.restype = C.c_size_t
-        L.e2e_asg_beam_stream_workspace_bytes.argtypes = [C.c_int] * 4
-        L.e2e_asg_beam_stream.restype = C.c_int
-        L.e2e_asg_beam_stream.argtypes = [vp, C.c_int, i64, i64, i64, vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                          vp, C.c_size_t, C.c_int,
-                                          C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p,
-                                          vp, C.c_size_t, vp, C.POINTER(AsgBeamOpts)]
-        L.e2e_ctc_scale_grads.restype = C.c_int
-        L.e2e_ctc_scale_grads.argtypes = [vp, C.c_int, vp, C.c_int, i64, vp]
-        L.e2e_ctc_greedy.restype = C.c_int
-        L.e2e_ctc_greedy.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     i64p, i64p, vp]
-        L.e2e_lm_load_arpa.restype = C.c_int
-        L.e2e_lm_load_arpa.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(vp)]
-        L.e2e_lm_free.argtypes = [vp]
-        L.e2e_lm_order.restype = C.c_int
-        L.e2e_lm_order.argtypes = [vp]
-        L.e2e_lm_device.restype = C.c_int
-        L.e2e_lm_device.argtypes = [vp]
-        L.e2e_lm_word_index.restype = C.c_uint32
-        L.e2e_lm_word_index.argtypes = [vp, C.c_char_p]
-        L.e2e_lm_score.restype = C.c_double
-        L.e2e_lm_score.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int, C.c_uint32]
-        L.e2e_ctc_beam_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_beam_workspace_bytes.argtypes = [C.c_int] * 4
-        L.e2e_ctc_beam_workspace_bytes_lm.restype = C.c_size_t
-        L.e2e_ctc_beam_workspace_bytes_lm.argtypes = [C.c_int] * 5
-        L.e2e_ctc_beam_max_width.restype = C.c_int
-        L.e2e_ctc_beam_max_width.argtypes = [C.c_int, C.c_int]
-        L.e2e_ctc_beam.restype = C.c_int
-        L.e2e_ctc_beam.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                   i64p, i64, i64p, vp, C.c_size_t, vp]
-        L.e2e_ctc_beam_nbest_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_beam_nbest_workspace_bytes.argtypes = [C.c_int] * 6
-        L.e2e_ctc_beam_nbest.restype = C.c_int
-        L.e2e_ctc_beam_nbest.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                         C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p, vp, C.c_size_t, vp]
-        L.e2e_ctc_beam_nbest_opt.restype = C.c_int
-        L.e2e_ctc_beam_nbest_opt.argtypes = L.e2e_ctc_beam_nbest.argtypes + [C.POINTER(BeamOpts)]
-        L.e2e_ctc_beam_stream_row_bytes.restype = C.c_size_t
-        L.e2e_ctc_beam_stream_row_bytes.argtypes = [C.c_int] * 5
-        L.e2e_ctc_beam_stream_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_beam_stream_workspace_bytes.argtypes = [C.c_int] * 4
-        L.e2e_ctc_beam_stream.restype = C.c_int
-        L.e2e_ctc_beam_stream.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                          vp, C.c_size_t, C.c_int, C.c_int,
-                                          C.c_int, i64p, i64, i64p, i64p, vp, vp, i64p, i64p,
-                                          vp, C.c_size_t, vp, C.POINTER(BeamOpts)]
-        L.e2e_ctc_label_cut_max.restype = C.c_int
-        L.e2e_ctc_label_cut_max.argtypes = []
-        L.e2e_ctc_label_cut_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_label_cut_workspace_bytes.argtypes = [C.c_int] * 4
-        L.e2e_ctc_label_cut.restype = C.c_int
-        L.e2e_ctc_label_cut.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_double, vp, vp, vp, C.c_size_t, vp]
-        L.e2e_ctc_beam_cut_max_width.restype = C.c_int
-        L.e2e_ctc_beam_cut_max_width.argtypes = [C.c_int, C.c_int]
-        L.e2e_ctc_beam_cut_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_beam_cut_workspace_bytes.argtypes = [C.c_int] * 7
-        L.e2e_ctc_beam_cut_stream_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_beam_cut_stream_workspace_bytes.argtypes = [C.c_int] * 6
-        L.e2e_ctc_beam_nbest_cut.restype = C.c_int
-        L.e2e_ctc_beam_nbest_cut.argtypes = L.e2e_ctc_beam_nbest_opt.argtypes + [C.c_int, C.c_double]
-        L.e2e_ctc_beam_stream_cut.restype = C.c_int
-        L.e2e_ctc_beam_stream_cut.argtypes = L.e2e_ctc_beam_stream.argtypes + [C.c_int, C.c_double]
-        L.e2e_lm_load_words.restype = C.c_int
-        L.e2e_lm_load_words.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(vp)]
-        L.e2e_lm_enable_lexicon.restype = C.c_int
-        L.e2e_lm_enable_lexicon.argtypes = [vp]
-        L.e2e_lm_has_lexicon.restype = C.c_int
-        L.e2e_lm_has_lexicon.argtypes = [vp]
-        L.e2e_lm_spelling_class.restype = C.c_int
-        L.e2e_lm_spelling_class.argtypes = [vp, C.c_char_p]
-        L.e2e_lm_load_transcriptions.restype = C.c_int
-        L.e2e_lm_load_transcriptions.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                                 C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(vp)]
-        L.e2e_lm_is_transcribed.restype = C.c_int
-        L.e2e_lm_is_transcribed.argtypes = [vp]
-        L.e2e_lm_transcriptions_dropped.restype = C.c_int
-        L.e2e_lm_transcriptions_dropped.argtypes = [vp]
-        L.e2e_lm_transcribe.restype = C.c_int
-        L.e2e_lm_transcribe.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.POINTER(C.c_uint32), C.c_int,
-                                        C.POINTER(C.c_int)]
-        L.e2e_lm_word_string.restype = C.c_char_p
-        L.e2e_lm_word_string.argtypes = [vp, C.c_uint32]
-        L.e2e_ctc_align_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_align_workspace_bytes.argtypes = [C.c_int] * 5
-        L.e2e_ctc_align.restype = C.c_int
-        L.e2e_ctc_align.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p,
-                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64, vp, C.c_size_t, vp]
-        L.e2e_ctc_wordseg_table_elems.restype = C.c_size_t
-        L.e2e_ctc_wordseg_table_elems.argtypes = [C.c_int] * 2
-        L.e2e_ctc_wordseg_workspace_bytes.restype = C.c_size_t
-        L.e2e_ctc_wordseg_workspace_bytes.argtypes = [C.c_int] * 2
-        L.e2e_ctc_wordseg_plan.restype = C.c_int
-        L.e2e_ctc_wordseg_plan.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64p, i64, i64p, i64p] + [C.c_int] * 7 + \
-                                          [vp, C.c_size_t, i64p, vp, C.c_size_t, vp]
-        L.e2e_ctc_wordseg_gather.restype = C.c_int
-        L.e2e_ctc_wordseg_gather.argtypes = [vp, C.c_int, i64, i64, i64, i64p, i64, i64p, i64p] + [C.c_int] * 4 + \
-                                            [vp, i64p, vp, C.c_int, C.c_int, C.c_int, vp, i64p, i64p, i64p, vp]
-        L.e2e_ctc_wordseg_finish.restype = C.c_int
-        L.e2e_ctc_wordseg_finish.argtypes = [vp, C.c_int, i64, i64, i64, i64p, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
-                                             C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
-        L.e2e_debug_gram_redo_flags.restype = C.c_int
-        L.e2e_debug_gram_redo_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
-        L.e2e_debug_noblank_redo_flags.restype = C.c_int
-        L.e2e_debug_noblank_redo_flags.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
-        L.e2e_debug_stream_copy.restype = C.c_int
-        L.e2e_debug_stream_copy.argtypes = [vp, vp, C.c_size_t, vp]
-        # (the dtype codes above are include/e2e_ctc.h's: the pybind layer, which is compiled against the header, carries them)
-        try:
-            from . import _C as _ext
-            assert (F32, F64, F16, BF16) == (_ext.F32, _ext.F64, _ext.F16, _ext.BF16), "dtype codes of _lib.py and include/e2e_ctc.h differ"
-        except ImportError:
-            pass
+        for name, sig in _C.SIGNATURES.items():
+            fn, (ret, _, params) = getattr(L, name), sig.partition(":")
+            fn.restype = _ctype(ret, False)
+            fn.argtypes = [_ctype(c, name.startswith("e2e_lm_")) for c in params]
         _lib = L
     return _lib
 
@@ -272,24 +100,6 @@ def load():
 def check(rc):
     if rc != 0:
         raise E2EError("libe2e_ctc: %s (code %d)" % (load().e2e_last_error().decode(errors="replace"), rc))
-
-
-def require_gpu():
-    if not torch.cuda.is_available():
-        raise RuntimeError("end2end_amd needs an AMD GPU (MI355X / gfx950) visible to PyTorch-ROCm; "
-                           "there is no CPU fallback in this package")
-
-
-def dtype_code(dt):
-    if dt == torch.float32:
-        return F32
-    if dt == torch.float64:
-        return F64
-    if dt == torch.float16:
-        return F16
-    if dt == torch.bfloat16:
-        return BF16
-    raise TypeError("unsupported dtype %s" % dt)
 
 
 def stream_ptr(device):

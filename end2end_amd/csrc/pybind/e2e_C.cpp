@@ -4,15 +4,26 @@
 // (tensor.data_ptr()), strides and sizes; every function forwards to exactly one extern "C" entry point and turns a
 // negative return code into the Python exception E2EError carrying e2e_last_error().
 //
+// The header's parameter lists are not written out again here: a wrapper's Python signature and its forwarding call are
+// deduced from the entry point's own type (Binder, below), and an entry gives only its argument names -- all but the three
+// loss calls that check their arguments first, which are lambdas and name each argument once more.  The same deduction
+// fills _C.SIGNATURES, from which end2end_amd/_lib.py types the ctypes view of the library.
+//
 // Compiled with plain g++ against the pybind11 headers (no torch headers, no HIP headers): end2end_amd/csrc/Makefile.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
 #include <cstdint>
+#include <optional>
+#include <sstream>
 #include <string>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../../include/e2e_ctc.h"
+#include "../../../include/e2e_ctc_debug.h"
 
 namespace py = pybind11;
 
@@ -26,8 +37,149 @@ inline void check(int rc) {
   if (rc != E2E_OK) throw E2EError(std::string("libe2e_ctc: ") + e2e_last_error() + " (code " + std::to_string(rc) + ")");
 }
 
+// ---- a C parameter as Python sees it: a pointer travels as an integer (data_ptr(), a stream, a model's handle), every
+// other type as itself ----
 template <typename T>
-inline T* ptr(uintptr_t a) { return reinterpret_cast<T*>(a); }
+using py_t = std::conditional_t<std::is_pointer_v<T>, uintptr_t, T>;
+
+template <typename T, typename V>
+inline T to_c(V v) {
+  if constexpr (std::is_pointer_v<T> && !std::is_pointer_v<V>) return reinterpret_cast<T>(static_cast<uintptr_t>(v));
+  else return v;
+}
+
+// fn(v...), every integer that stands for a pointer turned into that pointer: for the wrappers that are written out
+template <typename R, typename... A, typename... V>
+inline R forward(R (*fn)(A...), V... v) { return fn(to_c<A>(v)...); }
+
+// ---- one character per type, for SIGNATURES.  Lower case: values; upper case: the pointer to that value type ----
+template <typename T>
+constexpr char type_code() {
+  if constexpr (std::is_pointer_v<T>) {
+    using E = std::remove_cv_t<std::remove_pointer_t<T>>;
+    if constexpr (std::is_void_v<E>) return 'p';
+    else if constexpr (std::is_same_v<E, char>) return 's';
+    else if constexpr (std::is_same_v<E, const char*>) return 'S';
+    else if constexpr (std::is_same_v<E, e2e_lm>) return 'm';
+    else if constexpr (std::is_same_v<E, e2e_lm*>) return 'M';
+    else if constexpr (std::is_same_v<E, e2e_ctc_loss_opts>) return 'O';
+    else if constexpr (std::is_same_v<E, e2e_ctc_beam_opts>) return 'C';
+    else if constexpr (std::is_same_v<E, e2e_asg_beam_opts>) return 'A';
+    else if constexpr (std::is_same_v<E, e2e_gram_beam_opts>) return 'G';
+    else return type_code<E>() - 'a' + 'A';                    // I, Q, U, D
+  } else {
+    static_assert(std::is_void_v<T> || std::is_same_v<T, int> || std::is_same_v<T, int64_t> || std::is_same_v<T, size_t> ||
+                      std::is_same_v<T, double> || std::is_same_v<T, uint32_t> || std::is_same_v<T, long long>,
+                  "a type the C ABI has not used yet: give it a code here and a ctypes type in end2end_amd/_lib.py");
+    return std::is_void_v<T> ? 'v' : std::is_same_v<T, int> ? 'i' : std::is_same_v<T, int64_t> ? 'q'
+         : std::is_same_v<T, size_t> ? 'z' : std::is_same_v<T, double> ? 'd' : std::is_same_v<T, uint32_t> ? 'u' : 'l';
+  }
+}
+
+template <typename R, typename... A>
+std::string signature(R (*)(A...)) { return std::string{type_code<R>(), ':', type_code<A>()...}; }
+
+// ---- the wrapper of an entry point whose Python arguments are its C parameters, one to one ----
+template <auto Fn, bool Checked, typename = decltype(Fn)>
+struct direct;
+template <auto Fn, bool Checked, typename R, typename... A>
+struct direct<Fn, Checked, R (*)(A...)> {
+  auto operator()(py_t<A>... a) const {
+    if constexpr (Checked) check(Fn(to_c<A>(a)...));
+    else return Fn(to_c<A>(a)...);
+  }
+};
+
+// ---- the wrapper of an entry point whose options struct is spread into Python arguments: Python passes Make's parameters
+// where C takes `const O*`, everything before and after it one to one.  Make gives the struct, or nothing for NULL ----
+template <auto Fn, auto Make, typename = decltype(Fn), typename = decltype(Make)>
+struct spread;
+template <auto Fn, auto Make, typename... A, typename O, typename... E>
+struct spread<Fn, Make, int (*)(A...), std::optional<O> (*)(E...)> {
+  using Args = std::tuple<A...>;
+  static constexpr size_t at() {
+    size_t i = 0;
+    (void)((std::is_same_v<A, const O*> || (++i, false)) || ...);
+    return i;
+  }
+  static_assert(at() < sizeof...(A), "the entry point does not take these options");
+  template <size_t... H, size_t... T>
+  static auto wrapper(std::index_sequence<H...>, std::index_sequence<T...>) {
+    return [](py_t<std::tuple_element_t<H, Args>>... head, E... e, py_t<std::tuple_element_t<at() + 1 + T, Args>>... tail) {
+      std::optional<O> o = Make(e...);
+      check(Fn(to_c<std::tuple_element_t<H, Args>>(head)..., o ? &*o : nullptr,
+               to_c<std::tuple_element_t<at() + 1 + T, Args>>(tail)...));
+    };
+  }
+  static auto fn() { return wrapper(std::make_index_sequence<at()>{}, std::make_index_sequence<sizeof...(A) - at() - 1>{}); }
+};
+
+std::optional<e2e_ctc_loss_opts> loss_opts(double grad_scale, uintptr_t reduced, int reduction, int chains) {
+  return e2e_ctc_loss_opts{grad_scale, to_c<void*>(reduced), reduction, chains};
+}
+std::optional<e2e_ctc_beam_opts> ctc_beam_opts(bool restrict_to_lexicon) { return e2e_ctc_beam_opts{restrict_to_lexicon ? 1 : 0}; }
+std::optional<e2e_asg_beam_opts> asg_beam_opts(bool restrict_to_lexicon, uintptr_t timesteps) {
+  return e2e_asg_beam_opts{restrict_to_lexicon ? 1 : 0, to_c<int64_t*>(timesteps)};
+}
+// opts: None passes NULL; else (restrict_to_lexicon, timesteps) -- zeros included, to tell the two apart
+std::optional<e2e_gram_beam_opts> gram_beam_opts(py::object opts) {
+  if (opts.is_none()) return std::nullopt;
+  auto t = opts.cast<std::pair<bool, uintptr_t>>();
+  return e2e_gram_beam_opts{t.first ? 1 : 0, to_c<int64_t*>(t.second)};
+}
+
+template <typename F>
+struct arity : arity<decltype(&F::operator())> {};
+template <typename R, typename... A>
+struct arity<R (*)(A...)> : std::integral_constant<size_t, sizeof...(A)> {};
+template <typename C, typename R, typename... A>
+struct arity<R (C::*)(A...) const> : std::integral_constant<size_t, sizeof...(A)> {};
+
+// ---- what an entry of the module's table says: the C function, its name, and the Python names of the arguments ----
+struct Binder {
+  py::module_& m;
+  py::dict sigs;
+
+  // the signature alone: a symbol of the headers that no function of this module forwards to one to one
+  template <auto Fn>
+  void sig(const char* cname) { sigs[cname] = signature(Fn); }
+
+  // an entry point that returns a code: e2e_<name> becomes <name>(names...) -> None, raising E2EError
+  template <auto Fn>
+  void call(const char* cname, const char* names) { sig<Fn>(cname); def(cname + 4, names, direct<Fn, true>{}); }
+
+  // a query (*_bytes, *_max*, takes_dtype): e2e_<name> becomes <name>(positional arguments) -> its value
+  template <auto Fn>
+  void query(const char* cname) { sig<Fn>(cname); m.def(cname + 4, direct<Fn, false>{}); }
+
+  // an entry point whose options struct Python passes spread out (spread and the makers above): it becomes `name`
+  template <auto Fn, auto Make, typename... D>
+  void call_opts(const char* cname, const char* name, const char* names, D... defaults) {
+    sig<Fn>(cname);
+    def(name, names, spread<Fn, Make>::fn(), defaults...);
+  }
+
+  // f under `name` with the blank-separated `names`, the last of them with `defaults`.  One name per argument: a count
+  // that differs from f's arity fails the import.
+  template <typename F, typename... D>
+  void def(const char* name, const char* names, F f, D... defaults) {
+    std::vector<std::string> n;
+    std::istringstream in(names);
+    for (std::string s; in >> s;) n.push_back(s);
+    constexpr size_t N = arity<F>::value;
+    static_assert(sizeof...(D) <= N);
+    if (n.size() != N)
+      throw std::runtime_error(std::string(name) + ": " + std::to_string(n.size()) + " argument names for " + std::to_string(N) +
+                               " arguments");
+    def_named(name, n, f, std::make_index_sequence<N - sizeof...(D)>{}, std::index_sequence_for<D...>{},
+              std::make_tuple(defaults...));
+  }
+  template <typename F, size_t... I, size_t... J, typename T>
+  void def_named(const char* name, const std::vector<std::string>& n, F f, std::index_sequence<I...>, std::index_sequence<J...>,
+                 const T& defaults) {
+    m.def(name, f, py::arg(n[I].c_str())..., (py::arg(n[sizeof...(I) + J].c_str()) = std::get<J>(defaults))...);
+  }
+};
 
 // Owner of an e2e_lm handle (the decoder owns its KenLM model through a unique_ptr upstream, ctc_decoder.h:51).
 class LanguageModel {
@@ -111,44 +263,37 @@ PYBIND11_MODULE(_C, m) {
   m.attr("REDUCE_MEAN") = E2E_REDUCE_MEAN;
   m.attr("CHAINS_F64") = E2E_CHAINS_F64;
   m.attr("CHAINS_F32") = E2E_CHAINS_F32;
+  m.attr("WORDSEG_HEADER") = E2E_WORDSEG_HEADER;
+  m.attr("WORDSEG_WHOLE") = E2E_WORDSEG_WHOLE;
+  m.attr("WORDSEG_FRAME") = E2E_WORDSEG_FRAME;
+  m.attr("WORDSEG_CHUNK") = E2E_WORDSEG_CHUNK;
 
+  Binder b{m, py::dict()};
+  // SIGNATURES: every function of the two headers -> "<return>:<parameters>", one character per type (type_code)
+  m.attr("SIGNATURES") = b.sigs;
+
+  b.sig<e2e_ctc_abi_version>("e2e_ctc_abi_version");
   m.def("abi_version", [] { return e2e_ctc_abi_version(); });
+  b.sig<e2e_last_error>("e2e_last_error");
   m.def("last_error", [] { return std::string(e2e_last_error()); });
 
-  m.def("ctc_loss_workspace_bytes", [](int B, int T, int V, int Smax, int dtype, int algo) {
-    return e2e_ctc_loss_workspace_bytes(B, T, V, Smax, dtype, algo);
-  });
-
-  m.def("ctc_loss_takes_dtype", [](int dtype, int algo, int T, int V, int Smax, int64_t sB, int64_t sT, int64_t sV, uintptr_t x, uintptr_t grads) {
-    return e2e_ctc_loss_takes_dtype(dtype, algo, T, V, Smax, sB, sT, sV, reinterpret_cast<const void*>(x), reinterpret_cast<const void*>(grads)) != 0;
-  });
-
+  // ---- the losses ----
+  b.query<e2e_ctc_loss_workspace_bytes>("e2e_ctc_loss_workspace_bytes");
+  b.query<e2e_ctc_loss_takes_dtype>("e2e_ctc_loss_takes_dtype");
+  b.sig<e2e_ctc_loss_fwd_bwd>("e2e_ctc_loss_fwd_bwd");
   // (grad_scale / reduced / reduction / chains: e2e_ctc_loss_opts; the defaults are the plain call)
-  m.def("ctc_loss_fwd_bwd",
-        [](uintptr_t x, int dtype, bool input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
-           int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, int blank,
-           uintptr_t losses, uintptr_t grads, uintptr_t workspace, size_t workspace_bytes, int algo, uintptr_t stream,
-           double grad_scale, uintptr_t reduced, int reduction, int chains) {
-          e2e_ctc_loss_opts o{grad_scale, ptr<void>(reduced), reduction, chains};
-          check(e2e_ctc_loss_fwd_bwd_opt(ptr<const void>(x), dtype, input_is_logprobs ? 1 : 0, sB, sT, sV,
-                                         ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
-                                         ptr<const int64_t>(t_len), B, T, V, Smax, blank, ptr<void>(losses),
-                                         ptr<void>(grads), ptr<void>(workspace), workspace_bytes, algo,
-                                         ptr<void>(stream), &o));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("input_is_logprobs"), py::arg("sB"), py::arg("sT"), py::arg("sV"),
-        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
-        py::arg("V"), py::arg("Smax"), py::arg("blank"), py::arg("losses"), py::arg("grads"), py::arg("workspace"),
-        py::arg("workspace_bytes"), py::arg("algo"), py::arg("stream"), py::arg("grad_scale") = 1.0,
-        py::arg("reduced") = 0, py::arg("reduction") = E2E_REDUCE_NONE, py::arg("chains") = E2E_CHAINS_F64);
+  b.call_opts<e2e_ctc_loss_fwd_bwd_opt, loss_opts>("e2e_ctc_loss_fwd_bwd_opt", "ctc_loss_fwd_bwd",
+        "x dtype input_is_logprobs sB sT sV targets tgt_stride x_len t_len B T V Smax blank losses grads workspace "
+        "workspace_bytes algo stream grad_scale reduced reduction chains", 1.0, 0, E2E_REDUCE_NONE, E2E_CHAINS_F64);
+  b.call<e2e_ctc_scale_grads>("e2e_ctc_scale_grads", "grads dtype scale B row_elems stream");
 
-  m.def("ctc_noblank_workspace_bytes", [](int B, int T, int V, int Smax, int dtype) {
-    return e2e_ctc_noblank_workspace_bytes(B, T, V, Smax, dtype);
-  });
-
+  b.query<e2e_ctc_noblank_workspace_bytes>("e2e_ctc_noblank_workspace_bytes");
+  b.sig<e2e_ctc_noblank_fwd_bwd>("e2e_ctc_noblank_fwd_bwd");
   // (arguments the library would refuse are refused here too, before anything reaches the GPU)
-  m.def("ctc_noblank_fwd_bwd",
-        [](uintptr_t x, int dtype, bool input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
+  b.def("ctc_noblank_fwd_bwd",
+        "x dtype input_is_logprobs sB sT sV targets tgt_stride x_len t_len B T V Smax space_idx losses grads workspace "
+        "workspace_bytes stream grad_scale reduced reduction",
+        [](uintptr_t x, int dtype, int input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
            int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, int space_idx,
            uintptr_t losses, uintptr_t grads, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
            double grad_scale, uintptr_t reduced, int reduction) {
@@ -158,24 +303,18 @@ PYBIND11_MODULE(_C, m) {
                                   std::to_string(V) + ")");
           if (reduction < E2E_REDUCE_NONE || reduction > E2E_REDUCE_MEAN || (reduction != E2E_REDUCE_NONE && !reduced))
             throw py::value_error("ctc_noblank_fwd_bwd: bad reduction");
-          e2e_ctc_loss_opts o{grad_scale, ptr<void>(reduced), reduction, E2E_CHAINS_F64};
-          check(e2e_ctc_noblank_fwd_bwd(ptr<const void>(x), dtype, input_is_logprobs ? 1 : 0, sB, sT, sV,
-                                        ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
-                                        ptr<const int64_t>(t_len), B, T, V, Smax, space_idx, ptr<void>(losses),
-                                        ptr<void>(grads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+          e2e_ctc_loss_opts o{grad_scale, to_c<void*>(reduced), reduction, E2E_CHAINS_F64};
+          check(forward(e2e_ctc_noblank_fwd_bwd, x, dtype, input_is_logprobs, sB, sT, sV, targets, tgt_stride, x_len, t_len, B, T,
+                        V, Smax, space_idx, losses, grads, workspace, workspace_bytes, stream, &o));
         },
-        py::arg("x"), py::arg("dtype"), py::arg("input_is_logprobs"), py::arg("sB"), py::arg("sT"), py::arg("sV"),
-        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
-        py::arg("V"), py::arg("Smax"), py::arg("space_idx"), py::arg("losses"), py::arg("grads"), py::arg("workspace"),
-        py::arg("workspace_bytes"), py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0,
-        py::arg("reduction") = E2E_REDUCE_NONE);
+        1.0, 0, E2E_REDUCE_NONE);
 
-  m.def("gram_ctc_workspace_bytes", [](int B, int T, int V, int Smax, int max_order, int dtype) {
-    return e2e_gram_ctc_workspace_bytes(B, T, V, Smax, max_order, dtype);
-  });
-
-  m.def("gram_ctc_fwd_bwd",
-        [](uintptr_t x, int dtype, bool input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
+  b.query<e2e_gram_ctc_workspace_bytes>("e2e_gram_ctc_workspace_bytes");
+  b.sig<e2e_gram_ctc_fwd_bwd>("e2e_gram_ctc_fwd_bwd");
+  b.def("gram_ctc_fwd_bwd",
+        "x dtype input_is_logprobs sB sT sV targets tgt_stride x_len t_len B T V Smax keys cols n_grams radix max_order losses "
+        "grads workspace workspace_bytes stream grad_scale reduced reduction",
+        [](uintptr_t x, int dtype, int input_is_logprobs, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets,
            int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, uintptr_t keys,
            uintptr_t cols, int n_grams, int radix, int max_order, uintptr_t losses, uintptr_t grads, uintptr_t workspace,
            size_t workspace_bytes, uintptr_t stream, double grad_scale, uintptr_t reduced, int reduction) {
@@ -187,458 +326,155 @@ PYBIND11_MODULE(_C, m) {
           if (n_grams < 0 || (n_grams > 0 && (!keys || !cols))) throw py::value_error("gram_ctc_fwd_bwd: bad gram table");
           if (reduction < E2E_REDUCE_NONE || reduction > E2E_REDUCE_MEAN || (reduction != E2E_REDUCE_NONE && !reduced))
             throw py::value_error("gram_ctc_fwd_bwd: bad reduction");
-          e2e_ctc_loss_opts o{grad_scale, ptr<void>(reduced), reduction, E2E_CHAINS_F64};
-          check(e2e_gram_ctc_fwd_bwd(ptr<const void>(x), dtype, input_is_logprobs ? 1 : 0, sB, sT, sV,
-                                     ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
-                                     ptr<const int64_t>(t_len), B, T, V, Smax, ptr<const int64_t>(keys),
-                                     ptr<const int32_t>(cols), n_grams, radix, max_order, ptr<void>(losses),
-                                     ptr<void>(grads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+          e2e_ctc_loss_opts o{grad_scale, to_c<void*>(reduced), reduction, E2E_CHAINS_F64};
+          check(forward(e2e_gram_ctc_fwd_bwd, x, dtype, input_is_logprobs, sB, sT, sV, targets, tgt_stride, x_len, t_len, B, T, V,
+                        Smax, keys, cols, n_grams, radix, max_order, losses, grads, workspace, workspace_bytes, stream, &o));
         },
-        py::arg("x"), py::arg("dtype"), py::arg("input_is_logprobs"), py::arg("sB"), py::arg("sT"), py::arg("sV"),
-        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
-        py::arg("V"), py::arg("Smax"), py::arg("keys"), py::arg("cols"), py::arg("n_grams"), py::arg("radix"),
-        py::arg("max_order"), py::arg("losses"), py::arg("grads"), py::arg("workspace"), py::arg("workspace_bytes"),
-        py::arg("stream"), py::arg("grad_scale") = 1.0, py::arg("reduced") = 0, py::arg("reduction") = E2E_REDUCE_NONE);
+        1.0, 0, E2E_REDUCE_NONE);
 
-  m.def("asg_max_labels", [] { return e2e_asg_max_labels(); });
-  m.def("asg_max_target_length", [] { return e2e_asg_max_target_length(); });
-  m.def("asg_workspace_bytes", [](int B, int T, int V, int Smax, int dtype) {
-    return e2e_asg_workspace_bytes(B, T, V, Smax, dtype);
-  });
-
-  m.def("asg_fwd_bwd",
+  b.query<e2e_asg_max_labels>("e2e_asg_max_labels");
+  b.query<e2e_asg_max_target_length>("e2e_asg_max_target_length");
+  b.query<e2e_asg_workspace_bytes>("e2e_asg_workspace_bytes");
+  b.sig<e2e_asg_fwd_bwd>("e2e_asg_fwd_bwd");
+  b.def("asg_fwd_bwd",
+        "x dtype sB sT sV transitions targets tgt_stride x_len t_len B T V Smax losses grads tgrads workspace workspace_bytes "
+        "stream grad_scale",
         [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t targets,
            int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, uintptr_t losses,
            uintptr_t grads, uintptr_t tgrads, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
            double grad_scale) {
           if (dtype != E2E_F32 && dtype != E2E_F64) throw py::value_error("asg_fwd_bwd: dtype must be F32 or F64");
           e2e_ctc_loss_opts o{grad_scale, nullptr, E2E_REDUCE_NONE, E2E_CHAINS_F64};
-          check(e2e_asg_fwd_bwd(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
-                                ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
-                                ptr<const int64_t>(t_len), B, T, V, Smax, ptr<void>(losses), ptr<void>(grads),
-                                ptr<void>(tgrads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
+          check(forward(e2e_asg_fwd_bwd, x, dtype, sB, sT, sV, transitions, targets, tgt_stride, x_len, t_len, B, T, V, Smax,
+                        losses, grads, tgrads, workspace, workspace_bytes, stream, &o));
         },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
-        py::arg("targets"), py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"),
-        py::arg("V"), py::arg("Smax"), py::arg("losses"), py::arg("grads"), py::arg("tgrads"), py::arg("workspace"),
-        py::arg("workspace_bytes"), py::arg("stream"), py::arg("grad_scale") = 1.0);
+        1.0);
+  b.query<e2e_asg_viterbi_workspace_bytes>("e2e_asg_viterbi_workspace_bytes");
+  b.call<e2e_asg_viterbi>("e2e_asg_viterbi",
+                          "x dtype sB sT sV transitions x_len B T V path pad_value scores collapsed lengths workspace "
+                          "workspace_bytes stream");
 
-  m.def("asg_viterbi_workspace_bytes", [](int B, int T, int V) { return e2e_asg_viterbi_workspace_bytes(B, T, V); });
+  // ---- Gram-CTC decoding ----
+  b.call<e2e_gram_ctc_greedy>("e2e_gram_ctc_greedy",
+                              "x dtype sB sT sV x_len B T V gram_ids gram_len max_order out out_len cols cols_len stream");
+  b.query<e2e_gram_beam_max_width>("e2e_gram_beam_max_width");
+  b.query<e2e_gram_beam_workspace_bytes>("e2e_gram_beam_workspace_bytes");
+  b.call<e2e_gram_ctc_beam_nbest>("e2e_gram_ctc_beam_nbest",
+                                  "lp dtype sB sT sV x_len B T V gram_ids gram_len max_order beam_width nbest out max_out "
+                                  "out_len n_hyp scores workspace workspace_bytes stream");
+  b.query<e2e_gram_beam_workspace_bytes_lm>("e2e_gram_beam_workspace_bytes_lm");
+  b.call<e2e_gram_ctc_beam_nbest_lm>("e2e_gram_ctc_beam_nbest_lm",
+                                     "lp dtype sB sT sV x_len B T V gram_ids gram_len max_order num_base_labels beam_width "
+                                     "space_id lm lmwt wip oov_penalty nbest out max_out out_len n_hyp scores counts workspace "
+                                     "workspace_bytes stream");
+  b.call_opts<e2e_gram_ctc_beam_nbest_opt, gram_beam_opts>("e2e_gram_ctc_beam_nbest_opt", "gram_ctc_beam_nbest_opt",
+        "lp dtype sB sT sV x_len B T V gram_ids gram_len max_order num_base_labels beam_width space_id lm lmwt wip oov_penalty "
+        "nbest out max_out out_len n_hyp scores counts workspace workspace_bytes stream opts", py::none());
+  b.query<e2e_gram_beam_stream_row_bytes>("e2e_gram_beam_stream_row_bytes");
+  b.query<e2e_gram_beam_stream_workspace_bytes>("e2e_gram_beam_stream_workspace_bytes");
+  b.call_opts<e2e_gram_ctc_beam_stream, gram_beam_opts>("e2e_gram_ctc_beam_stream", "gram_ctc_beam_stream",
+        "lp dtype sB sT sV chunk_len B T V gram_ids gram_len max_order num_base_labels beam_width scored space_id lm lmwt wip "
+        "oov_penalty state row_bytes max_frames nbest out max_out out_len n_hyp scores counts frames_done workspace "
+        "workspace_bytes stream opts", py::none());
 
-  m.def("asg_viterbi",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t x_len, int B,
-           int T, int V, uintptr_t path, int64_t pad_value, uintptr_t scores, uintptr_t collapsed, uintptr_t lengths,
-           uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_asg_viterbi(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
-                                ptr<const int64_t>(x_len), B, T, V, ptr<int64_t>(path), pad_value, ptr<double>(scores),
-                                ptr<int64_t>(collapsed), ptr<int64_t>(lengths), ptr<void>(workspace), workspace_bytes,
-                                ptr<void>(stream)));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
-        py::arg("x_len"), py::arg("B"), py::arg("T"), py::arg("V"), py::arg("path"), py::arg("pad_value"),
-        py::arg("scores"), py::arg("collapsed"), py::arg("lengths"), py::arg("workspace"), py::arg("workspace_bytes"),
-        py::arg("stream"));
+  // ---- ASG decoding ----
+  b.query<e2e_asg_beam_max_width>("e2e_asg_beam_max_width");
+  b.query<e2e_asg_beam_workspace_bytes>("e2e_asg_beam_workspace_bytes");
+  b.sig<e2e_asg_beam_nbest>("e2e_asg_beam_nbest");
+  b.call_opts<e2e_asg_beam_nbest_opt, asg_beam_opts>("e2e_asg_beam_nbest_opt", "asg_beam_nbest",
+        "x dtype sB sT sV transitions x_len B T V num_replabels beam_width space_id lm lmwt wip oov_penalty nbest out max_out "
+        "out_len n_hyp scores counts workspace workspace_bytes stream restrict_to_lexicon timesteps", false, (uintptr_t)0);
+  b.query<e2e_asg_beam_stream_row_bytes>("e2e_asg_beam_stream_row_bytes");
+  b.query<e2e_asg_beam_stream_workspace_bytes>("e2e_asg_beam_stream_workspace_bytes");
+  b.call_opts<e2e_asg_beam_stream, asg_beam_opts>("e2e_asg_beam_stream", "asg_beam_stream",
+        "x dtype sB sT sV transitions chunk_len B T V num_replabels beam_width space_id lm lmwt wip oov_penalty state row_bytes "
+        "max_frames nbest out max_out out_len n_hyp scores counts frames_done workspace workspace_bytes stream "
+        "restrict_to_lexicon timesteps", false, (uintptr_t)0);
 
-  m.def("gram_ctc_greedy",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
-           uintptr_t gram_ids, uintptr_t gram_len, int max_order, uintptr_t out, uintptr_t out_len, uintptr_t cols,
-           uintptr_t cols_len, uintptr_t stream) {
-          check(e2e_gram_ctc_greedy(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V,
-                                    ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
-                                    ptr<int64_t>(out), ptr<int64_t>(out_len), ptr<int64_t>(cols), ptr<int64_t>(cols_len),
-                                    ptr<void>(stream)));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"), py::arg("out"),
-        py::arg("out_len"), py::arg("cols"), py::arg("cols_len"), py::arg("stream"));
-
-  m.def("gram_beam_max_width", [](int V, int max_order) { return e2e_gram_beam_max_width(V, max_order); });
-  m.def("gram_beam_workspace_bytes", [](int B, int T, int V, int max_order, int beam_width) {
-    return e2e_gram_beam_workspace_bytes(B, T, V, max_order, beam_width);
-  });
-
-  m.def("gram_ctc_beam_nbest",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
-           uintptr_t gram_ids, uintptr_t gram_len, int max_order, int beam_width, int nbest, uintptr_t out,
-           int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t workspace,
-           size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_gram_ctc_beam_nbest(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V,
-                                        ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
-                                        beam_width, nbest, ptr<int64_t>(out), max_out, ptr<int64_t>(out_len),
-                                        ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<void>(workspace), workspace_bytes,
-                                        ptr<void>(stream)));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"),
-        py::arg("beam_width"), py::arg("nbest"), py::arg("out"), py::arg("max_out"), py::arg("out_len"),
-        py::arg("n_hyp"), py::arg("scores"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
-
-  m.def("gram_beam_workspace_bytes_lm", [](int B, int T, int V, int max_order, int beam_width, bool with_lm) {
-    return e2e_gram_beam_workspace_bytes_lm(B, T, V, max_order, beam_width, with_lm ? 1 : 0);
-  });
-
-  m.def("gram_ctc_beam_nbest_lm",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
-           uintptr_t gram_ids, uintptr_t gram_len, int max_order, int num_base_labels, int beam_width, int space_id,
-           uintptr_t lm, double lmwt, double wip, double oov_penalty, int nbest, uintptr_t out, int64_t max_out,
-           uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t workspace,
-           size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_gram_ctc_beam_nbest_lm(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V,
-                                           ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
-                                           num_base_labels, beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip,
-                                           oov_penalty, nbest, ptr<int64_t>(out), max_out, ptr<int64_t>(out_len),
-                                           ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<int32_t>(counts),
-                                           ptr<void>(workspace), workspace_bytes, ptr<void>(stream)));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"),
-        py::arg("num_base_labels"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"), py::arg("lmwt"),
-        py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"), py::arg("out"), py::arg("max_out"), py::arg("out_len"),
-        py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("workspace"), py::arg("workspace_bytes"),
-        py::arg("stream"));
-
-  // opts: None passes NULL; else (restrict_to_lexicon, timesteps) -- zeros included, to tell the two apart
-  m.def("gram_ctc_beam_nbest_opt",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V,
-           uintptr_t gram_ids, uintptr_t gram_len, int max_order, int num_base_labels, int beam_width, int space_id,
-           uintptr_t lm, double lmwt, double wip, double oov_penalty, int nbest, uintptr_t out, int64_t max_out,
-           uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t workspace,
-           size_t workspace_bytes, uintptr_t stream, py::object opts) {
-          e2e_gram_beam_opts o{0, nullptr};
-          if (!opts.is_none()) {
-            auto t = opts.cast<std::pair<bool, uintptr_t>>();
-            o.restrict_to_lexicon = t.first ? 1 : 0;
-            o.timesteps = ptr<int64_t>(t.second);
-          }
-          check(e2e_gram_ctc_beam_nbest_opt(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V,
-                                            ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
-                                            num_base_labels, beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip,
-                                            oov_penalty, nbest, ptr<int64_t>(out), max_out, ptr<int64_t>(out_len),
-                                            ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<int32_t>(counts),
-                                            ptr<void>(workspace), workspace_bytes, ptr<void>(stream),
-                                            opts.is_none() ? nullptr : &o));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"),
-        py::arg("num_base_labels"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"), py::arg("lmwt"),
-        py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"), py::arg("out"), py::arg("max_out"), py::arg("out_len"),
-        py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("workspace"), py::arg("workspace_bytes"),
-        py::arg("stream"), py::arg("opts") = py::none());
-
-  m.def("gram_beam_stream_row_bytes", [](int max_frames, int V, int max_order, int beam_width, bool scored, bool with_lm) {
-    return e2e_gram_beam_stream_row_bytes(max_frames, V, max_order, beam_width, scored ? 1 : 0, with_lm ? 1 : 0);
-  });
-  m.def("gram_beam_stream_workspace_bytes", [](int B, int V, int max_order, int beam_width, bool scored, bool with_lm) {
-    return e2e_gram_beam_stream_workspace_bytes(B, V, max_order, beam_width, scored ? 1 : 0, with_lm ? 1 : 0);
-  });
-
-  // opts: None passes NULL; else (restrict_to_lexicon, timesteps), as gram_ctc_beam_nbest_opt takes them
-  m.def("gram_ctc_beam_stream",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t chunk_len, int B, int T, int V,
-           uintptr_t gram_ids, uintptr_t gram_len, int max_order, int num_base_labels, int beam_width, bool scored,
-           int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, uintptr_t state, size_t row_bytes,
-           int max_frames, int nbest, uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores,
-           uintptr_t counts, uintptr_t frames_done, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
-           py::object opts) {
-          e2e_gram_beam_opts o{0, nullptr};
-          if (!opts.is_none()) {
-            auto t = opts.cast<std::pair<bool, uintptr_t>>();
-            o.restrict_to_lexicon = t.first ? 1 : 0;
-            o.timesteps = ptr<int64_t>(t.second);
-          }
-          check(e2e_gram_ctc_beam_stream(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(chunk_len), B, T, V,
-                                         ptr<const int32_t>(gram_ids), ptr<const int32_t>(gram_len), max_order,
-                                         num_base_labels, beam_width, scored ? 1 : 0, space_id, ptr<const e2e_lm>(lm), lmwt,
-                                         wip, oov_penalty, ptr<void>(state), row_bytes, max_frames, nbest,
-                                         ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
-                                         ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(frames_done),
-                                         ptr<void>(workspace), workspace_bytes, ptr<void>(stream),
-                                         opts.is_none() ? nullptr : &o));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("chunk_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("gram_ids"), py::arg("gram_len"), py::arg("max_order"),
-        py::arg("num_base_labels"), py::arg("beam_width"), py::arg("scored"), py::arg("space_id"), py::arg("lm"),
-        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"), py::arg("row_bytes"),
-        py::arg("max_frames"), py::arg("nbest"), py::arg("out"), py::arg("max_out"), py::arg("out_len"), py::arg("n_hyp"),
-        py::arg("scores"), py::arg("counts"), py::arg("frames_done"), py::arg("workspace"), py::arg("workspace_bytes"),
-        py::arg("stream"), py::arg("opts") = py::none());
-
-  m.def("asg_beam_max_width", [](int V) { return e2e_asg_beam_max_width(V); });
-  m.def("asg_beam_workspace_bytes", [](int B, int T, int V, int beam_width, bool with_lm) {
-    return e2e_asg_beam_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0);
-  });
-
-  m.def("asg_beam_nbest",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t x_len, int B,
-           int T, int V, int num_replabels, int beam_width, int space_id, uintptr_t lm, double lmwt, double wip,
-           double oov_penalty, int nbest, uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp,
-           uintptr_t scores, uintptr_t counts, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream,
-           bool restrict_to_lexicon, uintptr_t timesteps) {
-          e2e_asg_beam_opts o{restrict_to_lexicon ? 1 : 0, ptr<int64_t>(timesteps)};
-          check(e2e_asg_beam_nbest_opt(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
-                                       ptr<const int64_t>(x_len), B, T, V, num_replabels, beam_width, space_id,
-                                       ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, nbest, ptr<int64_t>(out), max_out,
-                                       ptr<int64_t>(out_len), ptr<int64_t>(n_hyp), ptr<double>(scores),
-                                       ptr<int32_t>(counts), ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
-        py::arg("x_len"), py::arg("B"), py::arg("T"), py::arg("V"), py::arg("num_replabels"), py::arg("beam_width"),
-        py::arg("space_id"), py::arg("lm"), py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"),
-        py::arg("out"), py::arg("max_out"), py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"),
-        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon") = false,
-        py::arg("timesteps") = (uintptr_t)0);
-
-  m.def("asg_beam_stream_row_bytes", [](int max_frames, int V, int beam_width, bool with_lm) {
-    return e2e_asg_beam_stream_row_bytes(max_frames, V, beam_width, with_lm ? 1 : 0);
-  });
-  m.def("asg_beam_stream_workspace_bytes", [](int B, int V, int beam_width, bool with_lm) {
-    return e2e_asg_beam_stream_workspace_bytes(B, V, beam_width, with_lm ? 1 : 0);
-  });
-
-  m.def("asg_beam_stream",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t transitions, uintptr_t chunk_len, int B,
-           int T, int V, int num_replabels, int beam_width, int space_id, uintptr_t lm, double lmwt, double wip,
-           double oov_penalty, uintptr_t state, size_t row_bytes, int max_frames, int nbest, uintptr_t out,
-           int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t frames_done,
-           uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon, uintptr_t timesteps) {
-          e2e_asg_beam_opts o{restrict_to_lexicon ? 1 : 0, ptr<int64_t>(timesteps)};
-          check(e2e_asg_beam_stream(ptr<const void>(x), dtype, sB, sT, sV, ptr<const void>(transitions),
-                                    ptr<const int64_t>(chunk_len), B, T, V, num_replabels, beam_width, space_id,
-                                    ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, ptr<void>(state), row_bytes, max_frames,
-                                    nbest, ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
-                                    ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(frames_done),
-                                    ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("transitions"),
-        py::arg("chunk_len"), py::arg("B"), py::arg("T"), py::arg("V"), py::arg("num_replabels"), py::arg("beam_width"),
-        py::arg("space_id"), py::arg("lm"), py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"),
-        py::arg("row_bytes"), py::arg("max_frames"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
-        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("frames_done"),
-        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon") = false,
-        py::arg("timesteps") = (uintptr_t)0);
-
-  m.def("ctc_scale_grads",
-        [](uintptr_t grads, int dtype, uintptr_t scale, int B, int64_t row_elems, uintptr_t stream) {
-          check(e2e_ctc_scale_grads(ptr<void>(grads), dtype, ptr<const void>(scale), B, row_elems, ptr<void>(stream)));
-        },
-        py::arg("grads"), py::arg("dtype"), py::arg("scale"), py::arg("B"), py::arg("row_elems"), py::arg("stream"));
-
-  m.def("ctc_greedy",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
-           uintptr_t out, uintptr_t out_len, uintptr_t stream) {
-          check(e2e_ctc_greedy(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
-                               ptr<int64_t>(out), ptr<int64_t>(out_len), ptr<void>(stream)));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("out"), py::arg("out_len"), py::arg("stream"));
-
-  m.def("ctc_beam_workspace_bytes",
-        [](int B, int T, int V, int beam_width) { return e2e_ctc_beam_workspace_bytes(B, T, V, beam_width); });
-  m.def("ctc_beam_workspace_bytes_lm", [](int B, int T, int V, int beam_width, bool with_lm) {
-    return e2e_ctc_beam_workspace_bytes_lm(B, T, V, beam_width, with_lm ? 1 : 0);
-  });
-
-  m.def("ctc_beam_max_width", [](int V, bool with_lm) { return e2e_ctc_beam_max_width(V, with_lm ? 1 : 0); });
-
-  m.def("ctc_beam",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
-           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, uintptr_t out,
-           int64_t max_out, uintptr_t out_len, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_ctc_beam(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
-                             beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, ptr<int64_t>(out),
-                             max_out, ptr<int64_t>(out_len), ptr<void>(workspace), workspace_bytes, ptr<void>(stream)));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
-        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("out"), py::arg("max_out"),
-        py::arg("out_len"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
-
-  m.def("ctc_beam_nbest_workspace_bytes", [](int B, int T, int V, int beam_width, bool with_lm, bool with_timesteps) {
-    return e2e_ctc_beam_nbest_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0, with_timesteps ? 1 : 0);
-  });
-
-  m.def("ctc_beam_nbest",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
-           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, int nbest,
-           uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts,
-           uintptr_t timesteps, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon) {
-          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
-          check(e2e_ctc_beam_nbest_opt(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
-                                       beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, nbest,
-                                       ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
-                                       ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(timesteps),
-                                       ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
-        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
-        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
-        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon") = false);
-
-  m.def("ctc_beam_stream_row_bytes", [](int max_frames, int V, int beam_width, bool with_lm, bool with_timesteps) {
-    return e2e_ctc_beam_stream_row_bytes(max_frames, V, beam_width, with_lm ? 1 : 0, with_timesteps ? 1 : 0);
-  });
-  m.def("ctc_beam_stream_workspace_bytes", [](int B, int V, int beam_width, bool with_lm) {
-    return e2e_ctc_beam_stream_workspace_bytes(B, V, beam_width, with_lm ? 1 : 0);
-  });
-
-  m.def("ctc_beam_stream",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t chunk_len, int B, int T, int V, int blank,
-           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, uintptr_t state,
-           size_t row_bytes, int max_frames, bool with_timesteps, int nbest, uintptr_t out, int64_t max_out,
-           uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t timesteps,
-           uintptr_t frames_done, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon) {
-          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
-          check(e2e_ctc_beam_stream(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(chunk_len), B, T, V, blank,
-                                    beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, ptr<void>(state),
-                                    row_bytes, max_frames, with_timesteps ? 1 : 0, nbest, ptr<int64_t>(out), max_out,
-                                    ptr<int64_t>(out_len), ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<int32_t>(counts),
-                                    ptr<int64_t>(timesteps), ptr<int64_t>(frames_done), ptr<void>(workspace),
-                                    workspace_bytes, ptr<void>(stream), &o));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("chunk_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
-        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"), py::arg("row_bytes"),
-        py::arg("max_frames"), py::arg("with_timesteps"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
-        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
-        py::arg("frames_done"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"),
-        py::arg("restrict_to_lexicon") = false);
+  // ---- CTC decoding ----
+  b.call<e2e_ctc_greedy>("e2e_ctc_greedy", "x dtype sB sT sV x_len B T V blank out out_len stream");
+  b.query<e2e_ctc_beam_workspace_bytes>("e2e_ctc_beam_workspace_bytes");
+  b.query<e2e_ctc_beam_workspace_bytes_lm>("e2e_ctc_beam_workspace_bytes_lm");
+  b.query<e2e_ctc_beam_max_width>("e2e_ctc_beam_max_width");
+  b.call<e2e_ctc_beam>("e2e_ctc_beam",
+                       "lp dtype sB sT sV x_len B T V blank beam_width space_id lm lmwt wip oov_penalty out max_out out_len "
+                       "workspace workspace_bytes stream");
+  b.query<e2e_ctc_beam_nbest_workspace_bytes>("e2e_ctc_beam_nbest_workspace_bytes");
+  b.sig<e2e_ctc_beam_nbest>("e2e_ctc_beam_nbest");
+  b.call_opts<e2e_ctc_beam_nbest_opt, ctc_beam_opts>("e2e_ctc_beam_nbest_opt", "ctc_beam_nbest",
+        "lp dtype sB sT sV x_len B T V blank beam_width space_id lm lmwt wip oov_penalty nbest out max_out out_len n_hyp scores "
+        "counts timesteps workspace workspace_bytes stream restrict_to_lexicon", false);
+  b.query<e2e_ctc_beam_stream_row_bytes>("e2e_ctc_beam_stream_row_bytes");
+  b.query<e2e_ctc_beam_stream_workspace_bytes>("e2e_ctc_beam_stream_workspace_bytes");
+  b.call_opts<e2e_ctc_beam_stream, ctc_beam_opts>("e2e_ctc_beam_stream", "ctc_beam_stream",
+        "lp dtype sB sT sV chunk_len B T V blank beam_width space_id lm lmwt wip oov_penalty state row_bytes max_frames "
+        "with_timesteps nbest out max_out out_len n_hyp scores counts timesteps frames_done workspace workspace_bytes stream "
+        "restrict_to_lexicon", false);
 
   // per-frame label pruning: the selection alone, and the pruned searches (cutoff_top_n, cutoff_prob behind the unpruned
   // calls' arguments)
-  m.def("ctc_label_cut_max", [] { return e2e_ctc_label_cut_max(); });
-  m.def("ctc_label_cut_workspace_bytes",
-        [](int B, int T, int V, int cutoff_top_n) { return e2e_ctc_label_cut_workspace_bytes(B, T, V, cutoff_top_n); });
-  m.def("ctc_label_cut",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
-           int cutoff_top_n, double cutoff_prob, uintptr_t ids, uintptr_t n, uintptr_t workspace, size_t workspace_bytes,
-           uintptr_t stream) {
-          check(e2e_ctc_label_cut(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
-                                  cutoff_top_n, cutoff_prob, ptr<int32_t>(ids), ptr<int32_t>(n), ptr<void>(workspace),
-                                  workspace_bytes, ptr<void>(stream)));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("cutoff_top_n"), py::arg("cutoff_prob"), py::arg("ids"),
-        py::arg("n"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
-  m.def("ctc_beam_cut_max_width", [](int V, bool with_lm) { return e2e_ctc_beam_cut_max_width(V, with_lm ? 1 : 0); });
-  m.def("ctc_beam_cut_workspace_bytes",
-        [](int B, int T, int V, int beam_width, bool with_lm, bool with_timesteps, int cutoff_top_n) {
-          return e2e_ctc_beam_cut_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0, with_timesteps ? 1 : 0, cutoff_top_n);
-        });
-  m.def("ctc_beam_cut_stream_workspace_bytes", [](int B, int T, int V, int beam_width, bool with_lm, int cutoff_top_n) {
-    return e2e_ctc_beam_cut_stream_workspace_bytes(B, T, V, beam_width, with_lm ? 1 : 0, cutoff_top_n);
-  });
-  m.def("ctc_beam_nbest_cut",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t x_len, int B, int T, int V, int blank,
-           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, int nbest,
-           uintptr_t out, int64_t max_out, uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts,
-           uintptr_t timesteps, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon,
-           int cutoff_top_n, double cutoff_prob) {
-          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
-          check(e2e_ctc_beam_nbest_cut(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(x_len), B, T, V, blank,
-                                       beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, nbest,
-                                       ptr<int64_t>(out), max_out, ptr<int64_t>(out_len), ptr<int64_t>(n_hyp),
-                                       ptr<double>(scores), ptr<int32_t>(counts), ptr<int64_t>(timesteps),
-                                       ptr<void>(workspace), workspace_bytes, ptr<void>(stream), &o, cutoff_top_n, cutoff_prob));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("x_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
-        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
-        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
-        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"), py::arg("restrict_to_lexicon"),
-        py::arg("cutoff_top_n"), py::arg("cutoff_prob"));
-  m.def("ctc_beam_stream_cut",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t chunk_len, int B, int T, int V, int blank,
-           int beam_width, int space_id, uintptr_t lm, double lmwt, double wip, double oov_penalty, uintptr_t state,
-           size_t row_bytes, int max_frames, bool with_timesteps, int nbest, uintptr_t out, int64_t max_out,
-           uintptr_t out_len, uintptr_t n_hyp, uintptr_t scores, uintptr_t counts, uintptr_t timesteps,
-           uintptr_t frames_done, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream, bool restrict_to_lexicon,
-           int cutoff_top_n, double cutoff_prob) {
-          e2e_ctc_beam_opts o{restrict_to_lexicon ? 1 : 0};
-          check(e2e_ctc_beam_stream_cut(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(chunk_len), B, T, V, blank,
-                                        beam_width, space_id, ptr<const e2e_lm>(lm), lmwt, wip, oov_penalty, ptr<void>(state),
-                                        row_bytes, max_frames, with_timesteps ? 1 : 0, nbest, ptr<int64_t>(out), max_out,
-                                        ptr<int64_t>(out_len), ptr<int64_t>(n_hyp), ptr<double>(scores), ptr<int32_t>(counts),
-                                        ptr<int64_t>(timesteps), ptr<int64_t>(frames_done), ptr<void>(workspace),
-                                        workspace_bytes, ptr<void>(stream), &o, cutoff_top_n, cutoff_prob));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("chunk_len"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("blank"), py::arg("beam_width"), py::arg("space_id"), py::arg("lm"),
-        py::arg("lmwt"), py::arg("wip"), py::arg("oov_penalty"), py::arg("state"), py::arg("row_bytes"),
-        py::arg("max_frames"), py::arg("with_timesteps"), py::arg("nbest"), py::arg("out"), py::arg("max_out"),
-        py::arg("out_len"), py::arg("n_hyp"), py::arg("scores"), py::arg("counts"), py::arg("timesteps"),
-        py::arg("frames_done"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"),
-        py::arg("restrict_to_lexicon"), py::arg("cutoff_top_n"), py::arg("cutoff_prob"));
+  b.query<e2e_ctc_label_cut_max>("e2e_ctc_label_cut_max");
+  b.query<e2e_ctc_label_cut_workspace_bytes>("e2e_ctc_label_cut_workspace_bytes");
+  b.call<e2e_ctc_label_cut>("e2e_ctc_label_cut",
+                            "lp dtype sB sT sV x_len B T V blank cutoff_top_n cutoff_prob ids n workspace workspace_bytes stream");
+  b.query<e2e_ctc_beam_cut_max_width>("e2e_ctc_beam_cut_max_width");
+  b.query<e2e_ctc_beam_cut_workspace_bytes>("e2e_ctc_beam_cut_workspace_bytes");
+  b.query<e2e_ctc_beam_cut_stream_workspace_bytes>("e2e_ctc_beam_cut_stream_workspace_bytes");
+  b.call_opts<e2e_ctc_beam_nbest_cut, ctc_beam_opts>("e2e_ctc_beam_nbest_cut", "ctc_beam_nbest_cut",
+        "lp dtype sB sT sV x_len B T V blank beam_width space_id lm lmwt wip oov_penalty nbest out max_out out_len n_hyp scores "
+        "counts timesteps workspace workspace_bytes stream restrict_to_lexicon cutoff_top_n cutoff_prob");
+  b.call_opts<e2e_ctc_beam_stream_cut, ctc_beam_opts>("e2e_ctc_beam_stream_cut", "ctc_beam_stream_cut",
+        "lp dtype sB sT sV chunk_len B T V blank beam_width space_id lm lmwt wip oov_penalty state row_bytes max_frames "
+        "with_timesteps nbest out max_out out_len n_hyp scores counts timesteps frames_done workspace workspace_bytes stream "
+        "restrict_to_lexicon cutoff_top_n cutoff_prob");
 
-  m.def("ctc_align_workspace_bytes",
-        [](int B, int T, int V, int Smax, bool is_ctc) { return e2e_ctc_align_workspace_bytes(B, T, V, Smax, is_ctc ? 1 : 0); });
+  // ---- alignment, word-segmented CTC ----
+  b.query<e2e_ctc_align_workspace_bytes>("e2e_ctc_align_workspace_bytes");
+  b.call<e2e_ctc_align>("e2e_ctc_align",
+                        "lp dtype sB sT sV targets tgt_stride x_len t_len B T V Smax blank is_ctc out pad_value workspace "
+                        "workspace_bytes stream");
+  b.query<e2e_ctc_wordseg_table_elems>("e2e_ctc_wordseg_table_elems");
+  b.query<e2e_ctc_wordseg_workspace_bytes>("e2e_ctc_wordseg_workspace_bytes");
+  b.call<e2e_ctc_wordseg_plan>("e2e_ctc_wordseg_plan",
+                               "x dtype sB sT sV align targets tgt_stride x_len t_len B T V Smax blank space min_word_length "
+                               "table table_elems pool workspace workspace_bytes stream");
+  b.call<e2e_ctc_wordseg_gather>("e2e_ctc_wordseg_gather",
+                                 "x dtype sB sT sV targets tgt_stride x_len t_len B T V Smax table pool idx n_idx L S xg tg xlg "
+                                 "tlg stream");
+  b.call<e2e_ctc_wordseg_finish>("e2e_ctc_wordseg_finish",
+                                 "x dtype sB sT sV align B T V table g_grads g_losses g_idx n_idx L last losses grads workspace "
+                                 "workspace_bytes stream");
 
-  m.def("ctc_align",
-        [](uintptr_t lp, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets, int64_t tgt_stride,
-           uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, int blank, bool is_ctc, uintptr_t out,
-           int64_t pad_value, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_ctc_align(ptr<const void>(lp), dtype, sB, sT, sV, ptr<const int64_t>(targets), tgt_stride,
-                              ptr<const int64_t>(x_len), ptr<const int64_t>(t_len), B, T, V, Smax, blank,
-                              is_ctc ? 1 : 0, ptr<int64_t>(out), pad_value, ptr<void>(workspace), workspace_bytes,
-                              ptr<void>(stream)));
-        },
-        py::arg("lp"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("targets"),
-        py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"), py::arg("V"),
-        py::arg("Smax"), py::arg("blank"), py::arg("is_ctc"), py::arg("out"), py::arg("pad_value"),
-        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
+  // ---- the language model: the class below forwards to these ----
+  b.sig<e2e_lm_load_arpa>("e2e_lm_load_arpa");
+  b.sig<e2e_lm_load_words>("e2e_lm_load_words");
+  b.sig<e2e_lm_load_transcriptions>("e2e_lm_load_transcriptions");
+  b.sig<e2e_lm_free>("e2e_lm_free");
+  b.sig<e2e_lm_order>("e2e_lm_order");
+  b.sig<e2e_lm_device>("e2e_lm_device");
+  b.sig<e2e_lm_word_index>("e2e_lm_word_index");
+  b.sig<e2e_lm_score>("e2e_lm_score");
+  b.sig<e2e_lm_enable_lexicon>("e2e_lm_enable_lexicon");
+  b.sig<e2e_lm_has_lexicon>("e2e_lm_has_lexicon");
+  b.sig<e2e_lm_spelling_class>("e2e_lm_spelling_class");
+  b.sig<e2e_lm_is_transcribed>("e2e_lm_is_transcribed");
+  b.sig<e2e_lm_transcriptions_dropped>("e2e_lm_transcriptions_dropped");
+  b.sig<e2e_lm_transcribe>("e2e_lm_transcribe");
+  b.sig<e2e_lm_word_string>("e2e_lm_word_string");
 
-  m.attr("WORDSEG_HEADER") = E2E_WORDSEG_HEADER;
-  m.attr("WORDSEG_WHOLE") = E2E_WORDSEG_WHOLE;
-  m.attr("WORDSEG_FRAME") = E2E_WORDSEG_FRAME;
-  m.attr("WORDSEG_CHUNK") = E2E_WORDSEG_CHUNK;
-  m.def("ctc_wordseg_table_elems", [](int B, int T) { return e2e_ctc_wordseg_table_elems(B, T); });
-  m.def("ctc_wordseg_workspace_bytes", [](int B, int T) { return e2e_ctc_wordseg_workspace_bytes(B, T); });
-
-  m.def("ctc_wordseg_plan",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t align, uintptr_t targets,
-           int64_t tgt_stride, uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, int blank, int space,
-           int min_word_length, uintptr_t table, size_t table_elems, uintptr_t pool, uintptr_t workspace,
-           size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_ctc_wordseg_plan(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(align),
-                                     ptr<const int64_t>(targets), tgt_stride, ptr<const int64_t>(x_len),
-                                     ptr<const int64_t>(t_len), B, T, V, Smax, blank, space, min_word_length,
-                                     ptr<int32_t>(table), table_elems, ptr<int64_t>(pool), ptr<void>(workspace),
-                                     workspace_bytes, ptr<void>(stream)));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("align"), py::arg("targets"),
-        py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"), py::arg("V"),
-        py::arg("Smax"), py::arg("blank"), py::arg("space"), py::arg("min_word_length"), py::arg("table"),
-        py::arg("table_elems"), py::arg("pool"), py::arg("workspace"), py::arg("workspace_bytes"), py::arg("stream"));
-
-  m.def("ctc_wordseg_gather",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t targets, int64_t tgt_stride,
-           uintptr_t x_len, uintptr_t t_len, int B, int T, int V, int Smax, uintptr_t table, uintptr_t pool,
-           uintptr_t idx, int n_idx, int L, int S, uintptr_t xg, uintptr_t tg, uintptr_t xlg, uintptr_t tlg,
-           uintptr_t stream) {
-          check(e2e_ctc_wordseg_gather(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(targets), tgt_stride,
-                                       ptr<const int64_t>(x_len), ptr<const int64_t>(t_len), B, T, V, Smax,
-                                       ptr<const int32_t>(table), ptr<const int64_t>(pool), ptr<const int32_t>(idx),
-                                       n_idx, L, S, ptr<void>(xg), ptr<int64_t>(tg), ptr<int64_t>(xlg),
-                                       ptr<int64_t>(tlg), ptr<void>(stream)));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("targets"),
-        py::arg("tgt_stride"), py::arg("x_len"), py::arg("t_len"), py::arg("B"), py::arg("T"), py::arg("V"),
-        py::arg("Smax"), py::arg("table"), py::arg("pool"), py::arg("idx"), py::arg("n_idx"), py::arg("L"), py::arg("S"),
-        py::arg("xg"), py::arg("tg"), py::arg("xlg"), py::arg("tlg"), py::arg("stream"));
-
-  m.def("ctc_wordseg_finish",
-        [](uintptr_t x, int dtype, int64_t sB, int64_t sT, int64_t sV, uintptr_t align, int B, int T, int V,
-           uintptr_t table, uintptr_t g_grads, uintptr_t g_losses, uintptr_t g_idx, int n_idx, int L, bool last,
-           uintptr_t losses, uintptr_t grads, uintptr_t workspace, size_t workspace_bytes, uintptr_t stream) {
-          check(e2e_ctc_wordseg_finish(ptr<const void>(x), dtype, sB, sT, sV, ptr<const int64_t>(align), B, T, V,
-                                       ptr<const int32_t>(table), ptr<const void>(g_grads), ptr<const void>(g_losses),
-                                       ptr<const int32_t>(g_idx), n_idx, L, last ? 1 : 0, ptr<void>(losses),
-                                       ptr<void>(grads), ptr<void>(workspace), workspace_bytes, ptr<void>(stream)));
-        },
-        py::arg("x"), py::arg("dtype"), py::arg("sB"), py::arg("sT"), py::arg("sV"), py::arg("align"), py::arg("B"),
-        py::arg("T"), py::arg("V"), py::arg("table"), py::arg("g_grads"), py::arg("g_losses"), py::arg("g_idx"),
-        py::arg("n_idx"), py::arg("L"), py::arg("last"), py::arg("losses"), py::arg("grads"), py::arg("workspace"),
-        py::arg("workspace_bytes"), py::arg("stream"));
+  // ---- the diagnostics (include/e2e_ctc_debug.h): reached through end2end_amd._lib only ----
+  b.sig<e2e_debug_stream_copy>("e2e_debug_stream_copy");
+  b.sig<e2e_debug_occupy>("e2e_debug_occupy");
+  b.sig<e2e_debug_loss_route>("e2e_debug_loss_route");
+  b.sig<e2e_debug_chain_lean_input>("e2e_debug_chain_lean_input");
+  b.sig<e2e_debug_fast_state>("e2e_debug_fast_state");
+  b.sig<e2e_debug_fast_redo_failures>("e2e_debug_fast_redo_failures");
+  b.sig<e2e_debug_gram_redo_flags>("e2e_debug_gram_redo_flags");
+  b.sig<e2e_debug_noblank_redo_flags>("e2e_debug_noblank_redo_flags");
+  b.sig<e2e_debug_flagged_phases>("e2e_debug_flagged_phases");
+  b.sig<e2e_debug_flagged_counters>("e2e_debug_flagged_counters");
+  b.sig<e2e_debug_band_misses>("e2e_debug_band_misses");
+  b.sig<e2e_debug_segment_band>("e2e_debug_segment_band");
 
   py::class_<LanguageModel>(m, "LanguageModel")
       .def(py::init<const std::string&, const std::vector<std::string>&, bool>(), py::arg("path"), py::arg("labels"),

@@ -86,10 +86,7 @@ def c_abi_loss(x, targets, x_len, t_len, blank=0, logprobs=True, algo=_lib.ALGO_
 
 def loss_route(dtype_code, algo, B, T, V, Smax, chains=0, sB=None, sT=None, sV=1, x=256, grads=256):
     """e2e_debug_loss_route (include/e2e_ctc_debug.h); by default for contiguous, aligned tensors.  Needs no GPU."""
-    import ctypes
     L = _lib.load()
-    L.e2e_debug_loss_route.restype = ctypes.c_int
-    L.e2e_debug_loss_route.argtypes = [ctypes.c_int] * 7 + [ctypes.c_longlong] * 3 + [ctypes.c_void_p] * 2
     sT = V * sV if sT is None else sT
     sB = T * sT if sB is None else sB
     return L.e2e_debug_loss_route(dtype_code, algo, B, T, V, Smax, chains, sB, sT, sV, x, grads)

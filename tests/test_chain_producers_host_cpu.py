@@ -3,15 +3,12 @@
 offsets to an utterance's base address and multiplies a row number by four times the row stride in 24 bits, so it is only for
 shapes on which that arithmetic cannot wrap; a view whose T * sT passes 2^31 elements cannot be allocated in a test, so the
 rule is checked here, against its statement, on both sides of each bound."""
-import ctypes
 
 from end2end_amd import _lib
 
 
 def lean(dtype, T, V, sT, sV=1):
     L = _lib.load()
-    L.e2e_debug_chain_lean_input.restype = ctypes.c_int
-    L.e2e_debug_chain_lean_input.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64]
     return L.e2e_debug_chain_lean_input(dtype, T, V, sT, sV)
 
 

@@ -29,7 +29,6 @@ V = 29
 
 def fast_flags(keep, B, T):
     L = _lib.load()
-    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     flags, logz = (ctypes.c_int * B)(), (ctypes.c_double * (2 * B))()
     assert L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], flags, logz) == 0
     return np.array(list(flags))
@@ -37,7 +36,6 @@ def fast_flags(keep, B, T):
 
 def band_misses(keep, B, T):
     L = _lib.load()
-    L.e2e_debug_band_misses.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     n = ctypes.c_int(-1)
     assert L.e2e_debug_band_misses(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], ctypes.byref(n)) == 0
     return n.value
@@ -185,7 +183,6 @@ def test_a_window_that_cannot_fit_is_redone_in_f64():
     assert flags[0] & 8 and flags[1] == 0, flags
     assert band_misses(keep, 2, T) >= r["misses"]
     L = _lib.load()
-    L.e2e_debug_flagged_counters.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     to, fr = ctypes.c_int(-1), ctypes.c_int(-1)
     assert L.e2e_debug_flagged_counters(keep["workspace"].data_ptr(), 2, T, V, S, ctypes.byref(to), ctypes.byref(fr)) == 0
     assert to.value == 0, "%d bounded waits of the flagged launch ran out" % to.value

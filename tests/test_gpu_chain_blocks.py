@@ -54,7 +54,6 @@ def log_softmax(x):
 
 def fast_flags(keep, B, T, V):
     L = _lib.load()
-    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     flags, logz = (ctypes.c_int * B)(), (ctypes.c_double * (2 * B))()
     assert L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], flags, logz) == 0
     return list(flags)

@@ -155,7 +155,6 @@ def run(c, algo, raw_targets=False):
     la, ga = U.c_abi_loss(device_logits(c), c["tg"], c["xl"], c["tl"], c["blank"], c["logprobs"], algo, keep=keep, **pad)
     assert keep["Smax"] == WIDTH
     L = _lib.load()
-    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     flags, logz = (ctypes.c_int * B)(), (ctypes.c_double * (2 * B))()
     assert L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], flags, logz) == 0
     route = keep["route"]

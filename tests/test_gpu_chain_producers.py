@@ -204,7 +204,6 @@ def run(c, algo):
                           width=c["width"], padding=-1)
     assert keep["Smax"] == c["width"]
     L = _lib.load()
-    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     flags, logz = (ctypes.c_int * B)(), (ctypes.c_double * (2 * B))()
     assert L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], flags, logz) == 0
     route, pairs = keep["route"], 2 if c["width"] == 64 else 4

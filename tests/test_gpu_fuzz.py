@@ -362,8 +362,6 @@ def test_flagged_batch_is_right_while_another_stream_holds_the_cus(lds):
     L = _lib.load()
     if not hasattr(L, "e2e_debug_occupy"):
         pytest.skip("library without e2e_debug_occupy")
-    L.e2e_debug_occupy.restype = ctypes.c_int
-    L.e2e_debug_occupy.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p]
     d = U.dev()
     from test_gpu_regimes import aligned
     rng = np.random.default_rng(77)
@@ -397,7 +395,6 @@ def test_flagged_batch_is_right_while_another_stream_holds_the_cus(lds):
             U.assert_same(la, l_o, 1e-4, 2e-5, "losses (rep %d)" % rep)
             U.assert_same(ga, g_o, 1e-4, 2e-6, "grads (rep %d)" % rep)
             to, fr = ctypes.c_int(-1), ctypes.c_int(-1)
-            L.e2e_debug_flagged_counters.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
             L.e2e_debug_flagged_counters(keep["workspace"].data_ptr(), 12, 1000, 29, 200, ctypes.byref(to), ctypes.byref(fr))
             outcomes.append((to.value, fr.value))
     finally:
@@ -830,7 +827,6 @@ def _cs_flag_routes(keep, B, T, V):
     """what the flagged launch of a fast-path AUTO call did, from the flag words the chains and the segment kernel left
     (masked to the bits include/e2e_ctc_debug.h documents; 512 is the launch's own)"""
     L = _lib.load()
-    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     flags, logz = (ctypes.c_int * B)(), (ctypes.c_double * (2 * B))()
     assert L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, keep["Smax"], flags, logz) == 0
     raw = np.array(flags[:], dtype=np.int64)

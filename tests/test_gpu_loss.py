@@ -336,7 +336,6 @@ def test_range_flags_with_eight_pairs_per_lane_are_redone_in_f64_too(shape):
     import ctypes
     cnt = ctypes.c_int(-1)
     L = _lib.load()
-    L.e2e_debug_fast_redo_failures.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     assert L.e2e_debug_fast_redo_failures(keep["workspace"].data_ptr(), B, T, V, S, ctypes.byref(cnt)) == 0
     assert 0 <= cnt.value <= nflag // 2, "%d of %d flagged utterances were left to the full recomputation" % (cnt.value, nflag)
     U.assert_same(la, le, F32_RTOL, 2e-5, "losses")

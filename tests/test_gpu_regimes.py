@@ -41,8 +41,6 @@ def aligned(rng, B, T, V, S, boost, blank=0, short=()):
 def unsettled(keep, B, T, V, S):
     """utterances the exact kernel had to recompute in full; also: no bounded wait of the flagged launch may have run out"""
     L = _lib.load()
-    L.e2e_debug_fast_redo_failures.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-    L.e2e_debug_flagged_counters.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     cnt, to, fr = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
     assert L.e2e_debug_fast_redo_failures(keep["workspace"].data_ptr(), B, T, V, S, ctypes.byref(cnt)) == 0
     assert L.e2e_debug_flagged_counters(keep["workspace"].data_ptr(), B, T, V, S, ctypes.byref(to), ctypes.byref(fr)) == 0

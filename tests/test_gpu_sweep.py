@@ -159,7 +159,6 @@ def test_flagged_utterances_are_settled_by_the_segment_redo_not_by_the_exact_ker
     flagged = int(np.isnan(lf).sum())
     assert flagged >= 4 and np.isfinite(la).all()
     n = ctypes.c_int(-1)
-    L.e2e_debug_fast_redo_failures.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     assert L.e2e_debug_fast_redo_failures(kept["workspace"].data_ptr(), B, T, V, S, ctypes.byref(n)) == 0
     assert 0 <= n.value <= flagged // 4, (n.value, flagged)
 

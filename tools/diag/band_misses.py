@@ -11,9 +11,6 @@ import torch
 import bench
 from end2end_amd import _lib
 L = _lib.load()
-L.e2e_debug_fast_state.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
-L.e2e_debug_band_misses.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
-L.e2e_debug_segment_band.argtypes = [C.c_int]
 dev = torch.device("cuda", 0)
 w = bench.WORKLOAD
 B, T, V, S = w["B"], w["T"], w["V"], w["S"]

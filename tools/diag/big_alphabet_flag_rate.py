@@ -23,6 +23,6 @@ xl = torch.randint(T // 2, T + 1, (B,), generator=g); tl = torch.minimum(torch.r
 kept = {}
 lf, gf = U.c_abi_loss(x, tg, xl, tl, 0, False, _lib.ALGO_FAST, keep=kept)
 fw = (ctypes.c_int * B)(); lz = (ctypes.c_double * (2 * B))()
-L = _lib.load(); L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
+L = _lib.load()
 assert L.e2e_debug_fast_state(kept["workspace"].data_ptr(), B, T, V, S, fw, lz) == 0
 print("flag words:", collections.Counter(int(f) for f in fw), "; flagged (T, S):", [(int(xl[b]), int(tl[b])) for b in range(B) if fw[b]])

@@ -10,7 +10,6 @@ import numpy as np, torch
 import gpu_util as U
 from end2end_amd import _lib
 L = _lib.load()
-L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
 HAVE_ZDEV = hasattr(L, "e2e_debug_fast_zdev")          # (the instrumented build: E2E_CTC_LIB=build/diag/prof_lib.so)
 if HAVE_ZDEV: L.e2e_debug_fast_zdev.argtypes = [ctypes.c_void_p, ctypes.c_int]
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)

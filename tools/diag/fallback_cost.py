@@ -39,7 +39,6 @@ for boost in [1.0, 2.0, 4.0, 8.0]:
         res[name] = e0.elapsed_time(e1) / 5 * 1e3
         if name == "fast":
             flags = (C.c_int * B)(); logz = (C.c_double * (2 * B))()
-            L.e2e_debug_fast_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
             assert L.e2e_debug_fast_state(ws.data_ptr(), B, T, V, S, flags, logz) == 0
             f = np.array(flags[:]); nflag = int((f != 0).sum()); kinds = sorted(set(f[f != 0].tolist()))
     print("boost %.1f: %3d of %d flagged (flag words %s): fast-only %.0f us, auto (with exact fallback) %.0f us" % (boost, nflag, B, kinds, res["fast"], res["auto"]))

@@ -26,7 +26,6 @@ for (B, T, V, S) in shapes:
     for _ in range(5): call()
     e1.record(); torch.cuda.synchronize()
     fw = (ctypes.c_int * B)(); lz = (ctypes.c_double * (2 * B))()
-    L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     ok = L.e2e_debug_fast_state(ws.data_ptr(), B, T, V, S, fw, lz) == 0
     import collections
     if ok: print("   flag words (1 lengths, 2 blank label, 4 infeasible / inf, 8 range, 16 non-finite, 32 log Z mismatch, 64 tiny emissions, 128 hand-off, 512 redo failed):", dict(collections.Counter(int(f) for f in fw)))

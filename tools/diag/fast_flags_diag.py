@@ -15,7 +15,6 @@ def run(x, tg, xl, tl, logprobs, name):
     rc = L.e2e_ctc_loss_fwd_bwd(x.data_ptr(),0,int(logprobs),*x.stride(),tg.data_ptr(),tg.stride(0),xl_d.data_ptr(),tl_d.data_ptr(),B,T,V,Smax,0,losses.data_ptr(),grads.data_ptr(),ws.data_ptr(),ws.numel(),2,None)
     assert rc == 0, L.e2e_last_error()
     fl = (C.c_int*B)(); lz = (C.c_double*(2*B))()
-    L.e2e_debug_fast_state.argtypes=[C.c_void_p,C.c_int,C.c_int,C.c_int,C.c_int,C.c_void_p,C.c_void_p]
     L.e2e_debug_fast_state(ws.data_ptr(),B,T,V,Smax,fl,lz)
     fl = np.array(fl[:]); lz = np.array(lz[:]).reshape(B,2)
     print(name, "flags", fl[:16], "nflag", (fl!=0).sum(), "of", B)

@@ -16,7 +16,6 @@ rc = L.e2e_ctc_loss_fwd_bwd(x.data_ptr(), 0, 0, *x.stride(), tg.data_ptr(), tg.s
                             losses.data_ptr(), grads.data_ptr(), ws.data_ptr(), ws.numel(), 2, None)
 assert rc == 0
 fl = (C.c_int * B)(); lz = (C.c_double * (2 * B))()
-L.e2e_debug_fast_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 L.e2e_debug_fast_state(ws.data_ptr(), B, T, V, S, fl, lz)
 fl = np.array(fl[:]); lz = np.array(lz[:]).reshape(B, 2)
 print("flag words (1 lengths, 2 blank label, 4 infeasible/inf, 8 self-check/range, 16 non-finite, 32 log Z mismatch, 64 tiny emissions, 128 protocol):")

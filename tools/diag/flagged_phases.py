@@ -7,7 +7,6 @@ import torch
 import bench
 from end2end_amd import _lib
 L = _lib.load(); dev = torch.device("cuda", 0)
-L.e2e_debug_flagged_phases.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
 w = bench.WORKLOAD; B, T, V, S = w["B"], w["T"], w["V"], w["S"]
 def run(name, host):
     hp = bench.HotPath(tuple(t.to(dev) for t in host))

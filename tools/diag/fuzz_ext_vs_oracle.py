@@ -11,7 +11,6 @@ import numpy as np, torch
 import gpu_util as U, oracle_lib as O
 from end2end_amd import _lib
 L = _lib.load()
-L.e2e_debug_fast_redo_failures.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 bad = 0; tot = 0; off_fast = 0; exact = 0; marginal = 0
@@ -79,7 +78,6 @@ for case in range(n_cases):
             bad += 1
         if os.environ.get("FUZZ_ONLY"):
             fl = (ctypes.c_int * B)(); lz = (ctypes.c_double * (2 * B))()
-            L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
             L.e2e_debug_fast_state(keep["workspace"].data_ptr(), B, T, V, Smax, fl, lz)
             print(" flag words:", list(fl))
             for b in range(B):

@@ -48,7 +48,6 @@ for case in range(n_cases):
     lf, gf = U.c_abi_loss(x, tg[:, :max(Smax, 1)], xl, tl, blank, not fused, _lib.ALGO_FAST, keep=kept)
     if V <= 96:
         fw = (ctypes.c_int * B)(); lzw = (ctypes.c_double * (2 * B))()
-        _lib.load().e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
         if _lib.load().e2e_debug_fast_state(kept["workspace"].data_ptr(), B, T, V, max(Smax, 1), fw, lzw) == 0:
             for b in range(B):
                 if np.isfinite(le[b]): flagwords[(sharp, fw[b])] += 1

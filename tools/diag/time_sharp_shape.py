@@ -20,8 +20,6 @@ e0.record()
 for _ in range(3): call()
 e1.record(); torch.cuda.synchronize()
 fl = (ctypes.c_int * B)(); lz = (ctypes.c_double * (2 * B))(); un = ctypes.c_int(0)
-L.e2e_debug_fast_state.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
-L.e2e_debug_fast_redo_failures.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]
 L.e2e_debug_fast_state(ws.data_ptr(), B, T, V, S, fl, lz); L.e2e_debug_fast_redo_failures(ws.data_ptr(), B, T, V, S, ctypes.byref(un))
 print("B=%d T=%d V=%d S<=%d scale %g: %.3f ms per call, %d of %d utterances left the f32 lattice, %d recomputed by the exact kernel, finite %s" % (
     B, T, V, S, sharp, e0.elapsed_time(e1) / 3, sum(1 for v in fl if v & 511), B, un.value, bool(torch.isfinite(losses).all())))
