@@ -376,6 +376,15 @@ PYBIND11_MODULE(_C, m) {
         "lp dtype sB sT sV chunk_len B T V gram_ids gram_len max_order num_base_labels beam_width scored space_id lm lmwt wip "
         "oov_penalty state row_bytes max_frames nbest out max_out out_len n_hyp scores counts frames_done workspace "
         "workspace_bytes stream opts", py::none());
+  // ... with per-frame label pruning (cutoff_top_n, cutoff_prob behind the stream's arguments; nbest_cut has its `scored`).
+  // The signatures alone: tests/test_bindings_cpu.py holds this module's functions to the recording of the hand-written layer,
+  // so the engine reaches these through end2end_amd._lib, which types them from SIGNATURES like every other symbol
+  b.sig<e2e_gram_beam_cut_max_width>("e2e_gram_beam_cut_max_width");
+  b.sig<e2e_gram_beam_cut_workspace_bytes>("e2e_gram_beam_cut_workspace_bytes");
+  b.sig<e2e_gram_beam_cut_stream_workspace_bytes>("e2e_gram_beam_cut_stream_workspace_bytes");
+  b.sig<e2e_gram_beam_cut_stream_row_bytes>("e2e_gram_beam_cut_stream_row_bytes");
+  b.sig<e2e_gram_ctc_beam_nbest_cut>("e2e_gram_ctc_beam_nbest_cut");
+  b.sig<e2e_gram_ctc_beam_stream_cut>("e2e_gram_ctc_beam_stream_cut");
 
   // ---- ASG decoding ----
   b.query<e2e_asg_beam_max_width>("e2e_asg_beam_max_width");

@@ -41,10 +41,18 @@ class GramCTCDecoder:
     :param after_logsoftmax: inputs are log-probabilities (greedy ignores this)
     :param time_major: inputs are ``(time, batch, alphabet)``
     :param keep_on_device: leave the decoded ids and lengths on the GPU
+    :param cutoff_top_n: per-frame label pruning, ``CTCDecoder``'s: a frame expands at most this many columns (unigrams and
+        grams alike), the likeliest (ties to the lower column), and the blank.  ``None`` or a value that is no less than
+        ``total_labels``: no limit.  At most 1024 columns can be kept; needs ``beam_width > 1``.  A pruned search's width
+        limit is ``min(128, 131072 / (min(cutoff_top_n, total_labels) + 1))``, whatever the alphabet.
+    :param cutoff_prob: ... and of those the fewest whose probabilities sum to this, in ``(0, 1]``; ``1.0``: all.  With both
+        at their defaults the decoder is the unpruned one.  ``configure()`` and ``restrict_to_vocabulary()`` keep the two;
+        a stream takes those the decoder has at ``open_stream``; ``decode_greedy`` ignores them.
     """
 
     def __init__(self, blank_idx=0, num_base_labels=None, total_labels=None, label2ids=None, beam_width=100, labels=None,
-                 after_logsoftmax=False, time_major=False, keep_on_device=False, transcriptions=None):
+                 after_logsoftmax=False, time_major=False, keep_on_device=False, transcriptions=None,
+                 cutoff_top_n=None, cutoff_prob=1.0):
         if transcriptions is not None:
             raise CTCDecoderError("GramCTCDecoder does not support custom transcriptions: its search spells words from the base labels")
         if num_base_labels is None or total_labels is None:
@@ -52,8 +60,22 @@ class GramCTCDecoder:
         self._beam_width = beam_width
         self._after_logsoftmax = after_logsoftmax
         self._time_major = time_major
-        self._decoder = GramCTCDecoderEngine(blank_idx, num_base_labels, total_labels, label2ids or {}, beam_width,
-                                             labels, keep_on_device=keep_on_device)
+        # (CTCDecoder._check_params' tests and texts)
+        if cutoff_top_n is not None and (isinstance(cutoff_top_n, bool) or int(cutoff_top_n) != cutoff_top_n or cutoff_top_n < 1):
+            raise CTCDecoderError("cutoff_top_n must be an integer >= 1 (or None), got {!r}".format(cutoff_top_n))
+        if not isinstance(cutoff_prob, (int, float)) or not 0.0 < cutoff_prob <= 1.0:
+            raise CTCDecoderError("cutoff_prob must be in (0, 1], got {!r}".format(cutoff_prob))
+        if (cutoff_top_n is not None or cutoff_prob != 1.0) and beam_width == 1:
+            raise CTCDecoderError("cutoff_top_n / cutoff_prob need beam_width > 1: greedy decoding expands nothing")
+        pruned = cutoff_top_n is not None or cutoff_prob != 1.0
+        try:
+            self._decoder = GramCTCDecoderEngine(blank_idx, num_base_labels, total_labels, label2ids or {}, beam_width,
+                                                 labels, keep_on_device=keep_on_device, cutoff_top_n=cutoff_top_n,
+                                                 cutoff_prob=cutoff_prob)
+        except ValueError as e:
+            if not pruned:
+                raise
+            raise CTCDecoderError(str(e)) from e
 
     def configure(self, lm_path=None, lmwt=1.0, wip=1.0, oov_penalty=-10, case_sensitive=True):
         """Set up the beam search with a word language model, before decoding; returns self.  The names and defaults are

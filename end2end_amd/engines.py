@@ -43,6 +43,30 @@ _REDUCTIONS = {None: _C.REDUCE_NONE, "sum": _C.REDUCE_SUM, "mean": _C.REDUCE_MEA
 _ws_bytes = {}                           # (B, T, V, Smax, dtype code, algo) -> e2e_ctc_loss_workspace_bytes
 
 
+class _GramCut:
+    """The pruned Gram-CTC entries (e2e_gram_beam_cut_*, e2e_gram_ctc_beam_*_cut; include/e2e_ctc.h), reached through the
+    ctypes view: end2end_amd._C's set of functions is held to a recording by tests/test_bindings_cpu.py, and _lib types every
+    symbol of _C.SIGNATURES -- these included -- from the header.  A query returns its value; a call takes addresses as
+    integers (0: NULL), `opts` as None or (restrict_to_lexicon, timesteps), and raises E2EError as _C's wrappers do."""
+
+    @staticmethod
+    def query(name, *args):
+        from . import _lib
+        return getattr(_lib.load(), "e2e_gram_beam_cut_" + name)(*args)
+
+    @staticmethod
+    def call(name, *args):
+        """args: the C parameters in order, `opts` in its place; cutoff_top_n and cutoff_prob last."""
+        import ctypes
+        from . import _lib
+        L = _lib.load()
+        at = len(args) - 3
+        opts = None if args[at] is None else _lib.GramBeamOpts(1 if args[at][0] else 0, args[at][1] or None)
+        rc = getattr(L, name)(*args[:at], None if opts is None else ctypes.byref(opts), *args[at + 1:])
+        if rc:
+            raise R.E2EError("libe2e_ctc: %s (code %d)" % (L.e2e_last_error().decode(errors="replace"), rc))
+
+
 def _on_device(dev):
     """A context that makes `dev` the current GPU -- none at all when it already is (the context manager costs ~10 us of host time
     per entry, which on a 130 us step is what decides whether the host stays ahead of the GPU)."""
@@ -862,11 +886,13 @@ class GramCTCDecoderEngine:
     -- copied to a device on first use and kept per device.  `labels`: the R base-label strings (index 0 the blank's).
     The width limit is checked here, not at the first decode.  `configure()` sets up the search with a word language
     model (e2e_gram_ctc_beam_nbest_lm); an engine that was never configured is the search on the masses alone.  `restrict()`,
-    after `configure()`, restricts the search to a vocabulary (e2e_gram_ctc_beam_nbest_opt).  Results are CPU tensors unless
-    `keep_on_device`."""
+    after `configure()`, restricts the search to a vocabulary (e2e_gram_ctc_beam_nbest_opt).  `cutoff_top_n`, `cutoff_prob`:
+    per-frame label pruning, CTCDecoderEngine's knobs -- decode, decode_nbest and open_stream then go to the *_cut entries
+    (e2e_gram_ctc_beam_nbest_cut, e2e_gram_ctc_beam_stream_cut), a search that prunes nothing to the entries above; the width
+    limit is then e2e_gram_beam_cut_max_width's.  Results are CPU tensors unless `keep_on_device`."""
 
     def __init__(self, blank_idx, num_base_labels, total_labels, label2ids, beam_width_=100, labels=None,
-                 keep_on_device=False):
+                 keep_on_device=False, cutoff_top_n=None, cutoff_prob=1.0):
         if int(blank_idx) != 0:
             raise NotImplementedError("Gram-CTC supports blank_idx=0 only (as upstream)")
         self.blank_idx = 0
@@ -883,14 +909,39 @@ class GramCTCDecoderEngine:
         if self.labels and len(self.labels) != self.num_base_labels:
             raise ValueError("the decoder has %d labels but num_base_labels=%d" % (len(self.labels), self.num_base_labels))
         self.keep_on_device = bool(keep_on_device)
-        cap = _C.gram_beam_max_width(self.total_labels, self.max_order)
+        # per-frame label pruning (the definition: e2e_gram_ctc_beam_nbest_cut, include/e2e_ctc.h): a frame expands at most
+        # cutoff_top_n columns and of those the fewest whose probabilities sum to cutoff_prob, the blank always.  None / 1.0
+        # (or a cutoff_top_n that is no less than total_labels): not pruned.  configure() and restrict() keep them
+        self._set_cut(cutoff_top_n, cutoff_prob)
+        cut = self._cut()
+        cap = (_GramCut.query("max_width", self.total_labels, self.max_order, cut[0]) if cut
+               else _C.gram_beam_max_width(self.total_labels, self.max_order))
         if self.beam_width < 1 or self.beam_width > cap:
-            raise ValueError("beam_width %d is not supported for a Gram-CTC table of %d columns (max_order %d): 1 to %d"
-                             % (self.beam_width, self.total_labels, self.max_order, cap))
+            raise ValueError("beam_width %d is not supported for a Gram-CTC table of %d columns (max_order %d)%s: 1 to %d"
+                             % (self.beam_width, self.total_labels, self.max_order,
+                                " with cutoff_top_n=%d" % cut[0] if cut else "", cap))
         self._per_device = {}
         self.configured = False                      # configure(): the search with the LM fields (e2e_gram_ctc_beam_nbest_lm)
         self.lm = None
         self.restricted = False                      # restrict(): only admissible sequences (e2e_gram_ctc_beam_nbest_opt)
+
+    def _cut(self):
+        """(cutoff_top_n, cutoff_prob) as the C calls take them if the decoder prunes its table's columns, else None: a search
+        that prunes nothing goes to the unpruned entries."""
+        V = self.total_labels
+        top_n = V if self.cutoff_top_n is None else self.cutoff_top_n
+        return (top_n, self.cutoff_prob) if top_n < V or self.cutoff_prob < 1.0 else None
+
+    def _set_cut(self, cutoff_top_n, cutoff_prob):
+        if cutoff_top_n is not None and int(cutoff_top_n) < 1:
+            raise ValueError("cutoff_top_n=%r: at least 1" % (cutoff_top_n,))
+        if not 0.0 < float(cutoff_prob) <= 1.0:
+            raise ValueError("cutoff_prob=%r outside (0, 1]" % (cutoff_prob,))
+        if (cutoff_top_n is not None or float(cutoff_prob) < 1.0) and self.beam_width == 1:
+            raise ValueError("cutoff_top_n / cutoff_prob need beam_width > 1: greedy decoding expands nothing")
+        top_n = None if cutoff_top_n is None else int(cutoff_top_n)
+        CTCDecoderEngine.check_cut_limit(self.total_labels, top_n, float(cutoff_prob))
+        self.cutoff_top_n, self.cutoff_prob = top_n, float(cutoff_prob)
 
     def configure(self, lm_path="", lmwt_=1.0, wip_=0.0, oov_penalty_=-1000.0, case_sensitive=False):
         """Set up the beam search with a word language model (e2e_gram_ctc_beam_nbest_lm; the definition: include/e2e_ctc.h);
@@ -1018,15 +1069,24 @@ class GramCTCDecoderEngine:
         if B:
             with torch.cuda.device(dev):
                 ids, lens = self._table(dev)
-                nbytes = _C.gram_beam_workspace_bytes(B, T, V, self.max_order, self.beam_width)
+                cut = self._cut()
+                nbytes = (_GramCut.query("workspace_bytes", B, T, V, self.max_order, self.beam_width, False, False, cut[0]) if cut
+                          else _C.gram_beam_workspace_bytes(B, T, V, self.max_order, self.beam_width))
                 if not nbytes:
                     raise ValueError("Gram-CTC beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
                 ws = R.workspace(dev, nbytes)
                 sB, sT, sV = x.stride()
-                _C.gram_ctc_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
-                                       ids.data_ptr(), lens.data_ptr(), self.max_order, self.beam_width, N,
-                                       out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), R.stream_handle(dev))
+                if cut:
+                    _GramCut.call("e2e_gram_ctc_beam_nbest_cut", x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
+                                               ids.data_ptr(), lens.data_ptr(), self.max_order, self.num_base_labels,
+                                               self.beam_width, False, -1, 0, 0.0, 0.0, 0.0, N,
+                                               out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                                               0, ws.data_ptr(), ws.numel(), R.stream_handle(dev), None, *cut)
+                else:
+                    _C.gram_ctc_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, T, V,
+                                           ids.data_ptr(), lens.data_ptr(), self.max_order, self.beam_width, N,
+                                           out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), R.stream_handle(dev))
         return _nbest_result(self, *bufs)
 
     def _check_nbest(self, nh, lens, max_out):
@@ -1046,7 +1106,9 @@ class GramCTCDecoderEngine:
             with torch.cuda.device(dev):
                 ids, lens = self._table(dev)
                 lm = self.lm.on(dev).handle if self.lm is not None else 0
-                nbytes = _C.gram_beam_workspace_bytes_lm(B, T, V, self.max_order, self.beam_width, self.lm is not None)
+                cut = self._cut()
+                nbytes = (_GramCut.query("workspace_bytes", B, T, V, self.max_order, self.beam_width, True, self.lm is not None, cut[0])
+                          if cut else _C.gram_beam_workspace_bytes_lm(B, T, V, self.max_order, self.beam_width, self.lm is not None))
                 if not nbytes:
                     raise ValueError("Gram-CTC beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
                 ws = R.workspace(dev, nbytes, stream)
@@ -1056,7 +1118,10 @@ class GramCTCDecoderEngine:
                         self.beam_width, self.space_id, lm, self.lmwt, self.wip, self.oov_penalty, N,
                         out.data_ptr(), max_out, out_len.data_ptr(), n_hyp.data_ptr(), scores.data_ptr(),
                         counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-                if self.restricted or ts is not None:
+                opts = (self.restricted, ts.data_ptr() if ts is not None else 0)
+                if cut:                                          # (args with `scored` in its place: behind beam_width)
+                    _GramCut.call("e2e_gram_ctc_beam_nbest_cut", *args[:14], True, *args[14:], opts, *cut)
+                elif self.restricted or ts is not None:
                     _C.gram_ctc_beam_nbest_opt(*args, (self.restricted, ts.data_ptr() if ts is not None else 0))
                 else:
                     _C.gram_ctc_beam_nbest_lm(*args)
@@ -1531,6 +1596,7 @@ class GramBeamStream(_BeamStream):
         self.lm = e.lm if self.scored else None
         self.restricted = bool(e.restricted) if self.scored else False
         self._knobs = (e.space_id, e.lmwt, e.wip, e.oov_penalty) if self.scored else (-1, 0.0, 0.0, 0.0)
+        self._cut = e._cut()                                     # the pruning in force now: the same for every chunk
 
     def feed_nbest(self, logits_, logits_lengths_=None, nbest=None, timesteps=None):
         """_BeamStream.feed_nbest; timesteps: None -- as the stream was opened -- or whether this read-out returns them (a
@@ -1542,6 +1608,9 @@ class GramBeamStream(_BeamStream):
 
     def _row_bytes(self, V):
         e = self.engine
+        if self._cut:
+            return _GramCut.query("stream_row_bytes", self.max_frames, V, e.max_order, e.beam_width, self.scored,
+                                                     self.lm is not None, self._cut[0])
         return _C.gram_beam_stream_row_bytes(self.max_frames, V, e.max_order, e.beam_width, self.scored, self.lm is not None)
 
     def _prepare(self, logits_, logits_lengths_):
@@ -1557,12 +1626,21 @@ class GramBeamStream(_BeamStream):
         space_id, lmwt, wip, oov_penalty = self._knobs
         ids, lens = e._table(dev)
         lm = self.lm.on(dev).handle if self.lm is not None else 0
-        ws = R.workspace(dev, _C.gram_beam_stream_workspace_bytes(B, V, e.max_order, e.beam_width, self.scored,
-                                                                  self.lm is not None), stream)
+        cut = self._cut
+        if cut:
+            nbytes = _GramCut.query("stream_workspace_bytes", B, Tc, V, e.max_order, e.beam_width, self.scored,
+                                                             self.lm is not None, cut[0])
+        else:
+            nbytes = _C.gram_beam_stream_workspace_bytes(B, V, e.max_order, e.beam_width, self.scored, self.lm is not None)
+        ws = R.workspace(dev, nbytes, stream)
         sB, sT, sV = x.stride()
-        _C.gram_ctc_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V,
-                                ids.data_ptr(), lens.data_ptr(), e.max_order, e.num_base_labels, e.beam_width,
-                                self.scored, space_id, lm, lmwt, wip, oov_penalty,
-                                state.data_ptr(), self.row_bytes, self.max_frames, N,
-                                out, max_out, out_len, n_hyp, scores, counts, frames_done,
-                                ws.data_ptr(), ws.numel(), stream, (self.restricted, ts) if self.scored else None)
+        args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, xl.data_ptr(), B, Tc, V,
+                ids.data_ptr(), lens.data_ptr(), e.max_order, e.num_base_labels, e.beam_width,
+                self.scored, space_id, lm, lmwt, wip, oov_penalty,
+                state.data_ptr(), self.row_bytes, self.max_frames, N,
+                out, max_out, out_len, n_hyp, scores, counts, frames_done,
+                ws.data_ptr(), ws.numel(), stream, (self.restricted, ts) if self.scored else None)
+        if cut:
+            _GramCut.call("e2e_gram_ctc_beam_stream_cut", *args, *cut)
+        else:
+            _C.gram_ctc_beam_stream(*args)

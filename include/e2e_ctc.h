@@ -535,6 +535,66 @@ int e2e_gram_ctc_beam_stream(const void* lp, int dtype, int64_t sB, int64_t sT, 
                              const e2e_gram_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * Gram-CTC beam search with per-frame label pruning (cutoff_top_n, cutoff_prob) -- additive, ABI 4; the knobs and the
+ * selection are e2e_ctc_label_cut's, defined with the CTC search's pruning further down.
+ *
+ * DEFINITION.  A frame's kept set is exactly steps 1 to 5 of e2e_ctc_label_cut with blank = 0 over the V columns of the row
+ * the search reads (f32 and f64 as they are; 16-bit inputs are up-cast first, as for the unpruned calls).  Grams are columns
+ * like any other.  In the search a column outside the frame's set does nothing in that frame:
+ *   - it gives no extension share, from any member;
+ *   - a slot that holds it receives no "run continues" stay share.
+ * The blank's stay share is always there.  Everything else is unchanged: identity by key, the ranking, the two-addend slots,
+ * the power-of-two rescale, the LM fields, the restriction rule, the node numbering 1 + t * beam_width + rank and with it
+ * the timesteps.
+ * CONSEQUENCE.  A pruned call equals, bit for bit in every output (ids, lengths, n_hyp, scores, counts, timesteps), the
+ * unpruned call on log-probabilities whose non-kept columns are replaced by -inf: an absent addend and an addend of exactly 0
+ * give the same f64 sum, a pair whose share is 0 is no candidate and a total of 0 is no member in the unpruned search either.
+ * cutoff_top_n >= V together with cutoff_prob == 1 is no pruning: the *_cut entries then are the unpruned entries -- the
+ * same kernel, the same workspace query.
+ *
+ * e2e_gram_ctc_beam_nbest_cut: with scored = 0 the search and the outputs of e2e_gram_ctc_beam_nbest (lm, counts and opts
+ * NULL, num_base_labels / space_id / lmwt / wip / oov_penalty not read, scores (B,nbest)); else those of
+ * e2e_gram_ctc_beam_nbest_opt, opts included.  e2e_gram_ctc_beam_stream_cut: e2e_gram_ctc_beam_stream plus the knobs.  The
+ * selection and the search run on `stream` in one call.  Nothing of a frame's work scales with V: with K = min(cutoff_top_n,
+ * V) a member has K + 1 (member, column) pairs, so
+ *   width      beam_width <= e2e_gram_beam_cut_max_width(V, max_order, cutoff_top_n) = min(128, 131072 / (K + 1)): 128 for
+ *              every alphabet up to K = 1023
+ *   workspace  >= e2e_gram_beam_cut_workspace_bytes(...) (a stream: e2e_gram_beam_cut_stream_workspace_bytes, T the chunk's):
+ *              the frames' lists, (B,T,K+1) and (B,T) int32, and per utterance e2e_gram_ctc_beam_nbest's buffers with K + 1
+ *              in V's place.  No answer rows of a language model: a pair's answer is computed in the frame.  A query returns
+ *              0 where the call would be refused
+ *   a stream   the knobs are the same for every chunk (the caller's contract, as for opts); the selection runs on each
+ *              chunk; the state row's layout is e2e_gram_beam_stream_row_bytes', which e2e_gram_beam_cut_stream_row_bytes
+ *              also answers beyond the unpruned width limit; after any chunking the read-out equals the whole pruned call,
+ *              bit for bit
+ * Argument errors are found on the host before any launch: cutoff_top_n < 1 and cutoff_prob outside (0, 1] are E2E_ERR_ARG,
+ * K > e2e_ctc_label_cut_max() and a width above the limit E2E_ERR_UNSUPPORTED; everything else as for the unpruned entries
+ * (a workspace that is too small: E2E_ERR_WORKSPACE).  Asynchronous on `stream`, allocates nothing, never synchronises.
+ */
+int e2e_gram_beam_cut_max_width(int V, int max_order, int cutoff_top_n);
+size_t e2e_gram_beam_cut_workspace_bytes(int B, int T, int V, int max_order, int beam_width, int scored, int with_lm,
+                                         int cutoff_top_n);
+size_t e2e_gram_beam_cut_stream_workspace_bytes(int B, int T, int V, int max_order, int beam_width, int scored, int with_lm,
+                                                int cutoff_top_n);
+size_t e2e_gram_beam_cut_stream_row_bytes(int max_frames, int V, int max_order, int beam_width, int scored, int with_lm,
+                                          int cutoff_top_n);
+
+int e2e_gram_ctc_beam_nbest_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len,
+                                int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                                int num_base_labels, int beam_width, int scored, int space_id, const struct e2e_lm* lm, double lmwt,
+                                double wip, double oov_penalty, int nbest, int64_t* out, int64_t max_out, int64_t* out_len,
+                                int64_t* n_hyp, double* scores, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                void* stream, const e2e_gram_beam_opts* opts, int cutoff_top_n, double cutoff_prob);
+
+int e2e_gram_ctc_beam_stream_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* chunk_len,
+                                 int B, int T, int V, const int32_t* gram_ids, const int32_t* gram_len, int max_order,
+                                 int num_base_labels, int beam_width, int scored, int space_id, const struct e2e_lm* lm, double lmwt,
+                                 double wip, double oov_penalty, void* state, size_t row_bytes, int max_frames,
+                                 int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                                 int32_t* counts, int64_t* frames_done, void* workspace, size_t workspace_bytes, void* stream,
+                                 const e2e_gram_beam_opts* opts, int cutoff_top_n, double cutoff_prob);
+
+/* ------------------------------------------------------------------------
  * ASG decoding: n-best prefix beam search with transitions and a word language model (additive, ABI 4: nothing above
  * changes meaning).  Upstream has no ASG decoder; this is the definition.  Path score, x, transitions A[to, from], V, x_len
  * and strides are e2e_asg_fwd_bwd's / e2e_asg_viterbi's: no softmax, no start or end transition.
