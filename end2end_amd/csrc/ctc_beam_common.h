@@ -794,6 +794,7 @@ struct GenParams {
 inline int label_cut_k(int V, int cutoff_top_n) { return cutoff_top_n < V ? cutoff_top_n : V; }
 // the argument errors of a selection (E2E_ERR_ARG, the limit: E2E_ERR_UNSUPPORTED), before any launch
 int label_cut_check(int dtype, int B, int T, int V, int blank, int cutoff_top_n, double cutoff_prob);
+// blank < 0: no blank (asg_beam_cut.hip; f32 / f64, V <= 256, cutoff_prob 1): ids is (B,T,K), a frame's count is K
 int launch_label_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t sV, const int64_t* x_len, int B, int T, int V,
                      int blank, int cutoff_top_n, double cutoff_prob, int* ids, int* n, hipStream_t s);
 

@@ -12,7 +12,8 @@
 //   3. the K winners are gathered (in any order: an integer counter in LDS) and ranked by counting;
 //   4. cutoff_prob < 1: exp() of the winners in rank order, a fixed-shape (Hillis-Steele) f64 scan in LDS, the first place
 //      whose sum reaches cutoff_prob; cutoff_prob == 1 skips 3's ranking and this step;
-//   5. the kept winners and the blank are placed in ascending id by counting, -1 behind them.
+//   5. the kept winners and the blank are placed in ascending id by counting, -1 behind them (without a blank -- the ASG
+//      search's lists, BLANK = false -- the K winners alone, stride K).
 // No floating-point atomics: the f64 sums are a scan of fixed shape over a fixed order, so a call repeats bit for bit.
 #include "ctc_beam_common.h"
 
@@ -74,8 +75,11 @@ template <int G> __device__ __forceinline__ void cut_sync() {
   else __syncthreads();
 }
 
-template <typename IO, int G>
+// BLANK = false (the ASG search's lists: there is no blank, and cutoff_prob is 1): step 5 adds nothing, a frame's list is
+// its K winners in ascending id with stride K, and its count is K.
+template <typename IO, int G, bool BLANK = true>
 __global__ __launch_bounds__(kCutThreads) void label_cut_kernel(CutParams p) {
+  constexpr int kPad = BLANK ? 1 : 0;
   typedef CutKey<IO> KF;
   typedef typename KF::T KeyT;
   extern __shared__ __align__(16) unsigned char cut_smem[];
@@ -200,36 +204,43 @@ __global__ __launch_bounds__(kCutThreads) void label_cut_kernel(CutParams p) {
     for (int e = gt; e < K; e += G) rk[e] = 0;
   }
   // ---- the kept set in ascending id, the blank always among them ----
-  for (int e = gt; e < K; e += G) if (rk[e] < k && wi[e] == blank) sc[5] = 1;
-  cut_sync<G>();
-  const int extra = sc[5] ? 0 : 1;
-  if (extra && gt == 0) { wi[K] = blank; rk[K] = -1; }
-  cut_sync<G>();
+  int extra = 0;
+  if constexpr (BLANK) {
+    for (int e = gt; e < K; e += G) if (rk[e] < k && wi[e] == blank) sc[5] = 1;
+    cut_sync<G>();
+    extra = sc[5] ? 0 : 1;
+    if (extra && gt == 0) { wi[K] = blank; rk[K] = -1; }
+    cut_sync<G>();
+  } else {
+    cut_sync<G>();                                               // (the ranks are read below)
+  }
   const int nw = K + extra, nout = k + extra;
-  int* const out = p.ids + frame * ((int64_t)K + 1);
+  int* const out = p.ids + frame * ((int64_t)K + kPad);
   for (int e = gt; e < nw; e += G) {
     if (rk[e] >= k) continue;
     const int ie = wi[e];
     int pos = 0;
     for (int j = 0; j < nw; j++) pos += (rk[j] < k && wi[j] < ie) ? 1 : 0;
-    if (pos <= K) out[pos] = ie;
+    if (pos < K + kPad) out[pos] = ie;
   }
-  for (int e = nout + gt; e <= K; e += G) out[e] = -1;
+  for (int e = nout + gt; e < K + kPad; e += G) out[e] = -1;
   if (gt == 0) p.n[frame] = nout;
 }
 
-template <typename IO>
+template <typename IO, bool BLANK = true>
 int launch_cut_of(const CutParams& p0, hipStream_t s) {
   CutParams p = p0;
   typedef typename CutKey<IO>::T KeyT;
   const bool wave = p.V <= kWaveMaxV;
+  if (!BLANK && !wave) { set_error("a selection without a blank: V=%d, at most %d", p.V, kWaveMaxV); return E2E_ERR_UNSUPPORTED; }
   p.staged = (size_t)p.V * sizeof(KeyT) <= (size_t)kStageBytes ? 1 : 0;
   p.group_bytes = (int)cut_group_bytes(p.V, p.K, (int)sizeof(KeyT), p.staged != 0);
   const int per = wave ? kCutThreads / 64 : 1;
   const size_t lds = (size_t)p.group_bytes * per;
   const int64_t frames = (int64_t)p.B * p.T;
   const int64_t blocks = (frames + per - 1) / per;
-  const void* fn = wave ? reinterpret_cast<const void*>(&label_cut_kernel<IO, 64>)
+  const void* fn = !BLANK ? reinterpret_cast<const void*>(&label_cut_kernel<IO, 64, BLANK>)   // (only the wave form is built)
+                 : wave ? reinterpret_cast<const void*>(&label_cut_kernel<IO, 64>)
                         : reinterpret_cast<const void*>(&label_cut_kernel<IO, kCutThreads>);
   E2E_HIP_CHECK(allow_dynamic_lds(fn, (int)lds), "hipFuncSetAttribute");
   void* args[] = { &p };
@@ -260,6 +271,10 @@ int launch_label_cut(const void* lp, int dtype, int64_t sB, int64_t sT, int64_t 
   p.lp = lp; p.sB = sB; p.sT = sT; p.sV = sV; p.x_len = x_len;
   p.B = B; p.T = T; p.V = V; p.blank = blank; p.K = label_cut_k(V, cutoff_top_n);
   p.prob = cutoff_prob; p.ids = ids; p.n = n; p.staged = 0; p.group_bytes = 0;
+  if (blank < 0) {                                               // no blank (the ASG search): ids (B,T,K), cutoff_prob 1, f32 / f64
+    if (cutoff_prob != 1.0 || (dtype != E2E_F32 && dtype != E2E_F64)) { set_error("a selection without a blank: f32 / f64, cutoff_prob 1"); return E2E_ERR_ARG; }
+    return dtype == E2E_F32 ? launch_cut_of<float, false>(p, s) : launch_cut_of<double, false>(p, s);
+  }
   switch (dtype) {
     case E2E_F32: return launch_cut_of<float>(p, s);
     case E2E_F64: return launch_cut_of<double>(p, s);

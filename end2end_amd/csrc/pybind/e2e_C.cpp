@@ -399,6 +399,12 @@ PYBIND11_MODULE(_C, m) {
         "x dtype sB sT sV transitions chunk_len B T V num_replabels beam_width space_id lm lmwt wip oov_penalty state row_bytes "
         "max_frames nbest out max_out out_len n_hyp scores counts frames_done workspace workspace_bytes stream "
         "restrict_to_lexicon timesteps", false, (uintptr_t)0);
+  // ... with per-frame label pruning (cutoff_top_n behind the unpruned calls' arguments).  The signatures alone, as for the
+  // pruned Gram-CTC entries above: the engine reaches these through end2end_amd._lib
+  b.sig<e2e_asg_beam_cut_workspace_bytes>("e2e_asg_beam_cut_workspace_bytes");
+  b.sig<e2e_asg_beam_cut_stream_workspace_bytes>("e2e_asg_beam_cut_stream_workspace_bytes");
+  b.sig<e2e_asg_beam_nbest_cut>("e2e_asg_beam_nbest_cut");
+  b.sig<e2e_asg_beam_stream_cut>("e2e_asg_beam_stream_cut");
 
   // ---- CTC decoding ----
   b.call<e2e_ctc_greedy>("e2e_ctc_greedy", "x dtype sB sT sV x_len B T V blank out out_len stream");

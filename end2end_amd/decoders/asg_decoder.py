@@ -3,6 +3,8 @@ through emissions and learned transitions (e2e_asg_viterbi), its repeats merged 
 After ``configure(beam_width > 1, ...)``: n-best prefix beam search with the transitions and, optionally, a word language model
 (e2e_asg_beam_nbest).  ``restrict_to_vocabulary()`` restricts that search to the language model's words or to a word list,
 ``decode_nbest(..., timesteps=True)`` says at which frame each label entered the beam (e2e_asg_beam_nbest_opt).
+``prune(cutoff_top_n=K)`` makes a frame expand its K highest-scoring labels alone (e2e_asg_beam_nbest_cut; flashlight's
+``beam_size_token``); there is no ``cutoff_prob``, because ASG emissions are scores, not probabilities.
 ``open_stream(transitions, batch_size, max_frames)`` is the same search fed in chunks, the beams kept on the GPU in between
 (e2e_asg_beam_stream): after every chunk the result of ``decode`` / ``decode_nbest`` on everything fed so far.  The
 definitions are in include/e2e_ctc.h; upstream has no ASG decoder; the return conventions are CTCDecoder's.
@@ -103,6 +105,26 @@ class ASGDecoder:
             self._beam.restrict(None if lexicon is None else read_lexicon(lexicon))
         except ValueError as e:
             raise CTCDecoderError(str(e))
+        return self
+
+    def prune(self, cutoff_top_n=None):
+        """Per-frame label pruning of the beam search, after ``configure(beam_width > 1, ...)``; returns self.
+
+        :param cutoff_top_n: a frame expands only its ``cutoff_top_n`` highest-scoring labels (ties: the lower id), and a
+            hypothesis whose last label is not among them does not stay in that frame: it lives on only in its extensions.
+            ``None`` (or a value that is no less than the alphabet): not pruned.
+
+        There is no ``cutoff_prob``: ASG emissions are scores, not probabilities.  Works in either order with
+        ``restrict_to_vocabulary()``; streams opened afterwards use it; ``decode_path`` and best-path decoding ignore it.
+        A later ``configure()`` builds a new search and drops the setting.
+        """
+        if cutoff_top_n is not None and (isinstance(cutoff_top_n, bool) or not isinstance(cutoff_top_n, int) or cutoff_top_n < 1):
+            raise CTCDecoderError("cutoff_top_n must be an integer >= 1 (or None), got {!r}".format(cutoff_top_n))
+        if self._beam is None:
+            if cutoff_top_n is None:
+                return self
+            raise CTCDecoderError("cutoff_top_n needs beam_width > 1: best-path decoding expands nothing")
+        self._beam.prune(cutoff_top_n)
         return self
 
     def _batch_major(self, emissions, logits_lengths):

@@ -67,6 +67,28 @@ class _GramCut:
             raise R.E2EError("libe2e_ctc: %s (code %d)" % (L.e2e_last_error().decode(errors="replace"), rc))
 
 
+class _AsgCut:
+    """The pruned ASG entries (e2e_asg_beam_cut_*, e2e_asg_beam_*_cut; include/e2e_ctc.h), reached through the ctypes view as
+    _GramCut's are, and for the same reason.  A call takes addresses as integers (0: NULL), `opts` as (restrict_to_lexicon,
+    timesteps), cutoff_top_n last."""
+
+    @staticmethod
+    def query(name, *args):
+        from . import _lib
+        return getattr(_lib.load(), "e2e_asg_beam_cut_" + name)(*args)
+
+    @staticmethod
+    def call(name, *args):
+        import ctypes
+        from . import _lib
+        L = _lib.load()
+        at = len(args) - 2
+        opts = _lib.AsgBeamOpts(1 if args[at][0] else 0, args[at][1] or None)
+        rc = getattr(L, name)(*args[:at], ctypes.byref(opts), args[at + 1])
+        if rc:
+            raise R.E2EError("libe2e_ctc: %s (code %d)" % (L.e2e_last_error().decode(errors="replace"), rc))
+
+
 def _on_device(dev):
     """A context that makes `dev` the current GPU -- none at all when it already is (the context manager costs ~10 us of host time
     per entry, which on a 130 us step is what decides whether the host stays ahead of the GPU)."""
@@ -566,7 +588,8 @@ class ASGBeamEngine:
     labels of all V columns (the repeat columns' strings are never read), at the first call: only the emissions tell
     whether `labels` lists the characters or all columns.  The width limit is checked here when the
     alphabet is known, else at the first call -- before any launch either way.  `restrict()` restricts the search to a
-    vocabulary (e2e_asg_beam_nbest_opt).  Results are CPU tensors unless `keep_on_device`."""
+    vocabulary (e2e_asg_beam_nbest_opt); `prune()` sets per-frame label pruning (e2e_asg_beam_nbest_cut).  Results are CPU
+    tensors unless `keep_on_device`."""
 
     def __init__(self, labels=None, num_replabels=0, beam_width_=100, lm_path="", lmwt_=1.0, wip_=0.0,
                  oov_penalty_=-1000.0, case_sensitive=False, keep_on_device=False):
@@ -584,6 +607,7 @@ class ASGBeamEngine:
         self.lm = None
         self.restricted = False
         self._words = None                           # restrict(lexicon=...): the word list of the model that scores nothing
+        self.cutoff_top_n = None                     # prune(): per-frame label pruning, off
         if self.beam_width < 1 or self.beam_width > _C.asg_beam_max_width(1):
             raise ValueError("beam_width %d is not supported: 1 to %d" % (self.beam_width, _C.asg_beam_max_width(1)))
         self._lm_path = lm_path or ""
@@ -614,6 +638,21 @@ class ASGBeamEngine:
         if self.num_labels is not None:
             self._load_model(self.num_labels)
         return self
+
+    def prune(self, cutoff_top_n):
+        """Per-frame label pruning (the definition: e2e_asg_beam_nbest_cut, include/e2e_ctc.h); returns self.  A frame expands
+        its `cutoff_top_n` highest-scoring labels alone, and a member whose last label is not among them does not stay.
+        None: not pruned, as is a `cutoff_top_n` that is no less than the alphabet.  decode, decode_nbest and the streams
+        opened afterwards use it.  There is no cutoff_prob: ASG emissions are scores, not probabilities."""
+        if cutoff_top_n is not None and (isinstance(cutoff_top_n, bool) or not isinstance(cutoff_top_n, (int, np.integer))
+                                         or cutoff_top_n < 1):
+            raise ValueError("cutoff_top_n=%r: at least 1" % (cutoff_top_n,))
+        self.cutoff_top_n = None if cutoff_top_n is None else int(cutoff_top_n)
+        return self
+
+    def _cut(self, V):
+        """cutoff_top_n as the C calls take it if the search prunes an alphabet of V columns, else None: the unpruned entries."""
+        return self.cutoff_top_n if self.cutoff_top_n is not None and self.cutoff_top_n < V else None
 
     def _load_model(self, V):
         """The model over all V columns (the repeat columns' strings are never spelled), with its lexicon if restricted."""
@@ -694,16 +733,24 @@ class ASGBeamEngine:
             stream = R.stream_handle(dev)
             with _on_device(dev):
                 lm = self.lm.on(dev).handle if self.lm is not None else 0
-                nbytes = _C.asg_beam_workspace_bytes(B, T, V, self.beam_width, self.lm is not None)
+                cut = self._cut(V)
+                if cut:
+                    nbytes = _AsgCut.query("workspace_bytes", B, T, V, self.beam_width, self.lm is not None, cut)
+                else:
+                    nbytes = _C.asg_beam_workspace_bytes(B, T, V, self.beam_width, self.lm is not None)
                 if not nbytes:
                     raise ValueError("ASG beam search: %d frames at beam_width %d are not supported" % (T, self.beam_width))
                 ws = R.workspace(dev, nbytes, stream)
                 sB, sT, sV = x.stride()
-                _C.asg_beam_nbest(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
-                                  xl.data_ptr(), B, T, V, self.num_replabels, self.beam_width, self.space_id, lm,
-                                  self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
-                                  n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream,
-                                  self.restricted, ts.data_ptr() if ts is not None else 0)
+                args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
+                        xl.data_ptr(), B, T, V, self.num_replabels, self.beam_width, self.space_id, lm,
+                        self.lmwt, self.wip, self.oov_penalty, N, out.data_ptr(), max_out, out_len.data_ptr(),
+                        n_hyp.data_ptr(), scores.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                opts = (self.restricted, ts.data_ptr() if ts is not None else 0)
+                if cut:
+                    _AsgCut.call("e2e_asg_beam_nbest_cut", *args, opts, cut)
+                else:
+                    _C.asg_beam_nbest(*args, *opts)
         return _nbest_result(self, *bufs)
 
     def _check_nbest(self, nh, lens, max_out):
@@ -730,6 +777,7 @@ class ASGBeamStream(_BeamStream):
 
     def __init__(self, engine, transitions, batch_size, max_frames, device=None, timesteps=False):
         super().__init__(engine, batch_size, max_frames, device=device, timesteps=timesteps)
+        self.cutoff_top_n = engine.cutoff_top_n   # (the engine's setting when the stream was opened: the same for every chunk)
         self.transitions = None if transitions is None else transitions.detach()
         self._A = {}                              # dtype -> the transitions on the stream's device
 
@@ -765,13 +813,21 @@ class ASGBeamStream(_BeamStream):
         out, out_len, n_hyp, scores, counts, ts = bufs
         A = self._transitions_for(V, dev, x.dtype)
         lm = e.lm.on(dev).handle if e.lm is not None else 0
-        ws = R.workspace(dev, _C.asg_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None), stream)
+        cut = self.cutoff_top_n if self.cutoff_top_n is not None and self.cutoff_top_n < V else None
+        if cut:
+            nbytes = _AsgCut.query("stream_workspace_bytes", B, Tc, V, e.beam_width, e.lm is not None, cut)
+        else:
+            nbytes = _C.asg_beam_stream_workspace_bytes(B, V, e.beam_width, e.lm is not None)
+        ws = R.workspace(dev, nbytes, stream)
         sB, sT, sV = x.stride()
-        _C.asg_beam_stream(x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
-                           xl.data_ptr(), B, Tc, V, e.num_replabels, e.beam_width, e.space_id, lm,
-                           e.lmwt, e.wip, e.oov_penalty, state.data_ptr(), self.row_bytes, self.max_frames, N,
-                           out, max_out, out_len, n_hyp, scores, counts, frames_done, ws.data_ptr(), ws.numel(), stream,
-                           e.restricted, ts)
+        args = (x.data_ptr(), R.dtype_code(x.dtype), sB, sT, sV, A.data_ptr() if A is not None else 0,
+                xl.data_ptr(), B, Tc, V, e.num_replabels, e.beam_width, e.space_id, lm,
+                e.lmwt, e.wip, e.oov_penalty, state.data_ptr(), self.row_bytes, self.max_frames, N,
+                out, max_out, out_len, n_hyp, scores, counts, frames_done, ws.data_ptr(), ws.numel(), stream)
+        if cut:
+            _AsgCut.call("e2e_asg_beam_stream_cut", *args, (e.restricted, ts), cut)
+        else:
+            _C.asg_beam_stream(*args, e.restricted, ts)
 
 
 GRAM_MAX_ORDER = 8

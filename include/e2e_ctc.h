@@ -932,6 +932,60 @@ int e2e_asg_beam_stream(const void* x, int dtype, int64_t sB, int64_t sT, int64_
                         void* workspace, size_t workspace_bytes, void* stream, const e2e_asg_beam_opts* opts);
 
 /* ------------------------------------------------------------------------
+ * ASG beam search with per-frame label pruning (cutoff_top_n; flashlight's beam_size_token) -- additive, ABI 4: nothing
+ * above changes meaning.  e2e_asg_beam_nbest_cut is e2e_asg_beam_nbest_opt, e2e_asg_beam_stream_cut is e2e_asg_beam_stream,
+ * each with one more argument.
+ *
+ * DEFINITION.  For a frame's row x[t, 0..V) as the search reads it (f32 / f64) and cutoff_top_n >= 1:
+ *   1. order the labels by x descending, ties by label id ascending; NaN counts as -inf, -0 and +0 are one number;
+ *   2. K = min(cutoff_top_n, V); the frame's kept set is the first K of that order, written in ascending id.
+ * There is no always-kept label -- ASG has no blank -- so a frame keeps exactly K labels.  There is no cutoff_prob: ASG
+ * emissions are scores, not log-probabilities, and sum exp(x) means nothing for them (nor is a softmax of them defined here).
+ * In the search a label outside the frame's kept set does nothing in that frame:
+ *   - it is no candidate at frame 0;
+ *   - it gives no extension share, from any member;
+ *   - a member whose last label is not kept gets no stay share: it survives the frame only as a parent.
+ * Everything else is e2e_asg_beam_nbest_opt's: spellability and the restriction rule, the two-term symmetric log-sum,
+ * identity by key and ranking by key, the LM fields, the node numbering 1 + t * beam_width + rank and with it the timesteps,
+ * and the "no hypothesis left" end (n_hyp = 0, a stream's header dead) -- which pruning makes likelier: with K = 1 a frame
+ * whose one kept label no member can stay on or take ends the search.
+ * CONSEQUENCE.  A pruned call equals, bit for bit in every output (ids, lengths, n_hyp, scores, counts, timesteps,
+ * frames_done), the unpruned call on emissions whose non-kept columns are replaced by -inf: an extension or stay share of a
+ * -inf emission is -inf, the symmetric log-sum of -inf and v is v, and a -inf total is no candidate.
+ * cutoff_top_n >= V is no pruning: the *_cut entries then are the unpruned entries -- the same kernel, the same workspace.
+ *
+ *   limits     V <= e2e_asg_max_labels(), beam_width <= e2e_asg_beam_max_width(V): the unpruned ones
+ *   workspace  >= e2e_asg_beam_cut_workspace_bytes(...) (a stream: e2e_asg_beam_cut_stream_workspace_bytes, T the chunk's):
+ *              the frames' lists, (B,T,K) and (B,T) int32; 8 V^2 bytes for the transitions as f64; per utterance the pair
+ *              buffers of e2e_asg_beam_nbest with K in V's place; for a whole call the node pool.  A query returns 0 where
+ *              the call would be refused, and the unpruned query's value for cutoff_top_n >= V
+ *   a stream   cutoff_top_n is the same for every chunk (the caller's contract, as for opts); the selection runs on each
+ *              chunk; the state row and its header are e2e_asg_beam_stream_row_bytes', unchanged; after any chunking the
+ *              read-out equals the whole pruned call, bit for bit
+ * Argument errors are found on the host before any launch: cutoff_top_n < 1 is E2E_ERR_ARG, a workspace that is too small
+ * E2E_ERR_WORKSPACE, everything else as for the unpruned entries.  The selection, the transposition and the search run on
+ * `stream` in one call: asynchronous, allocates nothing, never synchronises, capturable.
+ */
+size_t e2e_asg_beam_cut_workspace_bytes(int B, int T, int V, int beam_width, int with_lm, int cutoff_top_n);
+size_t e2e_asg_beam_cut_stream_workspace_bytes(int B, int T, int V, int beam_width, int with_lm, int cutoff_top_n);
+
+int e2e_asg_beam_nbest_cut(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                           const int64_t* x_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                           const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                           int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                           const e2e_asg_beam_opts* opts, int cutoff_top_n);
+
+int e2e_asg_beam_stream_cut(const void* x, int dtype, int64_t sB, int64_t sT, int64_t sV, const void* transitions,
+                            const int64_t* chunk_len, int B, int T, int V, int num_replabels, int beam_width, int space_id,
+                            const e2e_lm* lm, double lmwt, double wip, double oov_penalty,
+                            void* state, size_t row_bytes, int max_frames,
+                            int nbest, int64_t* out, int64_t max_out, int64_t* out_len, int64_t* n_hyp, double* scores,
+                            int32_t* counts, int64_t* frames_done,
+                            void* workspace, size_t workspace_bytes, void* stream, const e2e_asg_beam_opts* opts,
+                            int cutoff_top_n);
+
+/* ------------------------------------------------------------------------
  * Custom transcriptions: a pronunciation lexicon, homophones included (additive, ABI 4: nothing above changes meaning).
  *
  * A transcription lexicon is a list of entries (word, t_1 .. t_k), k >= 1, every t_i a label of the decoder that is neither
