@@ -38,7 +38,11 @@ __global__ __launch_bounds__(kThreads) void ctc_align_kernel(AlignParams p) {
   int* ext = reinterpret_cast<int*>(row1 + Lmax);            // [Lmax] label of every cell
   int64_t* bestbuf = reinterpret_cast<int64_t*>(ext + ((Lmax + 3) & ~3));     // [chunk rows] (16-byte aligned, like what follows)
   unsigned char* codes = reinterpret_cast<unsigned char*>(bestbuf + kChunkBytes / 64);   // [chunk rows][L]
-  __shared__ int s_cell;
+  // Two words behind the codes: the walk's cell, handed from chunk to chunk, and the "a label is outside the alphabet"
+  // flag.  In the dynamic region like everything else: the kernel must have NO static LDS, the widest accepted lattice
+  // fills a workgroup's 160 KiB to the byte (a __shared__ word and __syncthreads_or's 256-byte scratch used to sit on top).
+  int& s_cell = reinterpret_cast<int*>(codes + kChunkBytes)[0];
+  int& s_bad = reinterpret_cast<int*>(codes + kChunkBytes)[1];
 
   int64_t* out = p.out + (int64_t)b * Tmax;
   const int64_t Tq = p.x_len[b], Sq = p.t_len[b];
@@ -50,21 +54,24 @@ __global__ __launch_bounds__(kThreads) void ctc_align_kernel(AlignParams p) {
   const int L = p.is_ctc ? 2 * S + 1 : S;
 
   // labels of the cells; a label outside the alphabet cannot be looked up: the row is left as padding
-  int bad = 0;
+  if (tid == 0) s_bad = 0;
+  __syncthreads();
   for (int i = tid; i < L; i += kThreads) {
     int64_t lab = p.blank;
     if (!p.is_ctc) lab = tg[i];
     else if (i & 1) lab = tg[i >> 1];
-    bad |= (lab < 0) | (lab >= V);
+    if ((lab < 0) | (lab >= V)) s_bad = 1;
     ext[i] = (int)lab;
   }
-  if (__syncthreads_or(bad)) {
+  __syncthreads();
+  if (s_bad) {
     for (int t = tid; t < T; t += kThreads) out[t] = p.pad;
     return;
   }
-  // :65-70 / :22-24: nothing to align
+  // :65-70 / :22-24: nothing to align -- every frame is the blank (upstream's np.zeros: its blank is 0); ASG has none: zeros
   if (L <= (p.is_ctc ? 1 : 0) || T == 1) {
-    for (int t = tid; t < T; t += kThreads) out[t] = 0;
+    const int64_t none = p.is_ctc ? p.blank : 0;
+    for (int t = tid; t < T; t += kThreads) out[t] = none;
     __syncthreads();
     if (tid == 0 && T == 1 && S >= 1) out[0] = tg[0];
     return;
@@ -239,10 +246,14 @@ __global__ __launch_bounds__(kThreads) void ctc_align_kernel(AlignParams p) {
   }
 }
 
-size_t align_lds_bytes(int Lmax) {
+// ALL of the kernel's LDS (it has none that is static): rows, labels, the chunk's cells and codes, and 64 bytes that hold
+// s_cell and s_bad.  <= 160 KiB up to Lmax = 6345: Smax = 3172 (CTC), 6345 (ASG) -- include/e2e_ctc.h states these two.
+constexpr size_t align_lds_bytes(int Lmax) {
   return sizeof(double) * 2 * (size_t)Lmax + sizeof(int) * (size_t)((Lmax + 3) & ~3) + sizeof(int64_t) * (kChunkBytes / 64) +
          kChunkBytes + 64;
 }
+constexpr int kMaxCells = 6345;
+static_assert(align_lds_bytes(kMaxCells) <= 160 * 1024 && align_lds_bytes(kMaxCells + 1) > 160 * 1024, "kMaxCells is the widest lattice that fits");
 
 }  // namespace
 }  // namespace e2e
@@ -266,9 +277,14 @@ extern "C" int e2e_ctc_align(const void* lp, int dtype, int64_t sB, int64_t sT, 
   if (B < 0 || T < 1 || V < 1 || Smax < 0) { set_error("bad sizes B=%d T=%d V=%d Smax=%d", B, T, V, Smax); return E2E_ERR_ARG; }
   if (blank < 0 || blank >= V) { set_error("blank=%d outside [0,%d)", blank, V); return E2E_ERR_ARG; }
   if (B > 0 && (!lp || !x_len || !t_len || !out || (Smax > 0 && !targets))) { set_error("null pointer argument"); return E2E_ERR_ARG; }
+  const int max_S = is_ctc ? (kMaxCells - 1) / 2 : kMaxCells;
+  if (Smax > max_S) {
+    set_error("forced alignment: Smax=%d is over the limit of %d labels (%s: a lattice of %d cells fills a workgroup's 160 KiB of LDS)",
+              Smax, max_S, is_ctc ? "CTC" : "ASG", kMaxCells);
+    return E2E_ERR_UNSUPPORTED;
+  }
   const int Lmax = is_ctc ? 2 * Smax + 1 : (Smax > 0 ? Smax : 1);
   const size_t lds = align_lds_bytes(Lmax);
-  if (lds > 160 * 1024) { set_error("forced alignment: Smax=%d needs %zu B of LDS (> 160 KiB)", Smax, lds); return E2E_ERR_UNSUPPORTED; }
   uintptr_t base = reinterpret_cast<uintptr_t>(workspace);
   const uintptr_t aligned = (base + 255) & ~(uintptr_t)255;
   const int Lpad = (Lmax + 15) & ~15;

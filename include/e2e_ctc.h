@@ -1166,7 +1166,16 @@ int e2e_ctc_beam_stream_cut(const void* lp, int dtype, int64_t sB, int64_t sT, i
  *             (upstream fills -100, :132).  Ties keep the earlier candidate in the order stay, previous cell, skip, as
  *             upstream's strict ">" does.  Too few frames for the labelling is not an error upstream and is not one
  *             here (same walk over -inf cells).  An utterance with invalid lengths or a target outside [0,V) gets a
- *             row of pad_value.
+ *             row of pad_value; so does x_len[b] = 0 (it has no frames).
+ *             Rows without a lattice: an empty target (is_ctc = 1, t_len[b] = 0) is `blank` on every frame (upstream's
+ *             zeros: its blank is 0).  One frame (x_len[b] = 1) and t_len[b] >= 1 is targets[b,0] whatever t_len[b] is --
+ *             upstream's quirk, kept; one frame and no target is `blank`.  is_ctc = 0 with t_len[b] = 0 is 0 on every
+ *             frame (upstream would index targets[0]; there is no blank to fall back on).
+ *   Smax      the width of `targets`.  The lattice of the widest possible target (2 Smax + 1 cells, is_ctc = 0: Smax)
+ *             has to fit a workgroup's 160 KiB of LDS, whatever t_len holds: is_ctc = 1: Smax <= 3172; is_ctc = 0:
+ *             Smax <= 6345.  Beyond that: E2E_ERR_UNSUPPORTED before any launch, e2e_last_error() names both numbers,
+ *             `out` is untouched.  Utterances of one batch may be swept in different forms (a lattice of at most 512
+ *             cells two cells per thread, a wider one in strides of 256): the result does not depend on the form.
  *   workspace >= e2e_ctc_align_workspace_bytes(...): one back-pointer byte per lattice cell and frame
  */
 size_t e2e_ctc_align_workspace_bytes(int B, int T, int V, int Smax, int is_ctc);

@@ -630,7 +630,7 @@ static void align_one(void* vctx, int b) {
 #define LP(t, v) lp[(int64_t)(t) * c->sT + (int64_t)(v) * c->sV]
   if (c->is_ctc) {
     const int L = 2 * S + 1;
-    for (int k = 0; k < T; k++) best[k] = 0;                        /* np.zeros, :63 */
+    for (int k = 0; k < T; k++) best[k] = c->blank;                 /* np.zeros, :63: upstream's blank is 0 */
     if (L == 1 || T == 1) {                                         /* :65-70 */
       if (L == 1) return;
       best[0] = tg[0];
